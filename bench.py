@@ -2,9 +2,13 @@
 """Headline benchmark (BASELINE.json): Cityscapes-shaped 1024x2048 images/sec, forward+backward+SGD of ADD
 (searched-dense C=2, F=20, all exits active) at bs=2 per GPU, on N MI355X of one node.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the line; `--dump-outputs DIR` writes what the last timed
+step handed its caller as float32 .npy files under DIR (see dump_outputs).  Everything measured or checked beside the headline
+(the fields listed below) runs only with `--full`.
 
 Prints ONE JSON line on rank 0.  Synthetic data (N(0,1) images, uniform labels with 5 % ignore), random-init
 weights of the named architecture (kaiming-scaled normals keyed on parameter names, so the CPU oracle gets the SAME
@@ -13,10 +17,10 @@ arithmetic `--math` names (library default otherwise: f16x3 = fp32 operands as t
 product terms on the fp16 matrix pipe, fp32 accumulation — split error below the rounding noise of an fp32 accumulation chain, see
 DESIGN.md §4.1; bf16x6, the default of rounds 2-5 = three bf16 terms, six product terms, is timed beside it as a second value).
 
-Besides the contract's fields the line carries, measured in this run on rank 0 at N=1:
+Every run's line also carries step_frac_mfma, the whole-step algorithmic FLOP/s over the fp32 matrix peak (computed from shapes and
+the timed steps).  With `--full`, besides the contract's fields the line carries, measured in this run on rank 0 at N=1:
   roofline           dominant kernel (decoder 3x3) AND `segment`: the north-star "ASPP + cell forward" segment, eval and
                      train mode, as fractions of the HBM roofline (SURVEY §8(d) algorithmic bytes) and of the MFMA peak
-  step_frac_mfma     whole-step algorithmic FLOP/s over the fp32 matrix peak
   per_exit_ms        config 4: EDM-gated dynamic inference, early / final exit, 1024x2048 and 1025x2049, and the mean latency
                      at 0 / 50 / 100 % early exits
   drop_in            the same step through the reference's own call pattern (model(x); loss.backward(); torch.optim.SGD.step())
@@ -45,6 +49,7 @@ PEAK_MFMA_BF16_TFLOPS = 2500.0                            # dense bf16 peak (spe
 SUSTAINED_MFMA_BF16_TFLOPS = 1950.0                       # measured on this pool: register-resident 32x32x16 bf16 loop, toggling operands (profiles/r03_mfma_clock_probe.txt)
 PEAK_HBM_GBS = 8000.0
 WEIGHT_SEED = 1001
+DUMP_SEED, DUMP_SAMPLE = 1002, 1 << 22                    # --dump-outputs: positions of the parameter / gradient sample (16 MB per array)
 # SURVEY §8(d), per image, fp32, 1024x2048: inference algorithmic bytes / training-forward extra / forward conv FLOPs per segment
 ALG_GB = {'stem': 0.630, 'cell': 1.275 + 0.144 + 0.598 + 0.271 + 0.880, 'low': 0.033, 'aspp': 0.069, 'decoder': 0.358}
 TRAIN_EXTRA_GB = {'stem': 0.671, 'cell': 2.098, 'low': 0.013, 'aspp': 0.168, 'decoder': 0.268}
@@ -421,6 +426,67 @@ def timed_region(ts, steps, warmup, world, rank, barrier, max_over_ranks, contra
     return dt, modes, losses
 
 
+def dump_outputs(ts, path):
+    """What the timed step hands its caller after the LAST timed step, as float32 .npy files under `path` (32 MB in all): `loss` (the
+    step's mean cross-entropy over the exits), and the updated parameters (`params`) and the step's gradients (`grads`), both flattened in
+    model.parameters() order, logical NCHW element order, at the same DUMP_SAMPLE positions drawn with DUMP_SEED (a fixed sample: the
+    whole network is 11.4 M parameters, 45 MB per array)."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    params = torch.cat([p.detach().reshape(-1) for p in ts.params])
+    grads = torch.cat([ts.g.pgrad_views[p].reshape(-1) for p in ts.params])
+    n = params.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(DUMP_SAMPLE, n), replace=False))
+    idx = torch.from_numpy(idx).to(params.device)
+    np.save(os.path.join(path, 'loss.npy'), ts.loss.detach().float().cpu().numpy())
+    np.save(os.path.join(path, 'params.npy'), params[idx].float().cpu().numpy())
+    np.save(os.path.join(path, 'grads.npy'), grads[idx].float().cpu().numpy())
+
+
+def dominant_kernel_roofline(ts, math, default_cfg):
+    """Roofline of the dominant kernel: the heaviest dense-conv launch (decoder 3x3 304->256) on the halo-patch kernel, timed on its
+    own (time_launch)."""
+    convs = [m for m in ts.g.meta if m['kind'] == 'conv_fwd']
+    top = max(convs, key=lambda m: m['flops'])
+    tk = time_launch(top['cmd'])
+    halo = bool(top.get('halo'))
+    terms = {'fp32': 1, 'bf16x6': 6, 'f16x3': 3, 'tail_x3': 3}[math] if halo else 1          # (the dominant launch is a decoder conv: a tail launch)
+    if terms == 1:
+        peak, kern = PEAK_MFMA_F32_TFLOPS, ('conv3_kernel' if halo else 'conv_kernel') + ' (v_mfma_f32_16x16x4_f32)'
+        peak_note = 'fp32 matrix peak'
+    else:
+        peak = PEAK_MFMA_BF16_TFLOPS / terms
+        el = 'bf16' if terms == 6 else 'f16'
+        kern = 'conv3b_kernel (v_mfma_f32_32x32x16_%s, %d %s product terms per fp32 product)' % (el, terms, 'bf16' if terms == 6 else 'fp16')
+        peak_note = 'dense %s MFMA peak %.0f TFLOP/s / %d matrix instructions per fp32 multiply-add' % (el, PEAK_MFMA_BF16_TFLOPS, terms)
+    ach = top['flops'] / tk / 1e12
+    # HBM-side traffic of that launch: PMC passes cannot run inside this process; the committed rocprofv3 --pmc measurement of the
+    # same kernel and shape (FETCH_SIZE x2 on gfx950 + WRITE_SIZE, separate passes: scripts/pmc_traffic.sh) is quoted, labelled
+    traffic, tsrc = None, None
+    tname = 'pmc_traffic_decoder_conv3b_f16x3' if math == 'f16x3' else 'pmc_traffic_decoder_conv3b'
+    tpath = next((q for q in (os.path.join(ROOT, 'profiles', 'r0%d_%s.json' % (r, tname)) for r in (5, 4, 3, 2)) if os.path.exists(q)),
+                 os.path.join(ROOT, 'profiles', 'r02_pmc_traffic_decoder_conv3b.json'))
+    if halo and math in ('bf16x6', 'f16x3') and default_cfg and os.path.exists(tpath):
+        try:
+            traffic, tsrc = json.load(open(tpath)).get('traffic_bytes_per_launch'), 'profiles/%s (rocprofv3 --pmc passes of the same kernel and shape; not measured in this run)' % os.path.basename(tpath)
+        except Exception:
+            pass
+    roof = {'bound': 'mfma', 'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s', 'frac': ach / peak, 'traffic': traffic,
+            'traffic_source': tsrc,
+            'peak_note': peak_note, 'executed_matrix_TFLOPs': ach * terms, 'frac_of_fp32_matrix_peak': ach / PEAK_MFMA_F32_TFLOPS,
+            'kernel': kern, 'launch_ms': tk * 1e3,
+            'launch_shape_NHWCinCoutKSD': list(top['shape']), 'algorithmic_gflop_per_launch': top['flops'] / 1e9,
+            'algorithmic_bytes_per_launch': top['bytes']}
+    if terms > 1:
+        # what this part SUSTAINS on a register-resident v_mfma_f32_32x32x16_bf16 loop (no memory traffic, every SIMD busy): the shader
+        # clock drops from 2.4 to ~1.95-2.05 GHz under that load (s_memtime / s_memrealtime, scripts/mfma_clock_probe.hip) — reported
+        # beside `frac`, which stays priced against the nominal (spec) peak
+        roof['measured_sustained_matrix_TFLOPs'] = SUSTAINED_MFMA_BF16_TFLOPS
+        roof['frac_of_measured_sustained'] = ach * terms / SUSTAINED_MFMA_BF16_TFLOPS
+        roof['sustained_source'] = 'profiles/r03_mfma_clock_probe.txt (1.90-2.07 PFLOP/s at 1.95-2.05 GHz; operands toggling every iteration: 1.93)'
+    return roof
+
+
 def alt_math_step(mode, genotype, a, x, t, dev, steps=10):
     """Second value beside the headline (NOT the headline): the same step in another arithmetic of the wide contractions — `bf16x6`, the
     six-term split-bf16 form that was the default through round 5, beside today's `f16x3`."""
@@ -463,8 +529,12 @@ def main():
     ap.add_argument('--width', type=int, default=2048)
     ap.add_argument('--F', type=int, default=20)
     ap.add_argument('--genotype', default='autodeeplab/genotype', help="cell genotype under searched_arch/ (config 5: --F 40 --genotype 40_5e_38_lr/genotype_1)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the segment roofline / per-exit latency / drop-in measurements')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what lies beside the headline: dominant-kernel roofline, the extras child, the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (loss, sampled parameters and gradients) as float32 .npy files under DIR")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the segment roofline / per-exit latency / drop-in measurements')
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--math', choices=['fp32', 'f16x3', 'bf16x6', 'bf16x3', 'tail_x3'], default=None,
                     help='arithmetic of the wide k x k contractions (default: the library default, see addk.get_precision())')
@@ -472,6 +542,8 @@ def main():
     ap.add_argument('--extras-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--force-sync', action='store_true', help='rehearse the N>1 path (RCCL SyncBN + gradient all-reduce) at world_size 1')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     genotype = np.load(os.path.join(ROOT, 'searched_arch', a.genotype + '.npy'))
     if a.cpu_baseline_child:
         print(json.dumps(_cpu_baseline_child(genotype, a.batch, a.height, a.width)))
@@ -571,65 +643,27 @@ def main():
     loss = float(ts.loss.item())
     if comm is not None:
         comm.check()              # a timed-out mailbox exchange raises here (bounded polls: csrc/comm.hip), on every rank
+    if a.dump_outputs and rank == 0:
+        dump_outputs(ts, a.dump_outputs)
     if rank != 0:
         ts.close()
         torch.cuda.synchronize()
         parallel.disable_sync_bn()
         torch.distributed.destroy_process_group()
         return
-    ms = dt / a.steps * 1e3
-    value = world * n * a.steps / dt
 
-    # roofline of the dominant kernel: the heaviest dense-conv launch (decoder 3x3 304->256) on the halo-patch kernel
-    convs = [m for m in ts.g.meta if m['kind'] == 'conv_fwd']
-    top = max(convs, key=lambda m: m['flops'])
-    tk = time_launch(top['cmd'])
-    fwd_flops = sum(m['flops'] for m in convs)
-    halo = bool(top.get('halo'))
-    terms = {'fp32': 1, 'bf16x6': 6, 'f16x3': 3, 'tail_x3': 3}[math] if halo else 1          # (the dominant launch is a decoder conv: a tail launch)
-    if terms == 1:
-        peak, kern = PEAK_MFMA_F32_TFLOPS, ('conv3_kernel' if halo else 'conv_kernel') + ' (v_mfma_f32_16x16x4_f32)'
-        peak_note = 'fp32 matrix peak'
-    else:
-        peak = PEAK_MFMA_BF16_TFLOPS / terms
-        el = 'bf16' if terms == 6 else 'f16'
-        kern = 'conv3b_kernel (v_mfma_f32_32x32x16_%s, %d %s product terms per fp32 product)' % (el, terms, 'bf16' if terms == 6 else 'fp16')
-        peak_note = 'dense %s MFMA peak %.0f TFLOP/s / %d matrix instructions per fp32 multiply-add' % (el, PEAK_MFMA_BF16_TFLOPS, terms)
-    ach = top['flops'] / tk / 1e12
-    # HBM-side traffic of that launch: PMC passes cannot run inside this process; the committed rocprofv3 --pmc measurement of the
-    # same kernel and shape (FETCH_SIZE x2 on gfx950 + WRITE_SIZE, separate passes: scripts/refresh_profiles_r04.sh) is quoted, labelled
-    traffic, tsrc = None, None
-    tname = 'pmc_traffic_decoder_conv3b_f16x3' if math == 'f16x3' else 'pmc_traffic_decoder_conv3b'
-    tpath = next((q for q in (os.path.join(ROOT, 'profiles', 'r0%d_%s.json' % (r, tname)) for r in (5, 4, 3, 2)) if os.path.exists(q)),
-                 os.path.join(ROOT, 'profiles', 'r02_pmc_traffic_decoder_conv3b.json'))
-    if halo and math in ('bf16x6', 'f16x3') and (n, h, w, a.F, a.genotype) == (2, 1024, 2048, 20, 'autodeeplab/genotype') and os.path.exists(tpath):
-        try:
-            traffic, tsrc = json.load(open(tpath)).get('traffic_bytes_per_launch'), 'profiles/%s (rocprofv3 --pmc passes of the same kernel and shape; not measured in this run)' % os.path.basename(tpath)
-        except Exception:
-            pass
-    roof = {'bound': 'mfma', 'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s', 'frac': ach / peak, 'traffic': traffic,
-            'traffic_source': tsrc,
-            'peak_note': peak_note, 'executed_matrix_TFLOPs': ach * terms, 'frac_of_fp32_matrix_peak': ach / PEAK_MFMA_F32_TFLOPS,
-            'kernel': kern, 'launch_ms': tk * 1e3,
-            'launch_shape_NHWCinCoutKSD': list(top['shape']), 'algorithmic_gflop_per_launch': top['flops'] / 1e9,
-            'algorithmic_bytes_per_launch': top['bytes']}
-    if terms > 1:
-        # what this part SUSTAINS on a register-resident v_mfma_f32_32x32x16_bf16 loop (no memory traffic, every SIMD busy): the shader
-        # clock drops from 2.4 to ~1.95-2.05 GHz under that load (s_memtime / s_memrealtime, scripts/mfma_clock_probe.hip) — reported
-        # beside `frac`, which stays priced against the guide's nominal peak
-        roof['measured_sustained_matrix_TFLOPs'] = SUSTAINED_MFMA_BF16_TFLOPS
-        roof['frac_of_measured_sustained'] = ach * terms / SUSTAINED_MFMA_BF16_TFLOPS
-        roof['sustained_source'] = 'profiles/r03_mfma_clock_probe.txt (1.90-2.07 PFLOP/s at 1.95-2.05 GHz; operands toggling every iteration: 1.93)'
+    fwd_flops = sum(m['flops'] for m in ts.g.meta if m['kind'] == 'conv_fwd')
     step_tflops = 3 * fwd_flops / (dt / a.steps) / 1e12
     out = contract_line(dt, ts.graph is not None and ts.use_graph)
     out.update({'ms_per_step_by_mode': modes,
            'loss': loss, 'first_step_losses': losses,
            'step_algorithmic_tflop': 3 * fwd_flops / 1e12,
            'step_tflops_per_gpu': step_tflops, 'step_frac_mfma': step_tflops / PEAK_MFMA_F32_TFLOPS,
-           'plan_device_gb': ts.nbytes / 1e9,
-           'roofline': roof})
+           'plan_device_gb': ts.nbytes / 1e9})
     default_cfg = (n, h, w, a.F, a.genotype) == (2, 1024, 2048, 20, 'autodeeplab/genotype')
-    extras = world == 1 and not a.no_extras and comm is None and default_cfg
+    if a.full:
+        out['roofline'] = roof = dominant_kernel_roofline(ts, math, default_cfg)
+    extras = a.full and world == 1 and not a.no_extras and comm is None and default_cfg
     if extras:
         # Segment roofline, per-exit latency, the drop-in path and the N > 1 code path at world 1 run in a CHILD process: they capture
         # hipGraphs of their own, start RCCL and replay captured collectives — one run in ~30 of round 3's bench ended without its JSON line
@@ -676,7 +710,7 @@ def main():
         if isinstance(merged.get('bf16x6'), dict) and 'ms_per_step' in merged['bf16x6']:
             out['ms_per_step_by_mode']['bf16x6'] = merged['bf16x6']['ms_per_step']          # a second value; `value` / `dtype` are the f16x3 ones
             out['bf16x6'] = merged['bf16x6']
-    if not a.no_cpu_baseline and world == 1 and default_cfg:
+    if a.full and not a.no_cpu_baseline and world == 1 and default_cfg:
         cb = cpu_baseline(n, h, w)
         out['cpu_baseline'] = cb
         if cb.get('dynamic_inference_cpu') and 'per_exit_ms' in out:

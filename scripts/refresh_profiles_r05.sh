@@ -5,10 +5,10 @@
 #   SQ counters + HBM-side traffic of the dominant kernel on the stand-alone harness, the inference forward trace.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05; rm -rf $O; mkdir -p $O
-timeout -k 10 700 python3 bench.py --steps 20 --warmup 3 > $O/bench_f16x3.json 2> $O/bench_f16x3.err || { tail -5 $O/bench_f16x3.err; exit 1; }
+timeout -k 10 700 python3 bench.py --full --steps 20 --warmup 3 > $O/bench_f16x3.json 2> $O/bench_f16x3.err || { tail -5 $O/bench_f16x3.err; exit 1; }
 echo "bench default done: $(python3 -c "import json;d=json.load(open('$O/bench_f16x3.json'));print(d['ms_per_step'], d['value'])")"
 for m in fp32 bf16x6 tail_x3; do
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --math $m > $O/bench_$m.json 2> /dev/null
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --math $m > $O/bench_$m.json 2> /dev/null
   echo "bench $m: $(python3 -c "import json;d=json.load(open('$O/bench_$m.json'));print(d['ms_per_step'], d['roofline']['launch_ms'], d['roofline']['frac'])")"
 done
 timeout -k 10 400 python3 bench.py --F 40 --genotype 40_5e_38_lr/genotype_1 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_config5_F40_genotype1.json 2> /dev/null
