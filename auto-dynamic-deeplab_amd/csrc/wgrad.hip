@@ -6,7 +6,8 @@
 // order [pixel][channel]; MFMA fragments are read with ds_read_b32, rows padded so that the two pixel
 // rows a 32-lane group touches fall on disjoint banks).  Wave partials are combined through LDS in a
 // fixed order and the per-slice tiles go to a workspace that addk reduces deterministically into dW.
-#include <stdlib.h>
+#include <string.h>
+#include <vector>
 #include "common.h"
 
 namespace {
@@ -1100,8 +1101,6 @@ __global__ void __launch_bounds__(256, 2) wgrad_h1b_kernel(const WgK pv, const W
 }
 constexpr size_t wg_h1b_lds(int np) { return (size_t)np * ((128 / 16) + H1_TP) * (H3_KP * 32 + 32) + 64; }      // + the waves' maxima (NP = 2)
 
-inline bool wgrad_split_narrow() { return addk_env("ADDK_WGRAD_SPLIT_NARROW", 1) != 0; }
-inline bool wgrad_split_enabled() { return addk_env("ADDK_WGRAD_SPLIT", 1) != 0; }
 constexpr size_t wg_h3b_lds(int nt, int np, int ng) { return (size_t)np * ((64 * nt / 16) * (H3_KP * 32 + 32) + ng * (3 * 104 * 32 + (ng > 1 ? 64 : 0))) + 64; }      // + the waves' maxima (NP = 2)
 
 // Halo-patch weight gradient of the cells' dense dilated convolutions (dil_conv_3x3 / dil_conv_5x5: 40/80/160 channels,
@@ -1888,40 +1887,51 @@ int pick_ctz(int C) {
   for (int k = 0; k < 4; ++k) { long cols = (long)cdiv(C, 16 * cands[k]) * 16 * cands[k]; if (bc < 0 || cols < bc) { bc = cols; best = cands[k]; } }
   return best;
 }
-// 0: pixel-split kernel; 1: output-split 128x64 (wide heads); 2: output-split 96x96 (80-channel cells);
-// 3: output-split 64x64 (64-channel stem); 4: output-split 128x128 (wide heads with >= 128 input channels)
+// The weight-gradient kernels.  The numbers are what addk_conv_wgrad_config returns in cfg[0] and a batch in meta[0].
+enum WgKind : int {
+  WG_PIX = 0,         // pixel-split kernel (wgrad_kernel)
+  WG_OS_128x64 = 1,   // output-split 128x64 (wide heads)
+  WG_OS_96x96 = 2,    // output-split 96x96 (80-channel cells)
+  WG_OS_64x64 = 3,    // output-split 64x64 (64-channel stem)
+  WG_H3 = 5,          // halo-patch kernel (3x3, stride 1, 'same' padding, wide): (64*NT co) x (16*NG c) tiles, the nine taps in the block
+  WG_RS = 6,          // register-streaming kernel for the narrow cell convolutions
+  WG_HK = 7,          // halo-patch kernel with the taps split across waves (the cells' dilated 3x3 / 5x5 convolutions)
+  WG_ST = 8,          // few input channels (stem0): all taps x channels in two column tiles of one workgroup
+  WG_H1 = 9,          // the split-precision halo-patch arithmetic for the wide 1x1 heads (wgrad_h1b_kernel)
+};
 int os_kind(int Cout, int C) {
-  if (Cout >= 128 && Cout % 128 == 0 && C >= 48) return 1;
-  if (Cout > 64 && Cout <= 96 && C > 64 && C <= 96) return 2;
-  if (Cout > 48 && Cout <= 64 && C > 48 && C <= 64) return 3;
-  return 0;
+  if (Cout >= 128 && Cout % 128 == 0 && C >= 48) return WG_OS_128x64;
+  if (Cout > 64 && Cout <= 96 && C > 64 && C <= 96) return WG_OS_96x96;
+  if (Cout > 48 && Cout <= 64 && C > 48 && C <= 64) return WG_OS_64x64;
+  return WG_PIX;
 }
 void pick_tiles(int Cout, int C, int* cty, int* ctz) {
   *cty = pick_cty(Cout); *ctz = pick_ctz(C);
   if (*cty == 8 && *ctz == 5) *ctz = 4;   // 8x5 accumulator tiles would not leave room for the staging registers
   switch (os_kind(Cout, C)) {
-    case 1: *cty = 8; *ctz = 4; break;
-    case 4: *cty = 8; *ctz = 8; break;
-    case 2: *cty = 6; *ctz = 6; break;
-    case 3: *cty = 4; *ctz = 4; break;
+    case WG_OS_128x64: *cty = 8; *ctz = 4; break;
+    case WG_OS_96x96: *cty = 6; *ctz = 6; break;
+    case WG_OS_64x64: *cty = 4; *ctz = 4; break;
     default: break;
   }
 }
-bool use_output_split(int Cout, int C) { return os_kind(Cout, C) != 0; }
-// 5: halo-patch kernel (3x3, stride 1, 'same' padding, wide): tiles are (64*NT co) x (16 c), the nine taps live in the block
+// blocks of one pixel slice of the pixel-split geometry (kinds 0-3)
+inline int pix_tiles(int Cout, int C, int taps) { int cty, ctz; pick_tiles(Cout, C, &cty, &ctz); return cdiv(Cout, 16 * cty) * taps * cdiv(C, 16 * ctz); }
+// terms of the split-precision weight-gradient kernels in precision mode `mode` for cty output-channel tiles per workgroup (0: the fp32
+// kernels); tail_x3 (mode 3): the 128-channel blocks are the exit heads (decoder, ASPP) -> three terms; stem1's 64-channel blocks and the
+// cells' convs keep six
+inline int wg_np_of(int cty, int mode) { return mode == 2 ? 3 : mode == 1 ? 2 : mode == 3 ? (cty == 8 ? 2 : 3) : 0; }
 bool h3_ok(const addk_conv_wgrad_args* a) {
   return (addk_get_fast_paths() & ADDK_FAST_WGRAD3) && a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == a->dil && a->dil >= 1 && a->dil <= 18 &&
          a->OH == a->H && a->OW == a->W && a->W >= 64 && a->Cout % 64 == 0 && a->src.C >= 16 &&
          aligned16(a->dy) && a->lddy % 4 == 0 && src_vec_ok(a->src) && (long)a->N * a->H * a->W >= 8192;
 }
-// 9: the split-bf16 halo-patch arithmetic for the wide 1x1 heads (wgrad_h1b_kernel), when the split kernels are in use
-inline bool h3b_runs(int cty);
-bool h1_ok(const addk_conv_wgrad_args* a) {
+// kind 9 runs in the split-precision modes only
+bool h1_ok(const addk_conv_wgrad_args* a, int mode) {
   return (addk_get_fast_paths() & ADDK_FAST_WGRAD3) && a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0 && a->OH == a->H && a->OW == a->W &&
          a->W >= 64 && a->Cout % 128 == 0 && a->src.C >= 64 && a->src.C % 4 == 0 && aligned16(a->dy) && a->lddy % 4 == 0 && src_vec_ok(a->src) &&
-         (!a->src.a || (aligned16(a->src.a) && aligned16(a->src.b))) && (long)a->N * a->H * a->W >= 8192 && h3b_runs(8);
+         (!a->src.a || (aligned16(a->src.a) && aligned16(a->src.b))) && (long)a->N * a->H * a->W >= 8192 && wg_np_of(8, mode);
 }
-// 6: register-streaming kernel for the narrow cell convolutions
 bool rs_ok(const addk_conv_wgrad_args* a) {
   return (addk_get_fast_paths() & ADDK_FAST_WGRAD_RS) && a->Cout <= 160 && a->Cout >= 16 && a->src.C >= 16 && a->KH * a->KW <= 25 &&
          aligned16(a->dy) && a->lddy % 4 == 0 && a->Cout % 4 == 0 && src_vec_ok(a->src) && (long)a->N * a->OH * a->OW >= 4096;
@@ -1935,8 +1945,7 @@ inline int rs_tile(int Cn) {
   const int nt = cdiv(Cn, RS_T); return cdiv(cdiv(Cn, nt), 4) * 4;
 }
 inline int rs_lay(int tile) { return tile <= 48 ? 3 : 4; }
-// 7: halo-patch kernel with the taps split across waves (the cells' dilated 3x3 / 5x5 convolutions)
-// output-channel tiles per block: 3 for the 5x5 (7 taps per wave -> 21 accumulator tiles), up to 5 for the 3x3 (3 taps per wave)
+// output-channel tiles per block of kind 7: 3 for the 5x5 (7 taps per wave -> 21 accumulator tiles), up to 5 for the 3x3 (3 taps per wave)
 inline int hk_ct(int Cout, int ks) { return (ks == 5 || Cout <= 48) ? 3 : 5; }
 inline int hk_tiles(int Cout, int C, int ks) { return cdiv(Cout, 16 * hk_ct(Cout, ks)) * cdiv(C, 16); }
 bool hk_ok(const addk_conv_wgrad_args* a) {
@@ -1945,37 +1954,55 @@ bool hk_ok(const addk_conv_wgrad_args* a) {
          a->Cout >= 32 && a->Cout <= 160 && a->Cout % 4 == 0 && a->src.C >= 16 && a->OW >= 32 &&
          aligned16(a->dy) && a->lddy % 4 == 0 && src_vec_ok(a->src) && (long)a->N * a->H * a->W >= 4096;
 }
-// 8: few input channels (stem0), all taps x channels in two column tiles of one workgroup (wgrad_st_kernel)
 bool st_ok(const addk_conv_wgrad_args* a) {
   return (addk_get_fast_paths() & ADDK_FAST_WGRAD_RS) && a->src.C <= 4 && a->KH * a->KW * a->src.C <= 32 && a->Cout <= 64 && a->Cout % 4 == 0 &&
          aligned16(a->dy) && a->lddy % 4 == 0 && (long)a->N * a->OH * a->OW >= 65536;
 }
-int kind_of(const addk_conv_wgrad_args* a) { return st_ok(a) ? 8 : h3_ok(a) ? 5 : h1_ok(a) ? 9 : hk_ok(a) ? 7 : rs_ok(a) ? 6 : os_kind(a->Cout, a->src.C); }
-// Halo-patch scheduling.  A block runs `steps` row segments; blocks are dispatched in grid order as CU slots free up
-// (2 resident blocks per CU at NT=2, 3 at NT=1), so what matters is that the LAST round of blocks is nearly full:
-// pick the segment count per block that minimises  ceil(blocks / slots) * (steps + start-up)  over the whole launch.
-struct H3Op { int tiles; long nseg; };
-// precision of the split-bf16 weight-gradient kernels for a launch of cty output-channel tiles per workgroup (0: fp32 kernels); tail_x3 (mode 3): the
-// 128-channel blocks are the exit heads (decoder, ASPP) -> three terms; stem1's 64-channel blocks keep six
-inline int wg_np_of(int cty) { const int m = addk_get_conv_precision(); return m == 2 ? 3 : m == 1 ? 2 : m == 3 ? (cty == 8 ? 2 : 3) : 0; }
-inline bool h3b_runs(int cty) { return wg_np_of(cty) && wgrad_split_enabled() && (cty == 8 || wgrad_split_narrow()); }
-// input-channel tiles per workgroup of the 3x3 halo-patch kernel: 2 (512 threads sharing one staged dy tile) on the split-bf16 kernel when the channels fill
+constexpr int ST_MAX_SPLITS = 1024;      // kind 8 slices the pixels only, into at most this many 1024-pixel slices
+// input-channel tiles per workgroup of kind 5: 2 (512 threads sharing one staged dy tile) on the split-precision kernel when the channels fill
 // whole pairs of tiles (a half-empty pair costs what the shared dy saves: 304 and 400 channels measured equal, 256 -7 %, stem1's 64 -> 64 -14 %)
-inline int h3_ng(int Cout, int C) {
+inline int h3_ng(int Cout, int C, int mode) {
   // (re-measured with the split-fp16 arithmetic: the shared dy tile still wins, 2.2 vs 2.38 ms per step: profiles/r05_wgrad_h3b_f16_pipelined.txt)
-  return (C % 32 == 0 && h3b_runs(Cout % 128 == 0 ? 8 : 4)) ? 2 : 1;
+  return (C % 32 == 0 && wg_np_of(Cout % 128 == 0 ? 8 : 4, mode)) ? 2 : 1;
 }
 inline int h3_tiles(int Cout, int C) { const int nt = Cout % 128 == 0 ? 2 : 1; return (Cout / (64 * nt)) * cdiv(C, 16); }
 // at most 32 workspace slices, or as many as it takes for the op alone to offer one block per slot (few-tile convs: stem1)
 inline int h3_max_splits(int tiles) { const int s = cdiv(768, tiles); return s > 32 ? s : 32; }
-inline int h3_splits(long nseg, int steps, int tiles, int cap_tiles = 0) {      // cap_tiles: the tile count the workspace was sized with
+// `budget` = workgroups this conv should contribute.  A lone launch needs ~1536 of them to fill the chip even if that
+// leaves a block a single 64-pixel step; inside a batch the other convs provide the parallelism, so each block gets
+// >= 8 steps and the per-block epilogue (cross-wave combine + partial tile written to the workspace) is amortised.
+int pick_splits(long P, int tiles, int budget = 1536, int min_steps = 1) {
+  long maxs = cdiv(P, (long)min_steps * KP);
+  long want = cdiv(budget, tiles);
+  long s = want < maxs ? want : maxs;
+  if (s < 1) s = 1;
+  if (s > 1024) s = 1024;
+  return (int)s;
+}
+
+// Everything decided for one weight gradient: the kernel, its geometry and how its pixel range is cut into slices.
+struct WgChoice {
+  int kind;             // WgKind
+  int cty, ctz;         // with kind and the precision mode, the variant (wg_variant): kinds 0-3: 16-channel output / input tiles per block;
+                        // 5: 4*NT and NG; 6: the lane layouts of dy and the activation; 7: CT and KS; 8: 4, 2; 9: 8, 4
+  int nyt, nzt, tiles;  // output- / input-channel tiles and the blocks of one slice (times the taps for kinds 0-3 and 6)
+  int vecY, vecZ;       // the descriptor's 16-byte load flags; kind 6: the operands' tile strides
+  long nseg;            // kinds 5, 7, 9: the pixels are cut as 64-pixel row segments, a step count per block for the batch (h3_pick_steps)
+  int slots;            //   resident blocks of the launch the step count is picked for
+  int px_chunk;         // kinds 6, 8: the pixels are cut into slices of about this many (kinds 0-3: pick_splits' budget)
+  int cap;              // kinds 5-9: the most slices, what addk_conv_wgrad_ws has sized the workspace for
+};
+// Halo-patch scheduling.  A block runs `steps` row segments; blocks are dispatched in grid order as CU slots free up
+// (2 resident blocks per CU at NT=2, 3 at NT=1), so what matters is that the LAST round of blocks is nearly full:
+// pick the segment count per block that minimises  ceil(blocks / slots) * (steps + start-up)  over the whole launch.
+inline int h3_splits(long nseg, int steps, int tiles) {
   int sp = cdiv(nseg, steps);
-  const int cap = h3_max_splits(cap_tiles ? cap_tiles : tiles);
+  const int cap = h3_max_splits(tiles);
   if (sp > cap) sp = cap;
   return cdiv(nseg, cdiv(nseg, sp));
 }
-int h3_pick_steps(const H3Op* ops, int n, int nt, int ng = 1) {
-  const long slots = ng == 2 ? 256 : nt == 2 ? 512 : 768;
+int h3_pick_steps(const WgChoice* ops, int n) {
+  const long slots = ops[0].slots;
   int best = 64; double best_cost = -1.0;
   for (int steps = 8; steps <= 256; ++steps) {
     long blocks = 0; long longest = 0;
@@ -1990,18 +2017,115 @@ int h3_pick_steps(const H3Op* ops, int n, int nt, int ng = 1) {
   }
   return best;
 }
-// `budget` = workgroups this conv should contribute.  A lone launch needs ~1536 of them to fill the chip even if that
-// leaves a block a single 64-pixel step; inside a batch the other convs provide the parallelism, so each block gets
-// >= 8 steps and the per-block epilogue (cross-wave combine + partial tile written to the workspace) is amortised.
-int pick_splits(long P, int tiles, int budget = 1536, int min_steps = 1) {
-  long maxs = cdiv(P, (long)min_steps * KP);
-  long want = cdiv(budget, tiles);
-  long s = want < maxs ? want : maxs;
-  if (s < 1) s = 1;
-  if (s > 1024) s = 1024;
-  return (int)s;
+
+int wg_choose(const addk_conv_wgrad_args* a, int mode, WgChoice& c) {
+  ADDK_REQUIRE(a && a->dy && a->src.x && a->dw, "conv_wgrad: null pointer");
+  ADDK_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0 && a->Cout > 0 && a->src.C > 0, "conv_wgrad: empty shape");
+  ADDK_REQUIRE(a->lddy >= a->Cout && a->src.ld >= a->src.C, "conv_wgrad: short stride");
+  ADDK_REQUIRE(a->w_choff + a->src.C <= a->cin_total && a->ldw >= a->KH * a->KW * a->cin_total, "conv_wgrad: weight layout");
+  ADDK_REQUIRE((a->src.a == nullptr) == (a->src.b == nullptr), "conv_wgrad: a/b must come together");
+  ADDK_REQUIRE((long)a->N * a->OH * a->OW < (1L << 30) && (long)a->N * a->H * a->W < (1L << 30), "conv_wgrad: tensor too large for 32-bit pixel indexing");
+  const int Cout = a->Cout, C = a->src.C, taps = a->KH * a->KW;
+  const long P = (long)a->N * a->OH * a->OW, nseg = (long)a->N * a->OH * cdiv(a->OW, H3_KP);
+  c = WgChoice{};
+  c.kind = os_kind(Cout, C);
+  pick_tiles(Cout, C, &c.cty, &c.ctz);
+  c.nyt = cdiv(Cout, 16 * c.cty); c.nzt = cdiv(C, 16 * c.ctz); c.tiles = c.nyt * taps * c.nzt;
+  c.vecY = aligned16(a->dy) && a->lddy % 4 == 0 && Cout % 4 == 0; c.vecZ = src_vec_ok(a->src);
+  const int pix_cap = pick_splits(P, c.tiles);      // the slices of a lone pixel-split launch: every workspace holds them
+  if (st_ok(a)) {
+    c.kind = WG_ST; c.cty = 4; c.ctz = 2; c.nyt = c.nzt = c.tiles = 1;
+    c.px_chunk = 1024; c.cap = ST_MAX_SPLITS;
+  } else if (h3_ok(a)) {
+    const int nt = Cout % 128 == 0 ? 2 : 1, ng = h3_ng(Cout, C, mode);
+    c.kind = WG_H3; c.cty = 4 * nt; c.ctz = ng; c.nyt = Cout / (64 * nt); c.nzt = cdiv(C, 16 * ng);
+    c.nseg = nseg; c.slots = ng == 2 ? 256 : nt == 2 ? 512 : 768; c.cap = h3_max_splits(h3_tiles(Cout, C));
+  } else if (h1_ok(a, mode)) {      // 128 output x 64 input channels per workgroup
+    c.kind = WG_H1; c.cty = 8; c.ctz = 4; c.nyt = Cout / 128; c.nzt = cdiv(C, 16 * H1_TP);
+    c.nseg = nseg; c.slots = 512; c.cap = pix_cap;
+  } else if (hk_ok(a)) {
+    const int ct = hk_ct(Cout, a->KH);
+    c.kind = WG_HK; c.cty = ct; c.ctz = a->KH; c.nyt = cdiv(Cout, 16 * ct); c.nzt = cdiv(C, 16);
+    c.nseg = nseg; c.slots = ct == 3 ? 768 : 512; c.cap = h3_max_splits(c.nyt * c.nzt);
+  } else if (rs_ok(a)) {      // <= 64-channel tiles, 2048-pixel slices (128 k-steps per wave)
+    c.kind = WG_RS; c.vecY = rs_tile(Cout); c.vecZ = rs_tile(C); c.cty = rs_lay(c.vecY); c.ctz = rs_lay(c.vecZ);
+    c.nyt = cdiv(Cout, c.vecY); c.nzt = cdiv(C, c.vecZ); c.tiles = c.nyt * taps * c.nzt;
+    c.px_chunk = 2048; c.cap = pix_cap;
+  }
+  if (c.nseg) c.tiles = c.nyt * c.nzt;
+  return 0;
 }
 
+// The kernel of a launch key (kind, cty, ctz) in precision mode `mode`.
+typedef void (*WgFn)(const WgK, const WgK*, const int4*);
+struct WgVariant { WgFn fn; unsigned threads; size_t lds; };
+constexpr int WG_MAX_DYN_LDS = 160 * 1024 - 64;      // dynamic LDS the split-precision kernels may ask for
+template <WgFn F> WgVariant wg_dyn_lds(unsigned threads, size_t lds) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(F), hipFuncAttributeMaxDynamicSharedMemorySize, WG_MAX_DYN_LDS);
+  (void)attr;
+  return {F, threads, lds};
+}
+template <int Y, bool B> WgFn wg_pix(int ctz) {
+  switch (ctz) {
+    case 1: return wgrad_kernel<Y, 1, B>;
+    case 3: return wgrad_kernel<Y, 3, B>;
+    case 4: return wgrad_kernel<Y, 4, B>;
+    case 5: if constexpr (Y != 8) return wgrad_kernel<Y, 5, B>; else return nullptr;
+    default: return nullptr;
+  }
+}
+template <int NT, int NG, bool B> WgVariant wg_h3b(int np) {
+  return np == 3 ? wg_dyn_lds<wgrad_h3b_kernel<NT, B, 3, NG>>(256 * NG, wg_h3b_lds(NT, 3, NG))
+                 : wg_dyn_lds<wgrad_h3b_kernel<NT, B, 2, NG>>(256 * NG, wg_h3b_lds(NT, 2, NG));
+}
+template <int KS, int CT, bool B> WgVariant wg_hk(int np) {
+  if (!np) return {wgrad_hk_kernel<KS, CT, B>, 256, 0};
+  return np == 3 ? wg_dyn_lds<wgrad_hkb_kernel<KS, CT, B, 3>>(256, wg_hkb_lds(KS, CT, 3))
+                 : wg_dyn_lds<wgrad_hkb_kernel<KS, CT, B, 2>>(256, wg_hkb_lds(KS, CT, 2));
+}
+// f16x3 (mode 1): the narrow cell convs' weight gradients on the fp16 matrix pipe too (ABAB: step 29.57 -> 29.2 ms)
+template <int LA, int LB, bool B> WgFn wg_rs(int mode) { return mode == 1 ? wgrad_rs_kernel<LA, LB, B, true> : wgrad_rs_kernel<LA, LB, B>; }
+// In the split-precision modes kinds 5, 7 and 9 run the split kernels (wgrad_h3b / hkb / h1b: stem1 0.76 -> 0.61 ms alone).  A batch is
+// replayed in the mode current at run time: the geometries only the split kernels have (kind 9, kind 5 with NG = 2) fail in fp32.
+template <bool B> int wg_variant(int kind, int cty, int ctz, int mode, WgVariant& v) {
+  const int np = wg_np_of(cty, mode);
+  v = {nullptr, 256, 0};
+  if ((kind == WG_H1 || (kind == WG_H3 && ctz == 2)) && !np) {
+    addk_set_error("conv_wgrad: launch prepared for the split-precision kernel, but the precision mode changed since");
+    return ADDK_ERR_INVALID;
+  }
+  switch (kind) {
+    case WG_PIX:
+      v.fn = cty == 2 ? wg_pix<2, B>(ctz) : cty == 3 ? wg_pix<3, B>(ctz) : cty == 4 ? wg_pix<4, B>(ctz) : cty == 5 ? wg_pix<5, B>(ctz) : cty == 8 ? wg_pix<8, B>(ctz) : nullptr;
+      break;
+    case WG_OS_128x64: v.fn = wgrad_os_kernel<4, 2, B>; break;
+    case WG_OS_96x96: v.fn = wgrad_os_kernel<3, 3, B>; break;
+    case WG_OS_64x64: v.fn = wgrad_os_kernel<2, 2, B>; break;
+    case WG_H3:
+      if (cty != 4 && cty != 8) break;
+      if (!np) v.fn = cty == 8 ? wgrad_h3_kernel<2, B> : wgrad_h3_kernel<1, B>;
+      else if (cty == 8) v = ctz == 2 ? wg_h3b<2, 2, B>(np) : wg_h3b<2, 1, B>(np);
+      else v = ctz == 2 ? wg_h3b<1, 2, B>(np) : wg_h3b<1, 1, B>(np);
+      break;
+    case WG_RS:
+      if ((cty == 3 || cty == 4) && (ctz == 3 || ctz == 4))
+        v.fn = cty == 3 ? (ctz == 3 ? wg_rs<3, 3, B>(mode) : wg_rs<3, 4, B>(mode)) : (ctz == 3 ? wg_rs<4, 3, B>(mode) : wg_rs<4, 4, B>(mode));
+      break;
+    case WG_HK:
+      if (ctz == 3 && cty == 3) v = wg_hk<3, 3, B>(np);
+      else if (ctz == 3 && cty == 5) v = wg_hk<3, 5, B>(np);
+      else if (ctz == 5 && cty == 3) v = wg_hk<5, 3, B>(np);
+      break;
+    case WG_ST: v.fn = wgrad_st_kernel<B>; break;
+    case WG_H1: v = np == 3 ? wg_dyn_lds<wgrad_h1b_kernel<B, 3>>(256, wg_h1b_lds(3)) : wg_dyn_lds<wgrad_h1b_kernel<B, 2>>(256, wg_h1b_lds(2)); break;
+    default: break;
+  }
+  if (!v.fn) { addk_set_error("conv_wgrad: no tile config"); return ADDK_ERR_UNSUPPORTED; }
+  return 0;
+}
+
+// the workspace slices of a conv are summed by one wave per 64 weights when there are many of them, else by one block per 256
+inline bool wg_wave_reduce(int splits, long n) { return splits > 16 && n <= 65536; }
 }  // namespace
 
 #ifdef ADDK_WG_DIAG
@@ -2020,203 +2144,65 @@ extern "C" int addk_wg_diag(unsigned long long* out8) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_wg_diag), h, sizeof h) == hipSuccess ? ADDK_OK : ADDK_ERR_INVALID;
 }
 #endif
+// The workspace bound, from the P / Cout / C / taps of a conv: the most slices of any kind its shape may get (the kinds' predicates
+// need the full arguments; these are the shape parts of them, widened).  Plans size their buffers with it.
 extern "C" int64_t addk_conv_wgrad_ws(int64_t P, int32_t Cout, int32_t C, int32_t taps) {
-  int cty, ctz; pick_tiles(Cout, C, &cty, &ctz);
-  int tiles = cdiv(Cout, 16 * cty) * taps * cdiv(C, 16 * ctz);
-  int splits = pick_splits(P, tiles);
-  if ((taps == 9 || taps == 25) && Cout >= 32 && Cout <= 160 && C >= 16) {      // cells' dilated convs: wgrad_hk_kernel
-    const int hs = h3_max_splits(hk_tiles(Cout, C, taps == 9 ? 3 : 5));
-    if (hs > splits) splits = hs;
-  }
-  if (taps == 9 && Cout % 64 == 0 && C >= 16) {      // the halo-patch kernel may be chosen
-    const int hs = h3_max_splits(h3_tiles(Cout, C));
-    if (hs > splits) splits = hs;
-  }
-  if (C <= 4 && taps * C <= 32 && Cout <= 64 && splits < 1024) splits = 1024;      // few input channels: wgrad_st_kernel slices the pixels only (st_ok)
+  int splits = pick_splits(P, pix_tiles(Cout, C, taps));      // kinds 0-3, and the cap of kinds 6 and 9
+  auto at_least = [&](int s) { if (s > splits) splits = s; };
+  if ((taps == 9 || taps == 25) && Cout >= 32 && Cout <= 160 && C >= 16) at_least(h3_max_splits(hk_tiles(Cout, C, taps == 9 ? 3 : 5)));   // kind 7
+  if (taps == 9 && Cout % 64 == 0 && C >= 16) at_least(h3_max_splits(h3_tiles(Cout, C)));                                              // kind 5
+  if (C <= 4 && taps * C <= 32 && Cout <= 64) at_least(ST_MAX_SPLITS);                                                                // kind 8
   return (int64_t)splits * Cout * taps * C;
 }
 
-static int wg_fill(const addk_conv_wgrad_args* a, WgK& k, int& cty, int& ctz, int& tiles, bool check_ws, int budget = 1536, int min_steps = 1, int h3_steps = 0) {
-  ADDK_REQUIRE(a && a->dy && a->src.x && a->dw && (a->ws || !check_ws), "conv_wgrad: null pointer");
-  ADDK_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0 && a->Cout > 0 && a->src.C > 0, "conv_wgrad: empty shape");
-  ADDK_REQUIRE(a->lddy >= a->Cout && a->src.ld >= a->src.C, "conv_wgrad: short stride");
-  ADDK_REQUIRE(a->w_choff + a->src.C <= a->cin_total && a->ldw >= a->KH * a->KW * a->cin_total, "conv_wgrad: weight layout");
-  ADDK_REQUIRE((a->src.a == nullptr) == (a->src.b == nullptr), "conv_wgrad: a/b must come together");
+// The descriptor of a weight gradient from its choice, with the pixel range cut into slices.  In a batch, `budget` and `min_steps` (kinds
+// 0-3) and `h3_steps` (kinds 5, 7, 9: one step count for the whole batch) come from the batch.
+static int wg_fill(const addk_conv_wgrad_args* a, const WgChoice& c, WgK& k, bool check_ws, int budget = 1536, int min_steps = 1, int h3_steps = 0) {
   k.dy = a->dy; k.lddy = a->lddy; k.Cout = a->Cout;
   k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
   k.KH = a->KH; k.KW = a->KW; k.stride = a->stride; k.pad = a->pad; k.dil = a->dil;
   k.src = a->src; k.ws = a->ws;
-  pick_tiles(a->Cout, a->src.C, &cty, &ctz);
-  k.taps = a->KH * a->KW; k.nyt = cdiv(a->Cout, 16 * cty); k.nzt = cdiv(a->src.C, 16 * ctz);
-  ADDK_REQUIRE((long)a->N * a->OH * a->OW < (1L << 30) && (long)a->N * a->H * a->W < (1L << 30), "conv_wgrad: tensor too large for 32-bit pixel indexing");
+  k.taps = a->KH * a->KW; k.nyt = c.nyt; k.nzt = c.nzt;
   k.P = a->N * a->OH * a->OW;
-  tiles = k.nyt * k.taps * k.nzt;
-  k.splits = pick_splits(k.P, tiles, budget, min_steps);
-  ADDK_REQUIRE(!check_ws || kind_of(a) == 5 || kind_of(a) == 7 || a->ws_floats >= (int64_t)k.splits * a->Cout * k.taps * a->src.C, "conv_wgrad: workspace too small");
-  k.chunkP = cdiv(cdiv(k.P, k.splits), KP) * KP;
-  const int kd = kind_of(a);      // ONE decision for geometry and launch: a shape several kernels accept (1x1, Cout = 128: h1 and rs) must not get the geometry of one and the launch of another
-  if (kd == 5) {      // halo-patch kernel: pixel range in 64-pixel row segments, never more slices than the workspace bound
-    const int nt = a->Cout % 128 == 0 ? 2 : 1, ng = h3_ng(a->Cout, a->src.C);
-    cty = 4 * nt; ctz = ng;
-    k.nyt = a->Cout / (64 * nt); k.nzt = cdiv(a->src.C, 16 * ng);
-    tiles = k.nyt * k.nzt;
-    const long nseg = (long)a->N * a->OH * cdiv(a->OW, H3_KP);
-    if (h3_steps <= 0) { H3Op o{tiles, nseg}; h3_steps = h3_pick_steps(&o, 1, nt, ng); }
-    k.splits = h3_splits(nseg, h3_steps, tiles, h3_tiles(a->Cout, a->src.C));
-    k.chunkP = cdiv(nseg, k.splits);
-    ADDK_REQUIRE(!check_ws || a->ws_floats >= (int64_t)k.splits * a->Cout * k.taps * a->src.C, "conv_wgrad: workspace too small");
-  }
-  if (kd == 9) {      // wide 1x1 heads on the split-bf16 kernel: 128 output x 64 input channels per workgroup, 64-pixel row segments
-    cty = 8; ctz = 4;
-    k.nyt = a->Cout / 128; k.nzt = cdiv(a->src.C, 16 * H1_TP);
-    tiles = k.nyt * k.nzt;
-    const long nseg = (long)a->N * a->OH * cdiv(a->OW, H3_KP);
-    if (h3_steps <= 0) { H3Op o{tiles, nseg}; h3_steps = h3_pick_steps(&o, 1, 2); }
-    long cap = addk_conv_wgrad_ws(k.P, a->Cout, a->src.C, 1) / ((long)a->Cout * a->src.C);      // slices the workspace was sized for
-    if (cap < 1) cap = 1;
-    long sp = cdiv(nseg, h3_steps); if (sp > cap) sp = cap; if (sp < 1) sp = 1;
-    k.chunkP = cdiv(nseg, sp);
-    k.splits = cdiv(nseg, k.chunkP);
-    ADDK_REQUIRE(!check_ws || a->ws_floats >= (int64_t)k.splits * a->Cout * k.taps * a->src.C, "conv_wgrad: workspace too small");
-  }
-  k.vecY = aligned16(a->dy) && a->lddy % 4 == 0 && a->Cout % 4 == 0;
-  k.vecZ = src_vec_ok(a->src);
-  if (kd == 8) {      // few input channels: one workgroup holds every (tap, channel) column; 1024-pixel slices, as many as the workspace bound allows
-    cty = 4; ctz = 2;
-    k.nyt = 1; k.nzt = 1; tiles = 1;
-    int sp = cdiv(k.P, 1024);
-    if (sp > 1024) sp = 1024;
+  k.vecY = c.vecY; k.vecZ = c.vecZ;
+  if (c.nseg) {      // 64-pixel row segments, h3_steps of them per block
+    if (h3_steps <= 0) h3_steps = h3_pick_steps(&c, 1);
+    int sp = cdiv(c.nseg, h3_steps); if (sp > c.cap) sp = c.cap;
+    k.chunkP = cdiv(c.nseg, sp);
+    k.splits = cdiv(c.nseg, k.chunkP);
+  } else if (c.px_chunk) {      // slices of about px_chunk pixels, a multiple of 4
+    int sp = cdiv(k.P, c.px_chunk); if (sp > c.cap) sp = c.cap;
     k.chunkP = cdiv(cdiv(k.P, sp), 4) * 4;
     k.splits = cdiv(k.P, k.chunkP);
-    ADDK_REQUIRE(!check_ws || a->ws_floats >= (int64_t)k.splits * a->Cout * k.taps * a->src.C, "conv_wgrad: workspace too small");
-  } else
-  if (kd == 7) {      // halo-patch kernel, taps split across waves: 64-pixel row segments like wgrad_h3
-    const int ct = hk_ct(a->Cout, a->KH);
-    cty = ct; ctz = a->KH;
-    k.nyt = cdiv(a->Cout, 16 * ct); k.nzt = cdiv(a->src.C, 16);
-    tiles = k.nyt * k.nzt;
-    const long nseg = (long)a->N * a->OH * cdiv(a->OW, H3_KP);
-    if (h3_steps <= 0) { H3Op o{tiles, nseg}; h3_steps = h3_pick_steps(&o, 1, ct == 3 ? 1 : 2); }
-    k.splits = h3_splits(nseg, h3_steps, tiles);
-    k.chunkP = cdiv(nseg, k.splits);
-    ADDK_REQUIRE(!check_ws || a->ws_floats >= (int64_t)k.splits * a->Cout * k.taps * a->src.C, "conv_wgrad: workspace too small");
-  } else
-  if (kd == 6) {      // register-streaming kernel: <= 64-channel tiles, 2048-pixel chunks (128 k-steps per wave), vecY/vecZ carry the tile strides
-    const int cap = pick_splits(k.P, tiles);
-    k.vecY = rs_tile(a->Cout); k.vecZ = rs_tile(a->src.C);
-    cty = rs_lay(k.vecY); ctz = rs_lay(k.vecZ);
-    k.nyt = cdiv(a->Cout, k.vecY); k.nzt = cdiv(a->src.C, k.vecZ);
-    tiles = k.nyt * k.taps * k.nzt;
-    const int rs_chunk = 2048;
-    int sp = cdiv(k.P, rs_chunk);
-    if (sp > cap) sp = cap;
-    if (sp < 1) sp = 1;
-    k.chunkP = cdiv(cdiv(k.P, sp), 4) * 4;
-    k.splits = cdiv(k.P, k.chunkP);
+  } else {      // `budget` blocks, slices of whole 64-pixel steps
+    k.splits = pick_splits(k.P, c.tiles, budget, min_steps);
+    k.chunkP = cdiv(cdiv(k.P, k.splits), KP) * KP;
   }
+  ADDK_REQUIRE(!check_ws || a->ws, "conv_wgrad: null pointer");
+  ADDK_REQUIRE(!check_ws || a->ws_floats >= (int64_t)k.splits * a->Cout * k.taps * a->src.C, "conv_wgrad: workspace too small");
   k.dw = a->dw; k.ldw = a->ldw; k.cin_total = a->cin_total; k.w_choff = a->w_choff; k.accumulate = a->accumulate;
   return 0;
 }
 
 static int wg_launch(int kind, int cty, int ctz, dim3 grid, hipStream_t st, const WgK& k, const WgK* ops, const int4* work) {
-  bool done = false;
-#define ADDK_OS(K_, TY_, TZ_) \
-  if (kind == K_) { \
-    if (ops) hipLaunchKernelGGL((wgrad_os_kernel<TY_, TZ_, true>), grid, dim3(256), 0, st, k, ops, work); \
-    else hipLaunchKernelGGL((wgrad_os_kernel<TY_, TZ_, false>), grid, dim3(256), 0, st, k, ops, work); \
-    done = true; }
-  ADDK_OS(1, 4, 2) ADDK_OS(2, 3, 3) ADDK_OS(3, 2, 2) ADDK_OS(4, 4, 4)
-#undef ADDK_OS
-  const int hk_np = addk_get_conv_precision() >= 2 ? 3 : addk_get_conv_precision() == 1 ? 2 : 0;      // (tail_x3: the cells' convs keep six terms)
-#define ADDK_HKB_(K_, C_, B_, P_) { \
-    static bool attr = false; \
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hkb_kernel<K_, C_, B_, P_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr = true; } \
-    hipLaunchKernelGGL((wgrad_hkb_kernel<K_, C_, B_, P_>), grid, dim3(256), wg_hkb_lds(K_, C_, P_), st, k, ops, work); done = true; }
-#define ADDK_HKB(K_, C_) \
-  if (kind == 7 && ctz == K_ && cty == C_ && hk_np && wgrad_split_enabled() && wgrad_split_narrow()) { \
-    if (ops) { if (hk_np == 3) ADDK_HKB_(K_, C_, true, 3) else ADDK_HKB_(K_, C_, true, 2) } \
-    else { if (hk_np == 3) ADDK_HKB_(K_, C_, false, 3) else ADDK_HKB_(K_, C_, false, 2) } }
-  ADDK_HKB(3, 3) ADDK_HKB(3, 5) ADDK_HKB(5, 3)
-#undef ADDK_HKB
-#undef ADDK_HKB_
-#define ADDK_HK(K_, C_) \
-  if (!done && kind == 7 && ctz == K_ && cty == C_) { \
-    if (ops) hipLaunchKernelGGL((wgrad_hk_kernel<K_, C_, true>), grid, dim3(256), 0, st, k, ops, work); \
-    else hipLaunchKernelGGL((wgrad_hk_kernel<K_, C_, false>), grid, dim3(256), 0, st, k, ops, work); \
-    done = true; }
-  ADDK_HK(3, 3) ADDK_HK(3, 5) ADDK_HK(5, 3)
-#undef ADDK_HK
-  if (kind == 8) {
-    if (ops) hipLaunchKernelGGL((wgrad_st_kernel<true>), grid, dim3(256), 0, st, k, ops, work);
-    else hipLaunchKernelGGL((wgrad_st_kernel<false>), grid, dim3(256), 0, st, k, ops, work);
-    done = true;
-  }
-  const bool rs_f16 = addk_get_conv_precision() == 1;      // f16x3: the narrow cell convs' weight gradients on the fp16 matrix pipe too (ABAB: step 29.57 -> 29.2 ms)
-#define ADDK_RS(A_, B_) \
-  if (kind == 6 && cty == A_ && ctz == B_) { \
-    if (rs_f16) { if (ops) hipLaunchKernelGGL((wgrad_rs_kernel<A_, B_, true, true>), grid, dim3(256), 0, st, k, ops, work); \
-                  else hipLaunchKernelGGL((wgrad_rs_kernel<A_, B_, false, true>), grid, dim3(256), 0, st, k, ops, work); } \
-    else if (ops) hipLaunchKernelGGL((wgrad_rs_kernel<A_, B_, true>), grid, dim3(256), 0, st, k, ops, work); \
-    else hipLaunchKernelGGL((wgrad_rs_kernel<A_, B_, false>), grid, dim3(256), 0, st, k, ops, work); \
-    done = true; }
-  ADDK_RS(3, 3) ADDK_RS(3, 4) ADDK_RS(4, 3) ADDK_RS(4, 4)
-#undef ADDK_RS
-  // 3x3 convolutions in a split-bf16 mode: the transposed-read kernel — the 128-channel blocks (decoder, ASPP) and the
-  // 64-channel blocks (stem1: 0.76 -> 0.61 ms alone; ADDK_WGRAD_SPLIT_NARROW=0 keeps stem1 and the cells' dilated convs on fp32)
-  const int wg_np = wg_np_of(cty);
-  if (kind == 5 && ctz == 2 && !h3b_runs(cty)) { addk_set_error("conv_wgrad: launch prepared for the split-bf16 kernel, but the precision mode / ADDK_WGRAD_SPLIT changed since"); return ADDK_ERR_INVALID; }
-#define ADDK_H3B_(N_, B_, P_, G_) { \
-    static bool attr = false; \
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_h3b_kernel<N_, B_, P_, G_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr = true; } \
-    hipLaunchKernelGGL((wgrad_h3b_kernel<N_, B_, P_, G_>), grid, dim3(256 * G_), wg_h3b_lds(N_, P_, G_), st, k, ops, work); done = true; }
-#define ADDK_H3B(N_, G_) \
-    if (ops) { if (wg_np == 3) ADDK_H3B_(N_, true, 3, G_) else ADDK_H3B_(N_, true, 2, G_) } \
-    else { if (wg_np == 3) ADDK_H3B_(N_, false, 3, G_) else ADDK_H3B_(N_, false, 2, G_) }
-  if (kind == 5 && cty == 8 && h3b_runs(cty)) { if (ctz == 2) { ADDK_H3B(2, 2) } else { ADDK_H3B(2, 1) } }
-  if (kind == 5 && cty == 4 && h3b_runs(cty)) { if (ctz == 2) { ADDK_H3B(1, 2) } else { ADDK_H3B(1, 1) } }
-#undef ADDK_H3B
-#undef ADDK_H3B_
-  if (kind == 9) {
-    if (!h3b_runs(8)) { addk_set_error("conv_wgrad: launch prepared for the split-bf16 kernel, but the precision mode / ADDK_WGRAD_SPLIT changed since"); return ADDK_ERR_INVALID; }
-#define ADDK_H1B_(B_, P_) { \
-      static bool attr = false; \
-      if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_h1b_kernel<B_, P_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr = true; } \
-      hipLaunchKernelGGL((wgrad_h1b_kernel<B_, P_>), grid, dim3(256), wg_h1b_lds(P_), st, k, ops, work); done = true; }
-    if (ops) { if (wg_np == 3) ADDK_H1B_(true, 3) else ADDK_H1B_(true, 2) }
-    else { if (wg_np == 3) ADDK_H1B_(false, 3) else ADDK_H1B_(false, 2) }
-#undef ADDK_H1B_
-  }
-#define ADDK_H3(NT_) \
-  if (!done && kind == 5 && cty == 4 * NT_) { \
-    if (ops) hipLaunchKernelGGL((wgrad_h3_kernel<NT_, true>), grid, dim3(256), 0, st, k, ops, work); \
-    else hipLaunchKernelGGL((wgrad_h3_kernel<NT_, false>), grid, dim3(256), 0, st, k, ops, work); \
-    done = true; }
-  ADDK_H3(1) ADDK_H3(2)
-#undef ADDK_H3
-#define ADDK_CASE(Y_, Z_) \
-  if (!done && cty == Y_ && ctz == Z_) { \
-    if (ops) hipLaunchKernelGGL((wgrad_kernel<Y_, Z_, true>), grid, dim3(256), 0, st, k, ops, work); \
-    else hipLaunchKernelGGL((wgrad_kernel<Y_, Z_, false>), grid, dim3(256), 0, st, k, ops, work); \
-    done = true; }
-  ADDK_CASE(2, 1) ADDK_CASE(2, 3) ADDK_CASE(2, 4) ADDK_CASE(2, 5)
-  ADDK_CASE(3, 1) ADDK_CASE(3, 3) ADDK_CASE(3, 4) ADDK_CASE(3, 5)
-  ADDK_CASE(4, 1) ADDK_CASE(4, 3) ADDK_CASE(4, 4) ADDK_CASE(4, 5)
-  ADDK_CASE(5, 1) ADDK_CASE(5, 3) ADDK_CASE(5, 4) ADDK_CASE(5, 5)
-  ADDK_CASE(8, 1) ADDK_CASE(8, 3) ADDK_CASE(8, 4)
-#undef ADDK_CASE
-  if (!done) { addk_set_error("conv_wgrad: no tile config"); return ADDK_ERR_UNSUPPORTED; }
+  WgVariant v;
+  const int mode = addk_get_conv_precision();
+  const int rc = ops ? wg_variant<true>(kind, cty, ctz, mode, v) : wg_variant<false>(kind, cty, ctz, mode, v);
+  if (rc) return rc;
+  hipLaunchKernelGGL(v.fn, grid, dim3(v.threads), v.lds, st, k, ops, work);
   return addk_check_launch("conv_wgrad");
 }
 
 extern "C" int addk_conv_wgrad(const addk_conv_wgrad_args* a, void* stream) {
-  WgK k; int cty, ctz, tiles;
-  int rc = wg_fill(a, k, cty, ctz, tiles, true);
+  WgChoice c; WgK k;
+  int rc = wg_choose(a, addk_get_conv_precision(), c);
+  if (!rc) rc = wg_fill(a, c, k, true);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  rc = wg_launch(kind_of(a), cty, ctz, dim3(tiles, k.splits), st, k, nullptr, nullptr);
+  rc = wg_launch(c.kind, c.cty, c.ctz, dim3(c.tiles, k.splits), st, k, nullptr, nullptr);
   if (rc) return rc;
   long n = (long)a->Cout * k.taps * a->src.C;
-  if (k.splits > 16 && n <= 65536) {
+  if (wg_wave_reduce(k.splits, n)) {
     hipLaunchKernelGGL(wgrad_reduce_wave_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, a->ws, k.splits, a->Cout, k.taps, a->src.C,
                        a->dw, a->ldw, a->cin_total, a->w_choff, a->accumulate);
   } else {
@@ -2229,83 +2215,61 @@ extern "C" int addk_conv_wgrad(const addk_conv_wgrad_args* a, void* stream) {
 
 // ---- batched weight gradients -------------------------------------------------------------------------------------
 extern "C" int addk_conv_wgrad_config(const addk_conv_wgrad_args* a, int32_t* cfg) {
-  WgK k; int cty, ctz, tiles;
-  int rc = wg_fill(a, k, cty, ctz, tiles, false);
+  WgChoice c; WgK k;
+  int rc = wg_choose(a, addk_get_conv_precision(), c);
+  if (!rc) rc = wg_fill(a, c, k, false);
   if (rc) return rc;
-  cfg[0] = kind_of(a); cfg[1] = cty; cfg[2] = ctz; cfg[3] = tiles * k.splits;
+  cfg[0] = c.kind; cfg[1] = c.cty; cfg[2] = c.ctz; cfg[3] = c.tiles * k.splits;
   return 0;
 }
 
 extern "C" int64_t addk_conv_wgrad_batch_prepare(const addk_conv_wgrad_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
   if (!a || n <= 0 || !meta) { addk_set_error("wgrad_batch_prepare: bad args"); return ADDK_ERR_INVALID; }
-  long nblocks = 0, nrblocks = 0;
-  int kind0 = -1, cty0 = 0, ctz0 = 0;
+  const int mode = addk_get_conv_precision();
+  std::vector<WgChoice> ch(n);
+  for (int i = 0; i < n; ++i) {
+    const int rc = wg_choose(&a[i], mode, ch[i]);
+    if (rc) return rc;
+    if (ch[i].kind != ch[0].kind || ch[i].cty != ch[0].cty || ch[i].ctz != ch[0].ctz) { addk_set_error("wgrad_batch_prepare: mixed tile configurations"); return ADDK_ERR_INVALID; }
+  }
   int budget = 8192 / n; if (budget < 32) budget = 32; if (budget > 1536) budget = 1536;
   const int min_steps = n >= 4 ? 8 : 1;
-  int h3_steps = 0;
-  const int kd0 = kind_of(&a[0]);
-  if (kd0 == 7) {
-    H3Op* ho = (H3Op*)malloc(sizeof(H3Op) * n);
-    for (int i = 0; i < n; ++i) { ho[i].tiles = hk_tiles(a[i].Cout, a[i].src.C, a[i].KH); ho[i].nseg = (long)a[i].N * a[i].OH * cdiv(a[i].OW, H3_KP); }
-    h3_steps = h3_pick_steps(ho, n, hk_ct(a[0].Cout, a[0].KH) == 3 ? 1 : 2);
-    free(ho);
-  }
-  if (kd0 == 9) {
-    H3Op* ho = (H3Op*)malloc(sizeof(H3Op) * n);
-    for (int i = 0; i < n; ++i) { ho[i].tiles = (a[i].Cout / 128) * cdiv(a[i].src.C, 16 * H1_TP); ho[i].nseg = (long)a[i].N * a[i].OH * cdiv(a[i].OW, H3_KP); }
-    h3_steps = h3_pick_steps(ho, n, 2);
-    free(ho);
-  }
-  if (kd0 == 5) {
-    H3Op* ho = (H3Op*)malloc(sizeof(H3Op) * n);
-    const int nt = a[0].Cout % 128 == 0 ? 2 : 1, ng = h3_ng(a[0].Cout, a[0].src.C);
-    for (int i = 0; i < n; ++i) {
-      const int nti = a[i].Cout % 128 == 0 ? 2 : 1;
-      ho[i].tiles = (a[i].Cout / (64 * nti)) * cdiv(a[i].src.C, 16 * h3_ng(a[i].Cout, a[i].src.C));
-      ho[i].nseg = (long)a[i].N * a[i].OH * cdiv(a[i].OW, H3_KP);
-    }
-    h3_steps = h3_pick_steps(ho, n, nt, ng);
-    free(ho);
-  }
+  const int h3_steps = ch[0].nseg ? h3_pick_steps(ch.data(), n) : 0;
+  std::vector<WgK> ops(n);
+  long nblocks = 0, nrblocks = 0;
   for (int i = 0; i < n; ++i) {
-    WgK k; int cty, ctz, tiles;
-    int rc = wg_fill(&a[i], k, cty, ctz, tiles, host_blob != nullptr, budget, min_steps, h3_steps);
+    const int rc = wg_fill(&a[i], ch[i], ops[i], host_blob != nullptr, budget, min_steps, h3_steps);
     if (rc) return rc;
-    int kind = kind_of(&a[i]);
-    if (i == 0) { kind0 = kind; cty0 = cty; ctz0 = ctz; }
-    if (kind != kind0 || cty != cty0 || ctz != ctz0) { addk_set_error("wgrad_batch_prepare: mixed tile configurations"); return ADDK_ERR_INVALID; }
-    nblocks += (long)tiles * k.splits;
-    long ne = (long)a[i].Cout * k.taps * a[i].src.C;
-    nrblocks += (k.splits > 16 && ne <= 65536) ? cdiv(ne, 64) : cdiv(ne, 256);
+    nblocks += (long)ch[i].tiles * ops[i].splits;
+    const long ne = (long)a[i].Cout * ops[i].taps * a[i].src.C;
+    nrblocks += wg_wave_reduce(ops[i].splits, ne) ? cdiv(ne, 64) : cdiv(ne, 256);
   }
   const int64_t off_work = ((int64_t)n * sizeof(WgK) + 15) / 16 * 16;
   const int64_t off_rwork = off_work + nblocks * (int64_t)sizeof(int4);
   const int64_t total = off_rwork + nrblocks * (int64_t)sizeof(int4);
-  meta[0] = kind0; meta[1] = cty0; meta[2] = ctz0; meta[3] = n; meta[4] = off_work; meta[5] = nblocks; meta[6] = off_rwork; meta[7] = nrblocks;
+  meta[0] = ch[0].kind; meta[1] = ch[0].cty; meta[2] = ch[0].ctz; meta[3] = n; meta[4] = off_work; meta[5] = nblocks; meta[6] = off_rwork; meta[7] = nrblocks;
   if (!host_blob) return total;
   if (blob_bytes < total) { addk_set_error("wgrad_batch_prepare: blob too small"); return ADDK_ERR_INVALID; }
-  WgK* ops = reinterpret_cast<WgK*>(host_blob);
+  memcpy(host_blob, ops.data(), (size_t)n * sizeof(WgK));
   int4* work = reinterpret_cast<int4*>(reinterpret_cast<char*>(host_blob) + off_work);
   int4* rwork = reinterpret_cast<int4*>(reinterpret_cast<char*>(host_blob) + off_rwork);
   long b = 0, rb = 0;
   for (int i = 0; i < n; ++i) {
-    int cty, ctz, tiles;
-    wg_fill(&a[i], ops[i], cty, ctz, tiles, true, budget, min_steps, h3_steps);
-    if (kind0 == 6) {
+    const int tiles = ch[i].tiles, sp = ops[i].splits;
+    if (ch[i].kind == WG_RS) {
       // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs, so within a group of 8 pixel chunks the tiles
       // (taps x channel blocks) of one chunk are placed 8 apart: they share an XCD and its L2 serves the 9/25 re-reads
       // of that chunk's dy / activation rows.
-      const int sp = ops[i].splits;
       for (int g0 = 0; g0 < sp; g0 += 8) {
         const int gn = sp - g0 < 8 ? sp - g0 : 8;
         for (int x = 0; x < tiles; ++x)
           for (int yy = 0; yy < gn; ++yy) work[b++] = make_int4(i, x, g0 + yy, 0);
       }
     } else
-    for (int y = 0; y < ops[i].splits; ++y)
+    for (int y = 0; y < sp; ++y)
       for (int x = 0; x < tiles; ++x) work[b++] = make_int4(i, x, y, 0);
-    long ne = (long)a[i].Cout * ops[i].taps * a[i].src.C;
-    if (ops[i].splits > 16 && ne <= 65536) { for (long e = 0; e < ne; e += 64) rwork[rb++] = make_int4(i, (int)e, 1, 0); }
+    const long ne = (long)a[i].Cout * ops[i].taps * a[i].src.C;
+    if (wg_wave_reduce(sp, ne)) { for (long e = 0; e < ne; e += 64) rwork[rb++] = make_int4(i, (int)e, 1, 0); }
     else { for (long e = 0; e < ne; e += 256) rwork[rb++] = make_int4(i, (int)e, 0, 0); }
   }
   return total;

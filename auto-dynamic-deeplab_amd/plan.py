@@ -345,18 +345,12 @@ class Graph:
         self.nstreams = max(1, int(nstreams))
         if self._evalbn:
             n = len(self._evalbn)
-            arr = (L.BnEvalEntry * n)(*self._evalbn)
-            host = torch.frombuffer(arr, dtype=torch.uint8)
-            tab = host.to(self.device) if self.device.type == 'cuda' else host.clone()
-            self.keep += [arr, tab]
+            tab = self._table(bytes((L.BnEvalEntry * n)(*self._evalbn)))
             self._evalbn_cmd.args[0], self._evalbn_cmd.args[1] = tab.data_ptr(), n
         self._emit_batched_dw_reductions()
         self._emit_batched_wgrads()
         if self._packs:
-            host = bytearray(b''.join(self._packs))
-            tab = torch.frombuffer(host, dtype=torch.uint8)
-            tab = tab.to(self.device) if self.device.type == 'cuda' else tab.clone()
-            self.keep.append(tab)
+            tab = self._table(b''.join(self._packs))
             self._pack_cmd.args[0], self._pack_cmd.args[1] = tab.data_ptr(), len(self._packs)
         batch = ((self.training and self.want_grad) or getattr(self, 'reorder', False)) and os.environ.get('ADDK_LEVEL_BATCH', '1') == '1'
         for lst in (self.fwd, self.bwd):
@@ -402,6 +396,27 @@ class Graph:
             for k in c.rd:
                 readers.setdefault(k[0], []).append((k, i))
         return level
+
+    def _table(self, data):
+        """A table of host bytes on the plan's device (a CPU copy in dry runs), kept alive with the plan."""
+        host = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+        tab = host.to(self.device) if self.device.type == 'cuda' else host.clone()
+        self.keep.append(tab)
+        return tab
+
+    def _prepare(self, prep, arr, n, what):
+        """A library `*_batch_prepare` call made twice: for the blob's size, then to fill it.  Returns the blob's bytes and the
+        meta array (kept alive with the plan: the batched launch reads it)."""
+        meta = (C.c_int64 * 8)()
+        size = prep(arr, n, None, 0, meta)
+        if size < 0:
+            L.check(int(size), what)
+        blob = (C.c_uint8 * size)()
+        rc = prep(arr, n, blob, size, meta)
+        if rc < 0:
+            L.check(int(rc), what)
+        self.keep.append(meta)
+        return bytes(blob), meta
 
     def _bind_late(self, lst, by_level):
         """Give every exchanged statistics vector (LateVec payload of an 'allreduce' command) its storage.  With level
@@ -473,23 +488,11 @@ class Graph:
                     continue
                 arr = (type(cs[0].payload) * n)(*[c.payload for c in cs])
                 if isinstance(size_of, str):   # pointwise / depthwise convs: the library turns the argument structs into kernel descriptors
-                    prep = getattr(self.lib, fname)
-                    meta = (C.c_int64 * 8)()
-                    size = prep(arr, n, None, 0, meta)
-                    if size < 0:
-                        L.check(int(size), fname)
-                    blob = (C.c_uint8 * size)()
-                    rc = prep(arr, n, blob, size, meta)
-                    if rc < 0:
-                        L.check(int(rc), fname)
-                    host = torch.frombuffer(bytearray(bytes(blob)), dtype=torch.uint8)
-                    tab = host.to(self.device) if self.device.type == 'cuda' else host.clone()
-                    self.keep += [arr, tab, meta]
+                    blob, meta = self._prepare(getattr(self.lib, fname), arr, n, fname)
+                    tab = self._table(blob)
                     m = Cmd(name + '_batch', getattr(self.lib, size_of), (tab.data_ptr(), meta))
                 else:
-                    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-                    tab = host.to(self.device) if self.device.type == 'cuda' else host.clone()
-                    self.keep += [arr, tab]
+                    tab = self._table(bytes(arr))
                     m = Cmd(name + '_batch', getattr(self.lib, fname), (tab.data_ptr(), n, max(int(size_of(c.payload)) for c in cs)))
                 m.rd = [r for c in cs for r in c.rd]
                 m.wr = [r for c in cs for r in c.wr]
@@ -530,11 +533,7 @@ class Graph:
             parts += [items[c * per:(c + 1) * per] for c in range(k) if items[c * per:(c + 1) * per]]
         for items in parts:
             n = len(items)
-            arr = (L.DwWreduceItem * n)(*[it for it, _, _ in items])
-            host = bytes(arr)
-            tab = torch.frombuffer(bytearray(host), dtype=torch.uint8)
-            tab = tab.to(self.device) if self.device.type == 'cuda' else tab.clone()
-            self.keep += [arr, tab]
+            tab = self._table(bytes((L.DwWreduceItem * n)(*[it for it, _, _ in items])))
             self._add(self.bwd, 'dw_wreduce_batch', self.lib.addk_dw_wreduce_batch, tab.data_ptr(), n,
                       rd=[ws for _, ws, _ in items], wr=[g for _, _, g in items])
 
@@ -578,20 +577,9 @@ class Graph:
                     ws = self.buf(wa.ws_floats)
                     wa.ws = ws.ptr
                     arr[i] = wa
-                meta = (C.c_int64 * 8)()
-                size = lib.addk_conv_wgrad_batch_prepare(arr, n, None, 0, meta)
-                if size < 0:
-                    L.check(int(size), 'conv_wgrad_batch_prepare')
-                host = (C.c_uint8 * size)()
-                rc = lib.addk_conv_wgrad_batch_prepare(arr, n, host, size, meta)
-                if rc < 0:
-                    L.check(int(rc), 'conv_wgrad_batch_prepare')
-                if self.device.type == 'cuda':
-                    blob = torch.frombuffer(host, dtype=torch.uint8).to(self.device)
-                else:                       # dry-run planning on CPU (tests)
-                    blob = torch.frombuffer(host, dtype=torch.uint8).clone()
-                self.keep += [arr, meta, blob]
-                self.nbytes += int(size)
+                host, meta = self._prepare(lib.addk_conv_wgrad_batch_prepare, arr, n, 'conv_wgrad_batch_prepare')
+                blob = self._table(host)
+                self.nbytes += len(host)
                 if os.environ.get('ADDK_DEBUG_WGRAD') == '1':      # algorithmic work of this batch (tuning aid)
                     fl = sum(2.0 * w.N * w.OH * w.OW * w.Cout * w.KH * w.KW * w.src.C for w, _, _ in items)
                     by = sum(4.0 * (w.N * w.OH * w.OW * w.Cout + w.N * w.H * w.W * w.src.C) for w, _, _ in items)

@@ -55,7 +55,7 @@ def test_full_size_train_mode_gradients_on_sentinel_convs(dev):
 @pytest.mark.parametrize('prec', ['bf16x6', 'f16x3'])
 @pytest.mark.parametrize('shape', [(2, 64, 128, 320, 128), (1, 70, 130, 200, 128), (2, 64, 128, 400, 256)], ids=['c320_o128', 'c200_o128_odd', 'c400_o256'])
 def test_wide_pointwise_weight_gradient_with_128_outputs(dev, shape, prec):
-    """1x1, C -> 128 (F = 32's heads): kind_of() picks the split-bf16 head kernel (9) and wg_fill must give it ITS geometry —
+    """1x1, C -> 128 (F = 32's heads): wg_choose() picks the split-bf16 head kernel (9) with ITS geometry —
     (Cout / 128) * cdiv(C, 64) tiles of 64-pixel row segments — not the register-streaming kernel's, which the same shape also passes."""
     import addk
     from addk import _lib as L

@@ -1,0 +1,116 @@
+"""Host-side choice of the weight-gradient kernel (wgrad.hip), no GPU: the library is called with aligned placeholder pointers (nothing is
+dereferenced before a launch).  For every shape x precision mode x fast-path mask: the launch key addk_conv_wgrad_config reports is the one a
+batch of that conv carries, and a workspace of exactly addk_conv_wgrad_ws floats passes the checked batch prepare.  The shapes of the GPU
+kernel tests get the kinds those tests assert."""
+import ctypes as C
+
+import pytest
+
+import addk
+from addk import _lib as L
+
+MODES = {'fp32': 0, 'f16x3': 1, 'bf16x6': 2, 'tail_x3': 3}
+PTR = {'dy': 0x10000000, 'x': 0x20000000, 'a': 0x30000000, 'b': 0x30001000, 'dw': 0x40000000, 'ws': 0x50000000}      # 16-byte aligned
+
+# name, N, H, W, Ci, Cout, k, stride, dil: the register-streaming / few-channel cases of
+# test_gpu_fast_kernels.test_register_streaming_wgrad_matches_fp64_reference
+RS_SHAPES = [
+    ('pw40', 2, 63, 127, 40, 40, 1, 1, 1), ('pw80', 1, 64, 128, 80, 80, 1, 1, 1), ('glue200', 1, 50, 90, 200, 40, 1, 1, 1),
+    ('reduce_s2', 2, 128, 96, 80, 40, 1, 2, 1), ('dense3_s2', 2, 97, 129, 48, 96, 3, 2, 1), ('pw160', 2, 32, 64, 160, 160, 1, 1, 1),
+    ('stem0_like', 2, 256, 511, 3, 64, 3, 2, 1)]
+# test_gpu_round5.test_wide_pointwise_weight_gradient_with_128_outputs: 1x1, C -> 128
+WIDE_PW_SHAPES = [('c320_o128', 2, 64, 128, 320, 128, 1, 1, 1), ('c200_o128_odd', 1, 70, 130, 200, 128, 1, 1, 1),
+                  ('c400_o256', 2, 64, 128, 400, 256, 1, 1, 1)]
+# the 3x3 / 5x5 halo cases of test_gpu_fast_kernels.SHAPES, one entry per source
+HALO_SHAPES = [
+    ('two_src_d1_s0', 1, 40, 256, 32, 128, 3, 1, 1), ('two_src_d1_s1', 1, 40, 256, 16, 128, 3, 1, 1),
+    ('odd_tail_d2', 2, 33, 129, 24, 64, 3, 1, 2), ('aspp_like_d6', 1, 70, 128, 48, 256, 3, 1, 6),
+    ('wide_blocks_d1', 2, 64, 256, 32, 256, 3, 1, 1), ('max_dil_d18', 1, 64, 128, 16, 64, 3, 1, 18),
+    ('tworow_odd', 2, 65, 300, 24, 128, 3, 1, 1), ('tworow_c64', 1, 129, 200, 32, 64, 3, 1, 1),
+    ('cell_dil5_40', 1, 70, 125, 40, 40, 5, 1, 2), ('cell_dil5_80', 2, 63, 127, 80, 80, 5, 1, 2),
+    ('cell_dil3_40', 1, 70, 125, 40, 40, 3, 1, 2), ('cell_dil3_160', 2, 40, 104, 32, 160, 3, 1, 2),
+    ('n16_two_src_s0', 2, 33, 200, 24, 48, 5, 1, 2), ('n16_two_src_s1', 2, 33, 200, 16, 48, 5, 1, 2),
+    ('n16_k8_d1', 2, 40, 130, 8, 40, 5, 1, 1), ('n16_c36', 1, 90, 100, 36, 36, 5, 1, 2),
+    ('l3_dil5_160', 2, 32, 64, 48, 160, 5, 1, 2), ('l3_dil3_160', 2, 32, 64, 32, 160, 3, 1, 2)]
+# the other kinds: the network's wide heads (output-split), 80- and 64-channel 1x1s, stem1, a strided dense conv, a small map
+OTHER_SHAPES = [
+    ('head_1x1_256', 2, 64, 128, 256, 256, 1, 1, 1), ('pw80_small', 2, 16, 32, 80, 80, 1, 1, 1), ('pw64_small', 2, 16, 32, 64, 64, 1, 1, 1),
+    ('stem1', 2, 256, 512, 64, 64, 3, 1, 1), ('stem2_s2', 2, 256, 512, 64, 128, 3, 2, 1), ('tiny', 1, 9, 11, 20, 24, 3, 1, 1)]
+ALL_SHAPES = RS_SHAPES + WIDE_PW_SHAPES + HALO_SHAPES + OTHER_SHAPES
+
+
+@pytest.fixture(scope='module')
+def lib():
+    lb = addk.load()
+    prec, fast = lb.addk_get_conv_precision(), lb.addk_get_fast_paths()
+    yield lb
+    lb.addk_set_fast_paths(fast)
+    lb.addk_set_conv_precision(prec)
+
+
+def _args(lb, shape):
+    _, N, H, W, Ci, Cout, k, s, d = shape
+    pad = d * (k // 2)
+    OH, OW = (H + 2 * pad - d * (k - 1) - 1) // s + 1, (W + 2 * pad - d * (k - 1) - 1) // s + 1
+    wa = L.ConvWgradArgs()
+    wa.dy, wa.lddy, wa.Cout = PTR['dy'], Cout, Cout
+    wa.N, wa.H, wa.W, wa.OH, wa.OW, wa.KH, wa.KW, wa.stride, wa.pad, wa.dil = N, H, W, OH, OW, k, k, s, pad, d
+    wa.src.x, wa.src.a, wa.src.b, wa.src.ld, wa.src.C, wa.src.relu = PTR['x'], PTR['a'], PTR['b'], Ci, Ci, 1
+    wa.dw, wa.ldw, wa.cin_total, wa.w_choff, wa.accumulate = PTR['dw'], k * k * Ci, Ci, 0, 0
+    wa.ws, wa.ws_floats = PTR['ws'], lb.addk_conv_wgrad_ws(N * OH * OW, Cout, Ci, k * k)
+    return wa
+
+
+def _config(lb, wa):
+    cfg = (C.c_int32 * 4)()
+    L.check(lb.addk_conv_wgrad_config(C.byref(wa), cfg), 'conv_wgrad_config')
+    return list(cfg)
+
+
+@pytest.mark.parametrize('fast', [31, 0])
+@pytest.mark.parametrize('mode', list(MODES))
+def test_config_key_matches_batch_and_workspace_bound_suffices(lib, mode, fast):
+    L.check(lib.addk_set_conv_precision(MODES[mode]), 'set_conv_precision')
+    lib.addk_set_fast_paths(fast)
+    for shape in ALL_SHAPES:
+        wa = _args(lib, shape)
+        cfg = _config(lib, wa)
+        arr = (L.ConvWgradArgs * 1)(wa)
+        meta = (C.c_int64 * 8)()
+        size = lib.addk_conv_wgrad_batch_prepare(arr, 1, None, 0, meta)
+        assert size > 0, (shape[0], lib.addk_last_error())
+        assert list(meta[:3]) == cfg[:3], (shape[0], list(meta[:3]), cfg)
+        blob = (C.c_uint8 * size)()
+        filled = (C.c_int64 * 8)()
+        rc = lib.addk_conv_wgrad_batch_prepare(arr, 1, blob, size, filled)      # checked: the workspace holds every slice
+        assert rc == size and list(filled) == list(meta), (shape[0], cfg, rc, size)
+        assert meta[5] == cfg[3], (shape[0], 'blocks of a one-conv batch with a lone launch\'s budget', meta[5], cfg)
+
+
+@pytest.mark.parametrize('mode', ['bf16x6', 'f16x3'])
+def test_gpu_test_shapes_get_their_kinds(lib, mode):
+    L.check(lib.addk_set_conv_precision(MODES[mode]), 'set_conv_precision')
+    for fast in (31, 0):
+        lib.addk_set_fast_paths(fast)
+        for shape in RS_SHAPES:
+            kind = _config(lib, _args(lib, shape))[0]
+            assert (kind == (8 if shape[4] <= 4 else 6)) == (fast == 31), (shape[0], fast, kind)
+    lib.addk_set_fast_paths(31)
+    for shape in WIDE_PW_SHAPES:
+        assert _config(lib, _args(lib, shape))[:3] == [9, 8, 4], shape[0]
+
+
+@pytest.mark.parametrize('mode', ['fp32', 'bf16x6', 'f16x3'])
+def test_halo_shapes_get_halo_kinds(lib, mode):
+    for fast, m in ((31, mode), (0, 'fp32')):          # the fast launch in each mode, the generic one in fp32
+        L.check(lib.addk_set_conv_precision(MODES[m]), 'set_conv_precision')
+        lib.addk_set_fast_paths(fast)
+        for shape in HALO_SHAPES:
+            _, N, H, W, Ci, Cout, k, s, d = shape
+            if shape[0].startswith('l3_') and m == 'fp32':
+                continue                                # below the fp32 halo kernel's floor: a split-kernel launch shape only
+            kind = _config(lib, _args(lib, shape))[0]
+            if Ci >= 16 and k == 3 and Cout % 64 == 0:
+                assert (kind == 5) == bool(fast & 4), (shape[0], fast, kind)
+            elif Ci >= 16 and Cout <= 160 and d <= 2:
+                assert (kind == 7) == bool(fast & 16), (shape[0], fast, kind)
