@@ -150,6 +150,8 @@ _SIGS = {
     'addk_conv_dgrad_pack_desc': (i32, [C.POINTER(ConvDgradArgs), vp]),
     'addk_conv_pack_batch': (i32, [vp, i32, vp]),
     'addk_conv_fwd_resample_ok': (i32, [C.POINTER(ConvArgs)]),
+    'addk_conv_fwd_config': (i32, [C.POINTER(ConvArgs), C.POINTER(i32)]),
+    'addk_conv_dgrad_config': (i32, [C.POINTER(ConvDgradArgs), C.POINTER(i32)]),
     'addk_debug_trace_fatal_signals': (i32, []),
     'addk_comm_mailbox_bytes': (i64, [i32, i64]),
     'addk_comm_alloc': (i32, [i32, i64, C.POINTER(vp), vp]),

@@ -175,9 +175,10 @@ static inline EwMap ew_map(int C) {
   EwMap m; m.nq = (C + 3) / 4; if (m.nq > 256) m.nq = 256; m.npl = 256 / m.nq; if (m.npl < 1) m.npl = 1; return m;
 }
 
-// pw.hip: register-stationary 1x1 convolution; 0 = launched, 1 = shape not covered (fall back), <0 = error
-int addk_pw_try_fwd(const addk_conv_args* a, int rows, void* stream);
-int addk_pw_try_dgrad(const addk_conv_dgrad_args* a, int rows, void* stream);
-// conv3.hip: halo-patch 3x3 stride-1 convolution (needs a->wpack); same return convention
-int addk_c3_try_fwd(const addk_conv_args* a, int rows, void* stream);
-int addk_c3_try_dgrad(const addk_conv_dgrad_args* a, int rows, void* stream);
+// Kernels that ask for more than the default 64 KB of dynamic LDS: addk_dyn_lds<kernel>(bytes) raises the kernel's limit before its first launch,
+// once per kernel and thread-safely (a function-local static per instantiation).
+constexpr int ADDK_MAX_DYN_LDS = 160 * 1024 - 64;
+template <auto F> void addk_dyn_lds(int bytes = ADDK_MAX_DYN_LDS) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(F), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  (void)attr;
+}

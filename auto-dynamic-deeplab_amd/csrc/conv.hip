@@ -16,7 +16,7 @@
 // Reference call sites: see include/addk.h (addk_conv_fwd / addk_conv_dgrad).
 #include <stdlib.h>
 #include <string.h>
-#include "common.h"
+#include "conv.h"
 
 namespace {
 
@@ -499,17 +499,17 @@ int fast_paths() {
   }
   return g_fast;
 }
-bool pw_enabled() { return (fast_paths() & ADDK_FAST_PW) != 0; }
+
+// PT and CT of a launch over P pixels
+void generic_tiles(long P, int Cn, int& pt, int& ct) { pt = pick_pt(P); ct = pick_ct(Cn, cdiv(P, 64 * pt)); }
 
 template <int MODE>
-int launch(ConvK& k, hipStream_t st, int grid_x = 0) {
-  const int pt = pick_pt(k.P);
+int launch(ConvK& k, int pt, int ct, int gx, hipStream_t st) {
   const int BP = 64 * pt;
   k.ntiles = cdiv(k.P, BP);
   for (int c = 0; c < k.ncls; ++c) k.cl[c].ntiles = cdiv(k.cl[c].P, BP);      // combined parity classes: k.P is the largest class
   k.red32 = k.P >= 4096;
-  const int ct = pick_ct(k.Cn, k.ntiles);
-  dim3 grid(grid_x > 0 ? grid_x : addk_conv_rows(k.P, k.Cn), cdiv(k.Cn, 16 * ct));   // workgroups beyond ntiles only write their (zero) slab row
+  dim3 grid(gx, cdiv(k.Cn, 16 * ct));      // workgroups beyond ntiles only write their (zero) slab row
 #define ADDK_CASE(PT_, CT_) \
   if (pt == PT_ && ct == CT_) { \
     hipLaunchKernelGGL((conv_kernel<PT_, CT_, MODE, PREC_F32>), grid, dim3(256), 0, st, k); \
@@ -519,6 +519,82 @@ int launch(ConvK& k, hipStream_t st, int grid_x = 0) {
 #undef ADDK_CASE
   addk_set_error("conv: no tile config");
   return ADDK_ERR_UNSUPPORTED;
+}
+
+void choose_generic(ConvChoice& c, long P, int Cn) {
+  c.kind = CK_GENERIC; c.P = P;
+  generic_tiles(P, Cn, c.v[0], c.v[1]);
+  c.v[2] = P >= 4096;
+  c.gx = c.rows; c.gy = cdiv(Cn, 16 * c.v[1]);
+}
+
+// Stride-2 data gradient: an input pixel only receives the taps whose offset matches its parity, (1,2,2,4) of the 9 taps of a 3x3 for the four
+// (row, column) parity classes.  A launch over one class's quarter of the pixels does 9/4 tap-chunks per pixel instead of 9 masked ones; each class
+// writes its own share of the (dA,dB) slab rows.  Classes that no tap reaches (3 of 4 for a 1x1 stride-2 conv: FactorizedReduce) have a zero
+// gradient: they are only launched when the gradient buffer is being first-touched (to write the zeros).
+void choose_parity(ConvChoice& c, const addk_conv_dgrad_args* a) {
+  const int rows = c.rows, Cn = a->dst.C;
+  int ntl[4], tl[4][9], nvalid = 0, tot = 0;
+  for (int cl = 0; cl < 4; ++cl) {
+    const int ph = cl >> 1, pw = cl & 1;
+    ntl[cl] = 0;
+    for (int kh = 0; kh < a->KH; ++kh)
+      for (int kw = 0; kw < a->KW; ++kw)
+        if ((ph + a->pad - kh * a->dil) % 2 == 0 && (pw + a->pad - kw * a->dil) % 2 == 0) tl[cl][ntl[cl]++] = kh * a->KW + kw;
+    if (ntl[cl]) ++nvalid;
+    tot += ntl[cl];
+  }
+  c.kind = CK_PARITY; c.ncls = 0; c.P = 0;
+  auto add = [&](int cl, int gx, int slab_row) {
+    ConvChoice::Cls& q = c.cls[c.ncls++];
+    q.ph = cl >> 1; q.pw = cl & 1;
+    q.MH = (a->H - q.ph + 1) / 2; q.MW = (a->W - q.pw + 1) / 2;
+    q.P = (long)a->N * q.MH * q.MW;
+    q.ntaps = ntl[cl] ? ntl[cl] : 1; q.kill = ntl[cl] ? 0 : 1;
+    for (int i = 0; i < 9; ++i) q.taplist[i] = i < ntl[cl] ? tl[cl][i] : 0;
+    q.gx = gx; q.slab_row = slab_row;
+    generic_tiles(q.P, Cn, q.pt, q.ct);
+    if (q.P > c.P) c.P = q.P;
+  };
+  if (rows >= 16) {
+    // ONE launch for all classes (each alone is rows/4 workgroups = one per CU at the stems' sizes: 1 wave per SIMD).  The slab rows
+    // (= workgroups) are shared out in proportion to the classes' tap counts so that they finish together; classes without taps get
+    // workgroups beyond the slab (they only store zeros, and only on a first touch).
+    int gx0 = 0, left = rows, seen = 0;
+    for (int pass = 0; pass < 2; ++pass)          // classes with taps first: their workgroups are the slab rows 0..rows-1
+      for (int cl = 0; cl < 4; ++cl) {
+        if ((ntl[cl] > 0) != (pass == 0)) continue;
+        if (pass == 1 && a->accumulate) continue;            // nothing to add
+        int gx;
+        if (pass == 0) {
+          ++seen;
+          gx = seen == nvalid ? left : (int)((long)rows * ntl[cl] / tot);
+          if (gx < 1) gx = 1;
+          if (gx > left - (nvalid - seen)) gx = left - (nvalid - seen);
+          left -= gx;
+        } else {
+          gx = rows / 4;
+        }
+        add(cl, gx, pass == 0 ? gx0 : -1);
+        c.cls[c.ncls - 1].gx0 = gx0; gx0 += gx;
+      }
+    c.launches = 1; c.gx = gx0;
+    generic_tiles(c.P, Cn, c.v[0], c.v[1]);
+  } else {
+    // one launch per class; with no class without taps (or rows not a multiple of their count) every class gets a quarter of the rows
+    if (nvalid == 0 || rows % nvalid != 0) nvalid = 0;
+    int vi = 0;
+    for (int cl = 0; cl < 4; ++cl) {
+      if (!ntl[cl] && nvalid && a->accumulate) continue;       // nothing to add
+      const int gx = ntl[cl] && nvalid ? rows / nvalid : rows / 4;
+      add(cl, gx, !nvalid ? cl * (rows / 4) : ntl[cl] ? vi++ * gx : -1);
+      c.cls[c.ncls - 1].gx0 = 0;
+    }
+    c.launches = c.ncls; c.gx = c.cls[0].gx;
+    c.v[0] = c.cls[0].pt; c.v[1] = c.cls[0].ct;
+  }
+  c.v[2] = c.P >= 4096; c.v[3] = c.ncls;
+  c.gy = cdiv(Cn, 16 * c.v[1]);
 }
 
 __global__ void mfma_selftest_kernel(float* out) {
@@ -555,70 +631,84 @@ extern "C" int addk_conv_rows(int64_t P, int32_t Cout) {
   return nt < 1024 ? nt : 1024;
 }
 
-extern "C" int addk_conv_fwd(const addk_conv_args* a, void* stream) {
+// The specialised kernels' shapes overlap only for 1x1 launches.  Forward: a 1x1 whose caller set up the split kernel's weight pack takes the
+// halo-patch kernel before the pointwise ones; data gradient: the pointwise kernels come first.  No wpack, no halo-patch kernel.
+int conv_choose_fwd(const addk_conv_args* a, int mode, int mask, ConvChoice& c) {
   ADDK_REQUIRE(a && a->nsrc >= 1 && a->nsrc <= ADDK_MAX_SRC, "conv_fwd: nsrc out of range");
   ADDK_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0 && a->Cout > 0, "conv_fwd: empty shape");
   ADDK_REQUIRE(a->KH > 0 && a->KW > 0 && a->stride > 0 && a->dil > 0, "conv_fwd: bad kernel geometry");
   ADDK_REQUIRE(a->w && a->y && a->ldy >= a->Cout, "conv_fwd: null/short output");
   ADDK_REQUIRE(!a->stats || a->stats_ld == 0 || a->stats_ld >= a->Cout, "conv_fwd: stats_ld < Cout");
-  // every output pixel must map inside the padded input (guards against OOB reads by construction:
-  // taps outside [0,H) are masked, so only the geometry of the output grid needs checking)
-  ConvK k;
   long ctot = 0;
-  k.vecA = 1;
   for (int i = 0; i < a->nsrc; ++i) {
-    k.src[i] = a->src[i];
     ADDK_REQUIRE(a->src[i].x && a->src[i].C > 0 && a->src[i].ld >= a->src[i].C, "conv_fwd: bad source %d", i);
     ADDK_REQUIRE((a->src[i].a == nullptr) == (a->src[i].b == nullptr), "conv_fwd: a/b must come together");
-    if (!src_vec_ok(a->src[i])) k.vecA = 0;
     ctot += a->src[i].C;
   }
   ADDK_REQUIRE(a->w_choff + ctot <= a->cin_total, "conv_fwd: sources exceed cin_total");
   ADDK_REQUIRE(a->ldw >= a->KH * a->KW * a->cin_total, "conv_fwd: ldw too small");
-  if (a->wpack && a->KH == 1 && a->KW == 1) {             // a 1x1 conv whose caller set up the split kernel's weight pack: that path first
-    int r = addk_c3_try_fwd(a, addk_conv_rows((long)a->N * a->OH * a->OW, a->Cout), stream);
-    if (r <= 0) return r;
-  }
-  if (pw_enabled()) {      // small pointwise shapes: register-stationary kernel (pw.hip)
-    int r = addk_pw_try_fwd(a, addk_conv_rows((long)a->N * a->OH * a->OW, a->Cout), stream);
-    if (r <= 0) return r;
-  }
-  if (a->wpack) {                                          // wide 3x3 stride-1: halo-patch kernel (conv3.hip)
-    int r = addk_c3_try_fwd(a, addk_conv_rows((long)a->N * a->OH * a->OW, a->Cout), stream);
-    if (r <= 0) return r;
-  }
+  const long P = (long)a->N * a->OH * a->OW;
+  c = ConvChoice{};
+  c.key = -1; c.launches = 1; c.rows = addk_conv_rows(P, a->Cout);
+  if (c3_choose_fwd(a, mode, mask, c)) return ADDK_OK;
+  if ((mask & ADDK_FAST_PW) && pw_choose_fwd(a, c)) return ADDK_OK;
   for (int i = 0; i < a->nsrc; ++i)
     ADDK_REQUIRE(a->src[i].rs_hw == 0, "conv_fwd: source %d is a resampled map (rs_hw) but the launch is not one addk_conv_fwd_resample_ok() accepts", i);
+  ADDK_REQUIRE(P < (1L << 30) && (long)a->N * a->H * a->W < (1L << 30), "conv_fwd: tensor too large for 32-bit pixel indexing");
+  choose_generic(c, P, a->Cout);
+  return ADDK_OK;
+}
+
+int conv_choose_dgrad(const addk_conv_dgrad_args* a, int mode, int mask, ConvChoice& c) {
+  ADDK_REQUIRE(a && a->dy && a->w && a->g && a->dst.x, "conv_dgrad: null pointer");
+  ADDK_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0 && a->Cout > 0 && a->dst.C > 0, "conv_dgrad: empty shape");
+  ADDK_REQUIRE(a->lddy >= a->Cout && a->ldg >= a->dst.C && a->dst.ld >= a->dst.C, "conv_dgrad: short stride");
+  ADDK_REQUIRE(a->w_choff + a->dst.C <= a->cin_total && a->ldw >= a->KH * a->KW * a->cin_total, "conv_dgrad: weight layout");
+  ADDK_REQUIRE((a->dst.a == nullptr) == (a->dst.b == nullptr), "conv_dgrad: a/b must come together");
+  const long P = (long)a->N * a->H * a->W;
+  c = ConvChoice{};
+  c.key = -1; c.launches = 1; c.rows = addk_conv_rows(P, a->dst.C);
+  if ((mask & ADDK_FAST_PW) && pw_choose_dgrad(a, c)) return ADDK_OK;
+  if (c3_choose_dgrad(a, mode, mask, c)) return ADDK_OK;
+  ADDK_REQUIRE(P < (1L << 30) && (long)a->N * a->OH * a->OW < (1L << 30), "conv_dgrad: tensor too large for 32-bit pixel indexing");
+  if (a->stride == 2 && a->KH * a->KW <= 9 && c.rows % 4 == 0 && a->H >= 2 && a->W >= 2) choose_parity(c, a);
+  else choose_generic(c, P, a->dst.C);
+  return ADDK_OK;
+}
+
+extern "C" int addk_conv_fwd(const addk_conv_args* a, void* stream) {
+  ConvChoice c;
+  if (const int rc = conv_choose_fwd(a, conv_precision(), fast_paths(), c)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (conv_kind_halo(c.kind)) return c3_run_fwd(c, a, st);
+  if (c.kind != CK_GENERIC) return pw_run_fwd(c, a, st);
+  ConvK k;
   k.nsrc = a->nsrc;
+  k.vecA = 1;
+  bool chan4 = true;
+  for (int i = 0; i < a->nsrc; ++i) {
+    k.src[i] = a->src[i];
+    if (!src_vec_ok(a->src[i])) k.vecA = 0;
+    chan4 = chan4 && (a->src[i].C % 4 == 0);
+  }
   k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
   k.KH = a->KH; k.KW = a->KW; k.stride = a->stride; k.pad = a->pad; k.dil = a->dil;
   k.Cn = a->Cout; k.ldw = a->ldw; k.cin_total = a->cin_total; k.w_choff = a->w_choff; k.ldy = a->ldy;
   k.w = a->w; k.y = a->y; k.bias = a->bias; k.bias_n = a->bias_n; k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
   k.accumulate = 0; k.dst = addk_src{nullptr, nullptr, nullptr, 0, 0, 0, 0};
   k.sub = 1; k.ph = k.pw = 0; k.MH = k.MW = 0; k.ntaps_l = 0; k.kill = 0; k.ncls = 0;
-  bool chan4 = true;
-  for (int i = 0; i < a->nsrc; ++i) chan4 = chan4 && (a->src[i].C % 4 == 0);
   k.vecB = aligned16(a->w) && a->ldw % 4 == 0 && a->cin_total % 4 == 0 && a->w_choff % 4 == 0 && chan4;
   k.vecY = aligned16(a->y) && a->ldy % 4 == 0;
-  k.P = (long)a->N * a->OH * a->OW;
-  ADDK_REQUIRE(k.P < (1L << 30) && (long)a->N * a->H * a->W < (1L << 30), "conv_fwd: tensor too large for 32-bit pixel indexing");
-  return launch<MODE_FWD>(k, (hipStream_t)stream);
+  k.P = c.P;
+  return launch<MODE_FWD>(k, c.v[0], c.v[1], c.gx, st);
 }
 
 extern "C" int addk_conv_dgrad(const addk_conv_dgrad_args* a, void* stream) {
-  ADDK_REQUIRE(a && a->dy && a->w && a->g && a->dst.x, "conv_dgrad: null pointer");
-  ADDK_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0 && a->Cout > 0 && a->dst.C > 0, "conv_dgrad: empty shape");
-  ADDK_REQUIRE(a->lddy >= a->Cout && a->ldg >= a->dst.C && a->dst.ld >= a->dst.C, "conv_dgrad: short stride");
-  ADDK_REQUIRE(a->w_choff + a->dst.C <= a->cin_total && a->ldw >= a->KH * a->KW * a->cin_total, "conv_dgrad: weight layout");
-  ADDK_REQUIRE((a->dst.a == nullptr) == (a->dst.b == nullptr), "conv_dgrad: a/b must come together");
-  if (pw_enabled()) {
-    int r = addk_pw_try_dgrad(a, addk_conv_rows((long)a->N * a->H * a->W, a->dst.C), stream);
-    if (r <= 0) return r;
-  }
-  if (a->wpack) {
-    int r = addk_c3_try_dgrad(a, addk_conv_rows((long)a->N * a->H * a->W, a->dst.C), stream);
-    if (r <= 0) return r;
-  }
+  ConvChoice c;
+  if (const int rc = conv_choose_dgrad(a, conv_precision(), fast_paths(), c)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (conv_kind_halo(c.kind)) return c3_run_dgrad(c, a, st);
+  if (c.kind != CK_GENERIC && c.kind != CK_PARITY) return pw_run_dgrad(c, a, st);
   ConvK k;
   k.nsrc = 1;
   k.src[0] = addk_src{a->dy, nullptr, nullptr, a->lddy, a->Cout, 0, 0};
@@ -631,94 +721,50 @@ extern "C" int addk_conv_dgrad(const addk_conv_dgrad_args* a, void* stream) {
   k.dst = a->dst; k.accumulate = a->accumulate;
   k.vecB = aligned16(a->w) && a->ldw % 4 == 0 && a->cin_total % 4 == 0 && a->w_choff % 4 == 0 && a->dst.C % 4 == 0;
   k.vecY = aligned16(a->g) && a->ldg % 4 == 0 && src_vec_ok(a->dst);
-  k.P = (long)a->N * a->H * a->W;
-  ADDK_REQUIRE(k.P < (1L << 30) && (long)a->N * a->OH * a->OW < (1L << 30), "conv_dgrad: tensor too large for 32-bit pixel indexing");
   k.sub = 1; k.ph = k.pw = 0; k.MH = k.MW = 0; k.ntaps_l = 0; k.kill = 0; k.ncls = 0;
-  const int rows = addk_conv_rows(k.P, a->dst.C);
-  if (a->stride == 2 && a->KH * a->KW <= 9 && rows % 4 == 0 && a->H >= 2 && a->W >= 2) {
-    // Stride 2: an input pixel only receives the taps whose offset matches its parity, (1,2,2,4) of the 9 taps of a 3x3
-    // for the four (row, column) parity classes.  One launch per class over that class's quarter of the pixels does
-    // 9/4 tap-chunks per pixel instead of 9 masked ones; each class writes its own quarter of the (dA,dB) slab rows.
-    const long Pfull = k.P;
-    // classes that no tap reaches (3 of 4 for a 1x1 stride-2 conv: FactorizedReduce) have a zero gradient: they are only
-    // launched when the gradient buffer is being first-touched (to write the zeros), and the (dA,dB) slab rows are shared
-    // out among the classes that do have taps.
-    int ntl[4], tl[4][9], nvalid = 0;
-    for (int cl = 0; cl < 4; ++cl) {
-      const int ph = cl >> 1, pw = cl & 1;
-      ntl[cl] = 0;
-      for (int kh = 0; kh < a->KH; ++kh)
-        for (int kw = 0; kw < a->KW; ++kw)
-          if ((ph + a->pad - kh * a->dil) % 2 == 0 && (pw + a->pad - kw * a->dil) % 2 == 0) tl[cl][ntl[cl]++] = kh * a->KW + kw;
-      if (ntl[cl]) ++nvalid;
+  k.P = c.P;
+  if (c.kind == CK_GENERIC) return launch<MODE_DGRAD>(k, c.v[0], c.v[1], c.gx, st);
+  k.sub = 2;
+  auto slab_at = [&](int row) { return k.slab && row >= 0 ? k.slab + (long)row * k.slab_ld * 2 : nullptr; };
+  if (c.launches == 1) {        // all classes in one launch: workgroups [gx0, gx0 + gx) run class i
+    for (int i = 0; i < c.ncls; ++i) {
+      const ConvChoice::Cls& q = c.cls[i];
+      ConvK::Cls& d = k.cl[i];
+      d.ph = q.ph; d.pw = q.pw; d.MH = q.MH; d.MW = q.MW; d.P = q.P; d.ntaps_l = q.ntaps; d.kill = q.kill; d.pad_ = 0;
+      for (int j = 0; j < 9; ++j) d.taplist[j] = q.taplist[j];
+      d.slab = slab_at(q.slab_row); d.gx0 = q.gx0;
     }
-    if (nvalid == 0 || rows % nvalid != 0) nvalid = 0;       // 0: fall back to a quarter of the rows per class, every class launched
-    if (rows >= 16) {
-      // ONE launch for all classes (each alone is rows/4 workgroups = one per CU at the stems' sizes: 1 wave per SIMD).
-      // The slab rows (= workgroups) are shared out in proportion to the classes' tap counts so that they finish together;
-      // classes without taps get workgroups beyond the slab (they only store zeros, and only on a first touch).
-      ConvK c = k;
-      c.sub = 2; c.ncls = 0;
-      int tot = 0, nv = 0;
-      for (int cl = 0; cl < 4; ++cl) { tot += ntl[cl]; if (ntl[cl]) ++nv; }
-      int gx0 = 0, left = rows, seen = 0;
-      long pmax = 0;
-      for (int pass = 0; pass < 2; ++pass)          // classes with taps first: their workgroups are the slab rows 0..rows-1
-        for (int cl = 0; cl < 4; ++cl) {
-          if ((ntl[cl] > 0) != (pass == 0)) continue;
-          if (pass == 1 && a->accumulate) continue;            // nothing to add
-          ConvK::Cls& q = c.cl[c.ncls];
-          q.ph = cl >> 1; q.pw = cl & 1;
-          q.MH = (a->H - q.ph + 1) / 2; q.MW = (a->W - q.pw + 1) / 2;
-          q.P = (long)a->N * q.MH * q.MW;
-          q.ntaps_l = ntl[cl] ? ntl[cl] : 1; q.kill = ntl[cl] ? 0 : 1; q.pad_ = 0;
-          for (int i = 0; i < 9; ++i) q.taplist[i] = i < ntl[cl] ? tl[cl][i] : 0;
-          int gx;
-          if (pass == 0) {
-            ++seen;
-            gx = seen == nv ? left : (int)((long)rows * ntl[cl] / tot);
-            if (gx < 1) gx = 1;
-            if (gx > left - (nv - seen)) gx = left - (nv - seen);
-            q.slab = k.slab ? k.slab + (long)gx0 * k.slab_ld * 2 : nullptr;
-            left -= gx;
-          } else {
-            gx = rows / 4; q.slab = nullptr;
-          }
-          q.gx0 = gx0; gx0 += gx;
-          if (q.P > pmax) pmax = q.P;
-          ++c.ncls;
-        }
-      if (nv == 0) return ADDK_OK;               // cannot happen for a convolution (some tap always matches some class)
-      c.P = pmax;
-      return launch<MODE_DGRAD>(c, (hipStream_t)stream, gx0);
-    }
-    int vi = 0;
-    for (int cl = 0; cl < 4; ++cl) {
-        const int ph = cl >> 1, pw = cl & 1;
-        ConvK c = k;
-        c.sub = 2; c.ph = ph; c.pw = pw;
-        c.MH = (a->H - ph + 1) / 2; c.MW = (a->W - pw + 1) / 2;
-        c.P = (long)a->N * c.MH * c.MW;
-        c.ntaps_l = ntl[cl];
-        for (int i = 0; i < ntl[cl]; ++i) c.taplist[i] = tl[cl][i];
-        int gx = rows / 4;
-        if (c.ntaps_l == 0) {
-          c.taplist[0] = 0; c.ntaps_l = 1; c.kill = 1;
-          if (nvalid) {
-            if (a->accumulate) continue;            // nothing to add
-            c.slab = nullptr;
-          }
-        } else if (nvalid) {
-          gx = rows / nvalid;
-          if (c.slab) c.slab = k.slab + (long)vi * gx * k.slab_ld * 2;
-          ++vi;
-        }
-        if (!nvalid && c.slab) c.slab = k.slab + (long)cl * (rows / 4) * k.slab_ld * 2;
-        int rc = launch<MODE_DGRAD>(c, (hipStream_t)stream, gx);
-        if (rc) return rc;
-    }
-    (void)Pfull;
-    return ADDK_OK;
+    k.ncls = c.ncls;
+    return launch<MODE_DGRAD>(k, c.v[0], c.v[1], c.gx, st);
   }
-  return launch<MODE_DGRAD>(k, (hipStream_t)stream);
+  for (int i = 0; i < c.ncls; ++i) {
+    const ConvChoice::Cls& q = c.cls[i];
+    ConvK s = k;
+    s.ph = q.ph; s.pw = q.pw; s.MH = q.MH; s.MW = q.MW; s.P = q.P; s.ntaps_l = q.ntaps; s.kill = q.kill;
+    for (int j = 0; j < 9; ++j) s.taplist[j] = q.taplist[j];
+    s.slab = slab_at(q.slab_row);
+    if (const int rc = launch<MODE_DGRAD>(s, q.pt, q.ct, q.gx, st)) return rc;
+  }
+  return ADDK_OK;
+}
+
+// cfg[8] = kind, template parameters (4), grid x, grid y, launches (include/addk.h)
+static void conv_config(const ConvChoice& c, int32_t* cfg) {
+  cfg[0] = c.kind;
+  for (int i = 0; i < 4; ++i) cfg[1 + i] = c.v[i];
+  cfg[5] = c.gx; cfg[6] = c.gy; cfg[7] = c.launches;
+}
+extern "C" int addk_conv_fwd_config(const addk_conv_args* a, int32_t* cfg) {
+  ADDK_REQUIRE(cfg, "conv_fwd_config: null cfg");
+  ConvChoice c;
+  if (const int rc = conv_choose_fwd(a, conv_precision(), fast_paths(), c)) return rc;
+  conv_config(c, cfg);
+  return ADDK_OK;
+}
+extern "C" int addk_conv_dgrad_config(const addk_conv_dgrad_args* a, int32_t* cfg) {
+  ADDK_REQUIRE(cfg, "conv_dgrad_config: null cfg");
+  ConvChoice c;
+  if (const int rc = conv_choose_dgrad(a, conv_precision(), fast_paths(), c)) return rc;
+  conv_config(c, cfg);
+  return ADDK_OK;
 }

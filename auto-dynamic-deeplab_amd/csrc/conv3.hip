@@ -15,6 +15,7 @@
 // Reference call sites: decoder.py:17-27 (3x3 conv+BN+ReLU x2), aspp_train.py:20-41 (dilated 3x3 branches),
 // ADD.py:220-232 (stem1); autograd of nn.Conv2d for the data gradient.
 #include "conv3b.h"
+#include "conv.h"
 
 namespace {
 
@@ -489,8 +490,6 @@ int c3b_wc(int Cn, long P) {
   return best;
 }
 
-bool c3_enabled() { return (addk_get_fast_paths() & ADDK_FAST_CONV3) != 0; }
-inline bool c3b_pointwise_enabled() { return addk_env("ADDK_C3B_POINTWISE", 1) != 0; }
 // bf16 planes of a launch (3: six product terms, 2: three), or 0 = the exact fp32 MFMA kernel.  Every halo launch takes the
 // split kernel, the <= 64-channel ones (stem1, the cells' 40-channel dilated convs) on 4-wave blocks = 2 channel tiles x 2
 // pixel halves (PH = 2; the first 2-wave form staged 13-22 slots per thread, spilled and was slower than fp32: 125 vs 78 us
@@ -500,14 +499,11 @@ inline bool c3b_pointwise_enabled() { return addk_env("ADDK_C3B_POINTWISE", 1) !
 // a sample of that spread: over four more draws at 2x512x1024 split-bf16 everywhere was CLOSER to fp64 than the fp32 kernels
 // in all four (median 0.40-0.89x the fp32 oracle's error against 0.84-1.22x; profiles/r02_split_threshold_study.txt).
 // addk_set_split_min_channels(n) keeps launches with fewer than n output channels on the fp32 kernel.
-int g_c3b_minc = -1;
-inline int c3_planes(int Cn, int taps) {
-  const int m = addk_get_conv_precision();
-  (void)taps;
-  if (g_c3b_minc < 0) g_c3b_minc = 0;
-  if (m == 0 || Cn < g_c3b_minc) return 0;
-  if (m == 3) return Cn >= 192 ? 2 : 3;          // tail_x3: three product terms in the exit heads (ASPP, decoder: 256 / 304 / 400 channels), six elsewhere
-  return m == 2 ? 3 : 2;
+int g_c3b_minc = 0;
+inline int c3_planes(int mode, int Cn) {
+  if (mode == 0 || Cn < g_c3b_minc) return 0;
+  if (mode == 3) return Cn >= 192 ? 2 : 3;       // tail_x3: three product terms in the exit heads (ASPP, decoder: 256 / 304 / 400 channels), six elsewhere
+  return mode == 2 ? 3 : 2;
 }
 // Column block (16-channel tiles per block).  128-channel blocks (2x2 waves) for the wide heads when that still
 // yields >= 512 blocks; otherwise the narrowest of 3/4/5 tiles that pads the channel count least (cells: 40 -> 3 tiles,
@@ -523,214 +519,218 @@ int c3_bct(int Cn, long P) {
   }
   return best;
 }
-// [r5] the 16-wide-tile kernel (conv3n.hip) takes the stride-1 3x3 / 5x5 launches at dilation <= 2 with at most 48 output channels (the cells' dilated convs at 40
-// channels, forward and data gradient).  ADDK_C3N=0: those launches stay on conv3b_kernel's 64-channel blocks.
-inline bool c3n_shape(int Cn, int taps, int dil, int stride) {
-  // (the 3x3 stays on conv3b_kernel: 24.8 against 25.4-26.8 us at 2x125x253 — one workgroup per CU leaves its 13 K-steps nothing to hide the staging behind;
-  //  ADDK_C3N=2 routes it here too)
-  const int on = addk_env("ADDK_C3N", 1);
-  return on != 0 && Cn <= 48 && (taps == 25 || (taps == 9 && on == 2)) && dil <= 2 && stride == 1 && c3_planes(Cn, taps) != 0;
-}
 inline int c3n_steps(int taps, int valid) { return valid <= 8 ? (taps + 3) / 4 : (taps + 1) / 2; }
-long c3_pack_floats(int Cn, int nchunks, long P, int taps, int dil = 0, int stride = 1) {
-  if (dil > 0 && c3n_shape(Cn, taps, dil, stride))     // 16-wide tiles: 1 KB per (K-step, 16-row tile, plane); a chunk has at most (taps + 1) / 2 steps
-    return (long)nchunks * ((taps + 1) / 2) * 3 * c3_planes(Cn, taps) * 256 + (c3_planes(Cn, taps) == 2 ? C3_TRAILER : 0);
-  if (const int np = c3_planes(Cn, taps)) {            // bf16 / fp16 planes: 1 KB per (tap, 32-row tile, plane); split-fp16: + the scale trailer (PackK.amax)
-    const int wc = c3b_wc(Cn, P);
-    return (long)cdiv(Cn, 32 * wc) * nchunks * taps * wc * np * 256 + (np == 2 ? C3_TRAILER : 0);
-  }
-  const int bct = c3_bct(Cn, P);
-  return (long)cdiv(Cn, 16 * bct) * nchunks * taps * bct * 256;
-}
-bool c3_geometry_ok(int KH, int KW, int stride, int pad, int dil, int H, int W, int OH, int OW, long P, int Cn, int ktot = 0, bool fwd = false) {
+
+// Does a halo-patch kernel take this geometry?  (H, W: input map; OH, OW: output map of the forward convolution, for both directions)
+bool c3_geometry_ok(int mode, int mask, int KH, int KW, int stride, int pad, int dil, int H, int W, int OH, int OW, long P, int Cn, bool fwd) {
+  if (!(mask & ADDK_FAST_CONV3)) return false;
   if (KH == 1 && KW == 1) {      // wide pointwise heads (ASPP 1x1, the 1280 -> 256 concat conv): the split kernel as a plain GEMM (KS = 1)
     // (the FORWARD of the cells' many-input glue convs, K = 200..800 -> 40..160, was measured on this path in round 3 and is NOT taken: 28.6 vs 29.4 us
     // per launch at 40 output channels, 41.6 vs 25.7 us at 80 — the streaming-K fp32 kernel (pwk_kernel) is memory-bound on those shapes)
-    (void)ktot;
-    return c3_enabled() && c3b_pointwise_enabled() && stride == 1 && dil == 1 && pad == 0 && OH == H && OW == W && Cn >= 192 && c3_planes(Cn, 1) != 0 &&
-           W >= 48 && P >= 2048;
+    return stride == 1 && dil == 1 && pad == 0 && OH == H && OW == W && Cn >= 192 && c3_planes(mode, Cn) != 0 && W >= 48 && P >= 2048;
   }
   if (stride == 2) {             // [r3] stem2 (3x3, stride 2, pad 1) forward on the split kernel: 128-channel blocks of 4 waves, de-interleaved patch rows
-    if (!(addk_env("ADDK_C3B_STRIDE2", 1) && c3_enabled() && KH == 3 && KW == 3 && dil == 1 && pad == 1 && OH == (H - 1) / 2 + 1 && OW == (W - 1) / 2 + 1 && c3_planes(Cn, 9) != 0 && OW >= 96)) return false;
+    if (!(KH == 3 && KW == 3 && dil == 1 && pad == 1 && OH == (H - 1) / 2 + 1 && OW == (W - 1) / 2 + 1 && c3_planes(mode, Cn) != 0 && OW >= 96)) return false;
     if (fwd) return Cn >= 96 && c3b_wc(Cn, (long)P) == 4 && P >= 8192;
-    return Cn >= 32 && Cn <= 64 && P >= 32768;      // data gradient: the four parity classes as 2-tile blocks (c3b_s2_dgrad)
+    return Cn >= 32 && Cn <= 64 && P >= 32768;      // data gradient: the four parity classes as 2-tile blocks (conv3s_kernel)
   }
-  if (!c3_enabled() || KH != KW || !(KH == 3 || KH == 5) || stride != 1 || dil < 1 || dil > c3_maxdil(KH)) return false;
+  if (KH != KW || !(KH == 3 || KH == 5) || stride != 1 || dil < 1 || dil > c3_maxdil(KH)) return false;
   if (!(pad == dil * (KH / 2) && OH == H && OW == W && Cn >= 32)) return false;
   if (dil <= 2 && H < 2 * dil) return false;      // two-row tiles (the one-row forms of these shapes are not instantiated)
   // the split kernel has half-width (64-pixel) tiles and also takes the 32x64 maps of level 3 (dil_conv at 160 channels: 152 us on
   // the generic kernel); the fp32 halo kernel keeps its 128-pixel tiles and the larger maps
-  if (c3_planes(Cn, KH * KW)) return W >= 48 && P >= 2048;
+  if (c3_planes(mode, Cn)) return W >= 48 && P >= 2048;
   return W >= 100 && P >= 8192;
 }
 
-// the pack of one launch on its own stream position (the plans hoist all packs into one addk_conv_pack_batch): split-fp16 packs run the amax pass first
-void c3_pack_now(const PackK& pk, int pb, hipStream_t st) {
-  if (pk.planes == 2) hipLaunchKernelGGL(c3_pack_amax_kernel, dim3(C3_AMAX_WG), dim3(256), 0, st, pk);
-  hipLaunchKernelGGL(c3_pack_kernel, dim3(pb), dim3(256), 0, st, pk);
+// Kind, tile walk, grid, LDS and weight-pack layout of a halo launch with Cn output channels over the N x H x W output map (data gradient: the
+// gradient map) whose K side is the chunks cvalid[0..nch) of <= 16 channels
+void c3_layout(ConvChoice& c, int mode, int dir, int Cn, int N, int H, int W, int taps, int dil, int st, int nch, const int* cvalid) {
+  const long P = (long)N * H * W;
+  const int np = c3_planes(mode, Cn);
+  const int ks = taps == 1 ? 1 : taps == 9 ? 3 : 5;
+  const long trailer = np == 2 ? C3_TRAILER : 0;      // split-fp16: the scale trailer of the pack (PackK.amax)
+  c.nchunks = nch; c.planes = np; c.dil_odd = 0; c.s2d = 0;
+  if (!np) {                        // exact fp32: conv3_kernel, 128-pixel one-row tiles, 16 x bct columns per block
+    c.kind = CK_HALO; c.bct = c3_bct(Cn, P); c.v[0] = c.bct; c.v[1] = ks;
+    c.nT = nch * taps; c.wp_blk = (long)nch * taps * c.bct * 256;
+    c.spr = cdiv(W, C3_BP); c.HT = H; c.ntiles = N * H * c.spr;
+    c.pack_floats = (long)cdiv(Cn, 16 * c.bct) * nch * taps * c.bct * 256;
+    c.pack_blocks = cdiv(c.pack_floats, 256 * 4);
+    c.gx = c.rows; c.gy = cdiv(Cn, 16 * c.bct);
+  } else if (st == 2 && dir == MODE_DGRAD) {
+    // stride-2 data gradient: every workgroup runs the four parity classes of the input pixel (1 / 2 / 2 / 4 taps) from one staged image of dy;
+    // a tile is dy row a x 64 positions b (gradient rows 2a, 2a + 1 x 128 pixels)
+    c.kind = CK_SPLIT_S2D; c.v[0] = np;
+    c.bct = 2; c.s2d = 1;
+    const long unit = (long)cdiv(Cn, 64) * nch * 2 * 64;       // 16-byte units per tap of the four class streams (c3b_pack_s2d_body)
+    c.nT = 9 * nch; c.wp_blk = unit * np;
+    c.HT = (H + 1) / 2; c.spr = cdiv((W + 1) / 2, 64); c.ntiles = N * c.HT * c.spr;
+    c.pack_floats = 9 * unit * np * 4 + trailer;
+    c.pack_blocks = cdiv(9 * unit, 256);
+    c.gx = c.rows < c.ntiles ? c.rows : c.ntiles; c.gy = 1;
+    c.lds = 2 * 64 * 16 + (size_t)np * 2 * (64 + 16) * 32;
+  } else if (Cn <= 48 && taps == 25 && dil <= 2 && st == 1) {
+    // [r5] the 16-wide-tile kernel (conv3n.hip) takes the 5x5 launches at dilation <= 2 with at most 48 output channels (the cells' dil_conv_5x5 at
+    // 40 channels, forward and data gradient).  The 3x3 stays on conv3b_kernel: 24.8 against 25.4-26.8 us at 2x125x253 — one workgroup per CU
+    // leaves its 13 K-steps nothing to hide the staging behind.
+    c.kind = CK_C3N; c.v[0] = ks; c.v[1] = np;
+    c.bct = 3; c.dil_odd = dil & 1; c.s2d = 2;
+    int steps = 0;
+    for (int i = 0; i < nch; ++i) steps += c3n_steps(taps, cvalid[i]);
+    c.nT = steps; c.wp_blk = 0;
+    c.HT = cdiv(H, 2 * dil) * dil; c.spr = cdiv(W, CN_BPX); c.ntiles = N * c.HT * c.spr;
+    // 1 KB per (K-step, 16-row tile, plane); a chunk has at most (taps + 1) / 2 steps
+    c.pack_floats = (long)nch * ((taps + 1) / 2) * 3 * np * 256 + trailer;
+    c.pack_blocks = cdiv((long)steps * 3 * 64, 256);
+    // one workgroup per tile at most: a workgroup without a tile would still queue for a CU's LDS and registers (989 slab rows against 252 tiles at 2x125x253)
+    c.gx = c.rows < c.ntiles ? c.rows : c.ntiles; c.gy = 1;
+    c.lds = 4 * 48 * 16 + (size_t)np * (ks + 1) * cn_pwp(ks) * 32;
+  } else {
+    const int wc = c3b_wc(Cn, P);
+    c.kind = CK_SPLIT; c.bct = wc; c.dil_odd = st == 2 ? 2 : (dil & 1);
+    c.nT = nch * taps; c.wp_blk = (long)nch * taps * wc * np * 64;          // 16-byte units per column block
+    const bool bigd = taps == 9 && dil > 2;
+    const int ph = wc == 2 ? 2 : 1;                                  // <= 64 channels: 4 waves = 2 channel tiles x 2 pixel halves
+    // half-width tiles where 128-pixel tiles leave the chip short of blocks (instantiated for 3- and 4-wave blocks)
+    const long blocks128 = (long)N * H * cdiv(W, C3_BP) * cdiv(Cn, 32 * wc);
+    const bool half = st == 1 && ph == 1 && (wc == 3 || wc == 4) && !(wc == 3 && bigd) && !(wc == 4 && ks == 5) && !(wc == 3 && ks == 1) && blocks128 < 384;      // (rows of <= 64 pixels land here too)
+    // quarter-width (32-pixel) tiles where even 64-pixel tiles leave the chip short of workgroups: the cells' dilated convs on the 32x64 maps ran as
+    // 128 workgroups of 3 waves — half the CUs idle, one wave per SIMD on the others, every LDS / weight round trip exposed
+    const long blocks64 = (long)N * H * cdiv(W, 64) * cdiv(Cn, 32 * wc);
+    const bool quarter = half && wc == 3 && !bigd && (ks == 3 || ks == 5) && blocks64 < 192;      // measured: 160 ch @ 32x64 85 -> 63 us (5x5), 45 -> 34 (3x3); 80 ch @ 63x127 (252 blocks) is slower quartered (53 -> 66)
+    const int bpx = st == 2 ? 64 : quarter ? 32 : half ? 64 : C3_BP;
+    // two-row tiles (2 rows, d apart, of half the one-row width) for the 3x3 / 5x5 launches at dilation <= 2: KS + 1 staged rows per two output rows
+    // (every 3x3 / 5x5 launch at dilation <= 2 of full width, or of half width on 3-wave blocks, takes them; c3_geometry_ok requires H >= 2 dil)
+    const bool tworow = st == 1 && (ks == 3 || ks == 5) && !bigd && (bpx == C3_BP || (bpx == 64 && wc == 3)) && H >= 2 * dil;
+    const int rpx = tworow ? bpx / 2 : bpx;                       // pixels per tile row
+    c.v[0] = wc; c.v[1] = ks; c.v[2] = rpx; c.v[3] = tworow ? 2 : 1;
+    c.HT = tworow ? cdiv(H, 2 * dil) * dil : H;
+    c.spr = cdiv(W, rpx); c.ntiles = N * c.HT * c.spr;
+    c.pack_floats = (long)cdiv(Cn, 32 * wc) * nch * taps * wc * np * 256 + trailer;      // 1 KB per (tap, 32-row tile, plane)
+    c.pack_blocks = cdiv((long)cdiv(Cn, 32 * wc) * c.nT * wc * 64, 256);              // one pack thread per (tile, lane)
+    // no workgroups without a tile (they would queue for LDS and registers just to write zeros); the channel blocks of a tile side by side (conv3b_kernel)
+    c.gx = (c.rows < c.ntiles ? c.rows : c.ntiles) * cdiv(Cn, 32 * wc); c.gy = 1;
+    c.lds = (size_t)((ph * 32 * wc * 16 + 15) & ~15) + (size_t)np * (tworow ? ks + 1 : ks) * cb_pwmax(ks, bigd, rpx, st) * 32;
+  }
+  if (c.pack_blocks > 4096) c.pack_blocks = 4096;
 }
 
-// stride-2 data gradient: one launch per parity class of the input pixel (each a stride-1 gather over dy with 1 / 2 / 2 / 4 taps and a
-// strided scatter of its outputs); the statistics-slab rows (= workgroups) are shared out in proportion to the tap counts
-int c3b_s2_dgrad(C3K& k, PackK& pk, int rows, hipStream_t st, bool packed, PackK* desc_out, int np) {
-  const int wc = 2;
-  pk.bct = wc; pk.mode = MODE_DGRAD; pk.Cn = k.Cn; pk.planes = np; pk.dil_odd = 0; pk.s2d = 1;
-  if (desc_out) { *desc_out = pk; return ADDK_OK; }
-  const long unit = (long)cdiv(k.Cn, 32 * wc) * pk.nchunks * wc * 64;
-  if (!packed) { int pb = cdiv(9 * unit, 256); if (pb > 4096) pb = 4096; c3_pack_now(pk, pb, st); }
-  // one launch: a tile is dy row a x 64 positions b (gradient rows 2a, 2a + 1 x 128 pixels), every workgroup runs all four parity classes from one staged image
-  const int HA = (k.OHo + 1) / 2, WA = (k.OWo + 1) / 2;
-  k.H = k.OHo; k.W = k.OWo;                 // the gradient map (k.IH, k.IW: the dy map)
-  k.HT = HA; k.spr = cdiv(WA, 64);
-  k.ntiles = k.N * HA * k.spr;
-  k.wp = pk.out;
-  k.wp_blk = unit * np;                       // 16-byte units per tap unit of the four class streams (c3b_pack_s2d_body)
-  k.nT = 9 * pk.nchunks;
-  k.red32 = 1;
-  k.slab_rows = rows;
-  dim3 grid(rows < k.ntiles ? rows : k.ntiles, 1);
-  if (!c3b_run_s2d(&k, np, grid, 0, st)) { addk_set_error("conv3b stride-2 data gradient: no instantiation"); return ADDK_ERR_UNSUPPORTED; }
-  return addk_check_launch("conv3b stride-2 data gradient");
+inline bool c3_pack_fits(const float* wpack, int64_t floats, int64_t need) { return wpack && aligned16(wpack) && floats >= need; }
+
+}  // namespace
+
+bool c3_choose_fwd(const addk_conv_args* a, int mode, int mask, ConvChoice& c) {
+  if (!c3_geometry_ok(mode, mask, a->KH, a->KW, a->stride, a->pad, a->dil, a->H, a->W, a->OH, a->OW, (long)a->N * a->OH * a->OW, a->Cout, true)) return false;
+  int cvalid[C3_MAXCH], nch = 0;
+  for (int i = 0; i < a->nsrc; ++i) {
+    if (!src_vec_ok(a->src[i]) || a->src[i].rs_hw) return false;
+    for (int c0 = 0; c0 < a->src[i].C; c0 += C3_BK) {
+      if (nch == C3_MAXCH) return false;
+      cvalid[nch++] = a->src[i].C - c0 < C3_BK ? a->src[i].C - c0 : C3_BK;
+    }
+  }
+  if (a->ldy % 4 || !aligned16(a->y)) return false;
+  ConvChoice h = c;
+  c3_layout(h, mode, MODE_FWD, a->Cout, a->N, a->OH, a->OW, a->KH * a->KW, a->dil, a->stride, nch, cvalid);
+  if (!c3_pack_fits(a->wpack, a->wpack_floats, h.pack_floats)) return false;
+  c = h;
+  return true;
+}
+bool c3_choose_dgrad(const addk_conv_dgrad_args* a, int mode, int mask, ConvChoice& c) {
+  if (!c3_geometry_ok(mode, mask, a->KH, a->KW, a->stride, a->pad, a->dil, a->H, a->W, a->OH, a->OW, (long)a->N * a->H * a->W, a->dst.C, false)) return false;
+  if (a->Cout % 4 || a->lddy % 4 || a->ldg % 4 || !aligned16(a->dy) || !aligned16(a->g) || !src_vec_ok(a->dst)) return false;
+  int cvalid[C3_MAXCH], nch = 0;
+  for (int c0 = 0; c0 < a->Cout; c0 += C3_BK) {
+    if (nch == C3_MAXCH) return false;
+    cvalid[nch++] = a->Cout - c0 < C3_BK ? a->Cout - c0 : C3_BK;
+  }
+  ConvChoice h = c;
+  c3_layout(h, mode, MODE_DGRAD, a->dst.C, a->N, a->H, a->W, a->KH * a->KW, a->dil, a->stride, nch, cvalid);
+  if (!c3_pack_fits(a->wpack, a->wpack_floats, h.pack_floats)) return false;
+  c = h;
+  return true;
 }
 
-// the <= 48-channel launches on 16-wide tiles (conv3n.hip)
-int c3n_launch(C3K& k, PackK& pk, int mode, int rows, hipStream_t st, bool packed, PackK* desc_out, int np) {
-  pk.bct = 3; pk.mode = mode; pk.Cn = k.Cn; pk.planes = np; pk.dil_odd = k.dil & 1; pk.s2d = 2;
-  int steps = 0;
-  for (int c = 0; c < pk.nchunks; ++c) { pk.sbase[c] = steps; steps += c3n_steps(pk.taps, pk.cvalid[c]); }
-  const int ks = pk.taps == 9 ? 3 : 5;
-  k.nT = steps;
-  k.wp = pk.out;
-  k.wp_blk = 0;
-  k.HT = cdiv(k.H, 2 * k.dil) * k.dil;
-  k.spr = cdiv(k.W, 128);
-  k.ntiles = k.N * k.HT * k.spr;
-  k.red32 = 1;
-  if (desc_out) { *desc_out = pk; return ADDK_OK; }
-  const long total = (long)steps * 3 * 64;
-  int pb = cdiv(total, 256); if (pb > 4096) pb = 4096;
-  if (!packed) c3_pack_now(pk, pb, st);
-  // one workgroup per tile at most: a workgroup without a tile would still queue for a CU's LDS and registers (989 slab rows against 252 tiles at 2x125x253)
-  k.slab_rows = rows;
-  if (!c3n_run(&k, ks, mode, np, dim3(rows < k.ntiles ? rows : k.ntiles, 1), st)) { addk_set_error("conv3n: no instantiation for %d taps", pk.taps); return ADDK_ERR_UNSUPPORTED; }
-  return addk_check_launch("conv3n");
+namespace {
+
+// the pack descriptor of a halo launch: the K chunks (fwd: channels of the sources inside a tap; dgrad: dy channels) and the choice's layout
+void c3_pack_fill(const ConvChoice& c, int dir, const float* w, int ldw, int cin_total, int w_choff, int taps, int wrows, int Cn,
+                  const addk_src* src, int nsrc, float* wpack, PackK& pk) {
+  pk = PackK{};
+  int nch = 0, choff = 0;
+  for (int i = 0; i < nsrc; ++i) {
+    for (int c0 = 0; c0 < src[i].C; c0 += C3_BK) {
+      pk.cbase[nch] = (dir == MODE_FWD ? w_choff : 0) + choff + c0;
+      pk.cvalid[nch] = src[i].C - c0 < C3_BK ? src[i].C - c0 : C3_BK;
+      ++nch;
+    }
+    choff += src[i].C;
+  }
+  pk.nchunks = nch; pk.taps = taps; pk.w = w; pk.ldw = ldw; pk.cin_total = cin_total; pk.w_choff = dir == MODE_FWD ? 0 : w_choff; pk.out = wpack;
+  pk.amax = c.planes == 2 ? wpack + (c.pack_floats - C3_TRAILER) : nullptr;
+  pk.wrows = wrows;
+  pk.mode = dir; pk.Cn = Cn; pk.bct = c.bct; pk.planes = c.planes; pk.dil_odd = c.dil_odd; pk.s2d = c.s2d;
+  if (c.kind == CK_C3N)
+    for (int i = 0, steps = 0; i < nch; ++i) { pk.sbase[i] = steps; steps += c3n_steps(taps, pk.cvalid[i]); }
+}
+void c3_pack_fill_fwd(const ConvChoice& c, const addk_conv_args* a, PackK& pk) {
+  c3_pack_fill(c, MODE_FWD, a->w, a->ldw, a->cin_total, a->w_choff, a->KH * a->KW, a->Cout, a->Cout, a->src, a->nsrc, a->wpack, pk);
+}
+void c3_pack_fill_dgrad(const ConvChoice& c, const addk_conv_dgrad_args* a, PackK& pk) {
+  const addk_src dy{a->dy, nullptr, nullptr, a->lddy, a->Cout, 0, 0};
+  c3_pack_fill(c, MODE_DGRAD, a->w, a->ldw, a->cin_total, a->w_choff, a->KH * a->KW, a->Cout, a->dst.C, &dy, 1, a->wpack, pk);
 }
 
-int c3b_launch(C3K& k, PackK& pk, int mode, int rows, hipStream_t st, bool packed, PackK* desc_out, int np) {
-  pk.s2d = 0;
-  if (k.st == 2 && mode == MODE_DGRAD) return c3b_s2_dgrad(k, pk, rows, st, packed, desc_out, np);
-  if (k.om == 1 && c3n_shape(k.Cn, pk.taps, k.dil, k.st)) return c3n_launch(k, pk, mode, rows, st, packed, desc_out, np);
-  const int wc = c3b_wc(k.Cn, k.P);
-  pk.bct = wc; pk.mode = mode; pk.Cn = k.Cn; pk.planes = np; pk.dil_odd = k.st == 2 ? 2 : (k.dil & 1);
-  k.nT = pk.nchunks * pk.taps;
-  k.wp = pk.out;
-  k.wp_blk = (long)pk.nchunks * pk.taps * wc * np * 64;          // 16-byte units per column block
-  const bool bigd = pk.taps == 9 && k.dil > 2;
-  const int ks = pk.taps == 1 ? 1 : pk.taps == 9 ? 3 : 5;
-  const int ph = wc == 2 ? 2 : 1;                                  // <= 64 channels: 4 waves = 2 channel tiles x 2 pixel halves
-  // half-width tiles where 128-pixel tiles leave the chip short of blocks (instantiated for 3- and 4-wave blocks)
-  const long blocks128 = (long)k.N * k.H * cdiv(k.W, C3_BP) * cdiv(k.Cn, 32 * wc);
-  const bool half = k.st == 1 && ph == 1 && (wc == 3 || wc == 4) && !(wc == 3 && bigd) && !(wc == 4 && ks == 5) && !(wc == 3 && ks == 1) && blocks128 < 384;      // (rows of <= 64 pixels land here too)
-  // quarter-width (32-pixel) tiles where even 64-pixel tiles leave the chip short of workgroups: the cells' dilated convs on the 32x64 maps ran as
-  // 128 workgroups of 3 waves — half the CUs idle, one wave per SIMD on the others, every LDS / weight round trip exposed
-  const long blocks64 = (long)k.N * k.H * cdiv(k.W, 64) * cdiv(k.Cn, 32 * wc);
-  const bool quarter = half && wc == 3 && !bigd && (ks == 3 || ks == 5) && blocks64 < 192;      // measured: 160 ch @ 32x64 85 -> 63 us (5x5), 45 -> 34 (3x3); 80 ch @ 63x127 (252 blocks) is slower quartered (53 -> 66)
-  const int bpx = k.st == 2 ? 64 : quarter ? 32 : half ? 64 : C3_BP;
-  // two-row tiles (2 rows, d apart, of half the one-row width) for the 3x3 / 5x5 launches at dilation <= 2: KS + 1 staged rows per two output rows
-  // (every 3x3 / 5x5 launch at dilation <= 2 of full width, or of half width on 3-wave blocks, takes them; c3_geometry_ok requires H >= 2 dil)
-  const bool tworow = k.st == 1 && (ks == 3 || ks == 5) && !bigd && k.om == 1 && (bpx == C3_BP || (bpx == 64 && wc == 3)) && k.H >= 2 * k.dil;
-  const int rpx = tworow ? bpx / 2 : bpx;                       // pixels per tile row
-  k.HT = tworow ? cdiv(k.H, 2 * k.dil) * k.dil : k.H;
-  k.spr = cdiv(k.W, rpx);
-  k.ntiles = k.N * k.HT * k.spr;
-  k.red32 = 1;
-  if (desc_out) { *desc_out = pk; return ADDK_OK; }
-  const long total = (long)cdiv(k.Cn, 32 * wc) * k.nT * wc * 64;   // pack threads: one per (tile, lane)
-  int pb = cdiv(total, 256); if (pb > 4096) pb = 4096;
-  if (!packed) c3_pack_now(pk, pb, st);
-  const size_t lds = (size_t)((ph * 32 * wc * 16 + 15) & ~15) + (size_t)np * (tworow ? ks + 1 : ks) * cb_pwmax(ks, bigd, rpx, k.st) * 32;
-  k.slab_rows = rows;
-  k.ny = cdiv(k.Cn, 32 * wc);
-  dim3 grid((rows < k.ntiles ? rows : k.ntiles) * k.ny, 1);      // no workgroups without a tile (they would queue for LDS and registers just to write zeros); the channel blocks of a tile side by side (conv3b_kernel)
-  // the instantiations live in conv3b_tr3 / conv3b_tr5 / conv3b_row / conv3b_s2.hip (compiled in parallel)
-  const bool done = tworow ? (ks == 3 ? c3b_run_tr3(&k, wc, rpx, mode, np, grid, lds, st) : c3b_run_tr5(&k, wc, rpx, mode, np, grid, lds, st)) != 0
-                  : k.st == 2 ? (ks == 3 && mode == MODE_FWD && c3b_run_s2f(&k, wc, bpx, np, grid, lds, st) != 0)
-                  : c3b_run_row(&k, wc, ks, bigd, bpx, mode, np, grid, lds, st) != 0;
-  if (!done) { addk_set_error("conv3b: no instantiation for %d waves, %d taps", wc, pk.taps); return ADDK_ERR_UNSUPPORTED; }
-  return addk_check_launch("conv3b");
-}
-
-int c3_launch(C3K& k, PackK& pk, int mode, int rows, hipStream_t st, bool packed, PackK* desc_out = nullptr) {
-  pk.planes = 0; pk.dil_odd = 0; pk.s2d = 0;
-  if (const int np = c3_planes(k.Cn, pk.taps)) return c3b_launch(k, pk, mode, rows, st, packed, desc_out, np);
-  const int bct = c3_bct(k.Cn, k.P);
-  pk.bct = bct; pk.mode = mode; pk.Cn = k.Cn;
-  k.nT = pk.nchunks * pk.taps;
-  k.wp = pk.out;
-  k.wp_blk = (long)pk.nchunks * pk.taps * bct * 256;
-  k.spr = cdiv(k.W, C3_BP);
-  k.ntiles = k.N * k.H * k.spr;
-  k.red32 = k.P >= 4096;
-  const long total = c3_pack_floats(k.Cn, pk.nchunks, k.P, pk.taps);
-  int pb = cdiv(total, 256 * 4); if (pb > 4096) pb = 4096;
-  if (desc_out) { *desc_out = pk; return ADDK_OK; }              // descriptor query only (addk_conv_*_pack_desc)
-  if (!packed) hipLaunchKernelGGL(c3_pack_kernel, dim3(pb), dim3(256), 0, st, pk);
-  dim3 grid(rows, cdiv(k.Cn, 16 * bct));
-  bool done = false;
+// the pack (unless a plan's addk_conv_pack_batch already wrote it), then the convolution; k holds the launch's tensors
+int c3_run(const ConvChoice& c, C3K& k, const PackK& pk, int dir, bool packed, hipStream_t st) {
+  k.wp = pk.out; k.wsc = pk.amax ? pk.amax + C3_AMAX_WG : nullptr;
+  k.nT = c.nT; k.wp_blk = c.wp_blk; k.HT = c.HT; k.spr = c.spr; k.ntiles = c.ntiles; k.slab_rows = c.rows;
+  k.red32 = c.kind == CK_HALO ? k.P >= 4096 : 1;
+  k.ny = c.kind == CK_SPLIT ? cdiv(k.Cn, 32 * c.v[0]) : 1;
+  if (!packed) {
+    if (pk.planes == 2) hipLaunchKernelGGL(c3_pack_amax_kernel, dim3(C3_AMAX_WG), dim3(256), 0, st, pk);
+    hipLaunchKernelGGL(c3_pack_kernel, dim3(c.pack_blocks), dim3(256), 0, st, pk);
+  }
+  const dim3 grid(c.gx, c.gy);
+  const int np = c.planes;
+  if (c.kind == CK_SPLIT_S2D) {
+    if (!c3b_run_s2d(&k, np, grid, c.lds, st)) { addk_set_error("conv3b stride-2 data gradient: no instantiation"); return ADDK_ERR_UNSUPPORTED; }
+    return addk_check_launch("conv3b stride-2 data gradient");
+  }
+  if (c.kind == CK_C3N) {
+    if (!c3n_run(&k, c.v[0], dir, np, grid, c.lds, st)) { addk_set_error("conv3n: no instantiation for %d taps", c.v[0] * c.v[0]); return ADDK_ERR_UNSUPPORTED; }
+    return addk_check_launch("conv3n");
+  }
+  if (c.kind == CK_SPLIT) {
+    // the instantiations live in conv3b_tr3 / conv3b_tr5 / conv3b_row / conv3b_s2.hip (compiled in parallel)
+    const int wc = c.v[0], ks = c.v[1], rpx = c.v[2];
+    const bool bigd = ks == 3 && k.dil > 2;
+    const bool done = c.v[3] == 2 ? (ks == 3 ? c3b_run_tr3(&k, wc, rpx, dir, np, grid, c.lds, st) : c3b_run_tr5(&k, wc, rpx, dir, np, grid, c.lds, st)) != 0
+                    : k.st == 2 ? (ks == 3 && dir == MODE_FWD && c3b_run_s2f(&k, wc, rpx, np, grid, c.lds, st) != 0)
+                    : c3b_run_row(&k, wc, ks, bigd, rpx, dir, np, grid, c.lds, st) != 0;
+    if (!done) { addk_set_error("conv3b: no instantiation for %d waves, %d taps", wc, ks * ks); return ADDK_ERR_UNSUPPORTED; }
+    return addk_check_launch("conv3b");
+  }
+  const int bct = c.v[0], ks = c.v[1];
 #define ADDK_C3(B_, K_) \
-  if (!done && bct == B_ && pk.taps == K_ * K_) { \
-    if (mode == MODE_FWD) hipLaunchKernelGGL((conv3_kernel<B_, K_, MODE_FWD>), grid, dim3(256), 0, st, k); \
+  if (bct == B_ && ks == K_) { \
+    if (dir == MODE_FWD) hipLaunchKernelGGL((conv3_kernel<B_, K_, MODE_FWD>), grid, dim3(256), 0, st, k); \
     else hipLaunchKernelGGL((conv3_kernel<B_, K_, MODE_DGRAD>), grid, dim3(256), 0, st, k); \
-    done = true; }
+    return addk_check_launch("conv3"); }
   ADDK_C3(3, 3) ADDK_C3(4, 3) ADDK_C3(5, 3) ADDK_C3(8, 3) ADDK_C3(3, 5) ADDK_C3(4, 5) ADDK_C3(5, 5)
 #undef ADDK_C3
-  if (!done) { addk_set_error("conv3: no instantiation for %d column tiles, %d taps", bct, pk.taps); return ADDK_ERR_UNSUPPORTED; }
-  return addk_check_launch("conv3");
+  addk_set_error("conv3: no instantiation for %d column tiles, %d taps", bct, ks * ks);
+  return ADDK_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
-// number of floats the packed-weight workspace of this launch needs; 0 = the halo-patch kernel does not apply
-extern "C" int64_t addk_conv_fwd_pack_floats(const addk_conv_args* a) {
-  if (!a || a->nsrc < 1 || a->nsrc > ADDK_MAX_SRC) return 0;
-  int ktot = 0;
-  for (int i = 0; i < a->nsrc; ++i) ktot += a->src[i].C;
-  if (!c3_geometry_ok(a->KH, a->KW, a->stride, a->pad, a->dil, a->H, a->W, a->OH, a->OW, (long)a->N * a->OH * a->OW, a->Cout, ktot, true)) return 0;
-  int nch = 0;
-  for (int i = 0; i < a->nsrc; ++i) { if (a->src[i].C % 4 || a->src[i].ld % 4) return 0; nch += cdiv(a->src[i].C, C3_BK); }
-  if (nch > C3_MAXCH || a->ldy % 4) return 0;
-  return c3_pack_floats(a->Cout, nch, (long)a->N * a->OH * a->OW, a->KH * a->KW, a->dil, a->stride);
-}
-extern "C" int64_t addk_conv_dgrad_pack_floats(const addk_conv_dgrad_args* a) {
-  if (!a) return 0;
-  if (!c3_geometry_ok(a->KH, a->KW, a->stride, a->pad, a->dil, a->H, a->W, a->OH, a->OW, (long)a->N * a->H * a->W, a->dst.C)) return 0;
-  if (a->Cout % 4 || a->lddy % 4 || a->ldg % 4 || a->dst.ld % 4 || a->dst.C % 4) return 0;
-  const int nch = cdiv(a->Cout, C3_BK);
-  if (nch > C3_MAXCH) return 0;
-  return c3_pack_floats(a->dst.C, nch, (long)a->N * a->H * a->W, a->KH * a->KW, a->dil, a->stride);
-}
-
-// 0 = launched, 1 = not covered (caller falls back to the generic kernel), <0 = error
-static int c3_fwd(const addk_conv_args* a, int rows, void* stream, PackK* desc_out) {
-  const int64_t need = addk_conv_fwd_pack_floats(a);
-  if (need == 0 || !a->wpack || a->wpack_floats < need) return 1;
-  if (!aligned16(a->y) || !aligned16(a->wpack)) return 1;
-  for (int i = 0; i < a->nsrc; ++i) if (!src_vec_ok(a->src[i])) return 1;
+int c3_run_fwd(const ConvChoice& c, const addk_conv_args* a, hipStream_t st) {
   C3K k; PackK pk;
+  c3_pack_fill_fwd(c, a, pk);
   k.nsrc = a->nsrc;
-  int nch = 0, choff = 0;
-  for (int i = 0; i < a->nsrc; ++i) {
-    k.src[i] = a->src[i];
-    for (int c0 = 0; c0 < a->src[i].C; c0 += C3_BK) {
-      pk.cbase[nch] = a->w_choff + choff + c0;
-      pk.cvalid[nch] = a->src[i].C - c0 < C3_BK ? a->src[i].C - c0 : C3_BK;
-      ++nch;
-    }
-    choff += a->src[i].C;
-  }
-  pk.nchunks = nch; pk.taps = a->KH * a->KW; pk.w = a->w; pk.ldw = a->ldw; pk.cin_total = a->cin_total; pk.w_choff = 0; pk.out = a->wpack;
-  pk.amax = c3_planes(a->Cout, pk.taps) == 2 ? a->wpack + (need - C3_TRAILER) : nullptr; k.wsc = pk.amax ? pk.amax + C3_AMAX_WG : nullptr;
-  pk.wrows = a->Cout;
+  for (int i = 0; i < a->nsrc; ++i) k.src[i] = a->src[i];
   k.N = a->N; k.H = a->OH; k.W = a->OW; k.IH = a->H; k.IW = a->W; k.dil = a->dil; k.st = a->stride;
   k.om = 1; k.oro = k.oco = 0; k.OHo = a->OH; k.OWo = a->OW;
   k.Cn = a->Cout; k.ldy = a->ldy; k.y = a->y; k.bias = a->bias; k.bias_n = a->bias_n;
@@ -738,25 +738,13 @@ static int c3_fwd(const addk_conv_args* a, int rows, void* stream, PackK* desc_o
   k.dst = addk_src{nullptr, nullptr, nullptr, 0, 0, 0, 0}; k.accumulate = 0;
   k.vecY = 1;
   k.P = (long)a->N * a->OH * a->OW;
-  return c3_launch(k, pk, MODE_FWD, rows, (hipStream_t)stream, a->wpack_ready != 0, desc_out);
+  return c3_run(c, k, pk, MODE_FWD, a->wpack_ready != 0, st);
 }
-
-static int c3_dgrad(const addk_conv_dgrad_args* a, int rows, void* stream, PackK* desc_out) {
-  const int64_t need = addk_conv_dgrad_pack_floats(a);
-  if (need == 0 || !a->wpack || a->wpack_floats < need) return 1;
-  if (!aligned16(a->dy) || !aligned16(a->g) || !aligned16(a->wpack) || !src_vec_ok(a->dst)) return 1;
+int c3_run_dgrad(const ConvChoice& c, const addk_conv_dgrad_args* a, hipStream_t st) {
   C3K k; PackK pk;
+  c3_pack_fill_dgrad(c, a, pk);
   k.nsrc = 1;
   k.src[0] = addk_src{a->dy, nullptr, nullptr, a->lddy, a->Cout, 0, 0};
-  int nch = 0;
-  for (int c0 = 0; c0 < a->Cout; c0 += C3_BK) {
-    pk.cbase[nch] = c0;
-    pk.cvalid[nch] = a->Cout - c0 < C3_BK ? a->Cout - c0 : C3_BK;
-    ++nch;
-  }
-  pk.nchunks = nch; pk.taps = a->KH * a->KW; pk.w = a->w; pk.ldw = a->ldw; pk.cin_total = a->cin_total; pk.w_choff = a->w_choff; pk.out = a->wpack;
-  pk.amax = c3_planes(a->dst.C, pk.taps) == 2 ? a->wpack + (need - C3_TRAILER) : nullptr; k.wsc = pk.amax ? pk.amax + C3_AMAX_WG : nullptr;
-  pk.wrows = a->Cout;
   k.N = a->N; k.H = a->H; k.W = a->W; k.IH = a->OH; k.IW = a->OW; k.dil = a->dil; k.st = a->stride;      // the gather runs over dy (OH x OW)
   k.om = 1; k.oro = k.oco = 0; k.OHo = a->H; k.OWo = a->W;
   k.Cn = a->dst.C; k.ldy = a->ldg; k.y = a->g; k.bias = nullptr; k.bias_n = nullptr;
@@ -764,8 +752,21 @@ static int c3_dgrad(const addk_conv_dgrad_args* a, int rows, void* stream, PackK
   k.dst = a->dst; k.accumulate = a->accumulate;
   k.vecY = 1;
   k.P = (long)a->N * a->H * a->W;
-  return c3_launch(k, pk, MODE_DGRAD, rows, (hipStream_t)stream, a->wpack_ready != 0, desc_out);
+  return c3_run(c, k, pk, MODE_DGRAD, a->wpack_ready != 0, st);
 }
+
+// Floats of `wpack` the launch's halo-patch kernel needs: the choice the launch would make with a large enough workspace.  0 = it takes another kernel.
+template <typename Args>
+static int64_t c3_pack_floats(const Args* a, int (*choose)(const Args*, int, int, ConvChoice&)) {
+  if (!a) return 0;
+  Args t = *a;
+  t.wpack = reinterpret_cast<float*>(alignof(float4)); t.wpack_floats = INT64_MAX;      // any aligned address: the choice never dereferences it
+  ConvChoice c;
+  if (choose(&t, addk_get_conv_precision(), addk_get_fast_paths(), c) || !conv_kind_halo(c.kind)) return 0;
+  return c.pack_floats;
+}
+extern "C" int64_t addk_conv_fwd_pack_floats(const addk_conv_args* a) { return c3_pack_floats(a, conv_choose_fwd); }
+extern "C" int64_t addk_conv_dgrad_pack_floats(const addk_conv_dgrad_args* a) { return c3_pack_floats(a, conv_choose_dgrad); }
 
 #ifdef ADDK_C3B_DIAG
 // (shader ticks, reference ticks, workgroups, 0) summed since the last call; resets the counters
@@ -776,23 +777,25 @@ extern "C" int addk_c3b_diag(unsigned long long* out12) {
 }
 #endif
 extern "C" int addk_set_split_min_channels(int c) { g_c3b_minc = c < 0 ? 0 : c; return ADDK_OK; }
-int addk_c3_try_fwd(const addk_conv_args* a, int rows, void* stream) { return c3_fwd(a, rows, stream, nullptr); }
-int addk_c3_try_dgrad(const addk_conv_dgrad_args* a, int rows, void* stream) { return c3_dgrad(a, rows, stream, nullptr); }
 
 // Hoisting the weight packs out of the step's critical path: a plan collects one descriptor per halo-patch launch,
 // uploads the table and runs ONE addk_conv_pack_batch at the start of the step; the launches then carry wpack_ready = 1.
 extern "C" int64_t addk_conv_pack_desc_bytes(void) { return (int64_t)sizeof(PackK); }
 extern "C" int addk_conv_fwd_pack_desc(const addk_conv_args* a, void* host_desc) {
   ADDK_REQUIRE(a && host_desc, "conv_fwd_pack_desc: null pointer");
-  const int r = c3_fwd(a, 1, nullptr, reinterpret_cast<PackK*>(host_desc));
-  if (r == 1) { addk_set_error("conv_fwd_pack_desc: the halo-patch kernel does not cover this launch"); return ADDK_ERR_UNSUPPORTED; }
-  return r;
+  ConvChoice c;
+  if (const int rc = conv_choose_fwd(a, addk_get_conv_precision(), addk_get_fast_paths(), c)) return rc;
+  if (!conv_kind_halo(c.kind)) { addk_set_error("conv_fwd_pack_desc: the launch does not take a halo-patch kernel"); return ADDK_ERR_UNSUPPORTED; }
+  c3_pack_fill_fwd(c, a, *reinterpret_cast<PackK*>(host_desc));
+  return ADDK_OK;
 }
 extern "C" int addk_conv_dgrad_pack_desc(const addk_conv_dgrad_args* a, void* host_desc) {
   ADDK_REQUIRE(a && host_desc, "conv_dgrad_pack_desc: null pointer");
-  const int r = c3_dgrad(a, 1, nullptr, reinterpret_cast<PackK*>(host_desc));
-  if (r == 1) { addk_set_error("conv_dgrad_pack_desc: the halo-patch kernel does not cover this launch"); return ADDK_ERR_UNSUPPORTED; }
-  return r;
+  ConvChoice c;
+  if (const int rc = conv_choose_dgrad(a, addk_get_conv_precision(), addk_get_fast_paths(), c)) return rc;
+  if (!conv_kind_halo(c.kind)) { addk_set_error("conv_dgrad_pack_desc: the launch does not take a halo-patch kernel"); return ADDK_ERR_UNSUPPORTED; }
+  c3_pack_fill_dgrad(c, a, *reinterpret_cast<PackK*>(host_desc));
+  return ADDK_OK;
 }
 extern "C" int addk_conv_pack_batch(const void* dev_descs, int32_t n, void* stream) {
   ADDK_REQUIRE(dev_descs && n > 0, "conv_pack_batch: bad args");

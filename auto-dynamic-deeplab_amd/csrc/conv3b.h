@@ -13,6 +13,8 @@ namespace {
 enum { MODE_FWD = 0, MODE_DGRAD = 1 };
 constexpr int C3_BP = 128;                 // pixels per tile (one row segment)
 constexpr int C3_BK = 16;                  // channels per chunk
+constexpr int CN_BPX = 128;                 // conv3n_kernel: pixels per tile row
+constexpr int cn_pwp(int ks) { return CN_BPX + (ks - 1) * 2; }       // conv3n_kernel: LDS row pitch in pixels (dilation <= 2)
 
 struct C3K {
   addk_src src[ADDK_MAX_SRC];
@@ -602,7 +604,7 @@ int c3b_run_tr5(const void* k, int wc, int rpx, int mode, int np, dim3 grid, siz
 int c3b_run_row(const void* k, int wc, int ks, bool bigd, int bpx, int mode, int np, dim3 grid, size_t lds, hipStream_t st);
 int c3b_run_s2f(const void* k, int wc, int bpx, int np, dim3 grid, size_t lds, hipStream_t st);
 int c3b_run_s2d(const void* k4, int np, dim3 grid, size_t lds, hipStream_t st);
-int c3n_run(const void* k, int ks, int mode, int np, dim3 grid, hipStream_t st);      // conv3n.hip: the <= 48-channel launches on 16-wide tiles
+int c3n_run(const void* k, int ks, int mode, int np, dim3 grid, size_t lds, hipStream_t st);      // conv3n.hip: the <= 48-channel 5x5 launches on 16-wide tiles
 #ifdef ADDK_C3B_DIAG
 void c3b_diag_tr3(unsigned long long* acc12); void c3b_diag_tr5(unsigned long long* acc12); void c3b_diag_row(unsigned long long* acc12); void c3b_diag_s2(unsigned long long* acc12);
 #endif

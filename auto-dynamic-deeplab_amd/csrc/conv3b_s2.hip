@@ -3,10 +3,8 @@
 #include "conv3b.h"
 
 #define C3B_GO(KERNEL, THREADS) { \
-    static bool attr = false; \
-    auto fn = &KERNEL; \
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr = true; } \
-    hipLaunchKernelGGL(fn, grid, dim3(THREADS), lds, st, k); return 1; }
+    addk_dyn_lds<KERNEL>(); \
+    hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), lds, st, k); return 1; }
 #ifdef ADDK_C3B_DIAG
 #define C3B_DIAG_READER(NAME) void NAME(unsigned long long* acc12) { \
     unsigned long long h[64][12]; \
@@ -297,15 +295,6 @@ __global__ void __launch_bounds__(256, 2) conv3s_kernel(const C3K p) {
 
 int c3b_run_s2d(const void* kp, int np, dim3 grid, size_t lds, hipStream_t st) {
   const C3K& k = *reinterpret_cast<const C3K*>(kp);
-  (void)lds;
-#define C3S_GO(P_) { \
-    static bool attr = false; \
-    auto fn = &conv3s_kernel<P_>; \
-    const size_t sz = 2 * 64 * 16 + (size_t)P_ * 2 * (64 + 16) * 32; \
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr = true; } \
-    hipLaunchKernelGGL(fn, grid, dim3(256), sz, st, k); return 1; }
-  if (np == 3) C3S_GO(3) else C3S_GO(2)
-#undef C3S_GO
-  return 0;
+  if (np == 3) C3B_GO(conv3s_kernel<3>, 256) else C3B_GO(conv3s_kernel<2>, 256)
 }
 C3B_DIAG_READER(c3b_diag_s2)

@@ -2,10 +2,8 @@
 #include "conv3b.h"
 
 #define C3B_GO(KERNEL, THREADS) { \
-    static bool attr = false; \
-    auto fn = &KERNEL; \
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr = true; } \
-    hipLaunchKernelGGL(fn, grid, dim3(THREADS), lds, st, k); return 1; }
+    addk_dyn_lds<KERNEL>(); \
+    hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), lds, st, k); return 1; }
 #ifdef ADDK_C3B_DIAG
 #define C3B_DIAG_READER(NAME) void NAME(unsigned long long* acc12) { \
     unsigned long long h[64][12]; \

@@ -1,5 +1,6 @@
-// conv3n.hip — the split-bf16 halo-patch convolution for AT MOST 48 OUTPUT CHANNELS (the cells' dil_conv_3x3 / dil_conv_5x5 at 40 channels,
+// conv3n.hip — the split-bf16 halo-patch 5x5 convolution for AT MOST 48 OUTPUT CHANNELS (the cells' dil_conv_5x5 at 40 channels,
 // operations.py:32-43 at F = 20, level 1; forward and data gradient) on 16-wide channel tiles: v_mfma_f32_16x16x32_bf16.
+// (The kernel body also has a 3x3 form, which is not instantiated: the 3x3 is faster on conv3b_kernel, conv3.hip c3_layout.)
 //
 // Why a second kernel.  conv3b_kernel's tiles are 32 output channels x 32 pixels x 16 input channels per matrix instruction: 40 output channels pad to 64 and
 // 40 input channels to 48 — 52 % of its matrix work is useful, and the matrix phase is 63-73 % of those launches' life (profiles/r05_c3b_ablation.txt).  Here:
@@ -19,8 +20,6 @@
 namespace {
 
 constexpr int CN_CT = 3;                    // 16-channel output tiles
-constexpr int CN_BPX = 128;                 // pixels per tile row
-constexpr int cn_pwp(int ks) { return CN_BPX + (ks - 1) * 2; }       // LDS row pitch in pixels (dilation <= 2)
 
 // reduce-scatter of 16 per-lane values over the 16 lanes of a DPP row (lane bits 3..0): lane l ends with the row's sum of value l & 15 in v[0]
 template <int N, int M>
@@ -399,19 +398,13 @@ __global__ void __launch_bounds__(256, 1) conv3n_kernel(const C3K p) {
 }  // namespace
 
 // 1 = launched, 0 = no instantiation; grid.x workgroups walk p.ntiles tiles of 2 rows x 128 pixels
-int c3n_run(const void* kp, int ks, int mode, int np, dim3 grid, hipStream_t st) {
+int c3n_run(const void* kp, int ks, int mode, int np, dim3 grid, size_t lds, hipStream_t st) {
   const C3K& k = *reinterpret_cast<const C3K*>(kp);
-#define C3N_GO(K_, M_, P_) { \
-    static bool attr = false; \
-    auto fn = &conv3n_kernel<K_, M_, P_>; \
-    const size_t lds = 4 * 48 * 16 + (size_t)P_ * (K_ + 1) * cn_pwp(K_) * 32; \
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64); attr = true; } \
-    hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, k); return 1; }
-#define C3N_K(K_) if (ks == K_) { \
-    if (mode == MODE_FWD) { if (np == 3) C3N_GO(K_, MODE_FWD, 3) else C3N_GO(K_, MODE_FWD, 2) } \
-    else { if (np == 3) C3N_GO(K_, MODE_DGRAD, 3) else C3N_GO(K_, MODE_DGRAD, 2) } }
-  C3N_K(3) C3N_K(5)
-#undef C3N_K
+  if (ks != 5) return 0;
+#define C3N_GO(M_, P_) { \
+    addk_dyn_lds<conv3n_kernel<5, M_, P_>>(); \
+    hipLaunchKernelGGL((conv3n_kernel<5, M_, P_>), grid, dim3(256), lds, st, k); return 1; }
+  if (mode == MODE_FWD) { if (np == 3) C3N_GO(MODE_FWD, 3) else C3N_GO(MODE_FWD, 2) }
+  else { if (np == 3) C3N_GO(MODE_DGRAD, 3) else C3N_GO(MODE_DGRAD, 2) }
 #undef C3N_GO
-  return 0;
 }

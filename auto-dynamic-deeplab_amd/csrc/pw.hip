@@ -11,7 +11,7 @@
 //     whole kernel; one butterfly + cross-wave LDS reduction at the very end writes the block's slab row.
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "conv.h"
 
 namespace {
 
@@ -518,22 +518,22 @@ static bool pw_config(PwK& k, int rows, PwCfg& c) {
 }
 
 template <int MODE>
-int pw_launch(PwK& k, int rows, hipStream_t st) {
-  PwCfg c;
-  if (!pw_config(k, rows, c)) return 1;                  // no instantiation: caller falls back to the general kernel
+int pw_launch(const ConvChoice& c, const PwK& k, hipStream_t st) {
+  const int ct = c.v[0], kg = c.v[1], rs = c.v[2], red32 = c.v[3];
   dim3 grid(c.gx, c.gy);          // (round 1 measured far fewer, fatter workgroups slower, 14 -> 36 us: the grid keeps >= ~500 workgroups on the large maps)
 #define ADDK_PW(CT_, KG_) \
-  if (c.ct == CT_ && c.kg == KG_) { \
-    if (MODE == PW_FWD && c.rs) { \
-      if (c.red32) hipLaunchKernelGGL((pw_kernel<CT_, KG_, PW_FWD, true, true>), grid, dim3(256), 0, st, k); \
+  if (ct == CT_ && kg == KG_) { \
+    if (MODE == PW_FWD && rs) { \
+      if (red32) hipLaunchKernelGGL((pw_kernel<CT_, KG_, PW_FWD, true, true>), grid, dim3(256), 0, st, k); \
       else hipLaunchKernelGGL((pw_kernel<CT_, KG_, PW_FWD, false, true>), grid, dim3(256), 0, st, k); \
-    } else if (c.red32) hipLaunchKernelGGL((pw_kernel<CT_, KG_, MODE, true>), grid, dim3(256), 0, st, k); \
+    } else if (red32) hipLaunchKernelGGL((pw_kernel<CT_, KG_, MODE, true>), grid, dim3(256), 0, st, k); \
     else hipLaunchKernelGGL((pw_kernel<CT_, KG_, MODE, false>), grid, dim3(256), 0, st, k); \
     return addk_check_launch("pw_conv"); }
   ADDK_PW(1, 3) ADDK_PW(2, 3) ADDK_PW(3, 3)
   ADDK_PW(1, 5) ADDK_PW(2, 5)
 #undef ADDK_PW
-  return 1;
+  addk_set_error("pw_conv: no instantiation");
+  return ADDK_ERR_UNSUPPORTED;
 }
 
 template <int MODE>
@@ -587,6 +587,11 @@ bool pw_fill_dgrad(const addk_conv_dgrad_args* a, PwK& k) {
   return true;
 }
 inline int pw_key(const PwCfg& c, int mode) { return (mode << 12) | (c.ct << 8) | (c.kg << 4) | (c.rs << 1) | c.red32; }
+void pw_choice(ConvChoice& c, const PwCfg& g, int mode) {
+  c.kind = CK_PW; c.v[0] = g.ct; c.v[1] = g.kg; c.v[2] = g.rs; c.v[3] = g.red32; c.gx = g.gx; c.gy = g.gy; c.key = pw_key(g, mode);
+}
+// the kernel descriptor of a launch whose choice is CK_PW (single launch or batch member)
+void pw_desc(const ConvChoice& c, PwK& k) { k.rows = c.rows; k.gx = c.gx; k.gy = c.gy; }
 
 
 // stem0 (ADD.py:153-157): 3x3 stride-2 convolution of the 3-channel image into 64 channels.  On the generic implicit-GEMM
@@ -673,10 +678,13 @@ __global__ void __launch_bounds__(256) stem0_kernel(const StemK p) {
   }
 }
 
-}  // namespace
-
-// Returns 0 when the launch was taken, 1 when the shape is not covered (caller falls back), <0 on error.
-static bool pwk_covers(const addk_conv_args* a, bool& rs) {
+// workgroups of the kernels that walk 16-pixel tiles four per workgroup (stem0, pwk): one per slab row, at most one per four tiles
+inline int gx_tiles16(long P, int rows) {
+  int gx = rows;
+  if (gx > cdiv(cdiv(P, 16), 4)) gx = cdiv(cdiv(P, 16), 4);
+  return gx < 1 ? 1 : gx;
+}
+bool pwk_covers(const addk_conv_args* a, bool& rs) {
   rs = false;
   if (a->KH != 1 || a->KW != 1 || a->stride != 1 || a->pad != 0 || a->bias_n || a->H != a->OH || a->W != a->OW) return false;
   if (!aligned16(a->y) || a->ldy % 4 || a->Cout % 4 || !aligned16(a->w) || a->ldw % 4 || a->w_choff % 4) return false;
@@ -692,71 +700,16 @@ static bool pwk_covers(const addk_conv_args* a, bool& rs) {
   if (ktot < 64 || a->Cout > 160 || (long)a->N * a->OH * a->OW < 1024) return false;
   return true;
 }
-static int pwk_try_fwd(const addk_conv_args* a, int rows, hipStream_t st) {
-  bool rs;
-  if (!pwk_covers(a, rs)) return 1;
-  PwkK k{};
-  for (int i = 0; i < a->nsrc; ++i) k.src[i] = a->src[i];
-  k.nsrc = a->nsrc; k.Cn = a->Cout; k.w = a->w; k.ldw = a->ldw; k.w_off = a->w_choff;
-  k.y = a->y; k.ldy = a->ldy; k.bias = a->bias;
-  k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
-  k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16); k.rows = rows;
-  k.H = a->OH; k.W = a->OW; k.rs_y = a->rs_y; k.rs_ldy = a->rs_ldy;
-  int ct = cdiv(a->Cout, 16); if (ct > 3) ct = 3;
-  k.gx = rows; if (k.gx > cdiv(k.ntiles16, 4)) k.gx = cdiv(k.ntiles16, 4); if (k.gx < 1) k.gx = 1;
-  dim3 grid(k.gx, cdiv(a->Cout, 16 * ct));
-  const bool red32 = k.P >= 4096;
-#define ADDK_PWK(CT_) \
-  if (ct == CT_) { \
-    if (rs) { \
-      if (red32) hipLaunchKernelGGL((pwk_kernel<CT_, true, true>), grid, dim3(256), 0, st, k); \
-      else hipLaunchKernelGGL((pwk_kernel<CT_, false, true>), grid, dim3(256), 0, st, k); \
-    } else if (red32) hipLaunchKernelGGL((pwk_kernel<CT_, true>), grid, dim3(256), 0, st, k); \
-    else hipLaunchKernelGGL((pwk_kernel<CT_, false>), grid, dim3(256), 0, st, k); \
-    return addk_check_launch("pwk_conv"); }
-  ADDK_PWK(1) ADDK_PWK(2) ADDK_PWK(3)
-#undef ADDK_PWK
-  return 1;
-}
-
-
 // stem0: 3 input channels (pixel stride 4), 3x3, stride 2, pad 1, 64 output channels, no prologue / bias
-static int stem0_try_fwd(const addk_conv_args* a, int rows, hipStream_t st) {
-  if (a->nsrc != 1 || a->KH != 3 || a->KW != 3 || a->stride != 2 || a->pad != 1 || a->dil != 1 || a->bias || a->bias_n) return 1;
+bool stem0_covers(const addk_conv_args* a) {
+  if (a->nsrc != 1 || a->KH != 3 || a->KW != 3 || a->stride != 2 || a->pad != 1 || a->dil != 1 || a->bias || a->bias_n) return false;
   const addk_src& s = a->src[0];
-  if (s.C != 3 || s.ld < 3 || s.a || s.b || s.relu || a->Cout != 64 || a->cin_total != 3 || a->w_choff != 0) return 1;
-  if (!aligned16(a->y) || a->ldy % 4 || a->ldy < 64) return 1;
-  if (a->OH != (a->H + 2 - 3) / 2 + 1 || a->OW != (a->W + 2 - 3) / 2 + 1) return 1;
-  StemK k{};
-  k.x = s.x; k.ld = s.ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
-  k.w = a->w; k.ldw = a->ldw; k.y = a->y; k.ldy = a->ldy;
-  k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
-  k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16); k.rows = rows;
-  k.gx = rows; if (k.gx > cdiv(k.ntiles16, 4)) k.gx = cdiv(k.ntiles16, 4); if (k.gx < 1) k.gx = 1;
-  if (k.P >= 4096) hipLaunchKernelGGL((stem0_kernel<4, true>), dim3(k.gx), dim3(256), 0, st, k);
-  else hipLaunchKernelGGL((stem0_kernel<4, false>), dim3(k.gx), dim3(256), 0, st, k);
-  return addk_check_launch("stem0");
+  if (s.C != 3 || s.ld < 3 || s.a || s.b || s.relu || a->Cout != 64 || a->cin_total != 3 || a->w_choff != 0) return false;
+  if (!aligned16(a->y) || a->ldy % 4 || a->ldy < 64) return false;
+  return a->OH == (a->H + 2 - 3) / 2 + 1 && a->OW == (a->W + 2 - 3) / 2 + 1;
 }
+}  // namespace
 
-int addk_pw_try_fwd(const addk_conv_args* a, int rows, void* stream) {
-  { const int r = stem0_try_fwd(a, rows, (hipStream_t)stream); if (r <= 0) return r; }
-  PwK k;
-  if (pw_fill_fwd(a, k)) {
-    const int r = pw_launch<PW_FWD>(k, rows, (hipStream_t)stream);
-    if (r <= 0) return r;
-  }
-  return pwk_try_fwd(a, rows, (hipStream_t)stream);       // many input channels / several sources: streaming-K kernel
-}
-extern "C" int addk_conv_fwd_resample_ok(const addk_conv_args* a) {
-  if (!a || a->nsrc < 1 || a->nsrc > ADDK_MAX_SRC || !(addk_get_fast_paths() & ADDK_FAST_PW)) return 0;
-  bool any = false;
-  for (int i = 0; i < a->nsrc; ++i) any = any || a->src[i].rs_hw != 0;
-  if (!any || a->wpack) return 0;
-  PwK k; PwCfg c;
-  if (pw_fill_fwd(a, k) && pw_config(k, addk_conv_rows((long)a->N * a->OH * a->OW, a->Cout), c)) return 1;
-  bool rs;
-  return pwk_covers(a, rs) ? 1 : 0;
-}
 // Data gradient of a 1x1 convolution with FEW output channels into a wide input — the classifier (decoder.py last_conv, 256 -> 19 classes):
 // 0.6 GF against 2 x 67 MB at config 2.  On the generic implicit-GEMM kernel (LDS tiles, 32-channel chunks with 19 live k slots) it took 110 us;
 // here a lane owns four input channels (64 lanes = 256 channels), keeps its K x 4 weights in registers, and a wave walks pixels: the K values of
@@ -830,69 +783,141 @@ __global__ void __launch_bounds__(256) k1s_dgrad_kernel(const K1sK p) {
     }
   }
 }
-static int k1s_try_dgrad(const addk_conv_dgrad_args* a, int rows, hipStream_t st) {
-  const int en = addk_env("ADDK_K1S", 1);
-  if (!en || a->KH != 1 || a->KW != 1 || a->stride != 1 || a->pad != 0 || a->H != a->OH || a->W != a->OW) return 1;
-  if (a->Cout > 32 || a->dst.C < 128 || a->dst.C > 256 || a->dst.C % 4) return 1;
-  if (!src_vec_ok(a->dst) || !aligned16(a->g) || a->ldg % 4 || !aligned16(a->w) || a->ldw % 4 || a->w_choff % 4) return 1;
-  if (a->dst.a && (!aligned16(a->dst.a) || !aligned16(a->dst.b))) return 1;
+static bool k1s_covers(const addk_conv_dgrad_args* a) {
+  if (a->KH != 1 || a->KW != 1 || a->stride != 1 || a->pad != 0 || a->H != a->OH || a->W != a->OW) return false;
+  if (a->Cout > 32 || a->dst.C < 128 || a->dst.C > 256 || a->dst.C % 4) return false;
+  if (!src_vec_ok(a->dst) || !aligned16(a->g) || a->ldg % 4 || !aligned16(a->w) || a->ldw % 4 || a->w_choff % 4) return false;
+  return !a->dst.a || (aligned16(a->dst.a) && aligned16(a->dst.b));
+}
+
+bool pw_choose_fwd(const addk_conv_args* a, ConvChoice& c) {
+  const long P = (long)a->N * a->OH * a->OW;
+  if (stem0_covers(a)) {
+    c.kind = CK_STEM0; c.v[0] = 4; c.v[1] = P >= 4096; c.gx = gx_tiles16(P, c.rows); c.gy = 1;
+    return true;
+  }
+  PwK k; PwCfg g;
+  if (pw_fill_fwd(a, k) && pw_config(k, c.rows, g)) { pw_choice(c, g, PW_FWD); return true; }
+  bool rs;
+  if (!pwk_covers(a, rs)) return false;       // many input channels / several sources: streaming-K kernel
+  int ct = cdiv(a->Cout, 16); if (ct > 3) ct = 3;
+  c.kind = CK_PWK; c.v[0] = ct; c.v[1] = rs; c.v[2] = P >= 4096; c.gx = gx_tiles16(P, c.rows); c.gy = cdiv(a->Cout, 16 * ct);
+  return true;
+}
+bool pw_choose_dgrad(const addk_conv_dgrad_args* a, ConvChoice& c) {
+  PwK k; PwCfg g;
+  if (pw_fill_dgrad(a, k)) {
+    if (!pw_config(k, c.rows, g)) return false;
+    pw_choice(c, g, PW_DGRAD);
+    return true;
+  }
+  if (!k1s_covers(a)) return false;
+  const long P = (long)a->N * a->H * a->W;
+  c.kind = CK_K1S; c.v[0] = a->Cout <= 20 ? 20 : 32; c.gx = c.rows > cdiv(P, 8) ? cdiv(P, 8) : c.rows; c.gy = 1;
+  if (c.gx < 1) c.gx = 1;
+  return true;
+}
+
+int pw_run_fwd(const ConvChoice& c, const addk_conv_args* a, hipStream_t st) {
+  if (c.kind == CK_PW) {
+    PwK k;
+    pw_fill_fwd(a, k); pw_desc(c, k);
+    return pw_launch<PW_FWD>(c, k, st);
+  }
+  if (c.kind == CK_STEM0) {
+    const addk_src& s = a->src[0];
+    StemK k{};
+    k.x = s.x; k.ld = s.ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
+    k.w = a->w; k.ldw = a->ldw; k.y = a->y; k.ldy = a->ldy;
+    k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
+    k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16); k.rows = c.rows; k.gx = c.gx;
+    if (c.v[1]) hipLaunchKernelGGL((stem0_kernel<4, true>), dim3(c.gx), dim3(256), 0, st, k);
+    else hipLaunchKernelGGL((stem0_kernel<4, false>), dim3(c.gx), dim3(256), 0, st, k);
+    return addk_check_launch("stem0");
+  }
+  PwkK k{};
+  for (int i = 0; i < a->nsrc; ++i) k.src[i] = a->src[i];
+  k.nsrc = a->nsrc; k.Cn = a->Cout; k.w = a->w; k.ldw = a->ldw; k.w_off = a->w_choff;
+  k.y = a->y; k.ldy = a->ldy; k.bias = a->bias;
+  k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
+  k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16); k.rows = c.rows;
+  k.H = a->OH; k.W = a->OW; k.rs_y = a->rs_y; k.rs_ldy = a->rs_ldy;
+  k.gx = c.gx;
+  const int ct = c.v[0], rs = c.v[1], red32 = c.v[2];
+  dim3 grid(c.gx, c.gy);
+#define ADDK_PWK(CT_) \
+  if (ct == CT_) { \
+    if (rs) { \
+      if (red32) hipLaunchKernelGGL((pwk_kernel<CT_, true, true>), grid, dim3(256), 0, st, k); \
+      else hipLaunchKernelGGL((pwk_kernel<CT_, false, true>), grid, dim3(256), 0, st, k); \
+    } else if (red32) hipLaunchKernelGGL((pwk_kernel<CT_, true>), grid, dim3(256), 0, st, k); \
+    else hipLaunchKernelGGL((pwk_kernel<CT_, false>), grid, dim3(256), 0, st, k); \
+    return addk_check_launch("pwk_conv"); }
+  ADDK_PWK(1) ADDK_PWK(2) ADDK_PWK(3)
+#undef ADDK_PWK
+  addk_set_error("pwk_conv: no instantiation");
+  return ADDK_ERR_UNSUPPORTED;
+}
+int pw_run_dgrad(const ConvChoice& c, const addk_conv_dgrad_args* a, hipStream_t st) {
+  if (c.kind == CK_PW) {
+    PwK k;
+    pw_fill_dgrad(a, k); pw_desc(c, k);
+    return pw_launch<PW_DGRAD>(c, k, st);
+  }
   K1sK k{};
   k.dy = a->dy; k.lddy = a->lddy; k.K = a->Cout; k.w = a->w; k.ldw = a->ldw; k.w_off = a->w_choff;
   k.dst = a->dst; k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate; k.slab = a->dab;
-  k.P = a->N * a->H * a->W; k.rows = rows; k.gx = rows; k.Cn = a->dst.C;
-  if (k.gx > cdiv(k.P, 8)) k.gx = cdiv(k.P, 8);
-  if (k.gx < 1) k.gx = 1;
-  if (a->Cout <= 20) hipLaunchKernelGGL((k1s_dgrad_kernel<20>), dim3(k.gx), dim3(256), 0, st, k);
-  else hipLaunchKernelGGL((k1s_dgrad_kernel<32>), dim3(k.gx), dim3(256), 0, st, k);
+  k.P = a->N * a->H * a->W; k.rows = c.rows; k.gx = c.gx; k.Cn = a->dst.C;
+  if (c.v[0] == 20) hipLaunchKernelGGL((k1s_dgrad_kernel<20>), dim3(c.gx), dim3(256), 0, st, k);
+  else hipLaunchKernelGGL((k1s_dgrad_kernel<32>), dim3(c.gx), dim3(256), 0, st, k);
   return addk_check_launch("conv_dgrad (1x1, few output channels)");
 }
-int addk_pw_try_dgrad(const addk_conv_dgrad_args* a, int rows, void* stream) {
-  PwK k;
-  if (!pw_fill_dgrad(a, k)) return k1s_try_dgrad(a, rows, (hipStream_t)stream);
-  return pw_launch<PW_DGRAD>(k, rows, (hipStream_t)stream);
+
+// 1: the launch runs on a pointwise kernel that samples its rs_hw sources itself (see include/addk.h)
+extern "C" int addk_conv_fwd_resample_ok(const addk_conv_args* a) {
+  if (!a || a->nsrc < 1 || a->nsrc > ADDK_MAX_SRC) return 0;
+  bool any = false;
+  for (int i = 0; i < a->nsrc; ++i) any = any || a->src[i].rs_hw != 0;
+  ConvChoice c;
+  return any && conv_choose_fwd(a, addk_get_conv_precision(), addk_get_fast_paths(), c) == ADDK_OK && (c.kind == CK_PW || c.kind == CK_PWK);
 }
 
 // ---- batched form: mutually independent pointwise convs (one dependency level of the cell DAG) in one launch -------
-// key >= 0: the launch runs on pw_kernel with that template variant (launches with equal keys can share a batch); -1: not
+// key >= 0: the launch's choice is pw_kernel with that template variant (launches with equal keys can share a batch); -1: not
 extern "C" int addk_conv_fwd_batch_key(const addk_conv_args* a) {
-  if (!a || !(addk_get_fast_paths() & ADDK_FAST_PW)) return -1;
-  PwK k; PwCfg c;
-  if (!pw_fill_fwd(a, k) || !pw_config(k, addk_conv_rows((long)a->N * a->OH * a->OW, a->Cout), c)) return -1;
-  return pw_key(c, PW_FWD);
+  ConvChoice c;
+  return conv_choose_fwd(a, addk_get_conv_precision(), addk_get_fast_paths(), c) == ADDK_OK && c.kind == CK_PW ? c.key : -1;
 }
 extern "C" int addk_conv_dgrad_batch_key(const addk_conv_dgrad_args* a) {
-  if (!a || !(addk_get_fast_paths() & ADDK_FAST_PW)) return -1;
-  PwK k; PwCfg c;
-  if (!pw_fill_dgrad(a, k) || !pw_config(k, addk_conv_rows((long)a->N * a->H * a->W, a->dst.C), c)) return -1;
-  return pw_key(c, PW_DGRAD);
+  ConvChoice c;
+  return conv_choose_dgrad(a, addk_get_conv_precision(), addk_get_fast_paths(), c) == ADDK_OK && c.kind == CK_PW ? c.key : -1;
 }
 // host_blob = NULL: returns the blob size in bytes.  meta[0..5] = key, n, gx, gy, reserved
-template <typename Args, typename Fill, typename Rows>
-static int64_t pw_batch_prepare(const Args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta, int mode, Fill fill, Rows rows_of) {
+template <typename Args>
+static int64_t pw_batch_prepare(const Args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta,
+                                int (*choose)(const Args*, int, int, ConvChoice&), bool (*fill)(const Args*, PwK&)) {
   if (!a || n <= 0 || !meta) { addk_set_error("conv_batch_prepare: bad args"); return ADDK_ERR_INVALID; }
   const int64_t total = (int64_t)n * sizeof(PwK);
   if (host_blob && blob_bytes < total) { addk_set_error("conv_batch_prepare: blob too small"); return ADDK_ERR_INVALID; }
+  const int mode = addk_get_conv_precision(), mask = addk_get_fast_paths();
   int key0 = -1, gx = 0, gy = 0;
   for (int i = 0; i < n; ++i) {
-    PwK k; PwCfg c;
-    if (!fill(&a[i], k) || !pw_config(k, rows_of(&a[i]), c)) { addk_set_error("conv_batch_prepare: launch %d is not a pointwise-kernel shape", i); return ADDK_ERR_INVALID; }
-    const int key = pw_key(c, mode);
-    if (i == 0) key0 = key;
-    if (key != key0) { addk_set_error("conv_batch_prepare: mixed kernel variants"); return ADDK_ERR_INVALID; }
+    ConvChoice c;
+    if (choose(&a[i], mode, mask, c) || c.kind != CK_PW) { addk_set_error("conv_batch_prepare: launch %d is not a pointwise-kernel shape", i); return ADDK_ERR_INVALID; }
+    if (i == 0) key0 = c.key;
+    if (c.key != key0) { addk_set_error("conv_batch_prepare: mixed kernel variants"); return ADDK_ERR_INVALID; }
     if (c.gx > gx) gx = c.gx;
     if (c.gy > gy) gy = c.gy;
-    if (host_blob) reinterpret_cast<PwK*>(host_blob)[i] = k;
+    if (host_blob) { PwK& k = reinterpret_cast<PwK*>(host_blob)[i]; fill(&a[i], k); pw_desc(c, k); }
   }
   meta[0] = key0; meta[1] = n; meta[2] = gx; meta[3] = gy;
   return total;
 }
 extern "C" int64_t addk_conv_fwd_batch_prepare(const addk_conv_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  return pw_batch_prepare(a, n, host_blob, blob_bytes, meta, PW_FWD, pw_fill_fwd,
-                          [](const addk_conv_args* x) { return addk_conv_rows((long)x->N * x->OH * x->OW, x->Cout); });
+  return pw_batch_prepare(a, n, host_blob, blob_bytes, meta, conv_choose_fwd, pw_fill_fwd);
 }
 extern "C" int64_t addk_conv_dgrad_batch_prepare(const addk_conv_dgrad_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  return pw_batch_prepare(a, n, host_blob, blob_bytes, meta, PW_DGRAD, pw_fill_dgrad,
-                          [](const addk_conv_dgrad_args* x) { return addk_conv_rows((long)x->N * x->H * x->W, x->dst.C); });
+  return pw_batch_prepare(a, n, host_blob, blob_bytes, meta, conv_choose_dgrad, pw_fill_dgrad);
 }
 extern "C" int addk_conv_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
   ADDK_REQUIRE(dev_blob && meta && meta[1] > 0 && meta[2] > 0 && meta[3] > 0, "conv_batch_run: bad args");

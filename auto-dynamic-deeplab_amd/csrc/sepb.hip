@@ -310,12 +310,8 @@ bool sepb_fill(const addk_sep_bwd_args* a, SepbK& k, SepbCfg& c) {
 template <int KS, int KG, int KP, int R>
 int sepb_go(bool batch, dim3 grid, hipStream_t st, const SepbK* one, const SepbK* tab) {
   typedef SepbGeo<KS, KG, KP, R> G;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sepb_kernel<KS, KG, KP, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sepb_batch_kernel<KS, KG, KP, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
-    attr = true;
-  }
+  addk_dyn_lds<sepb_kernel<KS, KG, KP, R>>((int)G::LDS);
+  addk_dyn_lds<sepb_batch_kernel<KS, KG, KP, R>>((int)G::LDS);
   if (batch) hipLaunchKernelGGL((sepb_batch_kernel<KS, KG, KP, R>), grid, dim3(256), G::LDS, st, tab);
   else hipLaunchKernelGGL((sepb_kernel<KS, KG, KP, R>), grid, dim3(256), G::LDS, st, *one);
   return addk_check_launch("sep_bwd");

@@ -487,12 +487,8 @@ bool sepf_fill(const addk_sep_args* a, SepfK& k, SepfCfg& c) {
 template <int KS, int KG, int KP, int R>
 int sepf_go(bool batch, dim3 grid, hipStream_t st, const SepfK* one, const SepfK* tab) {
   typedef SepfGeo<KS, KG, KP, R> G;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sepf_kernel<KS, KG, KP, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sepf_batch_kernel<KS, KG, KP, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
-    attr = true;
-  }
+  addk_dyn_lds<sepf_kernel<KS, KG, KP, R>>((int)G::LDS);
+  addk_dyn_lds<sepf_batch_kernel<KS, KG, KP, R>>((int)G::LDS);
   if (batch) hipLaunchKernelGGL((sepf_batch_kernel<KS, KG, KP, R>), grid, dim3(256), G::LDS, st, tab);
   else hipLaunchKernelGGL((sepf_kernel<KS, KG, KP, R>), grid, dim3(256), G::LDS, st, *one);
   return addk_check_launch("sep_fwd");

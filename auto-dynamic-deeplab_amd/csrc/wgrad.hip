@@ -2059,10 +2059,8 @@ int wg_choose(const addk_conv_wgrad_args* a, int mode, WgChoice& c) {
 // The kernel of a launch key (kind, cty, ctz) in precision mode `mode`.
 typedef void (*WgFn)(const WgK, const WgK*, const int4*);
 struct WgVariant { WgFn fn; unsigned threads; size_t lds; };
-constexpr int WG_MAX_DYN_LDS = 160 * 1024 - 64;      // dynamic LDS the split-precision kernels may ask for
 template <WgFn F> WgVariant wg_dyn_lds(unsigned threads, size_t lds) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(F), hipFuncAttributeMaxDynamicSharedMemorySize, WG_MAX_DYN_LDS);
-  (void)attr;
+  addk_dyn_lds<F>();
   return {F, threads, lds};
 }
 template <int Y, bool B> WgFn wg_pix(int ctz) {

@@ -101,9 +101,9 @@ typedef struct addk_conv_args {
                                  Points at this conv's first channel inside the row. */
   int32_t stats_ld;           /* channels per slab row (>= Cout; FactorizedReduce's two convs share one BN) */
   int32_t _pad;
-  float* wpack;               /* optional workspace of >= addk_conv_fwd_pack_floats() floats: lets wide 3x3 stride-1 'same'
-                                 convolutions run on the halo-patch kernel (weights re-packed into MFMA fragment order
-                                 per launch); NULL = generic kernel */
+  float* wpack;               /* optional workspace of >= addk_conv_fwd_pack_floats() floats, 16-byte aligned: lets the launches
+                                 that addk_conv_fwd_pack_floats() sizes run on a halo-patch kernel (weights re-packed into MFMA
+                                 fragment order); NULL, short or misaligned = another kernel */
   int64_t wpack_floats;
   int32_t wpack_ready;        /* 1: wpack already holds this launch's packed weights (addk_conv_pack_batch ran since the
                                  last weight update); 0: the launch packs them itself */
@@ -119,7 +119,8 @@ int addk_conv_fwd(const addk_conv_args* a, void* stream);
  * streaming-K pointwise kernel, pw.hip: ADD.py:84-90 `pre_preprocess` / `preprocess` behind F.interpolate), else 0: the caller
  * then runs addk_resize_fwd first.  Results are bit-identical either way (the same fp32 expressions in the same order). */
 int addk_conv_fwd_resample_ok(const addk_conv_args* a);
-/* floats of `wpack` this launch can use; 0 = the halo-patch kernel does not cover the shape */
+/* floats of `wpack` the launch needs to run on a halo-patch kernel, whatever `wpack` holds now; 0 = given such a workspace it would
+ * still take another kernel (no pack is read) */
 int64_t addk_conv_fwd_pack_floats(const addk_conv_args* a);
 /* Arithmetic of the wide k x k stride-1 contractions (the halo-patch kernels: forward, data gradient, weight gradient):
  *   0 = exact fp32 products on v_mfma_f32_16x16x4_f32;
@@ -171,12 +172,24 @@ typedef struct addk_conv_dgrad_args {
   int32_t _pad2;
 } addk_conv_dgrad_args;
 int addk_conv_dgrad(const addk_conv_dgrad_args* a, void* stream);
-int64_t addk_conv_dgrad_pack_floats(const addk_conv_dgrad_args* a);
+int64_t addk_conv_dgrad_pack_floats(const addk_conv_dgrad_args* a);    /* see addk_conv_fwd_pack_floats */
+/* The kernel a forward / data-gradient launch takes (the same choice the launch, the pack size and descriptor, the batch key and
+ * addk_conv_fwd_resample_ok read).  cfg[8] = kind, four template parameters, grid x, grid y, launches.  Kinds and parameters:
+ *   0 generic implicit GEMM: PT, CT, red32          1 the same over the parity classes of a stride-2 data gradient: PT, CT, red32,
+ *                                                     classes (launches > 1: one per class, the first one's parameters and grid)
+ *   2 stem0: CT, red32                               3 register-stationary 1x1: CT, KG, RS, red32 (the only kind a batch merges)
+ *   4 streaming-K 1x1 forward: CT, RS, red32         5 1x1 data gradient with <= 32 output channels: KMAX
+ *   6 fp32 halo patch: BCT, KS                       7 split-precision halo patch: WC, KS, pixels per tile row, rows per tile
+ *   8 split-precision stride-2 data gradient: planes 9 split-precision 5x5 on 16-wide tiles: KS, planes
+ * Kinds 6-9 read `wpack`. */
+int addk_conv_fwd_config(const addk_conv_args* a, int32_t* cfg);
+int addk_conv_dgrad_config(const addk_conv_dgrad_args* a, int32_t* cfg);
 /* Weight packs hoisted out of the step: fill one opaque descriptor (addk_conv_pack_desc_bytes() bytes, host memory) per
- * launch that has a wpack workspace, upload the array and run addk_conv_pack_batch once per step before the first
- * launch; those launches then set wpack_ready = 1. */
+ * launch that takes a halo-patch kernel (pack_desc fails for any other), upload the array and run addk_conv_pack_batch once
+ * per step before the first launch; those launches then set wpack_ready = 1. */
 /* Batched pointwise convolutions: mutually independent 1x1 launches (one dependency level of the cell DAG) that map to the
- * same kernel variant run as ONE launch.  key >= 0 names the variant (-1: the launch is not covered); prepare() fills a
+ * same kernel variant run as ONE launch.  key >= 0 names the variant of a launch that on its own would take the
+ * register-stationary kernel (kind 3 above; -1: any other kernel); prepare() fills a
  * host blob of kernel descriptors (host_blob = NULL: returns its size) and meta[4]; the caller uploads the blob once and
  * replays addk_conv_batch_run.  Same arithmetic as the single launches. */
 int addk_conv_fwd_batch_key(const addk_conv_args* a);

@@ -253,7 +253,7 @@ def test_dynamic_inference_gate_reads_the_pinned_word_the_fused_head_writes(dev)
                                    (1, 128, 256, 256, 19, True, False)], ids=['c256_k19', 'c128_noaffine_acc', 'c256_k32_acc', 'classifier_full_map'])
 def test_classifier_data_gradient_matches_fp64_and_the_generic_kernel(shape):
     """decoder.py last_conv backward: g = relu'(a x + b) * a * (dy W), (dA, dB) = sum over pixels of (m dz x, m dz); odd pixel counts (a wave's
-    second pixel of the last trip missing), accumulate, no lazy BatchNorm on the destination; against fp64 and against ADDK_K1S-less dispatch."""
+    second pixel of the last trip missing), accumulate, no lazy BatchNorm on the destination; against fp64."""
     import ctypes as C
     import torch
     from addk import _lib as L

@@ -19,7 +19,6 @@ VARIANTS = [
     ('unfused SepConv (fwd + bwd)', {'ADDK_FUSE_SEP': '0', 'ADDK_FUSE_SEP_BWD': '0'}),
     ('unfused SepConv backward only', {'ADDK_FUSE_SEP_BWD': '0'}),
     ('fp32 matrix kernels', {'ADDK_PROBE_PRECISION': 'fp32'}),
-    ('stem2 on the generic fp32 kernel', {'ADDK_C3B_STRIDE2': '0'}),
 ]
 
 
