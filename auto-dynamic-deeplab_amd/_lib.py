@@ -173,6 +173,8 @@ _SIGS = {
     'addk_finish_sample': (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     'addk_sep_fwd_supported': (i32, [C.POINTER(SepArgs)]),
     'addk_sep_rows': (i32, [C.POINTER(SepArgs)]),
+    'addk_sep_fwd_config': (i32, [C.POINTER(SepArgs), C.POINTER(i32)]),
+    'addk_sep_bwd_config': (i32, [C.POINTER(SepBwdArgs), C.POINTER(i32)]),
     'addk_bn_fin_ws_bytes': (i64, [i32, i32]),
     'addk_sep_bwd_rows': (i32, [C.POINTER(SepBwdArgs)]),
     'addk_sep_bwd': (i32, [C.POINTER(SepBwdArgs), vp]),
@@ -186,6 +188,8 @@ _SIGS = {
     'addk_dw_fwd': (i32, [C.POINTER(DwArgs), vp]),
     'addk_dw_bwd': (i32, [C.POINTER(DwBwdArgs), vp]),
     'addk_dw_rows': (i32, [i64, i32]),
+    'addk_dw_fwd_config': (i32, [C.POINTER(DwArgs), C.POINTER(i32)]),
+    'addk_dw_bwd_config': (i32, [C.POINTER(DwBwdArgs), C.POINTER(i32)]),
     'addk_dw_wreduce_batch': (i32, [vp, i32, vp]),
     'addk_dw_fwd_batch_key': (i32, [C.POINTER(DwArgs)]),
     'addk_dw_bwd_batch_key': (i32, [C.POINTER(DwBwdArgs)]),

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include "addk.h"
 
 void addk_set_error(const char* fmt, ...);
@@ -173,6 +174,38 @@ __device__ __forceinline__ int f16_scale_field(unsigned amax_bits) {
 struct EwMap { int nq, npl; };
 static inline EwMap ew_map(int C) {
   EwMap m; m.nq = (C + 3) / 4; if (m.nq > 256) m.nq = 256; m.npl = 256 / m.nq; if (m.npl < 1) m.npl = 1; return m;
+}
+// workgroups of such a kernel over P pixels = rows of its partial-sum slabs and workspaces (addk_ew_rows, addk_dw_rows): every block walks at least two
+// pixels per lane (>= 4 resident blocks per CU on the level-1 maps), 1024 rows at most
+static inline int ew_rows(long P, int C) {
+  const long r = P / ((long)ew_map(C).npl * 2);
+  return (int)(r < 1 ? 1 : r > 1024 ? 1024 : r);
+}
+
+// ---- table-driven batches (the *_batch_prepare entry points of pw.hip, dw.hip, sepf.hip, sepb.hip, resize.hip) ---------------------------------
+// The caller asks for the blob size (host_blob = NULL), then has the blob filled: n descriptors `Desc`, one per args[i].  `item` turns one argument struct into its
+// descriptor and what the merged launch needs of it (false: not a launch of the batched kernel); every item has item 0's key.  meta[0..3] = key, n, largest grid x,
+// largest grid y; *lds = largest dynamic LDS size.  Returns the blob size in bytes.
+struct BatchItem { int key, gx, gy; size_t lds; };
+template <typename Desc, typename Args, typename Item>
+int64_t batch_prepare(const char* what, const Args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta, Item item, size_t* lds = nullptr) {
+  if (!a || n <= 0 || !meta) { addk_set_error("%s: bad args", what); return ADDK_ERR_INVALID; }
+  const int64_t total = (int64_t)n * sizeof(Desc);
+  if (host_blob && blob_bytes < total) { addk_set_error("%s: blob too small", what); return ADDK_ERR_INVALID; }
+  BatchItem mx{-1, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    Desc d{}; BatchItem b{};
+    if (!item(&a[i], d, b)) { addk_set_error("%s: launch %d does not run on the batched kernel", what, i); return ADDK_ERR_INVALID; }
+    if (i == 0) mx.key = b.key;
+    if (b.key != mx.key) { addk_set_error("%s: mixed kernel variants", what); return ADDK_ERR_INVALID; }
+    if (b.gx > mx.gx) mx.gx = b.gx;
+    if (b.gy > mx.gy) mx.gy = b.gy;
+    if (b.lds > mx.lds) mx.lds = b.lds;
+    if (host_blob) memcpy(static_cast<char*>(host_blob) + (size_t)i * sizeof(Desc), &d, sizeof(Desc));
+  }
+  meta[0] = mx.key; meta[1] = n; meta[2] = mx.gx; meta[3] = mx.gy;
+  if (lds) *lds = mx.lds;
+  return total;
 }
 
 // Kernels that ask for more than the default 64 KB of dynamic LDS: addk_dyn_lds<kernel>(bytes) raises the kernel's limit before its first launch,

@@ -423,17 +423,17 @@ __global__ void __launch_bounds__(256) dw_wreduce_batch_kernel(const addk_dw_wre
   }
 }
 
-int dw_rows(long P, int C) {
-  EwMap m = ew_map(C);
-  long r = P / ((long)m.npl * 2);      // >= 4 resident blocks per CU on the level-1 maps
-  if (r < 1) r = 1;
-  if (r > 1024) r = 1024;
-  return (int)r;
-}
-
 }  // namespace
 
-extern "C" int addk_dw_rows(int64_t P, int32_t C) { return dw_rows(P, C); }
+extern "C" int addk_dw_rows(int64_t P, int32_t C) { return ew_rows(P, C); }
+
+// The kernel of one depthwise launch: the LDS-tiled kernel where dw_tile_* covers it, else the generic one.  dw_choose_fwd / dw_choose_bwd
+// check the arguments and decide; the launch, the batch key and prepare and addk_dw_*_config read the choice.
+struct DwChoice {
+  int tiled, bwd, taps;     // tiled: template parameter KS = t.k.KH; generic backward: NT = taps
+  int key;                  // batch key (kernel size | backward << 4): a tiled launch, shares a batch with equal keys; -1: none
+  DwT t;                    // the kernel argument (generic kernels: t.k) and, for every kernel, grid (gx, ngrp), shbytes, rows
+};
 
 static int dw_fill(DwK& k, const addk_src& src, int N, int H, int W, int OH, int OW, int KH, int KW, int stride, int pad, int dil) {
   ADDK_REQUIRE(src.x && src.C > 0 && src.C <= 1024 && src.ld >= src.C, "dw: bad source");
@@ -445,13 +445,17 @@ static int dw_fill(DwK& k, const addk_src& src, int N, int H, int W, int OH, int
   return 0;
 }
 
-
-// tile geometry of the LDS-tiled kernels; false: the launch is not covered (generic kernel)
-static bool dw_tile_fwd(const addk_dw_args* a, const DwK& k, DwT& t) {
-  if (!(k.vec && a->KH == a->KW && (a->KH == 3 || a->KH == 5) && (addk_get_fast_paths() & ADDK_FAST_DWTILE) && k.P >= 2048)) return false;
-  t.k = k;
+// tile geometry of the LDS-tiled kernels (t.k is filled); false: the launch is not covered (generic kernel).  The fast-path mask
+// (ADDK_FAST_DWTILE) is tested here and nowhere else: it gates the launch as well as the key.
+static bool dw_tile_groups(DwT& t) {
+  const DwK& k = t.k;
+  if (!(k.vec && k.KH == k.KW && (k.KH == 3 || k.KH == 5) && (addk_get_fast_paths() & ADDK_FAST_DWTILE) && k.P >= 2048)) return false;
   t.nqb = k.nq <= 10 ? k.nq : (k.nq % 10 == 0 ? 10 : 8);
   t.ngrp = cdiv(k.nq, t.nqb);
+  return true;
+}
+static bool dw_tile_fwd(const addk_dw_args* a, DwT& t) {
+  if (!dw_tile_groups(t)) return false;
   const int span = (a->KH - 1) * a->dil + 1;
   t.PW = (DW_TW - 1) * a->stride + span;
   const long row_bytes = (long)t.PW * t.nqb * 16;
@@ -466,11 +470,8 @@ static bool dw_tile_fwd(const addk_dw_args* a, const DwK& k, DwT& t) {
   t.shbytes = (unsigned)(((size_t)a->KH * a->KW * t.nqb * 4 + (size_t)t.PH * t.PW * t.nqb * 4) * sizeof(float));
   return true;
 }
-static bool dw_tile_bwd(const addk_dw_bwd_args* a, const DwK& k, int rows, DwT& t) {
-  if (!(k.vec && a->stride == 1 && a->KH == a->KW && (a->KH == 3 || a->KH == 5) && (addk_get_fast_paths() & ADDK_FAST_DWTILE) && k.P >= 2048)) return false;
-  t.k = k;
-  t.nqb = k.nq <= 10 ? k.nq : (k.nq % 10 == 0 ? 10 : 8);
-  t.ngrp = cdiv(k.nq, t.nqb);
+static bool dw_tile_bwd(const addk_dw_bwd_args* a, int rows, DwT& t) {
+  if (a->stride != 1 || !dw_tile_groups(t)) return false;
   const int halo = (a->KH - 1) * a->dil, taps = a->KH * a->KW;
   t.PW = DW_TW + halo;
   const long row_bytes = (long)t.PW * t.nqb * 16;
@@ -490,58 +491,69 @@ static bool dw_tile_bwd(const addk_dw_bwd_args* a, const DwK& k, int rows, DwT& 
   return true;
 }
 
-extern "C" int addk_dw_fwd(const addk_dw_args* a, void* stream) {
+static int dw_choose_fwd(const addk_dw_args* a, DwChoice& c) {
   ADDK_REQUIRE(a && a->w && a->y && a->ldy >= a->src.C, "dw_fwd: null/short output");
-  DwK k{};
-  int rc = dw_fill(k, a->src, a->N, a->H, a->W, a->OH, a->OW, a->KH, a->KW, a->stride, a->pad, a->dil);
-  if (rc) return rc;
+  c = DwChoice{};
+  DwT& t = c.t; DwK& k = t.k;
+  if (const int rc = dw_fill(k, a->src, a->N, a->H, a->W, a->OH, a->OW, a->KH, a->KW, a->stride, a->pad, a->dil)) return rc;
   k.w = a->w; k.y = a->y; k.ldy = a->ldy;
   k.P = (long)a->N * a->OH * a->OW;
   k.vec = src_vec_ok(a->src) && aligned16(a->y) && a->ldy % 4 == 0;
-  DwT t;
-  if (dw_tile_fwd(a, k, t)) {
-    dim3 grid((unsigned)t.gx, (unsigned)t.ngrp);
-    if (a->KH == 3) hipLaunchKernelGGL(dw_fwd_tile_kernel<3>, grid, dim3(256), t.shbytes, (hipStream_t)stream, t);
-    else            hipLaunchKernelGGL(dw_fwd_tile_kernel<5>, grid, dim3(256), t.shbytes, (hipStream_t)stream, t);
-    return addk_check_launch("dw_fwd_tile");
-  }
+  c.taps = a->KH * a->KW;
+  c.tiled = dw_tile_fwd(a, t);
+  c.key = c.tiled ? a->KH : -1;
+  if (c.tiled) return ADDK_OK;
   long blocks = cdiv(k.P, k.npl); if (blocks > 8192) blocks = 8192; if (blocks < 1) blocks = 1;
-  size_t sh = (size_t)a->KH * a->KW * k.nq * 4 * sizeof(float);
-  hipLaunchKernelGGL(dw_fwd_kernel, dim3((unsigned)blocks), dim3(256), sh, (hipStream_t)stream, k);
-  return addk_check_launch("dw_fwd");
+  t.gx = (int)blocks; t.ngrp = 1; t.shbytes = (unsigned)((size_t)c.taps * k.nq * 4 * sizeof(float));
+  return ADDK_OK;
 }
-
-extern "C" int addk_dw_bwd(const addk_dw_bwd_args* a, void* stream) {
+static int dw_choose_bwd(const addk_dw_bwd_args* a, DwChoice& c) {
   ADDK_REQUIRE(a && a->dy && a->w && a->dw && a->ws && a->lddy >= a->src.C, "dw_bwd: null pointer");
   ADDK_REQUIRE(!a->g || a->ldg >= a->src.C, "dw_bwd: short ldg");
-  DwK k{};
-  int rc = dw_fill(k, a->src, a->N, a->H, a->W, a->OH, a->OW, a->KH, a->KW, a->stride, a->pad, a->dil);
-  if (rc) return rc;
+  c = DwChoice{};
+  DwT& t = c.t; DwK& k = t.k;
+  if (const int rc = dw_fill(k, a->src, a->N, a->H, a->W, a->OH, a->OW, a->KH, a->KW, a->stride, a->pad, a->dil)) return rc;
   k.w = a->w; k.dy = a->dy; k.lddy = a->lddy; k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate;
   k.dab = (double*)a->dab; k.ws = a->ws;
   k.P = (long)a->N * a->H * a->W;
   k.vec = src_vec_ok(a->src) && aligned16(a->dy) && a->lddy % 4 == 0 && (!a->g || (aligned16(a->g) && a->ldg % 4 == 0));
-  const int taps = a->KH * a->KW, C4 = k.nq * 4;
-  const int rows = dw_rows(k.P, a->src.C);
-  size_t sh = (size_t)(taps * C4 + k.npl * C4 * 5) * sizeof(float);     // tap weights + [TG<=5][npl][C4] reduction panel (>= the fp64 (dA,dB) panel)
+  c.bwd = 1; c.taps = a->KH * a->KW;
+  const int rows = ew_rows(k.P, a->src.C);
+  c.tiled = dw_tile_bwd(a, rows, t);
+  c.key = c.tiled && a->defer_wreduce ? (a->KH | 16) : -1;             // the batched launch has no per-conv weight reduction
+  if (c.tiled) return ADDK_OK;
+  if (c.taps != 9 && c.taps != 25) { addk_set_error("dw_bwd: only 3x3 and 5x5 depthwise kernels are built"); return ADDK_ERR_UNSUPPORTED; }
+  // tap weights + [TG<=5][npl][C4] reduction panel (>= the fp64 (dA,dB) panel)
+  t.gx = t.rows = rows; t.ngrp = 1; t.shbytes = (unsigned)((size_t)(c.taps * k.nq * 4 + k.npl * k.nq * 4 * 5) * sizeof(float));
+  return ADDK_OK;
+}
+static int dw_launch(const DwChoice& c, hipStream_t st) {
+  const DwT& t = c.t;
+  const dim3 grid((unsigned)t.gx, (unsigned)t.ngrp);
+  const int ks = t.k.KH;
+  if (c.tiled && !c.bwd && ks == 3) hipLaunchKernelGGL(dw_fwd_tile_kernel<3>, grid, dim3(256), t.shbytes, st, t);
+  else if (c.tiled && !c.bwd)       hipLaunchKernelGGL(dw_fwd_tile_kernel<5>, grid, dim3(256), t.shbytes, st, t);
+  else if (c.tiled && ks == 3)      hipLaunchKernelGGL(dw_bwd_tile_kernel<3>, grid, dim3(256), t.shbytes, st, t);
+  else if (c.tiled)                 hipLaunchKernelGGL(dw_bwd_tile_kernel<5>, grid, dim3(256), t.shbytes, st, t);
+  else if (!c.bwd)                  hipLaunchKernelGGL(dw_fwd_kernel, grid, dim3(256), t.shbytes, st, t.k);
+  else if (c.taps == 9)             hipLaunchKernelGGL(dw_bwd_kernel<9>, grid, dim3(256), t.shbytes, st, t.k);
+  else                              hipLaunchKernelGGL(dw_bwd_kernel<25>, grid, dim3(256), t.shbytes, st, t.k);
+  return addk_check_launch(c.bwd ? "dw_bwd" : c.tiled ? "dw_fwd_tile" : "dw_fwd");
+}
+
+extern "C" int addk_dw_fwd(const addk_dw_args* a, void* stream) {
+  DwChoice c;
+  const int rc = dw_choose_fwd(a, c);
+  return rc ? rc : dw_launch(c, (hipStream_t)stream);
+}
+extern "C" int addk_dw_bwd(const addk_dw_bwd_args* a, void* stream) {
+  DwChoice c;
+  if (const int rc = dw_choose_bwd(a, c)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  bool tiled = false;
-  DwT t;
-  if (dw_tile_bwd(a, k, rows, t)) {
-    dim3 grid((unsigned)t.gx, (unsigned)t.ngrp);
-    if (taps == 9) hipLaunchKernelGGL(dw_bwd_tile_kernel<3>, grid, dim3(256), t.shbytes, st, t);
-    else           hipLaunchKernelGGL(dw_bwd_tile_kernel<5>, grid, dim3(256), t.shbytes, st, t);
-    tiled = true;
-  }
-  if (tiled) {}
-  else if (taps == 9) hipLaunchKernelGGL(dw_bwd_kernel<9>, dim3(rows), dim3(256), sh, st, k);
-  else if (taps == 25) hipLaunchKernelGGL(dw_bwd_kernel<25>, dim3(rows), dim3(256), sh, st, k);
-  else { addk_set_error("dw_bwd: only 3x3 and 5x5 depthwise kernels are built"); return ADDK_ERR_UNSUPPORTED; }
-  rc = addk_check_launch("dw_bwd");
-  if (rc) return rc;
+  if (const int rc = dw_launch(c, st)) return rc;
   if (a->defer_wreduce) return ADDK_OK;
-  int n = a->src.C * taps;
-  hipLaunchKernelGGL(dw_wreduce_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, a->ws, rows, n, a->dw, a->dw_accumulate);
+  const int n = a->src.C * c.taps;
+  hipLaunchKernelGGL(dw_wreduce_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, a->ws, c.t.rows, n, a->dw, a->dw_accumulate);
   return addk_check_launch("dw_wreduce");
 }
 
@@ -552,59 +564,40 @@ extern "C" int addk_dw_wreduce_batch(const addk_dw_wreduce_item* dev_items, int3
   return addk_check_launch("dw_wreduce_batch");
 }
 
+// cfg[8]: include/addk.h
+template <typename Args>
+static int dw_config(const Args* a, int32_t* cfg, int (*choose)(const Args*, DwChoice&)) {
+  ADDK_REQUIRE(cfg, "dw_config: null cfg");
+  DwChoice c;
+  if (const int rc = choose(a, c)) return rc;
+  const DwT& t = c.t;
+  cfg[0] = c.tiled; cfg[1] = t.k.KH; cfg[2] = c.tiled ? t.TH : 0; cfg[3] = t.gx; cfg[4] = t.ngrp; cfg[5] = (int32_t)t.shbytes; cfg[6] = t.rows; cfg[7] = c.key;
+  return ADDK_OK;
+}
+extern "C" int addk_dw_fwd_config(const addk_dw_args* a, int32_t* cfg) { return dw_config(a, cfg, dw_choose_fwd); }
+extern "C" int addk_dw_bwd_config(const addk_dw_bwd_args* a, int32_t* cfg) { return dw_config(a, cfg, dw_choose_bwd); }
+
 // ---- batched form of the LDS-tiled kernels: the independent depthwise convs of one dependency level in one launch --------
-static bool dw_fill_fwd_k(const addk_dw_args* a, DwK& k) {
-  if (!a || !a->w || !a->y || a->ldy < a->src.C) return false;
-  if (dw_fill(k, a->src, a->N, a->H, a->W, a->OH, a->OW, a->KH, a->KW, a->stride, a->pad, a->dil)) return false;
-  k.w = a->w; k.y = a->y; k.ldy = a->ldy;
-  k.P = (long)a->N * a->OH * a->OW;
-  k.vec = src_vec_ok(a->src) && aligned16(a->y) && a->ldy % 4 == 0;
-  return true;
-}
-static bool dw_fill_bwd_k(const addk_dw_bwd_args* a, DwK& k) {
-  if (!a || !a->dy || !a->w || !a->dw || !a->ws || a->lddy < a->src.C || (a->g && a->ldg < a->src.C)) return false;
-  if (dw_fill(k, a->src, a->N, a->H, a->W, a->OH, a->OW, a->KH, a->KW, a->stride, a->pad, a->dil)) return false;
-  k.w = a->w; k.dy = a->dy; k.lddy = a->lddy; k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate;
-  k.dab = (double*)a->dab; k.ws = a->ws;
-  k.P = (long)a->N * a->H * a->W;
-  k.vec = src_vec_ok(a->src) && aligned16(a->dy) && a->lddy % 4 == 0 && (!a->g || (aligned16(a->g) && a->ldg % 4 == 0));
-  return true;
-}
-// key >= 0 (= kernel size | backward << 4): the launch runs on the tiled kernel and can share a batch with equal keys
-extern "C" int addk_dw_fwd_batch_key(const addk_dw_args* a) {
-  DwK k{}; DwT t;
-  return (dw_fill_fwd_k(a, k) && dw_tile_fwd(a, k, t)) ? a->KH : -1;
-}
-extern "C" int addk_dw_bwd_batch_key(const addk_dw_bwd_args* a) {
-  DwK k{}; DwT t;
-  if (!a || !a->defer_wreduce) return -1;               // the batched launch has no per-conv weight reduction
-  return (dw_fill_bwd_k(a, k) && dw_tile_bwd(a, k, dw_rows(k.P, a->src.C), t)) ? (a->KH | 16) : -1;
-}
-template <typename Args, typename Setup>
-static int64_t dw_batch_prepare(const Args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta, int bwd, Setup setup) {
-  if (!a || n <= 0 || !meta) { addk_set_error("dw_batch_prepare: bad args"); return ADDK_ERR_INVALID; }
-  const int64_t total = (int64_t)n * sizeof(DwT);
-  if (host_blob && blob_bytes < total) { addk_set_error("dw_batch_prepare: blob too small"); return ADDK_ERR_INVALID; }
-  int ks = 0, gx = 0, gy = 0; unsigned sh = 0;
-  for (int i = 0; i < n; ++i) {
-    DwT t;
-    if (!setup(&a[i], t)) { addk_set_error("dw_batch_prepare: launch %d is not a tiled-kernel shape", i); return ADDK_ERR_INVALID; }
-    if (i == 0) ks = a[i].KH;
-    if (a[i].KH != ks) { addk_set_error("dw_batch_prepare: mixed kernel sizes"); return ADDK_ERR_INVALID; }
-    if (t.gx > gx) gx = t.gx;
-    if (t.ngrp > gy) gy = t.ngrp;
-    if (t.shbytes > sh) sh = t.shbytes;
-    if (host_blob) reinterpret_cast<DwT*>(host_blob)[i] = t;
-  }
-  meta[0] = ks | (bwd << 4); meta[1] = n; meta[2] = gx; meta[3] = gy; meta[4] = sh;
+extern "C" int addk_dw_fwd_batch_key(const addk_dw_args* a) { DwChoice c; return dw_choose_fwd(a, c) == ADDK_OK ? c.key : -1; }
+extern "C" int addk_dw_bwd_batch_key(const addk_dw_bwd_args* a) { DwChoice c; return dw_choose_bwd(a, c) == ADDK_OK ? c.key : -1; }
+// meta[0..4] = key, n, grid x, grid y, dynamic LDS bytes
+template <typename Args>
+static int64_t dw_batch_prepare(const char* what, const Args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta, int (*choose)(const Args*, DwChoice&)) {
+  size_t lds = 0;
+  const int64_t total = batch_prepare<DwT>(what, a, n, host_blob, blob_bytes, meta, [choose](const Args* x, DwT& t, BatchItem& b) {
+    DwChoice c;
+    if (choose(x, c) != ADDK_OK || c.key < 0) return false;
+    t = c.t; b = BatchItem{c.key, t.gx, t.ngrp, t.shbytes};
+    return true;
+  }, &lds);
+  if (total > 0) meta[4] = (int64_t)lds;
   return total;
 }
 extern "C" int64_t addk_dw_fwd_batch_prepare(const addk_dw_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  return dw_batch_prepare(a, n, host_blob, blob_bytes, meta, 0, [](const addk_dw_args* x, DwT& t) { DwK k{}; return dw_fill_fwd_k(x, k) && dw_tile_fwd(x, k, t); });
+  return dw_batch_prepare("dw_fwd_batch_prepare", a, n, host_blob, blob_bytes, meta, dw_choose_fwd);
 }
 extern "C" int64_t addk_dw_bwd_batch_prepare(const addk_dw_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  return dw_batch_prepare(a, n, host_blob, blob_bytes, meta, 1, [](const addk_dw_bwd_args* x, DwT& t) {
-    DwK k{}; return x->defer_wreduce && dw_fill_bwd_k(x, k) && dw_tile_bwd(x, k, dw_rows(k.P, x->src.C), t); });
+  return dw_batch_prepare("dw_bwd_batch_prepare", a, n, host_blob, blob_bytes, meta, dw_choose_bwd);
 }
 extern "C" int addk_dw_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
   ADDK_REQUIRE(dev_blob && meta && meta[1] > 0 && meta[2] > 0 && meta[3] > 0, "dw_batch_run: bad args");
@@ -613,12 +606,9 @@ extern "C" int addk_dw_batch_run(const void* dev_blob, const int64_t* meta, void
   dim3 grid((unsigned)meta[2], (unsigned)meta[3], (unsigned)meta[1]);
   const size_t sh = (size_t)meta[4];
   hipStream_t st = (hipStream_t)stream;
-  if (!bwd) {
-    if (ks == 3) hipLaunchKernelGGL(dw_fwd_tile_batch_kernel<3>, grid, dim3(256), sh, st, tab);
-    else         hipLaunchKernelGGL(dw_fwd_tile_batch_kernel<5>, grid, dim3(256), sh, st, tab);
-  } else {
-    if (ks == 3) hipLaunchKernelGGL(dw_bwd_tile_batch_kernel<3>, grid, dim3(256), sh, st, tab);
-    else         hipLaunchKernelGGL(dw_bwd_tile_batch_kernel<5>, grid, dim3(256), sh, st, tab);
-  }
+  if (!bwd && ks == 3) hipLaunchKernelGGL(dw_fwd_tile_batch_kernel<3>, grid, dim3(256), sh, st, tab);
+  else if (!bwd)       hipLaunchKernelGGL(dw_fwd_tile_batch_kernel<5>, grid, dim3(256), sh, st, tab);
+  else if (ks == 3)    hipLaunchKernelGGL(dw_bwd_tile_batch_kernel<3>, grid, dim3(256), sh, st, tab);
+  else                 hipLaunchKernelGGL(dw_bwd_tile_batch_kernel<5>, grid, dim3(256), sh, st, tab);
   return addk_check_launch("dw_batch");
 }

@@ -284,13 +284,6 @@ int ew_blocks(long P, int npl) {
   if (b > 8192) b = 8192;
   return (int)b;
 }
-int ew_rows(long P, int C) {
-  EwMap m = ew_map(C);
-  long r = P / ((long)m.npl * 2);
-  if (r < 1) r = 1;
-  if (r > 1024) r = 1024;
-  return (int)r;
-}
 
 }  // namespace
 

@@ -223,14 +223,6 @@ __global__ void __launch_bounds__(256) nchw_grad_kernel(const float* dy, const a
   }
 }
 
-int rows_for(long P, int C) {
-  EwMap m = ew_map(C);
-  long r = P / ((long)m.npl * 2);
-  if (r < 1) r = 1;
-  if (r > 1024) r = 1024;
-  return (int)r;
-}
-
 }  // namespace
 
 // Channel chunk c0.. of `src` (pointers advanced; a chunk is at most 1024 channels = 256 threads x 4)
@@ -245,7 +237,7 @@ extern "C" int addk_gap_fwd(const addk_src* src, int32_t N, int32_t HW, float* y
   ADDK_REQUIRE(src && src->x && y && ws && N > 0 && HW > 0 && src->C > 0 && ldy >= src->C, "gap_fwd: bad args");
   ADDK_REQUIRE((src->a == nullptr) == (src->b == nullptr), "gap_fwd: a/b must come together");
   hipStream_t st = (hipStream_t)stream;
-  const int rows = rows_for(HW, src->C);
+  const int rows = ew_rows(HW, src->C);
   for (int c0 = 0; c0 < src->C; c0 += 1024) {          // F=40 with a level-3 last stage has 1600 ASPP input channels
     const int n = src->C - c0 < 1024 ? src->C - c0 : 1024;
     GapK k{};
@@ -263,7 +255,7 @@ extern "C" int addk_gap_fwd(const addk_src* src, int32_t N, int32_t HW, float* y
 extern "C" int addk_gap_bwd(const addk_src* src, int32_t N, int32_t HW, const float* dy, int32_t lddy, float* g, int32_t ldg,
                             int32_t accumulate, double* dab, void* stream) {
   ADDK_REQUIRE(src && src->x && dy && g && N > 0 && HW > 0 && src->C > 0 && ldg >= src->C && lddy >= src->C, "gap_bwd: bad args");
-  const int rows = rows_for((long)N * HW, src->C);
+  const int rows = ew_rows((long)N * HW, src->C);
   for (int c0 = 0; c0 < src->C; c0 += 1024) {
     const int n = src->C - c0 < 1024 ? src->C - c0 : 1024;
     GapK k{};
@@ -325,7 +317,7 @@ extern "C" int addk_nhwc_to_nchw(const addk_src* src, int32_t N, int64_t HW, flo
 extern "C" int addk_nchw_grad_to_nhwc(const float* dy, const addk_src* src, int32_t N, int64_t HW, float* g, int32_t ldg,
                                       int32_t accumulate, double* dab, void* stream) {
   ADDK_REQUIRE(dy && src && src->x && g && N > 0 && HW > 0 && src->C > 0 && ldg >= src->C, "nchw_grad_to_nhwc: bad args");
-  int rows = rows_for((long)N * HW, src->C);
+  int rows = ew_rows((long)N * HW, src->C);
   hipLaunchKernelGGL(nchw_grad_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dy, *src, N, (long)HW, g, ldg, accumulate, (double*)dab, rows);
   return addk_check_launch("nchw_grad_to_nhwc");
 }

@@ -892,26 +892,17 @@ extern "C" int addk_conv_dgrad_batch_key(const addk_conv_dgrad_args* a) {
   ConvChoice c;
   return conv_choose_dgrad(a, addk_get_conv_precision(), addk_get_fast_paths(), c) == ADDK_OK && c.kind == CK_PW ? c.key : -1;
 }
-// host_blob = NULL: returns the blob size in bytes.  meta[0..5] = key, n, gx, gy, reserved
+// host_blob = NULL: returns the blob size in bytes.  meta[0..3] = key, n, gx, gy
 template <typename Args>
 static int64_t pw_batch_prepare(const Args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta,
                                 int (*choose)(const Args*, int, int, ConvChoice&), bool (*fill)(const Args*, PwK&)) {
-  if (!a || n <= 0 || !meta) { addk_set_error("conv_batch_prepare: bad args"); return ADDK_ERR_INVALID; }
-  const int64_t total = (int64_t)n * sizeof(PwK);
-  if (host_blob && blob_bytes < total) { addk_set_error("conv_batch_prepare: blob too small"); return ADDK_ERR_INVALID; }
   const int mode = addk_get_conv_precision(), mask = addk_get_fast_paths();
-  int key0 = -1, gx = 0, gy = 0;
-  for (int i = 0; i < n; ++i) {
+  return batch_prepare<PwK>("conv_batch_prepare", a, n, host_blob, blob_bytes, meta, [=](const Args* x, PwK& k, BatchItem& b) {
     ConvChoice c;
-    if (choose(&a[i], mode, mask, c) || c.kind != CK_PW) { addk_set_error("conv_batch_prepare: launch %d is not a pointwise-kernel shape", i); return ADDK_ERR_INVALID; }
-    if (i == 0) key0 = c.key;
-    if (c.key != key0) { addk_set_error("conv_batch_prepare: mixed kernel variants"); return ADDK_ERR_INVALID; }
-    if (c.gx > gx) gx = c.gx;
-    if (c.gy > gy) gy = c.gy;
-    if (host_blob) { PwK& k = reinterpret_cast<PwK*>(host_blob)[i]; fill(&a[i], k); pw_desc(c, k); }
-  }
-  meta[0] = key0; meta[1] = n; meta[2] = gx; meta[3] = gy;
-  return total;
+    if (choose(x, mode, mask, c) || c.kind != CK_PW) return false;
+    fill(x, k); pw_desc(c, k); b = BatchItem{c.key, c.gx, c.gy, 0};
+    return true;
+  });
 }
 extern "C" int64_t addk_conv_fwd_batch_prepare(const addk_conv_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
   return pw_batch_prepare(a, n, host_blob, blob_bytes, meta, conv_choose_fwd, pw_fill_fwd);

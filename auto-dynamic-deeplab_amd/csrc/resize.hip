@@ -428,14 +428,6 @@ __global__ void __launch_bounds__(256) resize_bwd_tab_batch_kernel(const RsTabIt
   resize_bwd_tab_body<MT>(e.p, e.tpr, e.ntiles, e.tw, blockIdx.x, e.rows);
 }
 
-int rs_rows(long P, int C) {
-  EwMap m = ew_map(C);
-  long r = P / ((long)m.npl * 2);
-  if (r < 1) r = 1;
-  if (r > 1024) r = 1024;
-  return (int)r;
-}
-
 // table-driven backward: 0 = not covered, else the taps-per-axis variant (5 / 9 / 17); fills the launch geometry
 int rs_tab_config(const addk_resize_bwd_args* a, RsK& k, RsTabItem& it, size_t& sh) {
   if (!a || a->nchw_in || !a->dy || !a->g || a->src.C <= 0 || a->src.C > 1024 || a->ldg < a->src.C || a->lddy < a->src.C) return 0;
@@ -452,7 +444,7 @@ int rs_tab_config(const addk_resize_bwd_args* a, RsK& k, RsTabItem& it, size_t& 
              up8 = a->OH <= 8 * a->H + 1 && a->OW <= 8 * a->W + 1;
   if (!(k.vec && a->src.C == m.nq * 4 && m.npl >= 2 && (up2 || up4 || up8) && (addk_get_fast_paths() & ADDK_FAST_DWTILE) && k.P < (1L << 30))) return 0;
   int tw = m.npl >= 4 ? m.npl * 4 : m.npl * 8; if (tw > RT_MAXW) tw = RT_MAXW; if (tw > a->W) tw = a->W;      // (2-3 pixel lanes: 260-512 channels)
-  it.tpr = cdiv(a->W, tw); it.ntiles = a->N * a->H * it.tpr; it.tw = tw; it.rows = rs_rows(k.P, a->src.C);
+  it.tpr = cdiv(a->W, tw); it.ntiles = a->N * a->H * it.tpr; it.tw = tw; it.rows = ew_rows(k.P, a->src.C);
   it.p = k;
   sh = (size_t)m.npl * m.nq * 4 * 2 * sizeof(double);
   return up2 ? 5 : up4 ? 9 : 17;
@@ -467,21 +459,14 @@ extern "C" int addk_resize_bwd_batch_key(const addk_resize_bwd_args* a) {
 }
 // host_blob = NULL: returns the blob size in bytes.  meta[0..3] = variant, n, grid x, dynamic LDS bytes
 extern "C" int64_t addk_resize_bwd_batch_prepare(const addk_resize_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  if (!a || n <= 0 || !meta) { addk_set_error("resize_bwd_batch_prepare: bad args"); return ADDK_ERR_INVALID; }
-  const int64_t total = (int64_t)n * sizeof(RsTabItem);
-  if (host_blob && blob_bytes < total) { addk_set_error("resize_bwd_batch_prepare: blob too small"); return ADDK_ERR_INVALID; }
-  int key0 = -1, gx = 0; size_t lds = 0;
-  for (int i = 0; i < n; ++i) {
-    RsK k; RsTabItem it; size_t sh;
-    const int key = rs_tab_config(&a[i], k, it, sh);
-    if (key <= 0) { addk_set_error("resize_bwd_batch_prepare: launch %d is not a table-driven shape", i); return ADDK_ERR_INVALID; }
-    if (i == 0) key0 = key;
-    if (key != key0) { addk_set_error("resize_bwd_batch_prepare: mixed kernel variants"); return ADDK_ERR_INVALID; }
-    if (it.rows > gx) gx = it.rows;
-    if (sh > lds) lds = sh;
-    if (host_blob) reinterpret_cast<RsTabItem*>(host_blob)[i] = it;
-  }
-  meta[0] = key0; meta[1] = n; meta[2] = gx; meta[3] = (int64_t)lds;
+  size_t lds = 0;
+  const int64_t total = batch_prepare<RsTabItem>("resize_bwd_batch_prepare", a, n, host_blob, blob_bytes, meta, [](const addk_resize_bwd_args* x, RsTabItem& it, BatchItem& b) {
+    RsK k; size_t sh;
+    const int key = rs_tab_config(x, k, it, sh);
+    b = BatchItem{key, it.rows, 1, sh};
+    return key > 0;
+  }, &lds);
+  if (total > 0) meta[3] = (int64_t)lds;
   return total;
 }
 extern "C" int addk_resize_bwd_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
@@ -570,7 +555,7 @@ extern "C" int addk_resize_bwd(const addk_resize_bwd_args* a, void* stream) {
     EwMap m = ew_map(a->src.C); k.nq = m.nq; k.npl = m.npl;
     k.vec = aligned16(a->dy) && a->lddy % 4 == 0 && aligned16(a->g) && a->ldg % 4 == 0 && a->src.C % 4 == 0 &&
             (!a->src.x || src_vec_ok(a->src));
-    int rows = rs_rows(k.P, a->src.C);
+    int rows = ew_rows(k.P, a->src.C);
     size_t sh = (size_t)m.npl * m.nq * 4 * 2 * sizeof(double);
     // at most x2 up-sampling (<= 5 taps per axis), vector-aligned, a few pixel lanes per workgroup: the table-driven kernel
     const bool up2 = a->OH <= 2 * a->H + 1 && a->OW <= 2 * a->W + 1, up4 = a->OH <= 4 * a->H + 1 && a->OW <= 4 * a->W + 1,

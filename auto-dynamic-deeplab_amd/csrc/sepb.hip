@@ -17,6 +17,7 @@
 // depthwise output.
 #include <stdlib.h>
 #include "common.h"
+#include "sep.h"
 
 namespace {
 
@@ -280,31 +281,26 @@ __global__ void __launch_bounds__(256, 2) sepb_batch_kernel(const SepbK* __restr
   sepb_body<KS, KG, KP, R>(p, sepb_sm);
 }
 
-struct SepbCfg { int ks, kg, kp, r; };
-inline int sepb_key(const SepbCfg& c) { return (c.ks << 16) | (c.kg << 12) | (c.kp << 4) | c.r; }
-
-bool sepb_fill(const addk_sep_bwd_args* a, SepbK& k, SepbCfg& c) {
-  if (!a || !(a->K == 3 || a->K == 5) || a->N <= 0 || a->H <= 0 || a->W <= 0) return false;
+// shapes the backward takes: sep_choose's, within 32-bit pixel indexing
+bool sepb_choose(const addk_sep_bwd_args* a, SepChoice& c) {
+  return a && sep_choose(a->N, a->H, a->W, a->src.C, a->Cout, a->K, c) && (long)a->N * a->H * a->W < (1L << 30);
+}
+// the arguments of a launch on the fused kernel; fills the choice
+bool sepb_args_ok(const addk_sep_bwd_args* a, SepChoice& c) {
+  if (!sepb_choose(a, c)) return false;
   const addk_src& s = a->src;
-  const int kg = cdiv(s.C, 16);
-  if (!(kg == 3 || kg == 5) || a->Cout != s.C || !s.x || !src_vec_ok(s) || !a->dw_w || !a->pw_w || !a->dy || !a->ws) return false;
+  if (!s.x || !src_vec_ok(s) || !a->dw_w || !a->pw_w || !a->dy || !a->ws) return false;
   if (!aligned16(a->dy) || a->lddy % 4 || a->lddy < a->Cout || a->ldw < s.C) return false;
-  if (a->g && (!aligned16(a->g) || a->ldg % 4 || a->ldg < s.C)) return false;
-  if ((long)a->N * a->H * a->W >= (1L << 30)) return false;
-  int kp = s.C; while (kp % 16 != 8) kp += 4;
-  if (!((kg == 3 && (kp == 40 || kp == 56)) || (kg == 5 && (kp == 72 || kp == 88)))) return false;
-  k = SepbK{};
-  k.dy = a->dy; k.lddy = a->lddy; k.src = s; k.N = a->N; k.H = a->H; k.W = a->W; k.C = s.C;
+  return !a->g || (aligned16(a->g) && a->ldg % 4 == 0 && a->ldg >= s.C);
+}
+// the kernel descriptor of checked arguments
+SepbK sepb_desc(const addk_sep_bwd_args* a, const SepChoice& c) {
+  SepbK k{};
+  k.dy = a->dy; k.lddy = a->lddy; k.src = a->src; k.N = a->N; k.H = a->H; k.W = a->W; k.C = a->src.C;
   k.dww = a->dw_w; k.pww = a->pw_w; k.ldw = a->ldw; k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate;
   k.dab = (double*)a->dab; k.ws = a->ws;
-  const long blocks2 = (long)a->N * cdiv(a->H, 8) * cdiv(a->W, 16);
-  // 80-channel tiles need 100-127 KB of LDS: one workgroup per CU.  That is fine while the launch has at most two rounds of them
-  // (config 2: 256 workgroups at 64x128) and LOSES to the separate depthwise / pointwise launches beyond (F = 40, 80 channels at
-  // 128x256 = 1024 workgroups: step 72.2 ms fused vs 66.5 ms unfused) — those shapes stay on the unfused kernels
-  if (kg == 5 && (long)a->N * cdiv(a->H, 4) * cdiv(a->W, 16) > 512) return false;
-  c.ks = a->K; c.kg = kg; c.kp = kp; c.r = (kg == 3 && blocks2 >= 384) ? 2 : 1;
-  k.tiles_x = cdiv(a->W, 16); k.tiles_y = cdiv(a->H, 4 * c.r); k.gx = a->N * k.tiles_y * k.tiles_x;
-  return true;
+  k.tiles_x = c.tiles_x; k.tiles_y = c.tiles_y; k.gx = c.gx;
+  return k;
 }
 
 template <int KS, int KG, int KP, int R>
@@ -317,12 +313,9 @@ int sepb_go(bool batch, dim3 grid, hipStream_t st, const SepbK* one, const SepbK
   return addk_check_launch("sep_bwd");
 }
 
-int sepb_dispatch(const SepbCfg& c, bool batch, dim3 grid, hipStream_t st, const SepbK* one, const SepbK* tab) {
-#define ADDK_SEPB(KS_, KG_, KP_, R_) if (c.ks == KS_ && c.kg == KG_ && c.kp == KP_ && c.r == R_) \
-    return sepb_go<KS_, KG_, KP_, R_>(batch, grid, st, one, tab);
-  ADDK_SEPB(3, 3, 40, 1) ADDK_SEPB(3, 3, 40, 2) ADDK_SEPB(5, 3, 40, 1) ADDK_SEPB(5, 3, 40, 2)
-  ADDK_SEPB(3, 3, 56, 1) ADDK_SEPB(3, 3, 56, 2) ADDK_SEPB(5, 3, 56, 1) ADDK_SEPB(5, 3, 56, 2)
-  ADDK_SEPB(3, 5, 72, 1) ADDK_SEPB(5, 5, 72, 1) ADDK_SEPB(3, 5, 88, 1) ADDK_SEPB(5, 5, 88, 1)
+int sepb_dispatch(const SepChoice& c, bool batch, dim3 grid, hipStream_t st, const SepbK* one, const SepbK* tab) {
+#define ADDK_SEPB(KS_, KG_, KP_, R_) if (sep_is(c, KS_, KG_, KP_, R_)) return sepb_go<KS_, KG_, KP_, R_>(batch, grid, st, one, tab);
+  ADDK_SEP_VARIANTS(ADDK_SEPB)
 #undef ADDK_SEPB
   addk_set_error("sep_bwd: no instantiation");
   return ADDK_ERR_UNSUPPORTED;
@@ -330,44 +323,32 @@ int sepb_dispatch(const SepbCfg& c, bool batch, dim3 grid, hipStream_t st, const
 
 }  // namespace
 
-// rows of `ws` ([rows][C][K*K] floats) and `dab` ([rows][C][2] fp64) the launch writes: one per workgroup; 0: shape not covered
-extern "C" int addk_sep_bwd_rows(const addk_sep_bwd_args* a) {
-  SepbK k; SepbCfg c;
-  if (!a) return 0;
-  addk_sep_bwd_args b = *a;
-  if (!b.ws) b.ws = reinterpret_cast<float*>(16);           // geometry query before the workspace exists
-  return (addk_get_fast_paths() & ADDK_FAST_PW) && sepb_fill(&b, k, c) ? k.gx : 0;
+// rows of `ws` ([rows][C][K*K] floats) and `dab` ([rows][C][2] fp64) the launch writes: one per workgroup; 0: the library does not
+// recommend the fused kernel for this shape.  Shape and mask only: the query comes before dy and the workspace exist.
+extern "C" int addk_sep_bwd_rows(const addk_sep_bwd_args* a) { SepChoice c; return sep_recommended() && sepb_choose(a, c) ? c.gx : 0; }
+extern "C" int addk_sep_bwd_batch_key(const addk_sep_bwd_args* a) { SepChoice c; return sep_recommended() && sepb_args_ok(a, c) ? sep_key(c) : -1; }
+extern "C" int addk_sep_bwd_config(const addk_sep_bwd_args* a, int32_t* cfg) {
+  ADDK_REQUIRE(a && cfg, "sep_bwd_config: null argument");
+  SepChoice c{};
+  sepb_choose(a, c);
+  return sep_config(c, addk_sep_bwd_rows(a) > 0, addk_sep_bwd_batch_key(a), cfg);
 }
 extern "C" int addk_sep_bwd(const addk_sep_bwd_args* a, void* stream) {
-  SepbK k; SepbCfg c;
-  ADDK_REQUIRE(sepb_fill(a, k, c), "sep_bwd: shape not covered (K in {3,5}, C == Cout in (32,48] or (64,80], aligned)");
+  SepChoice c;
+  ADDK_REQUIRE(sepb_args_ok(a, c), "sep_bwd: shape not covered (K in {3,5}, C == Cout in (32,48] or (64,80], aligned)");
+  const SepbK k = sepb_desc(a, c);
   return sepb_dispatch(c, false, dim3(k.gx), (hipStream_t)stream, &k, nullptr);
 }
-extern "C" int addk_sep_bwd_batch_key(const addk_sep_bwd_args* a) {
-  SepbK k; SepbCfg c;
-  if (!(addk_get_fast_paths() & ADDK_FAST_PW) || !sepb_fill(a, k, c)) return -1;
-  return sepb_key(c);
-}
 extern "C" int64_t addk_sep_bwd_batch_prepare(const addk_sep_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  if (!a || n <= 0 || !meta) { addk_set_error("sep_bwd_batch_prepare: bad args"); return ADDK_ERR_INVALID; }
-  const int64_t total = (int64_t)n * sizeof(SepbK);
-  if (host_blob && blob_bytes < total) { addk_set_error("sep_bwd_batch_prepare: blob too small"); return ADDK_ERR_INVALID; }
-  int key0 = -1, gx = 0;
-  for (int i = 0; i < n; ++i) {
-    SepbK k; SepbCfg c;
-    if (!sepb_fill(&a[i], k, c)) { addk_set_error("sep_bwd_batch_prepare: launch %d is not covered", i); return ADDK_ERR_INVALID; }
-    const int key = sepb_key(c);
-    if (i == 0) key0 = key;
-    if (key != key0) { addk_set_error("sep_bwd_batch_prepare: mixed kernel variants"); return ADDK_ERR_INVALID; }
-    if (k.gx > gx) gx = k.gx;
-    if (host_blob) reinterpret_cast<SepbK*>(host_blob)[i] = k;
-  }
-  meta[0] = key0; meta[1] = n; meta[2] = gx; meta[3] = 1;
-  return total;
+  return batch_prepare<SepbK>("sep_bwd_batch_prepare", a, n, host_blob, blob_bytes, meta, [](const addk_sep_bwd_args* x, SepbK& k, BatchItem& b) {
+    SepChoice c;
+    if (!sepb_args_ok(x, c)) return false;
+    k = sepb_desc(x, c); b = BatchItem{sep_key(c), c.gx, 1, 0};
+    return true;
+  });
 }
 extern "C" int addk_sep_bwd_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
   ADDK_REQUIRE(dev_blob && meta && meta[1] > 0 && meta[2] > 0, "sep_bwd_batch_run: bad args");
-  const int key = (int)meta[0];
-  SepbCfg c{(key >> 16) & 15, (key >> 12) & 15, (key >> 4) & 255, key & 15};
-  return sepb_dispatch(c, true, dim3((unsigned)meta[2], 1, (unsigned)meta[1]), (hipStream_t)stream, nullptr, reinterpret_cast<const SepbK*>(dev_blob));
+  return sepb_dispatch(sep_from_key((int)meta[0]), true, dim3((unsigned)meta[2], 1, (unsigned)meta[1]), (hipStream_t)stream, nullptr,
+                       reinterpret_cast<const SepbK*>(dev_blob));
 }

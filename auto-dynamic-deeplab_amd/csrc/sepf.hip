@@ -21,6 +21,7 @@
 #include <string.h>
 #include "common.h"
 #include "bnfin.h"
+#include "sep.h"
 
 namespace {
 
@@ -441,14 +442,11 @@ __global__ void __launch_bounds__(256, 2) sepf_batch_kernel(const SepfK* __restr
   sepf_body<KS, KG, KP, R>(p, sepf_sm);
 }
 
-struct SepfCfg { int ks, kg, kp, r; };
-inline int sepf_key(const SepfCfg& c) { return (c.ks << 16) | (c.kg << 12) | (c.kp << 4) | c.r; }
-
-bool sepf_fill(const addk_sep_args* a, SepfK& k, SepfCfg& c) {
-  if (!a || !(a->K == 3 || a->K == 5) || a->N <= 0 || a->H <= 0 || a->W <= 0) return false;
+// the arguments of a launch on the fused kernel (the shape rules are sep_choose's); fills the choice
+bool sepf_args_ok(const addk_sep_args* a, SepChoice& c) {
+  if (!a || !sep_choose(a->N, a->H, a->W, a->src.C, a->Cout, a->K, c)) return false;
   const addk_src& s = a->src;
-  const int kg = cdiv(s.C, 16);
-  if (!(kg == 3 || kg == 5) || a->Cout != s.C || !s.x || !src_vec_ok(s) || !a->dw_w || !a->pw_w || !a->y) return false;
+  if (!s.x || !src_vec_ok(s) || !a->dw_w || !a->pw_w || !a->y) return false;
   if (!aligned16(a->y) || a->ldy % 4 || a->ldy < a->Cout || !aligned16(a->pw_w) || a->ldw % 4 || a->ldw < s.C) return false;
   if (a->t && (!aligned16(a->t) || a->ldt % 4 || a->ldt < s.C)) return false;
   if (a->nterm < 0 || a->nterm > ADDK_MAX_TERMS || (a->ea == nullptr) != (a->eb == nullptr)) return false;
@@ -456,32 +454,28 @@ bool sepf_fill(const addk_sep_args* a, SepfK& k, SepfCfg& c) {
   if (a->ea && (!aligned16(a->ea) || !aligned16(a->eb))) return false;
   if (a->fin.a && (!a->stats || !a->fin_counter || !a->fin.b || a->fin.count <= 0)) return false;
   for (int i = 0; i < a->nterm; ++i) if (!a->term[i].x || a->term[i].C != a->Cout || !src_vec_ok(a->term[i])) return false;
-  int kp = s.C; while (kp % 16 != 8) kp += 4;
-  if (!((kg == 3 && (kp == 40 || kp == 56)) || (kg == 5 && (kp == 72 || kp == 88)))) return false;
-  k = SepfK{};
-  k.src = s; k.N = a->N; k.H = a->H; k.W = a->W; k.C = s.C;
+  return !a->stats || c.gx <= a->stats_rows;               // the caller sizes the slab with addk_sep_rows
+}
+// the library recommends the fused kernel for this launch (sep.h: what follows the fast-path mask)
+bool sepf_recommends(const addk_sep_args* a, SepChoice& c) { return sep_recommended() && sepf_args_ok(a, c); }
+// the kernel descriptor of checked arguments
+SepfK sepf_desc(const addk_sep_args* a, const SepChoice& c) {
+  SepfK k{};
+  k.src = a->src; k.N = a->N; k.H = a->H; k.W = a->W; k.C = a->src.C;
   k.dww = a->dw_w; k.pww = a->pw_w; k.ldw = a->ldw; k.y = a->y; k.ldy = a->ldy; k.t = a->t; k.ldt = a->ldt;
   k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
   k.ea = a->ea; k.eb = a->eb; k.nterm = a->nterm;
   for (int i = 0; i < a->nterm; ++i) k.term[i] = a->term[i];
-  // two rows per wave where that still gives the chip >= 1.5 workgroups per CU (the LDS patch of a KG = 5 tile is 56 KB at R = 1)
-  const long blocks2 = (long)a->N * cdiv(a->H, 8) * cdiv(a->W, 16);
-  // 80-channel tiles need 100-127 KB of LDS: one workgroup per CU.  That is fine while the launch has at most two rounds of them
-  // (config 2: 256 workgroups at 64x128) and LOSES to the separate depthwise / pointwise launches beyond (F = 40, 80 channels at
-  // 128x256 = 1024 workgroups: step 72.2 ms fused vs 66.5 ms unfused) — those shapes stay on the unfused kernels
-  if (kg == 5 && (long)a->N * cdiv(a->H, 4) * cdiv(a->W, 16) > 512) return false;
-  c.ks = a->K; c.kg = kg; c.kp = kp; c.r = (kg == 3 && blocks2 >= 384) ? 2 : 1;
-  k.tiles_x = cdiv(a->W, 16); k.tiles_y = cdiv(a->H, 4 * c.r); k.gx = a->N * k.tiles_y * k.tiles_x;
+  k.tiles_x = c.tiles_x; k.tiles_y = c.tiles_y; k.gx = c.gx;
   k.wt = addk_env("ADDK_SEPF_WT", 1);
   k.rows = a->stats_rows;
-  if (k.slab && k.gx > k.rows) return false;             // the caller sizes the slab with addk_sep_rows
   if (a->fin.a) {
     k.fin.a = a->fin.a; k.fin.b = a->fin.b; k.fin.mean = a->fin.mean; k.fin.invstd = a->fin.invstd; k.fin.gamma = a->fin.gamma; k.fin.beta = a->fin.beta;
     k.fin.running_mean = a->fin.running_mean; k.fin.running_var = a->fin.running_var; k.fin.count = a->fin.count;
     k.fin.momentum = a->fin.momentum; k.fin.eps = a->fin.eps;
     bnfin_bind_ws(k.fin, a->fin_counter, k.gx);
   }
-  return true;
+  return k;
 }
 
 template <int KS, int KG, int KP, int R>
@@ -494,11 +488,9 @@ int sepf_go(bool batch, dim3 grid, hipStream_t st, const SepfK* one, const SepfK
   return addk_check_launch("sep_fwd");
 }
 
-int sepf_dispatch(const SepfCfg& c, bool batch, dim3 grid, hipStream_t st, const SepfK* one, const SepfK* tab) {
-#define ADDK_SEPF(KS_, KG_, KP_, R_) if (c.ks == KS_ && c.kg == KG_ && c.kp == KP_ && c.r == R_) return sepf_go<KS_, KG_, KP_, R_>(batch, grid, st, one, tab);
-  ADDK_SEPF(3, 3, 40, 1) ADDK_SEPF(3, 3, 40, 2) ADDK_SEPF(5, 3, 40, 1) ADDK_SEPF(5, 3, 40, 2)
-  ADDK_SEPF(3, 3, 56, 1) ADDK_SEPF(3, 3, 56, 2) ADDK_SEPF(5, 3, 56, 1) ADDK_SEPF(5, 3, 56, 2)
-  ADDK_SEPF(3, 5, 72, 1) ADDK_SEPF(5, 5, 72, 1) ADDK_SEPF(3, 5, 88, 1) ADDK_SEPF(5, 5, 88, 1)
+int sepf_dispatch(const SepChoice& c, bool batch, dim3 grid, hipStream_t st, const SepfK* one, const SepfK* tab) {
+#define ADDK_SEPF(KS_, KG_, KP_, R_) if (sep_is(c, KS_, KG_, KP_, R_)) return sepf_go<KS_, KG_, KP_, R_>(batch, grid, st, one, tab);
+  ADDK_SEP_VARIANTS(ADDK_SEPF)
 #undef ADDK_SEPF
   addk_set_error("sep_fwd: no instantiation");
   return ADDK_ERR_UNSUPPORTED;
@@ -532,48 +524,34 @@ extern "C" int addk_sepf_diag(unsigned long long* out8) {
 }
 #endif
 // slab rows a fused launch writes (= its workgroups): the caller sizes `stats` with max(this, addk_conv_rows)
-extern "C" int addk_sep_rows(const addk_sep_args* a) {
-  SepfK k; SepfCfg c;
-  addk_sep_args b = *a; b.stats = nullptr; b.fin.a = nullptr;
-  return sepf_fill(&b, k, c) ? k.gx : 0;
-}
+extern "C" int addk_sep_rows(const addk_sep_args* a) { SepChoice c; return a && sep_choose(a->N, a->H, a->W, a->src.C, a->Cout, a->K, c) ? c.gx : 0; }
 // bytes of the zero-initialised workspace `fin_counter` points to, for a launch of `nblocks` workgroups and slab rows of ld channels
 extern "C" int64_t addk_bn_fin_ws_bytes(int32_t nblocks, int32_t ld) { return nblocks > 0 && ld > 0 ? bnfin_ws_bytes(nblocks, ld) : 0; }
-extern "C" int addk_sep_fwd_supported(const addk_sep_args* a) {
-  SepfK k; SepfCfg c;
-  return (addk_get_fast_paths() & ADDK_FAST_PW) && sepf_fill(a, k, c) ? 1 : 0;
+extern "C" int addk_sep_fwd_supported(const addk_sep_args* a) { SepChoice c; return sepf_recommends(a, c) ? 1 : 0; }
+// batched form (one dependency level): key >= 0 groups launches that share a kernel variant
+extern "C" int addk_sep_fwd_batch_key(const addk_sep_args* a) { SepChoice c; return sepf_recommends(a, c) ? sep_key(c) : -1; }
+extern "C" int addk_sep_fwd_config(const addk_sep_args* a, int32_t* cfg) {
+  ADDK_REQUIRE(a && cfg, "sep_fwd_config: null argument");
+  SepChoice c{};
+  sep_choose(a->N, a->H, a->W, a->src.C, a->Cout, a->K, c);
+  return sep_config(c, addk_sep_fwd_supported(a), addk_sep_fwd_batch_key(a), cfg);
 }
 extern "C" int addk_sep_fwd(const addk_sep_args* a, void* stream) {
-  SepfK k; SepfCfg c;
-  ADDK_REQUIRE(sepf_fill(a, k, c), "sep_fwd: shape not covered by the fused kernel (K in {3,5}, C == Cout in (32,48] or (64,80], aligned, stats_rows >= addk_sep_rows)");
+  SepChoice c;
+  ADDK_REQUIRE(sepf_args_ok(a, c), "sep_fwd: shape not covered by the fused kernel (K in {3,5}, C == Cout in (32,48] or (64,80], aligned, stats_rows >= addk_sep_rows)");
+  const SepfK k = sepf_desc(a, c);
   return sepf_dispatch(c, false, dim3(k.gx), (hipStream_t)stream, &k, nullptr);
 }
-// batched form (one dependency level): key >= 0 groups launches that share a kernel variant
-extern "C" int addk_sep_fwd_batch_key(const addk_sep_args* a) {
-  SepfK k; SepfCfg c;
-  if (!(addk_get_fast_paths() & ADDK_FAST_PW) || !sepf_fill(a, k, c)) return -1;
-  return sepf_key(c);
-}
 extern "C" int64_t addk_sep_fwd_batch_prepare(const addk_sep_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  if (!a || n <= 0 || !meta) { addk_set_error("sep_batch_prepare: bad args"); return ADDK_ERR_INVALID; }
-  const int64_t total = (int64_t)n * sizeof(SepfK);
-  if (host_blob && blob_bytes < total) { addk_set_error("sep_batch_prepare: blob too small"); return ADDK_ERR_INVALID; }
-  int key0 = -1, gx = 0;
-  for (int i = 0; i < n; ++i) {
-    SepfK k; SepfCfg c;
-    if (!sepf_fill(&a[i], k, c)) { addk_set_error("sep_batch_prepare: launch %d is not covered", i); return ADDK_ERR_INVALID; }
-    const int key = sepf_key(c);
-    if (i == 0) key0 = key;
-    if (key != key0) { addk_set_error("sep_batch_prepare: mixed kernel variants"); return ADDK_ERR_INVALID; }
-    if (k.gx > gx) gx = k.gx;
-    if (host_blob) reinterpret_cast<SepfK*>(host_blob)[i] = k;
-  }
-  meta[0] = key0; meta[1] = n; meta[2] = gx; meta[3] = 1;
-  return total;
+  return batch_prepare<SepfK>("sep_fwd_batch_prepare", a, n, host_blob, blob_bytes, meta, [](const addk_sep_args* x, SepfK& k, BatchItem& b) {
+    SepChoice c;
+    if (!sepf_args_ok(x, c)) return false;
+    k = sepf_desc(x, c); b = BatchItem{sep_key(c), c.gx, 1, 0};
+    return true;
+  });
 }
 extern "C" int addk_sep_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
   ADDK_REQUIRE(dev_blob && meta && meta[1] > 0 && meta[2] > 0, "sep_batch_run: bad args");
-  const int key = (int)meta[0];
-  SepfCfg c{key >> 16, (key >> 12) & 15, (key >> 4) & 255, key & 15};
-  return sepf_dispatch(c, true, dim3((unsigned)meta[2], 1, (unsigned)meta[1]), (hipStream_t)stream, nullptr, reinterpret_cast<const SepfK*>(dev_blob));
+  return sepf_dispatch(sep_from_key((int)meta[0]), true, dim3((unsigned)meta[2], 1, (unsigned)meta[1]), (hipStream_t)stream, nullptr,
+                       reinterpret_cast<const SepfK*>(dev_blob));
 }

@@ -418,6 +418,20 @@ class Graph:
         self.keep.append(meta)
         return bytes(blob), meta
 
+    @staticmethod
+    def _config(query, args):
+        """cfg[8] of a library `*_config` query: the kernel decision of the launch these arguments describe"""
+        cfg = (C.c_int32 * 8)()
+        L.check(query(C.byref(args), cfg), query.__name__)
+        return cfg
+
+    @staticmethod
+    def _batchable(cmd, key_fn, args):
+        """Let _level_batch merge `cmd` with the same-key commands of its level, if the library gives its arguments a batch key."""
+        bk = int(key_fn(C.byref(args)))
+        if bk >= 0:
+            cmd.payload, cmd.bkey = args, bk
+
     def _bind_late(self, lst, by_level):
         """Give every exchanged statistics vector (LateVec payload of an 'allreduce' command) its storage.  With level
         batching the vectors of one dependency level share one arena, in list order, and `_level_batch` replaces their
@@ -751,9 +765,7 @@ class Graph:
             self.keep.append(ar)
             cf = self._add(self.fwd, 'conv_fwd', lib.addk_conv_fwd, C.byref(ar),
                            rd=rd_src + [weight, bias, bias_n], wr=[out, stats, wpk, rs_out])
-            bk = int(lib.addk_conv_fwd_batch_key(C.byref(ar)))
-            if bk >= 0:
-                cf.payload, cf.bkey = ar, bk
+            self._batchable(cf, lib.addk_conv_fwd_batch_key, ar)
             self.meta.append(dict(kind='conv_fwd', cmd=cf, flops=2.0 * N * OH * OW * Cout * k * k * csum,
                                   bytes=4.0 * (N * H * W * csum + N * OH * OW * Cout + Cout * k * k * csum),
                                   shape=(N, H, W, csum, Cout, k, stride, dil), halo=npk > 0))
@@ -805,9 +817,7 @@ class Graph:
                         self.keep.append(da)
                         cd = self._add(self.bwd, 'conv_dgrad', lib.addk_conv_dgrad, C.byref(da), rd=[dy, weight] + self.lz(s),
                                        wr=[gs, slab, dpk])
-                        bk = int(lib.addk_conv_dgrad_batch_key(C.byref(da)))
-                        if bk >= 0:
-                            cd.payload, cd.bkey = da, bk
+                        self._batchable(cd, lib.addk_conv_dgrad_batch_key, da)
                     choff += s.C
             self._bwd_emitters.append(emit_bwd)
         return out
@@ -845,7 +855,7 @@ class Graph:
         return self.buf(rows * Cc * 4), rows      # fp64 [rows][C][2]
 
     def bn(self, raw, mod, slab=None, rows=0, post_relu=False, needs_grad=True, fuse=None):
-        """Apply BatchNorm module `mod` lazily to `raw`.  Training: statistics come from `slab`.  `fuse` = (args, cmd) of the
+        """Apply BatchNorm module `mod` lazily to `raw`.  Training: statistics come from `slab`.  `fuse` = (args, cmd, workgroups) of the
         producing launch when its kernel can finalize the statistics itself (last workgroup, csrc/bnfin.h): the finalize
         arguments go into `args.fin` and no bn_finalize launch is emitted (local BatchNorm only: the SyncBN exchange sits
         between the slab and the finalize)."""
@@ -888,11 +898,10 @@ class Graph:
             self.keep.append(fa)
             stat_wr = [a, b, st.mean, st.invstd] + ([mod.running_mean, mod.running_var] if fa.running_mean else [])
             if fuse is not None and not sync and os.environ.get('ADDK_FUSE_FINALIZE', '0') == '1':
-                args, cmd, fuse_blocks = fuse
+                args, cmd, nblk = fuse
                 for f_ in ('count', 'gamma', 'beta', 'running_mean', 'running_var', 'momentum', 'eps', 'a', 'b', 'mean', 'invstd'):
                     setattr(args.fin, f_, getattr(fa, f_))
-                nblk, sld = fuse_blocks(args)
-                ctr = self.buf((int(lib.addk_bn_fin_ws_bytes(nblk, sld)) + 3) // 4, zero=True)   # ticket counters + group rows of this BatchNorm call
+                ctr = self.buf((int(lib.addk_bn_fin_ws_bytes(nblk, Cc)) + 3) // 4, zero=True)   # ticket counters + group rows of this BatchNorm call
                 args.fin_counter = ctr.ptr
                 cmd.rd += [r for r in (_region(mod.weight), _region(mod.bias)) if r]
                 cmd.wr += [r for r in (_region(x) for x in stat_wr + [ctr]) if r]
@@ -1000,9 +1009,7 @@ class Graph:
         self.keep.append(ar)
         if fwd:
             cdw = self._add(self.fwd, 'dw_fwd', lib.addk_dw_fwd, C.byref(ar), rd=self.lz(src) + [conv_mod.weight], wr=[out])
-            bk = int(lib.addk_dw_fwd_batch_key(C.byref(ar)))
-            if bk >= 0:
-                cdw.payload, cdw.bkey = ar, bk
+            self._batchable(cdw, lib.addk_dw_fwd_batch_key, ar)
         act = Act(out, None, False, self.want_grad)
         if self.want_grad:
             def emit_bwd():
@@ -1035,37 +1042,25 @@ class Graph:
                 self.keep.append(ba)
                 cdb = self._add(self.bwd, 'dw_bwd', lib.addk_dw_bwd, C.byref(ba), rd=[dy, conv_mod.weight] + self.lz(src),
                                 wr=[gs, slab, ws])
-                bk = int(lib.addk_dw_bwd_batch_key(C.byref(ba)))
-                if bk >= 0:
-                    cdb.payload, cdb.bkey = ba, bk
+                self._batchable(cdb, lib.addk_dw_bwd_batch_key, ba)
             self._bwd_emitters.append(emit_bwd)
         return act
 
-    def _sep_bwd(self, src, dw_mod, pw_mod, raw, t=None, probe=False):
+    def _sep_bwd_args(self, src, dw_mod, pw_mod):
+        """addk_sep_bwd arguments of one SepConv half, all but the gradients and the workspace"""
+        ba = L.SepBwdArgs()
+        ba.N, ba.H, ba.W, ba.K, ba.Cout, ba.ldw = src.N, src.H, src.W, dw_mod.kernel_size[0], pw_mod.out_channels, src.C
+        ba.src, ba.dw_w, ba.pw_w = self.src(src, True), self.param(dw_mod.weight), self.param(pw_mod.weight)
+        return ba
+
+    def _sep_bwd(self, src, dw_mod, pw_mod, raw, t, rows):
         """Backward of one SepConv half as ONE launch (addk_sep_bwd, csrc/sepb.hip): data gradient of the pointwise conv and the
         whole depthwise backward, the gradient between them staying on chip; the pointwise WEIGHT gradient joins the deferred
-        weight-gradient batches.  probe=True only asks whether the kernel covers the shape."""
+        weight-gradient batches.  `rows`: the launch's workgroups (addk_sep_bwd_config)."""
         lib = self.lib
         k = dw_mod.kernel_size[0]
         N, H, W, Cc = src.N, src.H, src.W, src.C
         Cout = pw_mod.out_channels
-
-        def fill(ba, dy_ptr, dy_ld):
-            ba.dy, ba.lddy = dy_ptr, dy_ld
-            ba.N, ba.H, ba.W, ba.K = N, H, W, k
-            ba.src = self.src(src, True)
-            ba.Cout, ba.ldw = Cout, Cc
-            ba.dw_w, ba.pw_w = self.param(dw_mod.weight), self.param(pw_mod.weight)
-        def fill_w(wa, dy_ptr, dy_ld, t_src, gp, acc):
-            wa.dy, wa.lddy, wa.Cout = dy_ptr, dy_ld, Cout
-            wa.N, wa.H, wa.W, wa.OH, wa.OW, wa.KH, wa.KW, wa.stride, wa.pad, wa.dil = N, H, W, H, W, 1, 1, 1, 0, 1
-            wa.src = t_src
-            wa.dw, wa.ldw, wa.cin_total, wa.w_choff, wa.accumulate = gp, Cc, Cc, 0, acc
-        if probe:
-            ba = L.SepBwdArgs()
-            fill(ba, raw.ptr, raw.ld)
-            ok = int(lib.addk_sep_bwd_rows(C.byref(ba))) > 0
-            return ok
 
         def emit_bwd():
             if not self.grad_ready(raw):
@@ -1074,13 +1069,15 @@ class Graph:
             # pointwise weight gradient: dW[co][ci] = sum_p dy[p][co] t[p][ci]
             wa = L.ConvWgradArgs()
             gp, acc = self.param_grad(pw_mod.weight, (0, Cc))
-            fill_w(wa, dy.ptr, dy.ld, self.src(t), gp, acc)
+            wa.dy, wa.lddy, wa.Cout = dy.ptr, dy.ld, Cout
+            wa.N, wa.H, wa.W, wa.OH, wa.OW, wa.KH, wa.KW, wa.stride, wa.pad, wa.dil = N, H, W, H, W, 1, 1, 1, 0, 1
+            wa.src = self.src(t)
+            wa.dw, wa.ldw, wa.cin_total, wa.w_choff, wa.accumulate = gp, Cc, Cc, 0, acc
             wa.ws_floats = lib.addk_conv_wgrad_ws(N * H * W, Cout, Cc, 1)
             self._wgrads.append((wa, [dy] + self.lz(t), self.pgrad[pw_mod.weight], (id(pw_mod.weight), 0, Cc)))
             # fused data gradient + depthwise backward
-            ba = L.SepBwdArgs()
-            fill(ba, dy.ptr, dy.ld)
-            rows = int(lib.addk_sep_bwd_rows(C.byref(ba)))
+            ba = self._sep_bwd_args(src, dw_mod, pw_mod)
+            ba.dy, ba.lddy = dy.ptr, dy.ld
             gs = slab = None
             if src.needs_grad:
                 gs = self.grad(src.raw)
@@ -1098,11 +1095,14 @@ class Graph:
             self.keep.append(ba)
             cb = self._add(self.bwd, 'sep_bwd', lib.addk_sep_bwd, C.byref(ba), rd=[dy, dw_mod.weight, pw_mod.weight] + self.lz(src),
                            wr=[gs, slab, ws])
-            bk = int(lib.addk_sep_bwd_batch_key(C.byref(ba)))
-            if bk >= 0:
-                cb.payload, cb.bkey = ba, bk
+            self._batchable(cb, lib.addk_sep_bwd_batch_key, ba)
         self._bwd_emitters.append(emit_bwd)
-        return True
+
+    def _sep_fusable(self, dw_mod, pw_mod, sum_terms, training):
+        """The halves the fused kernels are written for (ADDK_FUSE_SEP=0: none); which shapes run fused is the library's decision."""
+        return (os.environ.get('ADDK_FUSE_SEP', '1') == '1' and dw_mod.stride[0] == 1 and dw_mod.dilation[0] == 1
+                and dw_mod.padding[0] == dw_mod.kernel_size[0] // 2 and pw_mod.kernel_size[0] == 1
+                and (sum_terms is None or not (training or self.want_grad)))
 
     def sep_half(self, src, dw_mod, pw_mod, bn_mod, sum_terms=None, out=None):
         """One half of SepConv (operations.py:51-54 / 55-58): ReLU -> depthwise k x k -> pointwise 1x1 -> BN (lazy), as ONE
@@ -1119,12 +1119,12 @@ class Graph:
         ar.src = self.src(src, True)
         ar.N, ar.H, ar.W, ar.K, ar.Cout, ar.ldw = N, H, W, k, Cout, Cc
         ar.dw_w, ar.pw_w = self.param(dw_mod.weight), self.param(pw_mod.weight)
-        fused = (os.environ.get('ADDK_FUSE_SEP', '1') == '1' and dw_mod.stride[0] == 1 and dw_mod.dilation[0] == 1
-                 and dw_mod.padding[0] == k // 2 and pw_mod.kernel_size[0] == 1 and (sum_terms is None or not (training or self.want_grad)))
+        fused = self._sep_fusable(dw_mod, pw_mod, sum_terms, training)
         if fused:
             raw = out if (out is not None and sum_terms is not None) else self.tensor(N, H, W, Cout)
             ar.y, ar.ldy = raw.ptr, raw.ld
-            fused = bool(lib.addk_sep_fwd_supported(C.byref(ar)))
+            fcfg = self._config(lib.addk_sep_fwd_config, ar)          # asked once: fused or not, the launch's workgroups
+            fused = fcfg[0] == 1
         if not fused:
             t = self.dwconv(src, dw_mod, relu_in=True)
             act = self.conv_bn([t], pw_mod, bn_mod, relu_in=False)
@@ -1132,13 +1132,14 @@ class Graph:
         t = None
         slab = rows = None
         if training:
-            rows = max(int(lib.addk_sep_rows(C.byref(ar))), int(lib.addk_conv_rows(N * H * W, Cout)))
+            rows = max(fcfg[6], int(lib.addk_conv_rows(N * H * W, Cout)))
             slab = self.buf(rows * Cout * 4)
             ar.stats_rows = rows
         if self.want_grad:
-            if os.environ.get('ADDK_FUSE_SEP_BWD', '1') == '1' and self._sep_bwd(src, dw_mod, pw_mod, raw, probe=True):
+            bcfg = self._config(lib.addk_sep_bwd_config, self._sep_bwd_args(src, dw_mod, pw_mod)) if os.environ.get('ADDK_FUSE_SEP_BWD', '1') == '1' else [0]
+            if bcfg[0] == 1:
                 t = Act(self.tensor(N, H, W, Cc), None, False, True)           # depthwise output: written by the fused forward, read by the pointwise weight gradient
-                self._sep_bwd(src, dw_mod, pw_mod, raw, t=t)
+                self._sep_bwd(src, dw_mod, pw_mod, raw, t, bcfg[6])
             else:
                 t = self.dwconv(src, dw_mod, relu_in=True, fwd=False)
                 self.conv([t], pw_mod.weight, Cout, 1, out=raw, stats=slab, fwd=False)       # backward of the pointwise half
@@ -1159,15 +1160,8 @@ class Graph:
             rd += [st.a, st.b]
         self.keep.append(ar)
         c = self._add(self.fwd, 'sep_fwd', lib.addk_sep_fwd, C.byref(ar), rd=rd, wr=[raw, slab, t.raw if t is not None else None])
-        if sum_terms is not None:
-            bk = int(lib.addk_sep_fwd_batch_key(C.byref(ar)))
-            if bk >= 0:
-                c.payload, c.bkey = ar, bk
-            return Act(raw, None, False, False)
-        act = self.bn(raw, bn_mod, slab, rows or 0, fuse=(ar, c, lambda a_: (int(lib.addk_sep_rows(C.byref(a_))), Cout)))
-        bk = int(lib.addk_sep_fwd_batch_key(C.byref(ar)))         # after bn(): the fused finalize is part of the launch's validity
-        if bk >= 0:
-            c.payload, c.bkey = ar, bk
+        act = Act(raw, None, False, False) if sum_terms is not None else self.bn(raw, bn_mod, slab, rows or 0, fuse=(ar, c, fcfg[5]))
+        self._batchable(c, lib.addk_sep_fwd_batch_key, ar)        # after bn(): the fused finalize is part of the launch's validity
         return act
 
     def affine_sum(self, terms, out=None, relu_out=False):
@@ -1267,9 +1261,8 @@ class Graph:
                         src.bn.slabs.append((slab, rows))
                 self.keep.append(ba)
                 crb = self._add(self.bwd, 'resize_bwd', lib.addk_resize_bwd, C.byref(ba), rd=[dy] + self.lz(src), wr=[gs, slab])
-                bk = int(lib.addk_resize_bwd_batch_key(C.byref(ba))) if os.environ.get('ADDK_BATCH_RESIZE_BWD', '1') == '1' else -1
-                if bk >= 0:
-                    crb.payload, crb.bkey = ba, bk
+                if os.environ.get('ADDK_BATCH_RESIZE_BWD', '1') == '1':
+                    self._batchable(crb, lib.addk_resize_bwd_batch_key, ba)
             self._bwd_emitters.append(emit_bwd)
         return res
 

@@ -236,7 +236,16 @@ int addk_conv_wgrad_batch_run(const void* dev_blob, const int64_t* meta, void* s
  * two-level reduction — whose counters the launch leaves at zero again).  In inference t = NULL and the epilogue can apply the op's own
  * (frozen) BatchNorm and add the other branches of the cell block (ADD.py:108):
  *     y = ea[c]*acc + eb[c] + sum_i relu_i?(a_i*term_i + b_i)        (ea == NULL: plain y = acc)
- * Covered shapes: K in {3,5}, C == Cout in (32, 48] or (64, 80], 16-byte aligned tensors; addk_sep_fwd_supported says so.
+ * Covered shapes: K in {3,5}, C == Cout in (32, 48] or (64, 80], 16-byte aligned tensors; 80 channels up to 512 workgroups.
+ *
+ * Forward and backward share ONE tile choice, made from (N, H, W, C, Cout, K) alone (csrc/sep.h): the same shape gets the same
+ * variant (ks, kg, kp, r) and the same tiles in both directions.  The fast-path mask (ADDK_FAST_PW) gates what the library
+ * RECOMMENDS: addk_sep_fwd_supported, addk_sep_bwd_rows, the batch keys, cfg[0] and cfg[7] below.  addk_sep_rows is plain
+ * geometry, and a direct addk_sep_fwd / addk_sep_bwd call (or a batch prepared from such arguments) runs the fused kernel
+ * whatever the mask says.
+ * addk_sep_fwd_config / addk_sep_bwd_config: cfg[8] = fused (1: recommended; forward = addk_sep_fwd_supported, arguments checked;
+ * backward = addk_sep_bwd_rows > 0, shape and mask only, so that it can be asked before dy and ws exist), ks, kg, kp, r, grid x,
+ * rows (= grid x; cfg[1..6] are 0 for a shape the kernels do not take), batch key or -1.
  * ------------------------------------------------------------------------------------- */
 typedef struct addk_sep_args {
   addk_src src;                     /* lazy input of the depthwise conv (x, a, b, relu) */
@@ -256,8 +265,9 @@ typedef struct addk_sep_args {
   void* fin_counter;
 } addk_sep_args;
 int64_t addk_bn_fin_ws_bytes(int32_t nblocks, int32_t ld);
-int addk_sep_rows(const addk_sep_args* a);               /* slab rows (= workgroups) of the fused launch; 0: not covered */
-int addk_sep_fwd_supported(const addk_sep_args* a);      /* 1: the fused kernel covers this launch */
+int addk_sep_rows(const addk_sep_args* a);               /* slab rows (= workgroups) of the fused launch; 0: shape not covered */
+int addk_sep_fwd_supported(const addk_sep_args* a);      /* 1: the fused kernel covers this launch and the mask allows it */
+int addk_sep_fwd_config(const addk_sep_args* a, int32_t* cfg);
 int addk_sep_fwd(const addk_sep_args* a, void* stream);
 /* table-driven batch of the fused halves of one dependency level (same protocol as addk_conv_fwd_batch_prepare / addk_conv_batch_run) */
 int addk_sep_fwd_batch_key(const addk_sep_args* a);
@@ -279,7 +289,8 @@ typedef struct addk_sep_bwd_args {
   double* dab;                      /* or NULL */
   float* ws;
 } addk_sep_bwd_args;
-int addk_sep_bwd_rows(const addk_sep_bwd_args* a);
+int addk_sep_bwd_rows(const addk_sep_bwd_args* a);       /* reads the shape only; 0: not recommended */
+int addk_sep_bwd_config(const addk_sep_bwd_args* a, int32_t* cfg);
 int addk_sep_bwd(const addk_sep_bwd_args* a, void* stream);
 int addk_sep_bwd_batch_key(const addk_sep_bwd_args* a);
 int64_t addk_sep_bwd_batch_prepare(const addk_sep_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta);
@@ -323,6 +334,11 @@ int64_t addk_dw_fwd_batch_prepare(const addk_dw_args* a, int32_t n, void* host_b
 int64_t addk_dw_bwd_batch_prepare(const addk_dw_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta);
 int addk_dw_batch_run(const void* dev_blob, const int64_t* meta, void* stream);
 int addk_dw_rows(int64_t P, int32_t C);
+/* The kernel a depthwise launch takes (what the launch, the batch key and prepare read): cfg[8] = kind (0 generic, 1 LDS-tiled:
+ * 3x3 / 5x5, 16-byte aligned, >= 2048 pixels, backward stride 1, ADDK_FAST_DWTILE set), kernel size, rows per tile (generic: 0),
+ * grid x, grid y, dynamic LDS bytes, workspace rows (forward: 0), batch key or -1. */
+int addk_dw_fwd_config(const addk_dw_args* a, int32_t* cfg);
+int addk_dw_bwd_config(const addk_dw_bwd_args* a, int32_t* cfg);
 
 /* ---------------------------------------------------------------------------------------
  * BatchNorm statistics (F.batch_norm training mode, batchnorm.py:51-53; eps=1e-5, mom=0.1).
