@@ -11,7 +11,7 @@
 //     KP = 8 (mod 16) makes the tap reads of stage 2 conflict-free (sepf.hip);
 //   * stage 2: lane (li, kq) owns R input pixels x 4 channels of group g: per kernel row it reads KS shifted dt quads, feeds dz
 //     and the KS weight-gradient products, and reduces the latter over the 16 pixel lanes with four DPP row adds (fixed
-//     order: bit-reproducible); per-wave partials meet in LDS, one row [C][KS*KS] of the weight-gradient workspace and one row
+//     order: bit-reproducible); the four row bands' partials meet in LDS, one row [C][KS*KS] of the weight-gradient workspace and one row
 //     [C][2] of the (dA, dB) slab per workgroup.
 // The pointwise WEIGHT gradient stays with the batched register-streaming kernel (wgrad.hip), which reads dy and the stored
 // depthwise output.
@@ -42,12 +42,20 @@ __device__ __forceinline__ float row_sum16(float v) {
   return v;
 }
 
+// waves per workgroup.  Stage 1 hands the 16-pixel tiles of the patch and stage 2 the 4 * KG (row band, channel group) items round-robin to
+// NW waves; the arithmetic of a tile / an item does not depend on which wave runs it.  A tile is one workgroup and the grid is one or two
+// workgroups per CU (sep.h), so NW sets the waves per SIMD: 16 waves for the 80-channel tiles (one workgroup per CU), 8 for the 40-channel
+// 3x3 (two per CU), both 4 waves per SIMD within 128 VGPRs; the 40-channel 5x5 needs ~146 VGPRs and stays at 4 waves.
+template <int KS, int KG>
+struct SepbWaves { static constexpr int NW = KG == 5 ? 16 : KS == 3 ? 8 : 4, WPS = NW == 4 ? 2 : 4; };
+
 template <int KS, int KG, int KP, int R>
 struct SepbGeo {
+  static constexpr int NW = SepbWaves<KS, KG>::NW, NTHR = 64 * NW, WPS = SepbWaves<KS, KG>::WPS;   // waves, threads, waves per SIMD the launch bounds ask for
   static constexpr int CT = KG, PH = 4 * R + KS - 1, PW = 16 + KS - 1, NPIX = PH * PW, KQ = KP / 4, NT16 = (NPIX + 15) / 16;
   static constexpr int PATCH = NT16 * 16 * KP + 8;
   static constexpr int DWL = KS * KS * KG * 16, PWL = KG * CT * 64 * 4;
-  static constexpr int DWS = 4 * KS * KS * KG * 16;                // per-wave weight-gradient partials [4][KS*KS][KG*16]
+  static constexpr int DWS = 4 * KS * KS * KG * 16;                // per-row-band weight-gradient partials [4][KS*KS][KG*16]
   static constexpr int RED = 4 * KG * 16 * 2 * 2;                  // floats: [4][KG*16][2] doubles
   static constexpr size_t LDS = (size_t)(PATCH + DWL + PWL + DWS + RED) * 4;
 };
@@ -61,7 +69,8 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
   float* pwl = dwl + G::DWL;                     // [KG][CT][64] float4: A fragments of W^T
   float* dws = pwl + G::PWL;                     // [4][NT][KG*16]
   double* red = reinterpret_cast<double*>(dws + G::DWS);
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, kq = lane >> 4;
+  constexpr int NW = G::NW, NTHR = G::NTHR;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), li = lane & 15, kq = lane >> 4;
   const int C = p.C;
   int b = blockIdx.x;
   const int tx = b % p.tiles_x; b /= p.tiles_x;
@@ -89,15 +98,15 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
   dy_load(wave, dcur);
   __builtin_amdgcn_sched_barrier(0);
   // ---- weights -> LDS (the tap table's channels beyond C are zeroed by threads that write no weight there: no barrier in between) ----
-  for (int i = t; i < NT * (KG * 16 - C); i += 256) {
+  for (int i = t; i < NT * (KG * 16 - C); i += NTHR) {
     const int tp = i / (KG * 16 - C), c = C + i - tp * (KG * 16 - C);
     dwl[tp * (KG * 16) + c] = 0.f;
   }
-  for (int i = t; i < C * NT; i += 256) {
+  for (int i = t; i < C * NT; i += NTHR) {
     const int c = i / NT, tp = i - c * NT;
     dwl[(NT - 1 - tp) * (KG * 16) + c] = ((const gfloat*)p.dww)[i];
   }
-  for (int s = t; s < KG * CT * 64; s += 256) {          // A[row = ci = 16 i + (ln & 15)][k = co = 16 g + 4 (ln >> 4) + e] = W[co][ci]
+  for (int s = t; s < KG * CT * 64; s += NTHR) {          // A[row = ci = 16 i + (ln & 15)][k = co = 16 g + 4 (ln >> 4) + e] = W[co][ci]
     const int g = s / (CT * 64), rem = s - g * (CT * 64), i = rem >> 6, ln = rem & 63;
     const int ci = i * 16 + (ln & 15), co = 16 * g + 4 * (ln >> 4);
     const bool ok = ci < C && co < C;
@@ -108,7 +117,7 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
     lds_st4(pwl + s * 4, v);
   }
   if (KQ > C / 4) {                                      // zero the padding quads of every patch pixel (never written by stage 1)
-    for (int i = t; i < G::NT16 * 16 * (KQ - C / 4); i += 256) {
+    for (int i = t; i < G::NT16 * 16 * (KQ - C / 4); i += NTHR) {
       const int px = i / (KQ - C / 4), q = C / 4 + i - px * (KQ - C / 4);
       lds_st4(patch + px * KP + 4 * q, zero4());
     }
@@ -117,11 +126,11 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
   __syncthreads();
 
   // ---- stage 1: dt = W^T dy on the haloed patch, 16 pixels at a time ----
-  for (int j = wave; j < G::NT16; j += 4) {
+  for (int j = wave; j < G::NT16; j += NW) {
     const int pix = 16 * j + li;
     const float* dp; bool ok;
     dy_geom(j, dp, ok);
-    dy_load(j + 4, dnxt);                                  // the next tile of this wave: in flight under this tile's matrix work (masked beyond the patch)
+    dy_load(j + NW, dnxt);                                  // the next tile of this wave: in flight under this tile's matrix work (masked beyond the patch)
     float4 d[KG];
 #pragma unroll
     for (int g = 0; g < KG; ++g) {
@@ -154,20 +163,22 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
   }
   __syncthreads();
 
-  // ---- stage 2: depthwise backward; wave = input rows [wave*R, wave*R + R) x 16 pixels ----
+  // ---- stage 2: depthwise backward; a work item is (row band rb: input rows [rb*R, rb*R + R) x 16 pixels, channel group g), item 4 g + rb
+  // goes to wave (4 g + rb) % NW: NW is a multiple of 4, so a wave keeps ONE band and walks the groups g = wave / 4, + NW / 4, ... ----
+  const int rb = wave & 3;
   int pp[R]; bool pin[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const int ih = ih0 + wave * R + r, iw = iw0 + li;
+    const int ih = ih0 + rb * R + r, iw = iw0 + li;
     pin[r] = ih < p.H && iw < p.W;
     pp[r] = (n * p.H + ih) * p.W + iw;
   }
   const bool relu = p.src.relu != 0;
-  float* mydws = dws + wave * (NT * KG * 16);
+  float* mydws = dws + rb * (NT * KG * 16);
   double (*rd)[KG * 16][2] = reinterpret_cast<double (*)[KG * 16][2]>(red);
   // real loops over the channel group and the kernel row: fully unrolled, hipcc hoists every LDS read of the 15 (group, row)
   // bodies to the top (234-256 VGPRs and scratch spills for KS = 5); one body at a time needs ~100
-  // [r4] the operands of the NEXT channel group (input values, the gradient to accumulate into) are requested at the top of a group's
+  // [r4] the operands of this wave's NEXT item (input values, the gradient to accumulate into) are requested at the top of an item's
   // body and arrive under its LDS / VALU work: the loop used to open with a dependent round trip per group and close with another
   float4 xn[R], on[R];
   auto pre = [&](int g) {
@@ -181,9 +192,9 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
       if (p.g && p.accumulate) on[r] = ld4(p.g + (okx ? (long)pp[r] * p.ldg + 4 * q : 0));
     }
   };
-  pre(0);
+  pre(wave >> 2);
 #pragma unroll 1
-  for (int g = 0; g < KG; ++g) {
+  for (int g = wave >> 2; g < KG; g += NW / 4) {       // a wave with no item (left) falls through to the barrier
     const int q = 4 * g + kq;
     const int qr = q < KQ ? q : q - 2;
     const bool cok = 4 * q < C;
@@ -192,7 +203,7 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
     float4 x[R], z[R], dz[R], oacc[R]; bool m[R][4];
 #pragma unroll
     for (int r = 0; r < R; ++r) { x[r] = xn[r]; oacc[r] = on[r]; }
-    pre(g + 1);
+    pre(g + NW / 4);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const bool okx = pin[r] && cok;
@@ -203,7 +214,7 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
       if (!relu) z[r] = make_float4(okx ? zp.x : 0.f, okx ? zp.y : 0.f, okx ? zp.z : 0.f, okx ? zp.w : 0.f);
       dz[r] = zero4();
     }
-    const float* pb = patch + ((wave * R) * PW + li) * KP + 4 * qr;
+    const float* pb = patch + ((rb * R) * PW + li) * KP + 4 * qr;
 #pragma unroll 1
     for (int fr = 0; fr < KS; ++fr) {                    // flipped kernel row: patch row i = fr + r feeds input row r
       float4 wr[KS], dwa[KS];
@@ -249,13 +260,13 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
         double a2 = sA[e], b2 = sB[e];
 #pragma unroll
         for (int mk = 1; mk < 16; mk <<= 1) { a2 += __shfl_xor(a2, mk); b2 += __shfl_xor(b2, mk); }
-        if (li == 0) { rd[wave][4 * q + e][0] = a2; rd[wave][4 * q + e][1] = b2; }
+        if (li == 0) { rd[rb][4 * q + e][0] = a2; rd[rb][4 * q + e][1] = b2; }
       }
     }
   }
   __syncthreads();
-  // ---- one workspace row per workgroup: the four waves in fixed order; the flipped tap index goes back to [c][tap] ----
-  for (int i = t; i < C * NT; i += 256) {
+  // ---- one workspace row per workgroup: the four row bands in fixed order; the flipped tap index goes back to [c][tap] ----
+  for (int i = t; i < C * NT; i += NTHR) {
     const int c = i / NT, tp = i - c * NT;
     const int o = (NT - 1 - tp) * (KG * 16) + c;
     const float s = (dws[o] + dws[NT * KG * 16 + o]) + (dws[2 * NT * KG * 16 + o] + dws[3 * NT * KG * 16 + o]);
@@ -269,12 +280,12 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
 }
 
 template <int KS, int KG, int KP, int R>
-__global__ void __launch_bounds__(256, 2) sepb_kernel(const SepbK p) {
+__global__ void __launch_bounds__((SepbGeo<KS, KG, KP, R>::NTHR), (SepbGeo<KS, KG, KP, R>::WPS)) sepb_kernel(const SepbK p) {
   extern __shared__ __attribute__((aligned(16))) float sepb_sm[];
   sepb_body<KS, KG, KP, R>(p, sepb_sm);
 }
 template <int KS, int KG, int KP, int R>
-__global__ void __launch_bounds__(256, 2) sepb_batch_kernel(const SepbK* __restrict__ tab) {
+__global__ void __launch_bounds__((SepbGeo<KS, KG, KP, R>::NTHR), (SepbGeo<KS, KG, KP, R>::WPS)) sepb_batch_kernel(const SepbK* __restrict__ tab) {
   extern __shared__ __attribute__((aligned(16))) float sepb_sm[];
   const SepbK p = tab[blockIdx.z];
   if ((int)blockIdx.x >= p.gx) return;
@@ -308,8 +319,8 @@ int sepb_go(bool batch, dim3 grid, hipStream_t st, const SepbK* one, const SepbK
   typedef SepbGeo<KS, KG, KP, R> G;
   addk_dyn_lds<sepb_kernel<KS, KG, KP, R>>((int)G::LDS);
   addk_dyn_lds<sepb_batch_kernel<KS, KG, KP, R>>((int)G::LDS);
-  if (batch) hipLaunchKernelGGL((sepb_batch_kernel<KS, KG, KP, R>), grid, dim3(256), G::LDS, st, tab);
-  else hipLaunchKernelGGL((sepb_kernel<KS, KG, KP, R>), grid, dim3(256), G::LDS, st, *one);
+  if (batch) hipLaunchKernelGGL((sepb_batch_kernel<KS, KG, KP, R>), grid, dim3(G::NTHR), G::LDS, st, tab);
+  else hipLaunchKernelGGL((sepb_kernel<KS, KG, KP, R>), grid, dim3(G::NTHR), G::LDS, st, *one);
   return addk_check_launch("sep_bwd");
 }
 

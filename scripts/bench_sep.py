@@ -2,7 +2,10 @@
 """Micro-benchmark of one SepConv half (operations.py:51-54) through the C ABI: the fused launch of csrc/sepf.hip against the
 launches it replaces (depthwise + pointwise [+ bn_finalize | + affine_sum]), at the cell shapes of config 2.  Each variant is
 captured into a hipGraph of REP dependent repetitions (the output of one is the input of the next, as in the network) and
-timed with HIP events.      python scripts/bench_sep.py"""
+timed with HIP events.      python scripts/bench_sep.py
+With --bwd: the fused backward launch of csrc/sepb.hip (addk_sep_bwd) at the same shapes, first-touch and accumulating, in a graph of
+REP dependent repetitions (the gradient one launch writes is the dy of the next).  ADDK_LIB selects another build of the library, so one
+variant can be timed under two libraries:      ADDK_LIB=/path/to/libaddk.so python scripts/bench_sep.py --bwd"""
 import ctypes as C
 import os
 import sys
@@ -14,13 +17,76 @@ import addk                                    # noqa: E402
 import addk._lib as L                          # noqa: E402
 
 REP = 20
+SHAPES = [(2, 128, 256, 40, 3), (2, 128, 256, 40, 5), (2, 125, 253, 40, 5), (2, 64, 128, 80, 3), (2, 64, 128, 80, 5), (2, 63, 127, 80, 5),
+          (1, 128, 256, 40, 5), (1, 64, 128, 80, 5)]
+
+
+def time_graph(seq):
+    """us per call of `seq` [(fn, args)], captured once into a graph and replayed 10 times after 3 warm replays"""
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        st = s.cuda_stream
+        for fn, args in seq:
+            L.check(fn(*args, st), 'warm')
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            for fn, args in seq:
+                L.check(fn(*args, s.cuda_stream), 'cap')
+        for _ in range(3):
+            g.replay()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        for _ in range(10):
+            g.replay()
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / (10 * len(seq))
+
+
+def main_bwd():
+    lb = L.load()
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    print('library: %s' % L.LIB_PATH)
+    for N, H, W, Cc, k in SHAPES:
+        P = N * H * W
+        x = torch.randn(P, Cc, device=dev)
+        bufs = [torch.randn(P, Cc, device=dev) for _ in range(2)]
+        a, b = torch.rand(Cc, device=dev) + 0.5, torch.randn(Cc, device=dev) * 0.1
+        # weights scaled for a gain near one per repetition: the chain of 230 launches neither overflows nor dies out
+        wdw, wpw = torch.randn(Cc, k * k, device=dev) / k, torch.randn(Cc, Cc, device=dev) / Cc ** 0.5
+        keep, res, cfg = [], {}, (C.c_int32 * 8)()
+        for acc in (0, 1):
+            seq = []
+            for r in range(REP):
+                ba = L.SepBwdArgs()
+                ba.dy, ba.lddy, ba.N, ba.H, ba.W, ba.K = bufs[r % 2].data_ptr(), Cc, N, H, W, k
+                ba.src.x, ba.src.a, ba.src.b, ba.src.ld, ba.src.C, ba.src.relu = x.data_ptr(), a.data_ptr(), b.data_ptr(), Cc, Cc, 1
+                ba.Cout, ba.ldw, ba.dw_w, ba.pw_w = Cc, Cc, wdw.data_ptr(), wpw.data_ptr()
+                rows = lb.addk_sep_bwd_rows(C.byref(ba))
+                assert rows > 0, 'the fused backward does not take this shape'
+                dab, ws = torch.zeros(rows, Cc, 2, dtype=torch.float64, device=dev), torch.zeros(rows, Cc, k * k, device=dev)
+                ba.g, ba.ldg, ba.accumulate, ba.dab, ba.ws = bufs[(r + 1) % 2].data_ptr(), Cc, acc, dab.data_ptr(), ws.data_ptr()
+                L.check(lb.addk_sep_bwd_config(C.byref(ba), cfg), 'sep_bwd_config')
+                keep.extend([ba, dab, ws])
+                seq.append((lb.addk_sep_bwd, (C.byref(ba),)))
+            if acc:                                   # accumulating into the buffer the next launch reads would grow without bound
+                for bf in bufs:
+                    bf.normal_()
+                wpw.mul_(0.0)
+            res[acc] = time_graph(seq)
+        mb = (3 + 1) * P * Cc * 4 / 1e6
+        print('N=%d %3dx%-3d C=%-3d k=%d  <%d,%d,%d,%d>  (dy+x+g, +g when accumulating: %.1f MB)  sep_bwd first touch %.1f us  accumulate %.1f us' % (
+            (N, H, W, Cc, k) + tuple(cfg[1:5]) + (mb, res[0], res[1])), flush=True)
 
 
 def main():
+    if '--bwd' in sys.argv[1:]:
+        return main_bwd()
     lb = L.load()
     dev = torch.device('cuda:0')
-    shapes = [(2, 128, 256, 40, 3), (2, 128, 256, 40, 5), (2, 125, 253, 40, 5), (2, 64, 128, 80, 3), (2, 64, 128, 80, 5), (2, 63, 127, 80, 5),
-              (1, 128, 256, 40, 5), (1, 64, 128, 80, 5)]
+    shapes = SHAPES
     torch.manual_seed(0)
     for N, H, W, Cc, k in shapes:
         P = N * H * W
@@ -114,25 +180,7 @@ def main():
                         seq.extend(old(src, dst, mode))
                 if not seq:
                     continue
-                s = torch.cuda.Stream()
-                with torch.cuda.stream(s):
-                    st = s.cuda_stream
-                    for fn, args in seq:
-                        L.check(fn(*args, st), 'warm')
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=s):
-                        for fn, args in seq:
-                            L.check(fn(*args, s.cuda_stream), 'cap')
-                    for _ in range(3):
-                        g.replay()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(s)
-                    for _ in range(10):
-                        g.replay()
-                    e1.record(s)
-                    torch.cuda.synchronize()
-                    res[(variant, mode)] = e0.elapsed_time(e1) * 1e3 / (10 * REP)
+                res[(variant, mode)] = time_graph(seq) * len(seq) / REP
         mb = 2 * P * Cc * 4 / 1e6
         print('N=%d %3dx%-3d C=%-3d k=%d  (in+out %.1f MB)  train: fused %.1f us  fused+finalize launch %.1f us  dw+pw+finalize %.1f us | eval(+sum): fused %.1f us  dw+pw+sum %.1f us' % (
             N, H, W, Cc, k, mb, res[('fused', 'train')], res[('fused_sepfin', 'train')], res[('old', 'train')], res[('fused', 'eval')], res[('old', 'eval')]), flush=True)

@@ -1,4 +1,6 @@
-"""Summarise a rocprofv3 kernel trace CSV: per-kernel totals for the LAST bench step (between the last two sgd launches)."""
+"""Summarise a rocprofv3 kernel trace CSV: per-kernel totals for the LAST bench step (between the last two sgd launches).
+trace_summary.py CSV [ROWS [SUBSTR]]: with SUBSTR, the launch-to-launch spread (min / median / max / standard deviation) of the
+kernels whose name contains it follows the table."""
 import csv, collections, glob, sys
 f = sys.argv[1]
 rows = list(csv.DictReader(open(f)))
@@ -16,3 +18,12 @@ for r in last:
     agg[k][0] += 1; agg[k][1] += dur(r)
 for k, (c, t) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:int(sys.argv[2]) if len(sys.argv) > 2 else 30]:
     print('%-46s %5d %8.2f ms %5.1f%%  avg %8.1f us' % (k, c, t / 1e6, 100.0 * t / tot, t / c / 1e3))
+if len(sys.argv) > 3:
+    per = collections.defaultdict(list)
+    for r in last:
+        if sys.argv[3] in r['Kernel_Name']:
+            per[r['Kernel_Name'].replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0][:44]].append(dur(r) / 1e3)
+    print('launch-to-launch spread of *%s* in that step (us)' % sys.argv[3])
+    for k, v in sorted(per.items()):
+        v.sort(); m = sum(v) / len(v)
+        print('%-46s %5d  min %7.1f  median %7.1f  max %7.1f  mean %7.1f  sd %5.2f' % (k, len(v), v[0], v[len(v) // 2], v[-1], m, (sum((x - m) ** 2 for x in v) / len(v)) ** 0.5))
