@@ -6,7 +6,6 @@ once into a single launch list that is cut into segments — [stems+cells up to 
 import torch
 
 from .module import ensure_layout
-from . import plan as _plan
 from .plan import Act, Graph
 
 
@@ -88,11 +87,8 @@ class DynamicPlan:
         if cmds is None:          # every command belongs to exactly one segment: re-order and schedule the slice on its own
             cmds = list(g.fwd[i0:i1])
             if os.environ.get('ADDK_LEVEL_BATCH', '1') == '1':
-                g._level_batch(cmds)
-            _plan.schedule(cmds, g.nstreams)
-            for c in cmds:
-                if c.event:
-                    c.event = torch.cuda.Event()
+                g.level_batch(cmds)
+            g.place(cmds)
             self.segs[(i0, i1)] = cmds
         if self.calls < 3 or os.environ.get('ADDK_GRAPH_INFER', '1') != '1':
             g.run_parallel(cmds, None)

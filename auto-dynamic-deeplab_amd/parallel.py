@@ -190,7 +190,7 @@ class SyncBNComm:
 
     def emit_allreduce(self, g, lst, vec):
         """Append the all-reduce of one statistics vector (plan.LateVec) to command list `lst`.  When the list is level-
-        ordered, the exchanges of one level are merged into one all-reduce of their shared arena (plan.Graph._level_batch)."""
+        ordered, the exchanges of one level are merged into one all-reduce of their shared arena (plan.Graph.level_batch)."""
         c = g._add(lst, 'allreduce', self._allreduce_vec, vec, rd=[vec], wr=[vec], pin=True)     # RCCL call: main stream only
         c.payload = vec
         return c
@@ -220,7 +220,7 @@ class GradSync:
         del self.works[:]
 
     def insert(self, g, bwd):
-        from .plan import Cmd, _overlap, _region
+        from .plan import Cmd, _overlap
         esz = self.flat_g.element_size()
         base = self.flat_g.untyped_storage().data_ptr()
         spans = []                                    # (lo, hi) float offsets of every parameter's gradient, address order
@@ -229,20 +229,10 @@ class GradSync:
             spans.append((lo, lo + (v.numel() + 3) // 4 * 4))
         spans.sort()
         total = self.flat_g.numel()
-        # last writer of every 16-byte-aligned span
-        last = {}
-        for i, c in enumerate(bwd):
-            for r in getattr(c, 'wr', ()):
-                if r[0] == base:
-                    last.setdefault((r[1], r[2]), i)
-                    last[(r[1], r[2])] = i
+        last = {r: i for i, c in enumerate(bwd) for r in c.wr if r[0] == base}      # last writer of every region of the flat buffer
+
         def ready(lo, hi):
-            k = (lo * esz, hi * esz)
-            best = -1
-            for (a, b), i in last.items():
-                if a < k[1] and k[0] < b:
-                    best = max(best, i)
-            return best
+            return max((i for r, i in last.items() if _overlap(r, (base, lo * esz, hi * esz))), default=-1)
         target = -(-total // self.nbuckets)
         buckets, cur_lo, cur_rdy = [], 0, -1
         for lo, hi in spans:

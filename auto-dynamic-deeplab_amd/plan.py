@@ -22,6 +22,19 @@ from . import _lib as L
 TRACE_BN = None        # diagnostics (tests/tools): a list that receives (BatchNorm module, raw TRef) of every Graph.bn call
 
 
+def _on(name, default='1'):
+    """An ADDK_* switch, read when a plan is emitted (tests change the environment between two plan builds)."""
+    return os.environ.get(name, default) == '1'
+
+
+def _env_int(name, default):
+    return int(os.environ.get(name, default))
+
+
+def _ptr(x):
+    return None if x is None else x.ptr
+
+
 class Buf:
     """Flat fp32 device buffer."""
     __slots__ = ('t', 'ptr', 'n', 'gbuf', 'ginit')
@@ -48,6 +61,12 @@ class TRef:
     @property
     def P(self):
         return self.N * self.H * self.W
+
+    @property
+    def cols(self):
+        """channel interval [c0, c1) of this view inside the pixel row"""
+        c0 = self.off % self.ld if self.ld else 0
+        return c0, c0 + self.C
 
     def chan(self, c0, C):
         assert 0 <= c0 and c0 + C <= self.C
@@ -161,8 +180,7 @@ def _region(x):
     if x is None:
         return None
     if isinstance(x, TRef):
-        lo = x.off % x.ld if x.ld else 0
-        return (id(x.buf), lo, lo + x.C)
+        return (id(x.buf),) + x.cols
     if isinstance(x, Vec):
         return (id(x.buf), 0, 1 << 30)
     if isinstance(x, LateVec):
@@ -182,27 +200,57 @@ def _overlap(a, b):
     return a[0] == b[0] and a[1] < b[2] and b[1] < a[2]
 
 
+def deps(cmds):
+    """The hazard tracker: for every command, in list order, the set of earlier indices it has to follow (every RAW, WAW and WAR
+    relation on overlapping regions of the sequential list, directly or through the commands yielded)."""
+    writers, readers = {}, {}            # buffer id -> [(region, idx)]
+    for i, c in enumerate(cmds):
+        d = set()
+        for k in c.rd:
+            d.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
+        for k in c.wr:
+            d.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
+            d.update(j for r, j in readers.get(k[0], ()) if _overlap(r, k))
+        yield d
+        for k in c.wr:      # this write stands for the earlier accesses it FULLY covers, and only for those: a partly covered one stays listed
+            covered = lambda r: r[1] >= k[1] and r[2] <= k[2]      # noqa: E731
+            writers[k[0]] = [(r, j) for r, j in writers.get(k[0], ()) if not covered(r)] + [(k, i)]
+            readers[k[0]] = [(r, j) for r, j in readers.get(k[0], ()) if not covered(r)]
+        for k in c.rd:
+            readers.setdefault(k[0], []).append((k, i))
+
+
+def levels(cmds):
+    """Dependency level (longest path from the inputs) of every command of a launch list."""
+    level = []
+    for d in deps(cmds):
+        level.append(1 + max(level[j] for j in d) if d else 0)
+    return level
+
+
+def level_order(cmds, merge=None):
+    """Re-order a launch list in place by dependency level.  Commands of one level never depend on each other, so any order inside
+    a level is valid; program order of the original list is kept.  `merge(commands of one level) -> commands` may rewrite a level."""
+    buckets = collections.defaultdict(list)
+    for c, lv in zip(cmds, levels(cmds)):
+        buckets[lv].append(c)
+    cmds[:] = [c for lv in sorted(buckets) for c in (merge(buckets[lv]) if merge else buckets[lv])]
+
+
 def schedule(cmds, nstreams):
     """Assign every command a stream and the cross-stream waits it needs.  A command follows the stream of its most
     recent dependency when that dependency is still the tail of its stream (a chain stays on one stream, no event);
     otherwise it opens on the least recently used stream and waits on events.  Program order inside a stream plus the
     recorded waits preserve every RAW/WAW/WAR relation of the sequential list."""
-    writers, readers = {}, {}            # buffer id -> [(region, idx)]
     tail = [-1] * nstreams               # index of the last command on each stream
     # vector clocks: clock[i][t] = latest command of stream t known to have completed before command i starts.  A wait
     # that a previous wait already implies TRANSITIVELY (A -> B -> C and A -> C) is dropped (fewer event edges in the graph).
     clock = []
-    for i, c in enumerate(cmds):
-        deps = set()
-        for k in c.rd:
-            deps.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-        for k in c.wr:
-            deps.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-            deps.update(j for r, j in readers.get(k[0], ()) if _overlap(r, k))
+    for i, (c, dep) in enumerate(zip(cmds, deps(cmds))):
         if c.pin or nstreams == 1:
             st = 0
-        elif deps:
-            last = max(deps)
+        elif dep:
+            last = max(dep)
             ls = cmds[last].stream
             st = ls if tail[ls] == last else min(range(nstreams), key=lambda t: tail[t])
         else:
@@ -213,11 +261,11 @@ def schedule(cmds, nstreams):
         # other direction runs on the main stream instead.
         if st != 0:
             vc0 = clock[tail[st]] if tail[st] >= 0 else [-1] * nstreams
-            if any(0 < cmds[j].stream < st and vc0[cmds[j].stream] < j for j in deps):
+            if any(0 < cmds[j].stream < st and vc0[cmds[j].stream] < j for j in dep):
                 st = 0
         vc = list(clock[tail[st]]) if tail[st] >= 0 else [-1] * nstreams
         waits = []
-        for j in sorted(deps, reverse=True):
+        for j in sorted(dep, reverse=True):
             t = cmds[j].stream
             if t != st and vc[t] < j:
                 waits.append(j)
@@ -226,15 +274,88 @@ def schedule(cmds, nstreams):
         clock.append(vc)
         c.stream, c.waits = st, tuple(waits)
         tail[st] = i
-        for k in c.wr:
-            writers[k[0]] = [(r, j) for r, j in writers.get(k[0], ()) if not (r[1] >= k[1] and r[2] <= k[2])] + [(k, i)]
-            readers[k[0]] = [(r, j) for r, j in readers.get(k[0], ()) if not (r[1] >= k[1] and r[2] <= k[2])]   # only readers this write fully covers are implied by it
-        for k in c.rd:
-            readers.setdefault(k[0], []).append((k, i))
     need = set(j for c in cmds for j in c.waits)
     for j in need:
         cmds[j].event = True
     return cmds
+
+
+def _covered(intervals, c0, c1):
+    """how much of [c0, c1) a list of disjoint intervals covers"""
+    return sum(max(0, min(c1, b) - max(c0, a)) for a, b in intervals)
+
+
+def _first_touch(intervals, c0, c1, what):
+    """0 the first time [c0, c1) is written in backward order (the interval is recorded), 1 once it has been written whole."""
+    covered = _covered(intervals, c0, c1)
+    if covered == 0:
+        intervals.append((c0, c1))
+        return 0
+    if covered == c1 - c0:
+        return 1
+    raise NotImplementedError('partially initialised %s [%d,%d) vs %s' % (what, c0, c1, intervals))
+
+
+def _out_hw(H, W, k, stride, pad, dil):
+    return (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
+def _chunks(items, least):
+    """`items` cut into ADDK_WGRAD_CHUNKS (3) runs of equal length, in emission (= backward) order, if a run then holds at least `least`"""
+    k = _env_int('ADDK_WGRAD_CHUNKS', 3)
+    per = max(1, -(-len(items) // (k if len(items) >= least * k else 1)))
+    return [items[i:i + per] for i in range(0, len(items), per)]
+
+
+def _set_geom(x, geom):
+    """conv geometry onto an argument struct (ConvArgs, ConvDgradArgs, ConvWgradArgs, DwArgs, DwBwdArgs)"""
+    x.N, x.H, x.W, x.OH, x.OW, x.KH, x.KW, x.stride, x.pad, x.dil = geom
+
+
+# How Graph.level_batch turns the same-kind, same-key launches of one dependency level into ONE launch.  `per_level`: the members of
+# a level are merged whatever their network segment, and a lone member is replaced too.
+class _Table(collections.namedtuple('_Table', 'fn size')):
+    """a table of the members' argument structs -> fn(table, count, largest `size` field)"""
+    per_level = False
+
+    def build(self, g, name, cs):
+        tab = g._table(bytes((type(cs[0].payload) * len(cs))(*[c.payload for c in cs])))
+        return Cmd(name + '_batch', getattr(g.lib, self.fn), (tab.data_ptr(), len(cs), max(int(getattr(c.payload, self.size)) for c in cs)))
+
+
+class _Prepared(collections.namedtuple('_Prepared', 'prepare run')):
+    """the library turns the members' argument structs into kernel descriptors: prepare -> blob + meta -> run(blob, meta)"""
+    per_level = False
+
+    def build(self, g, name, cs):
+        arr = (type(cs[0].payload) * len(cs))(*[c.payload for c in cs])
+        blob, meta = g._prepare(getattr(g.lib, self.prepare), arr, len(cs), self.prepare)
+        return Cmd(name + '_batch', getattr(g.lib, self.run), (g._table(blob).data_ptr(), meta))
+
+
+class _Arena(collections.namedtuple('_Arena', '')):
+    """SyncBN exchanges: the vectors of a level are contiguous in one arena (Graph._bind_late) -> ONE plain all-reduce of it"""
+    per_level = True
+
+    def build(self, g, name, cs):
+        arena, total, f64 = cs[0].arena
+        assert all(c.arena[0] is arena for c in cs)
+        t = arena.t[:total]
+        m = Cmd('allreduce_packed', g.world._allreduce, (t.view(torch.float64) if f64 else t,), pin=True)
+        m.members = len(cs)
+        return m
+
+
+BATCHED = {'bn_finalize': _Table('addk_bn_finalize_batch', 'C'), 'bn_bwd': _Table('addk_bn_bwd_batch', 'C'),
+           'bn_bwd_apply': _Table('addk_bn_bwd_apply_batch', 'P'),
+           'slab_reduce': _Table('addk_slab_reduce_batch', 'C'), 'bn_bwd_coeffs': _Table('addk_bn_bwd_coeffs_batch', 'C'),
+           'conv_fwd': _Prepared('addk_conv_fwd_batch_prepare', 'addk_conv_batch_run'),
+           'conv_dgrad': _Prepared('addk_conv_dgrad_batch_prepare', 'addk_conv_batch_run'),
+           'dw_fwd': _Prepared('addk_dw_fwd_batch_prepare', 'addk_dw_batch_run'), 'dw_bwd': _Prepared('addk_dw_bwd_batch_prepare', 'addk_dw_batch_run'),
+           'sep_fwd': _Prepared('addk_sep_fwd_batch_prepare', 'addk_sep_batch_run'),
+           'sep_bwd': _Prepared('addk_sep_bwd_batch_prepare', 'addk_sep_bwd_batch_run'),
+           'resize_bwd': _Prepared('addk_resize_bwd_batch_prepare', 'addk_resize_bwd_batch_run'),
+           'allreduce': _Arena()}
 
 
 class Graph:
@@ -248,6 +369,9 @@ class Graph:
         self._bwd_emitters = []       # closures emitting backward commands, run in reverse
         self.keep = []                # keep ctypes structs / tensors alive
         self.pgrad = {}               # param -> grad tensor
+        self.pgrad_views = None       # param -> view of a flat gradient buffer to use as its gradient (train.TrainStep)
+        self.reorder = False          # level-order and batch the lists although this is not a training plan (set before finalize)
+        self.fuse_ce = False          # logits outputs feed the fused up-sampling + cross-entropy launch (train.TrainStep)
         self.pginit = set()
         self._pcols = {}
         self.params = []              # ordered unique params touched
@@ -256,6 +380,7 @@ class Graph:
         self.nbytes = 0
         self._bufs = []               # owns every device buffer: kernels only see raw pointers
         self.nstreams = 1             # set by finalize(nstreams=k)
+        self._streams = None          # side streams of run_parallel, created on first use
         self.tag = ''                 # segment label stamped on emitted commands (stem / cell / low / aspp / decoder)
         self._evalbn, self._evalbn_cmd = [], None
         self._dwreds = []             # deferred depthwise weight-gradient reductions (item, workspace, grad tensor)
@@ -289,24 +414,11 @@ class Graph:
 
     def acc_flag(self, gref):
         """0 the first time a channel interval of a gradient buffer is written in backward order, 1 afterwards."""
-        iv = gref.buf.ginit
-        c0 = gref.off % gref.ld if gref.ld else 0
-        c1 = c0 + gref.C
-        covered = sum(max(0, min(c1, b) - max(c0, a)) for a, b in iv)
-        if covered == 0:
-            iv.append((c0, c1))
-            return 0
-        if covered == c1 - c0:
-            return 1
-        raise NotImplementedError('partially initialised gradient interval [%d,%d) vs %s' % (c0, c1, iv))
+        return _first_touch(gref.buf.ginit, *gref.cols, 'gradient interval')
 
     def grad_ready(self, tref):
         b = tref.buf.gbuf
-        if b is None:
-            return False
-        c0 = tref.off % tref.ld if tref.ld else 0
-        c1 = c0 + tref.C
-        return sum(max(0, min(c1, y) - max(c0, x)) for x, y in b.ginit) == c1 - c0
+        return b is not None and _covered(b.ginit, *tref.cols) == tref.C
 
     def param(self, p):
         if p not in self.pgrad:          # Tensor hashes by identity
@@ -320,19 +432,10 @@ class Graph:
         ranges of one weight): first touch of an interval overwrites, later touches accumulate."""
         self.param(p)
         if self.pgrad[p] is None:
-            views = getattr(self, 'pgrad_views', None)
+            views = self.pgrad_views
             self.pgrad[p] = views[p] if views is not None and p in views else torch.empty_like(p)
             self._pcols[p] = []
-        iv = self._pcols[p]
-        c0, c1 = cols if cols is not None else (0, 1 << 30)
-        covered = sum(max(0, min(c1, b) - max(c0, a)) for a, b in iv)
-        if covered == 0:
-            iv.append((c0, c1))
-            acc = 0
-        elif covered == c1 - c0 or (cols is None and iv == [(0, 1 << 30)]):
-            acc = 1
-        else:
-            raise NotImplementedError('partially initialised weight-gradient columns')
+        acc = _first_touch(self._pcols[p], *(cols or (0, 1 << 30)), 'weight-gradient columns')      # no `cols`: the whole tensor
         self.pginit.add(p)
         return self.pgrad[p].data_ptr(), acc
 
@@ -352,50 +455,22 @@ class Graph:
         if self._packs:
             tab = self._table(b''.join(self._packs))
             self._pack_cmd.args[0], self._pack_cmd.args[1] = tab.data_ptr(), len(self._packs)
-        batch = ((self.training and self.want_grad) or getattr(self, 'reorder', False)) and os.environ.get('ADDK_LEVEL_BATCH', '1') == '1'
+        batch = ((self.training and self.want_grad) or self.reorder) and _on('ADDK_LEVEL_BATCH')
         for lst in (self.fwd, self.bwd):
             self._bind_late(lst, by_level=batch)          # storage of the exchanged statistics vectors: one arena per level
             if batch:
-                self._level_batch(lst)
+                self.level_batch(lst)
         if self.grad_sync is not None:
             self.grad_sync.insert(self, self.bwd)          # bucketed gradient all-reduces, each right after its last producer
         for lst in (self.fwd, self.bwd):
-            for i, c in enumerate(lst):
-                if not isinstance(c, Cmd):           # commands appended as plain triples (e.g. collectives): pinned to the main stream
-                    lst[i] = Cmd(c[0], c[1], c[2], pin=True)
-            schedule(lst, self.nstreams)
-            for c in lst:
-                if c.event:
-                    c.event = torch.cuda.Event()
+            self.place(lst)
 
-    _BATCHED = {'bn_finalize': ('addk_bn_finalize_batch', lambda p: p.C), 'bn_bwd': ('addk_bn_bwd_batch', lambda p: p.C),
-                'bn_bwd_apply': ('addk_bn_bwd_apply_batch', lambda p: p.P),
-                'slab_reduce': ('addk_slab_reduce_batch', lambda p: p.C), 'bn_bwd_coeffs': ('addk_bn_bwd_coeffs_batch', lambda p: p.C),
-                'conv_fwd': ('addk_conv_fwd_batch_prepare', 'addk_conv_batch_run'), 'conv_dgrad': ('addk_conv_dgrad_batch_prepare', 'addk_conv_batch_run'),
-                'dw_fwd': ('addk_dw_fwd_batch_prepare', 'addk_dw_batch_run'), 'dw_bwd': ('addk_dw_bwd_batch_prepare', 'addk_dw_batch_run'),
-                'sep_fwd': ('addk_sep_fwd_batch_prepare', 'addk_sep_batch_run'),
-                'sep_bwd': ('addk_sep_bwd_batch_prepare', 'addk_sep_bwd_batch_run'),
-                'resize_bwd': ('addk_resize_bwd_batch_prepare', 'addk_resize_bwd_batch_run'),
-                'allreduce': (None, None)}
-
-    @staticmethod
-    def _levels(lst):
-        """Dependency level (longest path from the inputs) of every command of a launch list."""
-        writers, readers, level = {}, {}, []
-        for i, c in enumerate(lst):
-            deps = set()
-            for k in c.rd:
-                deps.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-            for k in c.wr:
-                deps.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-                deps.update(j for r, j in readers.get(k[0], ()) if _overlap(r, k))
-            level.append(1 + max(level[j] for j in deps) if deps else 0)
-            for k in c.wr:
-                writers[k[0]] = [(r, j) for r, j in writers.get(k[0], ()) if not (r[1] >= k[1] and r[2] <= k[2])] + [(k, i)]
-                readers[k[0]] = [(r, j) for r, j in readers.get(k[0], ()) if not (r[1] >= k[1] and r[2] <= k[2])]   # only readers this write fully covers are implied by it
-            for k in c.rd:
-                readers.setdefault(k[0], []).append((k, i))
-        return level
+    def place(self, lst):
+        """Schedule a launch list on this plan's streams and create the events its cross-stream waits need."""
+        schedule(lst, self.nstreams)
+        for c in lst:
+            if c.event:
+                c.event = torch.cuda.Event()
 
     def _table(self, data):
         """A table of host bytes on the plan's device (a CPU copy in dry runs), kept alive with the plan."""
@@ -434,14 +509,14 @@ class Graph:
 
     def _bind_late(self, lst, by_level):
         """Give every exchanged statistics vector (LateVec payload of an 'allreduce' command) its storage.  With level
-        batching the vectors of one dependency level share one arena, in list order, and `_level_batch` replaces their
+        batching the vectors of one dependency level share one arena, in list order, and `level_batch` replaces their
         commands by ONE all-reduce of the arena; otherwise each gets its own buffer.  Runs before any table-driven batch is
         built, because the producers (slab_reduce / bn_bwd) and consumers (bn_finalize / bn_bwd_coeffs) of a vector sit on
         other levels and carry its address in their argument structs."""
-        ars = [(i, c) for i, c in enumerate(lst) if isinstance(c, Cmd) and c.name == 'allreduce' and isinstance(c.payload, LateVec)]
+        ars = [(i, c) for i, c in enumerate(lst) if c.name == 'allreduce' and isinstance(c.payload, LateVec)]
         if not ars:
             return
-        level = self._levels(lst) if by_level else list(range(len(lst)))
+        level = levels(lst) if by_level else list(range(len(lst)))
         groups = collections.defaultdict(list)
         for i, c in ars:
             groups[(level[i], c.payload.f64)].append(c)
@@ -456,64 +531,48 @@ class Graph:
             for c in cs:
                 c.arena = (arena, total, f64)
 
-    def _level_batch(self, lst):
-        """Reorder a launch list by dependency LEVEL (longest path from the inputs) and merge the mutually independent
-        BatchNorm vector launches of one level into one table-driven launch each.  The cell DAG offers ~10 independent
-        branches per level, so the 312 finalize / 312 backward / 312 apply launches of a step — each a ~10 us latency
-        chain on the critical path — shrink to one launch per level.  Commands of one level never depend on each other,
-        so any order inside a level is valid; program order of the original list is kept."""
-        level = Graph._levels(lst)
-        buckets = collections.defaultdict(list)
-        for i, c in enumerate(lst):
-            buckets[level[i]].append(c)
-        # [r4] kinds left as single launches.  In the TRAINING step the fused SepConv halves run better one by one (33.6-33.7 vs 33.95-34.0 ms per
-        # step, ABAB on one box): a merged launch waits for its latest input and holds every consumer back, and these launches are long enough
-        # (15-70 us) for the two streams to overlap them; every other kind measured slower or equal un-merged (bn_bwd +1.3 ms, bn_bwd_apply +0.9,
-        # conv_dgrad +0.4), and inference (exit latency, forward segment) is equal or better with the halves merged.  ADDK_NO_BATCH=kind,... overrides.
+    def _unmerged_kinds(self):
+        """[r4] Kinds level_batch leaves as single launches.  In the TRAINING step the fused SepConv halves run better one by one (33.6-33.7 vs
+        33.95-34.0 ms per step, ABAB on one box): a merged launch waits for its latest input and holds every consumer back, and these launches
+        are long enough (15-70 us) for the two streams to overlap them; every other kind measured slower or equal un-merged (bn_bwd +1.3 ms,
+        bn_bwd_apply +0.9, conv_dgrad +0.4), and inference (exit latency, forward segment) is equal or better with the halves merged.
+        ADDK_NO_BATCH=kind,... overrides."""
         env = os.environ.get('ADDK_NO_BATCH')
-        single = set(filter(None, env.split(','))) if env is not None else ({'sep_fwd', 'sep_bwd'} if (getattr(self, 'training', False) and getattr(self, 'want_grad', False)) else set())
-        out = []
-        for lv in sorted(buckets):
-            groups = collections.defaultdict(list)
-            for c in buckets[lv]:
-                if c.name in self._BATCHED and c.payload is not None and c.name not in single:
+        if env is not None:
+            return set(filter(None, env.split(',')))
+        return {'sep_fwd', 'sep_bwd'} if self.training and self.want_grad else set()
+
+    def level_batch(self, lst):
+        """Reorder a launch list by dependency LEVEL (level_order) and merge the mutually independent same-kind launches of one level
+        into one table-driven launch each (BATCHED).  The cell DAG offers ~10 independent branches per level, so the 312 finalize /
+        312 backward / 312 apply launches of a step — each a ~10 us latency chain on the critical path — shrink to one launch per level."""
+        single = self._unmerged_kinds()
+
+        def merge(cmds):
+            out, groups = [], collections.defaultdict(list)
+            for c in cmds:
+                how = BATCHED.get(c.name)
+                if how is None or c.payload is None or c.name in single:
+                    out.append(c)
+                else:
                     # the segment tag is part of the key: a merged launch never mixes network segments (stem / cell / low / aspp / decoder), so the
                     # per-segment figures bench.segment_roofline reports time exactly that segment's work (ADVICE r04); all-reduces stay per level
-                    groups[(c.name, c.bkey, '' if c.name == 'allreduce' else c.tag)].append(c)
-                else:
-                    out.append(c)
+                    groups[(c.name, c.bkey, '' if how.per_level else c.tag)].append(c)
             for (name, _, _), cs in groups.items():
-                if len(cs) == 1 and name != 'allreduce':
+                how = BATCHED[name]
+                if len(cs) == 1 and not how.per_level:
                     out.append(cs[0])
                     continue
-                fname, size_of = self._BATCHED[name]
-                n = len(cs)
-                if name == 'allreduce':        # SyncBN exchanges of one level: their vectors are contiguous in one arena (_bind_late) -> ONE plain all-reduce
-                    arena, total, f64 = cs[0].arena
-                    assert all(c.arena[0] is arena for c in cs)
-                    t = arena.t[:total]
-                    m = Cmd('allreduce_packed', self.world._allreduce, (t.view(torch.float64) if f64 else t,), pin=True)
-                    m.rd = [r for c in cs for r in c.rd]
-                    m.wr = [r for c in cs for r in c.wr]
-                    m.tag = cs[0].tag
-                    m.tags = {c.tag for c in cs}
-                    m.members = len(cs)
-                    out.append(m)
-                    continue
-                arr = (type(cs[0].payload) * n)(*[c.payload for c in cs])
-                if isinstance(size_of, str):   # pointwise / depthwise convs: the library turns the argument structs into kernel descriptors
-                    blob, meta = self._prepare(getattr(self.lib, fname), arr, n, fname)
-                    tab = self._table(blob)
-                    m = Cmd(name + '_batch', getattr(self.lib, size_of), (tab.data_ptr(), meta))
-                else:
-                    tab = self._table(bytes(arr))
-                    m = Cmd(name + '_batch', getattr(self.lib, fname), (tab.data_ptr(), n, max(int(size_of(c.payload)) for c in cs)))
+                m = how.build(self, name, cs)
                 m.rd = [r for c in cs for r in c.rd]
                 m.wr = [r for c in cs for r in c.wr]
                 m.tag = cs[0].tag
-                m.tags = {c.tag for c in cs}           # a merged launch may hold members of several network segments (bench.segment_roofline checks)
+                m.tags = {c.tag for c in cs}           # the segments of the members (bench.segment_roofline checks)
                 out.append(m)
-        lst[:] = out
+            return out
+        level_order(lst, merge)
+
+    _level_batch = level_batch      # the name this method had while it was private: code outside this tree still looks it up
 
     def _hoist_pack(self, desc_fn, args, weight, wpk, create):
         """Move the weight pack of a halo-patch conv launch out of the launch: all packs of the plan (forward and data
@@ -539,13 +598,7 @@ class Graph:
                 waves.append(([], set()))
             waves[-1][0].append((it, ws, grad))
             waves[-1][1].add(it.dw)
-        nchunk = int(os.environ.get('ADDK_WGRAD_CHUNKS', '3'))
-        parts = []
-        for items, _ in waves:           # cut in emission (= backward) order so the early parts overlap with the backward pass
-            k = nchunk if len(items) >= 8 * nchunk else 1
-            per = -(-len(items) // k)
-            parts += [items[c * per:(c + 1) * per] for c in range(k) if items[c * per:(c + 1) * per]]
-        for items in parts:
+        for items in [part for items, _ in waves for part in _chunks(items, 8)]:
             n = len(items)
             tab = self._table(bytes((L.DwWreduceItem * n)(*[it for it, _, _ in items])))
             self._add(self.bwd, 'dw_wreduce_batch', self.lib.addk_dw_wreduce_batch, tab.data_ptr(), n,
@@ -565,26 +618,17 @@ class Graph:
             L.check(lib.addk_conv_wgrad_config(C.byref(wa), cfg), 'conv_wgrad_config')
             key = (cfg[0], cfg[1], cfg[2])
             for groups, used in waves:
-                if not any(r[0] == region[0] and r[1] < region[2] and region[1] < r[2] for r in used):
+                if not any(_overlap(r, region) for r in used):
                     break
             else:
                 groups, used = {}, []
                 waves.append((groups, used))
             used.append(region)
             groups.setdefault(key, []).append((wa, rd, grad))
-        nchunk = int(os.environ.get('ADDK_WGRAD_CHUNKS', '3'))
         for groups, _ in waves:
-            split = {}
-            for key, items in groups.items():
-                # big groups (the cells' 1x1 / dilated convs: ~100-300 ops) are cut into `nchunk` batches in emission order
-                # (= backward order): the early batches only need the gradients of the late cells, so the level pass can
-                # place them in the middle of the backward pass where they overlap with it on the second stream
-                k = nchunk if len(items) >= 32 * nchunk else 1
-                per = -(-len(items) // k)
-                for c in range(k):
-                    if items[c * per:(c + 1) * per]:
-                        split[(key, c)] = items[c * per:(c + 1) * per]
-            for (key, _c), items in split.items():
+            # big groups (the cells' 1x1 / dilated convs: ~100-300 ops) are cut into batches (_chunks): the early batches only need the gradients
+            # of the late cells, so the level pass can place them in the middle of the backward pass where they overlap with it on the second stream
+            for key, items in [(key, part) for key, items in groups.items() for part in _chunks(items, 32)]:
                 n = len(items)
                 arr = (L.ConvWgradArgs * n)()
                 for i, (wa, _, _) in enumerate(items):
@@ -594,7 +638,7 @@ class Graph:
                 host, meta = self._prepare(lib.addk_conv_wgrad_batch_prepare, arr, n, 'conv_wgrad_batch_prepare')
                 blob = self._table(host)
                 self.nbytes += len(host)
-                if os.environ.get('ADDK_DEBUG_WGRAD') == '1':      # algorithmic work of this batch (tuning aid)
+                if _on('ADDK_DEBUG_WGRAD', '0'):      # algorithmic work of this batch (tuning aid)
                     fl = sum(2.0 * w.N * w.OH * w.OW * w.Cout * w.KH * w.KW * w.src.C for w, _, _ in items)
                     by = sum(4.0 * (w.N * w.OH * w.OW * w.Cout + w.N * w.H * w.W * w.src.C) for w, _, _ in items)
                     shapes = collections.Counter((w.OH, w.OW, w.Cout, w.src.C, w.KH, w.stride) for w, _, _ in items)
@@ -657,24 +701,29 @@ class Graph:
             main.wait_event(e)
 
     def _side_streams(self):
-        if getattr(self, '_streams', None) is None:
+        if self._streams is None:
             self._streams = [torch.cuda.Stream(device=self.device) for _ in range(self.nstreams - 1)]
         return self._streams
 
     def _pending(self, act):
         return act.rs is not None and not act.rs.done
 
+    def _map(self, act, fold):
+        """The map a consumer of lazy activation `act` reads.  fold=True (a consumer that samples a deferred resize itself): the map to
+        interpolate; otherwise act.raw, a still-deferred resize being emitted as its own launch now."""
+        if self._pending(act):
+            if fold:
+                return act.rs.src
+            act.rs.emit()
+        return act.raw
+
     def src(self, act, relu_in=False, fold=False):
-        """Source descriptor of a lazy activation.  fold=True (a consumer that samples a deferred resize itself): the descriptor
-        points at the map to interpolate; otherwise a still-deferred resize is emitted as its own launch now."""
+        """Source descriptor of a lazy activation (`fold`: see _map)."""
         s = L.Src()
-        if fold and self._pending(act):
-            r = act.rs.src
-            s.x, s.ld, s.rs_hw = r.ptr, r.ld, (r.H << 16) | r.W
-        else:
-            if self._pending(act):
-                act.rs.emit()
-            s.x, s.ld = act.raw.ptr, act.raw.ld
+        r = self._map(act, fold)
+        s.x, s.ld = r.ptr, r.ld
+        if r is not act.raw:
+            s.rs_hw = (r.H << 16) | r.W
         if act.bn is not None:
             s.a, s.b = act.bn.a.ptr, act.bn.b.ptr
         s.C, s.relu = act.raw.C, int(bool(act.relu or relu_in))
@@ -682,19 +731,50 @@ class Graph:
 
     def lz(self, act, fold=False):
         """Memory regions a consumer of lazy activation `act` reads."""
-        if fold and self._pending(act):
-            first = act.rs.src
-        else:
-            if self._pending(act):
-                act.rs.emit()
-            first = act.raw
-        return [first] + ([act.bn.a, act.bn.b] if act.bn is not None else [])
+        return [self._map(act, fold)] + ([act.bn.a, act.bn.b] if act.bn is not None else [])
 
-    def _dab(self, act, rows):
-        """Allocate a (dA,dB) partial slab for a lazy source whose BN is in training mode."""
-        if act.bn is None or not act.bn.training or not self.want_grad:
-            return None
-        return self.buf(rows * act.C * 4)      # fp64 [rows][C][2]
+    def _backward(self, out, emit):
+        """Register the backward emitter of the op that wrote `out`: finalize() calls `emit(dy)` in reverse op order, if a consumer
+        has written the gradient `dy` of `out` by then."""
+        def em():
+            if self.grad_ready(out):
+                emit(self.grad(out))
+        self._bwd_emitters.append(em)
+
+    def _grad_into(self, src, rows=None):
+        """The gradient edge into lazy source `src`: (gradient twin of src.raw, 0 = first touch / 1 = accumulate, slab).  `rows`: the
+        workgroup rows of the launch that also produces the (dA,dB) partials of src's BatchNorm; when that BatchNorm is in training
+        mode the fp64 [rows][C][2] slab is allocated here and handed to it.  rows=None: the launch produces none."""
+        gs = self.grad(src.raw)
+        acc = self.acc_flag(gs)
+        slab = None
+        if rows is not None and src.bn is not None and src.bn.training and self.want_grad:
+            slab = self.buf(rows * src.C * 4)
+            src.bn.slabs.append((slab, rows))
+        return gs, acc, slab
+
+    def _defer_wgrad(self, dy, s, relu_in, weight, geom, ldw, cin_total, choff):
+        """Record the gradient of columns [choff, choff + s.C) of `weight` (source `s`, output gradient `dy`) for the batched launches
+        at the end of the backward pass (_emit_batched_wgrads)."""
+        wa = L.ConvWgradArgs()
+        wa.dy, wa.lddy, wa.Cout = dy.ptr, dy.ld, dy.C
+        _set_geom(wa, geom)
+        wa.src = self.src(s, relu_in)
+        cols = (choff, choff + s.C)
+        gp, acc = self.param_grad(weight, cols)
+        wa.dw, wa.ldw, wa.cin_total, wa.w_choff, wa.accumulate = gp, ldw, cin_total, choff, acc
+        wa.ws_floats = self.lib.addk_conv_wgrad_ws(dy.P, dy.C, s.C, geom[5] * geom[6])
+        self._wgrads.append((wa, [dy] + self.lz(s), self.pgrad[weight], (id(weight),) + cols))
+
+    def _defer_dw_wreduce(self, weight, rows, n):
+        """Workspace of a depthwise weight gradient: its [rows][n] partials are reduced at the end of the backward pass, all convs in one
+        launch (_emit_batched_dw_reductions).  Returns (workspace, gradient pointer, accumulate)."""
+        gp, acc = self.param_grad(weight)
+        ws = self.buf(rows * n)
+        it = L.DwWreduceItem()
+        it.ws, it.dw, it.rows, it.n, it.accumulate = ws.ptr, gp, rows, n, acc
+        self._dwreds.append((it, ws, self.pgrad[weight]))
+        return ws, gp, acc
 
     # ---------------- ops ----------------
     def conv(self, srcs, weight, Cout, k, stride=1, pad=0, dil=1, relu_in=False, bias=None, bias_n=None,
@@ -704,11 +784,8 @@ class Graph:
         lib = self.lib
         a0 = srcs[0]
         N, H, W = a0.N, a0.H, a0.W
-        if out_hw is None:
-            OH = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1
-            OW = (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
-        else:
-            OH, OW = out_hw
+        OH, OW = out_hw or _out_hw(H, W, k, stride, pad, dil)
+        geom = (N, H, W, OH, OW, k, k, stride, pad, dil)
         csum = sum(s.C for s in srcs)
         cin_total = cin_total or csum
         if out is None:
@@ -724,17 +801,13 @@ class Graph:
             # the pointwise kernels cover the shape (addk_conv_fwd_resample_ok): no resize launch, no resized tensor at inference; in
             # training the launch also writes the resized tensor, which the backward pass reads (ADDK_FOLD_RESIZE=0: never)
             fold = (k == 1 and stride == 1 and pad == 0 and out_hw is None and any(self._pending(s) for s in srcs)
-                    and os.environ.get('ADDK_FOLD_RESIZE', '1') == '1')
+                    and _on('ADDK_FOLD_RESIZE'))
             ar.nsrc = len(srcs)
-            ar.N, ar.H, ar.W, ar.OH, ar.OW = N, H, W, OH, OW
-            ar.KH = ar.KW = k
-            ar.stride, ar.pad, ar.dil, ar.Cout = stride, pad, dil, Cout
-            ar.ldw, ar.cin_total, ar.w_choff, ar.ldy = ldw, cin_total, w_choff, out.ld
+            _set_geom(ar, geom)
+            ar.Cout, ar.ldw, ar.cin_total, ar.w_choff, ar.ldy = Cout, ldw, cin_total, w_choff, out.ld
             ar.w, ar.y = wptr, out.ptr
             ar.bias = self.param(bias) if bias is not None else None
-            ar.bias_n = bias_n.ptr if bias_n is not None else None
-            ar.stats = stats.ptr if stats is not None else None
-            ar.stats_ld = stats_ld
+            ar.bias_n, ar.stats, ar.stats_ld = _ptr(bias_n), _ptr(stats), stats_ld
             rs_out = None
             if fold:
                 for i, s in enumerate(srcs):
@@ -773,11 +846,7 @@ class Graph:
         if self.want_grad:
             srcs_l = list(srcs)
 
-            def emit_bwd():
-                if not self.grad_ready(out):
-                    return
-                dy = self.grad(out)
-                P = N * OH * OW
+            def emit_bwd(dy):
                 if bias is not None:
                     self._colsum(dy, bias, per_image=False)
                 if bias_n is not None:
@@ -785,29 +854,16 @@ class Graph:
                     self._colsum_n(dy, gbn)
                 choff = w_choff
                 for s in srcs_l:
-                    # weight gradient
-                    wa = L.ConvWgradArgs()
-                    wa.dy, wa.lddy, wa.Cout = dy.ptr, dy.ld, Cout
-                    wa.N, wa.H, wa.W, wa.OH, wa.OW, wa.KH, wa.KW, wa.stride, wa.pad, wa.dil = N, H, W, OH, OW, k, k, stride, pad, dil
-                    wa.src = self.src(s, relu_in)
-                    gp, acc = self.param_grad(weight, (choff, choff + s.C))
-                    wa.dw, wa.ldw, wa.cin_total, wa.w_choff, wa.accumulate = gp, ldw, cin_total, choff, acc
-                    wa.ws_floats = lib.addk_conv_wgrad_ws(P, Cout, s.C, k * k)
-                    self._wgrads.append((wa, [dy] + self.lz(s), self.pgrad[weight], (id(weight), choff, choff + s.C)))
+                    self._defer_wgrad(dy, s, relu_in, weight, geom, ldw, cin_total, choff)
                     # data gradient
                     if s.needs_grad:
                         da = L.ConvDgradArgs()
                         da.dy, da.lddy, da.Cout = dy.ptr, dy.ld, Cout
-                        da.N, da.H, da.W, da.OH, da.OW, da.KH, da.KW, da.stride, da.pad, da.dil = N, H, W, OH, OW, k, k, stride, pad, dil
+                        _set_geom(da, geom)
                         da.w, da.ldw, da.cin_total, da.w_choff = wptr, ldw, cin_total, choff
                         da.dst = self.src(s, relu_in)
-                        gs = self.grad(s.raw)
-                        da.g, da.ldg, da.accumulate = gs.ptr, gs.ld, self.acc_flag(gs)
-                        rows = lib.addk_conv_rows(N * H * W, s.C)
-                        slab = self._dab(s, rows)
-                        if slab is not None:
-                            da.dab = slab.ptr
-                            s.bn.slabs.append((slab, rows))
+                        gs, da.accumulate, slab = self._grad_into(s, lib.addk_conv_rows(N * H * W, s.C))
+                        da.g, da.ldg, da.dab = gs.ptr, gs.ld, _ptr(slab)
                         dpk = None
                         npk = int(lib.addk_conv_dgrad_pack_floats(C.byref(da)))
                         if npk > 0:
@@ -819,7 +875,7 @@ class Graph:
                                        wr=[gs, slab, dpk])
                         self._batchable(cd, lib.addk_conv_dgrad_batch_key, da)
                     choff += s.C
-            self._bwd_emitters.append(emit_bwd)
+            self._backward(out, emit_bwd)
         return out
 
     def _colsum(self, dy, bias, per_image):
@@ -869,9 +925,9 @@ class Graph:
         st = BNState(mod, Cc, a, b, training, count)
         gam = self.param(mod.weight) if mod.weight is not None else None
         bet = self.param(mod.bias) if mod.bias is not None else None
+        sync = self.world is not None and getattr(mod, 'sync', False) and (self.world.size > 1 or self.world.force)      # cross-rank statistics
         if training:
             st.mean, st.invstd = self.vec(Cc), self.vec(Cc)
-            sync = self.world is not None and getattr(mod, 'sync', False) and (self.world.size > 1 or self.world.force)
             fa = L.BnFinalizeArgs()
             if sync:
                 red = LateVec(4 * Cc, f64=True)      # fp64 [C][2], summed over ranks
@@ -897,7 +953,7 @@ class Graph:
             fa.a, fa.b, fa.mean, fa.invstd = a.ptr, b.ptr, st.mean.ptr, st.invstd.ptr
             self.keep.append(fa)
             stat_wr = [a, b, st.mean, st.invstd] + ([mod.running_mean, mod.running_var] if fa.running_mean else [])
-            if fuse is not None and not sync and os.environ.get('ADDK_FUSE_FINALIZE', '0') == '1':
+            if fuse is not None and not sync and _on('ADDK_FUSE_FINALIZE', '0'):
                 args, cmd, nblk = fuse
                 for f_ in ('count', 'gamma', 'beta', 'running_mean', 'running_var', 'momentum', 'eps', 'a', 'b', 'mean', 'invstd'):
                     setattr(args.fin, f_, getattr(fa, f_))
@@ -935,7 +991,7 @@ class Graph:
                 ba.nslab, ba.C, ba.count = len(st.slabs), Cc, st.count
                 # dy_raw = G + c1 + c2*(x - mean): the mean is subtracted first, as the reference does (batchnorm.py:51-53), instead
                 # of folding -c2*mean into c1 where it cancels against c2*x (ADDK_BN_CENTERED=0 restores the folded form)
-                centered = os.environ.get('ADDK_BN_CENTERED', '1') == '1'
+                centered = _on('ADDK_BN_CENTERED')
                 ba.centered = int(centered)
                 mu = st.mean if centered else None
                 ba.gamma, ba.mean, ba.invstd, ba.a = gam, st.mean.ptr, st.invstd.ptr, a.ptr
@@ -949,7 +1005,6 @@ class Graph:
                     pg = []
                 rd_bn = [sl for sl, _ in st.slabs] + [mod.weight, st.mean, st.invstd, a]
                 c1, c2 = self.vec(Cc), self.vec(Cc)
-                sync = self.world is not None and getattr(mod, 'sync', False) and (self.world.size > 1 or self.world.force)
                 self.keep.append(ba)
                 if sync:
                     dmv = LateVec(2 * Cc)              # (dmean, dvar) contributions of this rank, summed over ranks
@@ -966,12 +1021,12 @@ class Graph:
                     ba.c1, ba.c2 = c1.ptr, c2.ptr
                     self._add(self.bwd, 'bn_bwd', lib.addk_bn_bwd, C.byref(ba), rd=rd_bn, wr=pg + [c1, c2]).payload = ba
                 # dy_raw = G + c1 + c2*x, in place on the accumulated gradient
-                cap = self._add(self.bwd, 'bn_bwd_apply', lib.addk_bn_bwd_apply, g.ptr, g.ld, raw.ptr, raw.ld, mu.ptr if mu else None,
+                cap = self._add(self.bwd, 'bn_bwd_apply', lib.addk_bn_bwd_apply, g.ptr, g.ld, raw.ptr, raw.ld, _ptr(mu),
                                 c1.ptr, c2.ptr, raw.P, Cc, g.ptr, g.ld, rd=[g, raw, c1, c2, mu], wr=[g])
                 if Cc % 4 == 0 and Cc <= 1024 and g.ld % 4 == 0 and raw.ld % 4 == 0 and g.ptr % 16 == 0 and raw.ptr % 16 == 0:
                     it = L.BnApplyItem()
                     it.g, it.x, it.c1, it.c2, it.out, it.P = g.ptr, raw.ptr, c1.ptr, c2.ptr, g.ptr, raw.P
-                    it.mean = mu.ptr if mu else None
+                    it.mean = _ptr(mu)
                     it.ldg, it.ldx, it.ldo, it.C = g.ld, raw.ld, g.ld, Cc
                     cap.payload = it
             self._bwd_emitters.append(emit_bwd)
@@ -982,8 +1037,7 @@ class Graph:
         k = conv_mod.kernel_size[0]
         a0 = srcs[0]
         stride, pad, dil = conv_mod.stride[0], conv_mod.padding[0], conv_mod.dilation[0]
-        OH = (a0.H + 2 * pad - dil * (k - 1) - 1) // stride + 1
-        OW = (a0.W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+        OH, OW = _out_hw(a0.H, a0.W, k, stride, pad, dil)
         Cout = conv_mod.out_channels
         slab = rows = None
         training = self.training and bn_mod.training
@@ -998,13 +1052,13 @@ class Graph:
         k = conv_mod.kernel_size[0]
         stride, pad, dil = conv_mod.stride[0], conv_mod.padding[0], conv_mod.dilation[0]
         N, H, W, Cc = src.N, src.H, src.W, src.C
-        OH = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1
-        OW = (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+        OH, OW = _out_hw(H, W, k, stride, pad, dil)
+        geom = (N, H, W, OH, OW, k, k, stride, pad, dil)
         out = self.tensor(N, OH, OW, Cc)
         wptr = self.param(conv_mod.weight)
         ar = L.DwArgs()
         ar.src = self.src(src, relu_in)
-        ar.N, ar.H, ar.W, ar.OH, ar.OW, ar.KH, ar.KW, ar.stride, ar.pad, ar.dil = N, H, W, OH, OW, k, k, stride, pad, dil
+        _set_geom(ar, geom)
         ar.w, ar.y, ar.ldy = wptr, out.ptr, out.ld
         self.keep.append(ar)
         if fwd:
@@ -1012,38 +1066,24 @@ class Graph:
             self._batchable(cdw, lib.addk_dw_fwd_batch_key, ar)
         act = Act(out, None, False, self.want_grad)
         if self.want_grad:
-            def emit_bwd():
-                if not self.grad_ready(out):
-                    return
-                dy = self.grad(out)
+            def emit_bwd(dy):
                 ba = L.DwBwdArgs()
                 ba.dy, ba.lddy = dy.ptr, dy.ld
-                ba.N, ba.H, ba.W, ba.OH, ba.OW, ba.KH, ba.KW, ba.stride, ba.pad, ba.dil = N, H, W, OH, OW, k, k, stride, pad, dil
+                _set_geom(ba, geom)
                 ba.src = self.src(src, relu_in)
                 ba.w = wptr
                 rows = lib.addk_dw_rows(N * H * W, Cc)
+                gs = slab = None
                 if src.needs_grad:
-                    gs = self.grad(src.raw)
-                    ba.g, ba.ldg, ba.accumulate = gs.ptr, gs.ld, self.acc_flag(gs)
-                    slab = self._dab(src, rows)
-                    if slab is not None:
-                        ba.dab = slab.ptr
-                        src.bn.slabs.append((slab, rows))
-                else:
-                    gs = slab = None
-                gp, acc = self.param_grad(conv_mod.weight)
-                ba.dw, ba.dw_accumulate = gp, acc
-                ws = self.buf(rows * Cc * k * k)
-                ba.ws = ws.ptr
-                ba.defer_wreduce = 1          # the [rows][C][k*k] partials are reduced at the end of the backward pass, all convs in one launch
-                it = L.DwWreduceItem()
-                it.ws, it.dw, it.rows, it.n, it.accumulate = ws.ptr, gp, rows, Cc * k * k, acc
-                self._dwreds.append((it, ws, self.pgrad[conv_mod.weight]))
+                    gs, ba.accumulate, slab = self._grad_into(src, rows)
+                    ba.g, ba.ldg, ba.dab = gs.ptr, gs.ld, _ptr(slab)
+                ws, ba.dw, ba.dw_accumulate = self._defer_dw_wreduce(conv_mod.weight, rows, Cc * k * k)
+                ba.ws, ba.defer_wreduce = ws.ptr, 1
                 self.keep.append(ba)
                 cdb = self._add(self.bwd, 'dw_bwd', lib.addk_dw_bwd, C.byref(ba), rd=[dy, conv_mod.weight] + self.lz(src),
                                 wr=[gs, slab, ws])
                 self._batchable(cdb, lib.addk_dw_bwd_batch_key, ba)
-            self._bwd_emitters.append(emit_bwd)
+            self._backward(out, emit_bwd)
         return act
 
     def _sep_bwd_args(self, src, dw_mod, pw_mod):
@@ -1062,45 +1102,27 @@ class Graph:
         N, H, W, Cc = src.N, src.H, src.W, src.C
         Cout = pw_mod.out_channels
 
-        def emit_bwd():
-            if not self.grad_ready(raw):
-                return
-            dy = self.grad(raw)
+        def emit_bwd(dy):
             # pointwise weight gradient: dW[co][ci] = sum_p dy[p][co] t[p][ci]
-            wa = L.ConvWgradArgs()
-            gp, acc = self.param_grad(pw_mod.weight, (0, Cc))
-            wa.dy, wa.lddy, wa.Cout = dy.ptr, dy.ld, Cout
-            wa.N, wa.H, wa.W, wa.OH, wa.OW, wa.KH, wa.KW, wa.stride, wa.pad, wa.dil = N, H, W, H, W, 1, 1, 1, 0, 1
-            wa.src = self.src(t)
-            wa.dw, wa.ldw, wa.cin_total, wa.w_choff, wa.accumulate = gp, Cc, Cc, 0, acc
-            wa.ws_floats = lib.addk_conv_wgrad_ws(N * H * W, Cout, Cc, 1)
-            self._wgrads.append((wa, [dy] + self.lz(t), self.pgrad[pw_mod.weight], (id(pw_mod.weight), 0, Cc)))
+            self._defer_wgrad(dy, t, False, pw_mod.weight, (N, H, W, H, W, 1, 1, 1, 0, 1), Cc, Cc, 0)
             # fused data gradient + depthwise backward
             ba = self._sep_bwd_args(src, dw_mod, pw_mod)
             ba.dy, ba.lddy = dy.ptr, dy.ld
             gs = slab = None
             if src.needs_grad:
-                gs = self.grad(src.raw)
-                ba.g, ba.ldg, ba.accumulate = gs.ptr, gs.ld, self.acc_flag(gs)
-                slab = self._dab(src, rows)
-                if slab is not None:
-                    ba.dab = slab.ptr
-                    src.bn.slabs.append((slab, rows))
-            gpw, accw = self.param_grad(dw_mod.weight)
-            ws = self.buf(rows * Cc * k * k)
+                gs, ba.accumulate, slab = self._grad_into(src, rows)
+                ba.g, ba.ldg, ba.dab = gs.ptr, gs.ld, _ptr(slab)
+            ws = self._defer_dw_wreduce(dw_mod.weight, rows, Cc * k * k)[0]
             ba.ws = ws.ptr
-            it = L.DwWreduceItem()
-            it.ws, it.dw, it.rows, it.n, it.accumulate = ws.ptr, gpw, rows, Cc * k * k, accw
-            self._dwreds.append((it, ws, self.pgrad[dw_mod.weight]))
             self.keep.append(ba)
             cb = self._add(self.bwd, 'sep_bwd', lib.addk_sep_bwd, C.byref(ba), rd=[dy, dw_mod.weight, pw_mod.weight] + self.lz(src),
                            wr=[gs, slab, ws])
             self._batchable(cb, lib.addk_sep_bwd_batch_key, ba)
-        self._bwd_emitters.append(emit_bwd)
+        self._backward(raw, emit_bwd)
 
     def _sep_fusable(self, dw_mod, pw_mod, sum_terms, training):
         """The halves the fused kernels are written for (ADDK_FUSE_SEP=0: none); which shapes run fused is the library's decision."""
-        return (os.environ.get('ADDK_FUSE_SEP', '1') == '1' and dw_mod.stride[0] == 1 and dw_mod.dilation[0] == 1
+        return (_on('ADDK_FUSE_SEP') and dw_mod.stride[0] == 1 and dw_mod.dilation[0] == 1
                 and dw_mod.padding[0] == dw_mod.kernel_size[0] // 2 and pw_mod.kernel_size[0] == 1
                 and (sum_terms is None or not (training or self.want_grad)))
 
@@ -1136,7 +1158,7 @@ class Graph:
             slab = self.buf(rows * Cout * 4)
             ar.stats_rows = rows
         if self.want_grad:
-            bcfg = self._config(lib.addk_sep_bwd_config, self._sep_bwd_args(src, dw_mod, pw_mod)) if os.environ.get('ADDK_FUSE_SEP_BWD', '1') == '1' else [0]
+            bcfg = self._config(lib.addk_sep_bwd_config, self._sep_bwd_args(src, dw_mod, pw_mod)) if _on('ADDK_FUSE_SEP_BWD') else [0]
             if bcfg[0] == 1:
                 t = Act(self.tensor(N, H, W, Cc), None, False, True)           # depthwise output: written by the fused forward, read by the pointwise weight gradient
                 self._sep_bwd(src, dw_mod, pw_mod, raw, t, bcfg[6])
@@ -1144,8 +1166,7 @@ class Graph:
                 t = self.dwconv(src, dw_mod, relu_in=True, fwd=False)
                 self.conv([t], pw_mod.weight, Cout, 1, out=raw, stats=slab, fwd=False)       # backward of the pointwise half
             ar.t, ar.ldt = t.raw.ptr, t.raw.ld
-        ar.stats = slab.ptr if slab is not None else None
-        ar.stats_ld = 0
+        ar.stats, ar.stats_ld = _ptr(slab), 0
         rd = self.lz(src) + [dw_mod.weight, pw_mod.weight]
         if sum_terms is not None:
             # inference: y = a*acc + b (this op's frozen BatchNorm) + the other branches, written straight into the block's slot
@@ -1183,22 +1204,15 @@ class Graph:
         ng = self.want_grad and any(t.needs_grad for t in terms)
         act = Act(out, None, False, ng)
         if ng:
-            def emit_bwd():
-                if not self.grad_ready(out):
-                    return
-                do = self.grad(out)
+            def emit_bwd(do):
                 ba = L.AffineSumBwdArgs()
                 rows = lib.addk_ew_rows(out.P, out.C)
                 wr_ = []
                 for i, t in enumerate(terms):
                     ba.term[i] = self.src(t)
                     if t.needs_grad:
-                        gt = self.grad(t.raw)
-                        ba.g[i], ba.ldg[i], ba.accumulate[i] = gt.ptr, gt.ld, self.acc_flag(gt)
-                        slab = self._dab(t, rows)
-                        if slab is not None:
-                            ba.dab[i] = slab.ptr
-                            t.bn.slabs.append((slab, rows))
+                        gt, ba.accumulate[i], slab = self._grad_into(t, rows)
+                        ba.g[i], ba.ldg[i], ba.dab[i] = gt.ptr, gt.ld, _ptr(slab)
                         wr_ += [gt, slab]
                 ba.nterm, ba.P, ba.C = len(terms), out.P, out.C
                 ba.dout, ba.lddo = do.ptr, do.ld
@@ -1206,7 +1220,7 @@ class Graph:
                 self.keep.append(ba)
                 self._add(self.bwd, 'affine_sum_bwd', lib.addk_affine_sum_bwd, C.byref(ba),
                           rd=[do, out] + [r for t in terms for r in self.lz(t)], wr=wr_)
-            self._bwd_emitters.append(emit_bwd)
+            self._backward(out, emit_bwd)
         return act
 
     def materialize(self, act, relu_in=False):
@@ -1242,28 +1256,19 @@ class Graph:
             rs = Resample(src.raw, emit_fwd)      # deferred: a 1x1 consumer samples src.raw itself (Graph.conv), anyone else emits it
         res = Act(out, None if relu else src.bn, False, src.needs_grad, rs=rs)
         if self.want_grad and src.needs_grad:
-            def emit_bwd():
-                if not self.grad_ready(out):
-                    return
-                dy = self.grad(out)
+            def emit_bwd(dy):
                 ba = L.ResizeBwdArgs()
                 ba.dy, ba.lddy, ba.nchw_in = dy.ptr, dy.ld, 0
                 ba.src = self.src(carrier, relu_in)
                 ba.N, ba.H, ba.W, ba.OH, ba.OW = N, H, W, OH, OW
-                gs = self.grad(src.raw)
-                ba.g, ba.ldg, ba.accumulate = gs.ptr, gs.ld, self.acc_flag(gs)
-                slab = None
-                if relu:
-                    rows = lib.addk_ew_rows(N * H * W, Cc)
-                    slab = self._dab(src, rows)
-                    if slab is not None:
-                        ba.dab = slab.ptr
-                        src.bn.slabs.append((slab, rows))
+                # without a pending ReLU the BatchNorm passed through the interpolation: its (dA,dB) come from the consumers of `res`
+                gs, ba.accumulate, slab = self._grad_into(src, lib.addk_ew_rows(N * H * W, Cc) if relu else None)
+                ba.g, ba.ldg, ba.dab = gs.ptr, gs.ld, _ptr(slab)
                 self.keep.append(ba)
                 crb = self._add(self.bwd, 'resize_bwd', lib.addk_resize_bwd, C.byref(ba), rd=[dy] + self.lz(src), wr=[gs, slab])
-                if os.environ.get('ADDK_BATCH_RESIZE_BWD', '1') == '1':
+                if _on('ADDK_BATCH_RESIZE_BWD'):
                     self._batchable(crb, lib.addk_resize_bwd_batch_key, ba)
-            self._bwd_emitters.append(emit_bwd)
+            self._backward(out, emit_bwd)
         return res
 
     def resize_to_nchw(self, src, OH, OW):
@@ -1274,7 +1279,7 @@ class Graph:
         lib = self.lib
         assert src.bn is None and not src.relu
         N, H, W, Cc = src.N, src.H, src.W, src.C
-        if (getattr(self, 'fuse_ce', False) and self.want_grad and src.needs_grad
+        if (self.fuse_ce and self.want_grad and src.needs_grad
                 and lib.addk_ce_upsample_supported(N, H, W, OH, OW, Cc) == 1):
             out = OutRef(None)
             out.fused_ce, out.shape, out.ce = True, (N, Cc, OH, OW), None
@@ -1288,8 +1293,8 @@ class Graph:
                 ce = out.ce
                 a.target, a.class_w, a.ignore_index = ce['target'].data_ptr(), ce['class_w'], ce['ignore_index']
                 a.wsum, a.scale, a.loss_out = ce['wsum'].data_ptr(), ce['scale'], ce['loss'].data_ptr()
-                gs = self.grad(src.raw)
-                a.g, a.ldg, a.accumulate = gs.ptr, gs.ld, self.acc_flag(gs)
+                gs, a.accumulate, _ = self._grad_into(src)
+                a.g, a.ldg = gs.ptr, gs.ld
                 ws = torch.zeros(int(lib.addk_ce_upsample_ws_floats(N, H, W)), dtype=torch.float32, device=self.device)
                 a.ws = ws.data_ptr()
                 self.keep += [a, ws]
@@ -1316,8 +1321,8 @@ class Graph:
                 ba.dy_scale = out.dy_scale
                 ba.src = self.src(src)
                 ba.N, ba.H, ba.W, ba.OH, ba.OW = N, H, W, OH, OW
-                gs = self.grad(src.raw)
-                ba.g, ba.ldg, ba.accumulate = gs.ptr, gs.ld, self.acc_flag(gs)
+                gs, ba.accumulate, _ = self._grad_into(src)
+                ba.g, ba.ldg = gs.ptr, gs.ld
                 self.keep.append(ba)
                 out.bwd_args = ba
                 self._add(self.bwd, 'resize_nchw_bwd', lib.addk_resize_bwd, C.byref(ba), rd=self.lz(src), wr=[gs])
@@ -1335,19 +1340,11 @@ class Graph:
         self._add(self.fwd, 'gap_fwd', lib.addk_gap_fwd, C.byref(s), N, H * W, out.ptr, out.ld, ws.ptr, 1, rd=self.lz(src), wr=[out, ws])
         act = Act(out, None, False, self.want_grad and src.needs_grad)
         if act.needs_grad:
-            def emit_bwd():
-                if not self.grad_ready(out):
-                    return
-                dy = self.grad(out)
-                gs = self.grad(src.raw)
-                acc = self.acc_flag(gs)
-                rows2 = lib.addk_ew_rows(N * H * W, Cc)
-                slab = self._dab(src, rows2)
-                if slab is not None:
-                    src.bn.slabs.append((slab, rows2))
+            def emit_bwd(dy):
+                gs, acc, slab = self._grad_into(src, lib.addk_ew_rows(N * H * W, Cc))
                 self._add(self.bwd, 'gap_bwd', lib.addk_gap_bwd, C.byref(s), N, H * W, dy.ptr, dy.ld, gs.ptr, gs.ld, acc,
-                          slab.ptr if slab is not None else None, rd=[dy] + self.lz(src), wr=[gs, slab])
-            self._bwd_emitters.append(emit_bwd)
+                          _ptr(slab), rd=[dy] + self.lz(src), wr=[gs, slab])
+            self._backward(out, emit_bwd)
         return act
 
     def edm_head(self, src, conv_w, lins, host_out=None):
@@ -1356,7 +1353,7 @@ class Graph:
         written to (the gate of dynamic_inference reads it there: no device-to-host copy).  Returns the [N,1,1,1] Act, or None when the
         kernel does not cover the arguments (the caller then emits the generic launches)."""
         lib = self.lib
-        if self.want_grad or os.environ.get('ADDK_FUSE_EDM', '1') != '1':
+        if self.want_grad or not _on('ADDK_FUSE_EDM'):
             return None
         N, H, W = src.N, src.H, src.W
         ar = L.EdmArgs()
@@ -1382,7 +1379,7 @@ class Graph:
     def pool3(self, src, stride, mode):
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
-        OH, OW = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+        OH, OW = _out_hw(H, W, 3, stride, 1, 1)
         out = self.tensor(N, OH, OW, Cc)
         s = self.src(src)
         self.keep.append(s)
@@ -1392,14 +1389,11 @@ class Graph:
         if act.needs_grad:
             assert src.bn is None or not src.bn.training, 'pool3 backward through a lazy training BN is not built (cold path)'
 
-            def emit_bwd():
-                if not self.grad_ready(out):
-                    return
-                dy = self.grad(out)
-                gs = self.grad(src.raw)
+            def emit_bwd(dy):
+                gs, acc, _ = self._grad_into(src)
                 self._add(self.bwd, 'pool3_bwd', lib.addk_pool3_bwd, C.byref(s), N, H, W, OH, OW, stride, mode, dy.ptr, dy.ld,
-                          gs.ptr, gs.ld, self.acc_flag(gs), rd=[dy] + self.lz(src), wr=[gs])
-            self._bwd_emitters.append(emit_bwd)
+                          gs.ptr, gs.ld, acc, rd=[dy] + self.lz(src), wr=[gs])
+            self._backward(out, emit_bwd)
         return act
 
     def zeros(self, N, H, W, Cc):
@@ -1440,14 +1434,9 @@ class Graph:
         out = OutRef(y)
         if self.want_grad and act.needs_grad:
             def emit_bwd():
-                gs = self.grad(act.raw)
-                acc = self.acc_flag(gs)
-                rows = lib.addk_ew_rows(N * H * W, Cc)
-                slab = self._dab(act, rows)
-                if slab is not None:
-                    act.bn.slabs.append((slab, rows))
+                gs, acc, slab = self._grad_into(act, lib.addk_ew_rows(N * H * W, Cc))
                 out.bwd_cmd = self._add(self.bwd, 'out_grad', lib.addk_nchw_grad_to_nhwc, None, C.byref(s), N, H * W, gs.ptr, gs.ld,
-                                        acc, slab.ptr if slab is not None else None, rd=self.lz(act), wr=[gs, slab])
+                                        acc, _ptr(slab), rd=self.lz(act), wr=[gs, slab])
             self._bwd_emitters.append(emit_bwd)
         return out
 

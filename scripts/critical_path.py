@@ -23,22 +23,8 @@ import bench                # noqa: E402
 
 
 def deps_of(cmds):
-    from addk.plan import _overlap
-    writers, readers, deps = {}, {}, []
-    for i, c in enumerate(cmds):
-        d = set()
-        for k in c.rd:
-            d.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-        for k in c.wr:
-            d.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-            d.update(j for r, j in readers.get(k[0], ()) if _overlap(r, k))
-        deps.append(sorted(d))
-        for k in c.wr:
-            writers[k[0]] = [(r, j) for r, j in writers.get(k[0], ()) if not (r[1] >= k[1] and r[2] <= k[2])] + [(k, i)]
-            readers[k[0]] = [(r, j) for r, j in readers.get(k[0], ()) if not (r[1] >= k[1] and r[2] <= k[2])]
-        for k in c.rd:
-            readers.setdefault(k[0], []).append((k, i))
-    return deps
+    from addk.plan import deps
+    return [sorted(d) for d in deps(cmds)]
 
 
 def main():

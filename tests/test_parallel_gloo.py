@@ -67,7 +67,7 @@ def _syncbn_math(rank, world):
     v1, v2 = LateVec(4 * C, f64=True), LateVec(16, f64=True)
     comm.emit_allreduce(g, g.fwd, v1); comm.emit_allreduce(g, g.fwd, v2)
     v1.bind(arena, 0); v2.bind(arena, 4 * C)
-    # the merged form plan.Graph._level_batch emits for one level: ONE plain all-reduce of the arena
+    # the merged form plan.Graph.level_batch emits for one level: ONE plain all-reduce of the arena
     assert comm._allreduce(arena.t.view(torch.float64), 0) == 0
     tri = world * (world + 1) / 2
     assert torch.equal(v2.view(), torch.full((8,), tri, dtype=torch.float64))

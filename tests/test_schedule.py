@@ -1,4 +1,4 @@
-"""Host logic of the launch-list scheduler (plan.schedule) and of the level re-ordering pass (Graph._level_batch) on
+"""Host logic of the launch-list scheduler (plan.schedule) and of the level re-ordering pass (plan.level_order) on
 synthetic command DAGs: dependencies survive, the stream assignment respects the constraint that makes hipGraph capture
 safe on ROCm 7.2 (two side streams never wait on each other in both directions), implied waits are pruned."""
 import random
@@ -87,19 +87,13 @@ def test_implied_waits_are_pruned():
     assert len(c.waits) <= 1
 
 
-class _FakeGraph:
-    """Just enough of Graph for _level_batch (no batchable payloads: pure re-ordering)."""
-    _BATCHED = {}
-    _level_batch = P.Graph._level_batch
-
-
 @pytest.mark.parametrize('seed', [3, 4, 5, 6])
 def test_level_order_is_a_valid_topological_order(seed):
     cmds = _cmds(250, 14, seed)
     deps = _deps(cmds)
     ident = {id(c): i for i, c in enumerate(cmds)}
     lst = list(cmds)
-    _FakeGraph()._level_batch(lst)
+    P.level_order(lst)
     assert sorted(ident[id(c)] for c in lst) == list(range(len(cmds)))          # a permutation
     pos = {ident[id(c)]: k for k, c in enumerate(lst)}
     for i in range(len(cmds)):

@@ -1,0 +1,345 @@
+#!/usr/bin/env python
+"""Fingerprints of the dry-built launch plans, for refactors of the planner (plan.py, parallel.py, dynamic.py): a change that is
+not meant to change a plan must leave every fingerprint as it is.  No GPU: launches are stubbed the way tests/test_plan_dryrun.py
+and tests/test_sep_dispatch.py do it.
+
+Per plan and per launch list the ordered records of every command are hashed: name, tag, tags, members, stream, waits, whether it
+records an event, batch key, payload (type and bytes), the read / write regions and every argument; argument structs, meta arrays
+and the tables the arguments point to are taken as bytes.  Memory is made address-independent by ONE rule: an 8-byte-aligned word,
+an integer argument or a region key that falls inside a known allocation becomes (ordinal of the allocation, byte offset).  Known
+allocations are the plan's buffers in creation order, then the parameters, the plan-owned gradients, the kept tensors and the
+tensors of the plan's front end (inputs, outputs, loss scalars, module buffers) in first-seen order.  Region keys that are object
+identities (plan.LateVec before it is bound) are numbered in first-seen order over the lists.  Also recorded: nbytes, the number and
+sizes of the buffers, the number of hoisted weight packs.
+
+    python tests/tools/plan_fingerprint.py                 # writes tests/golden/plan_fingerprint.json (run it on the commit to pin)
+    python tests/tools/plan_fingerprint.py --check         # compares with the fixture, exit status 1 on a difference
+    python tests/tools/plan_fingerprint.py --dump DIR      # also writes every record as text, one file per list (to diff two commits)
+
+tests/test_plan_fingerprint.py calls fingerprints() and compares with the fixture.  Every struct the planner fills is a ctypes
+object (zero-initialised) and every library-made blob is written into zeroed memory, so no byte needs masking: two runs of this tool
+in different processes give equal hashes."""
+import argparse
+import bisect
+import collections
+import ctypes as C
+import gc
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for _p in (ROOT, os.path.join(ROOT, 'tests')):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+OUT = os.path.join(ROOT, 'tests', 'golden', 'plan_fingerprint.json')
+
+ENVS = (('default', {}), ('no_level_batch', {'ADDK_LEVEL_BATCH': '0'}))
+_BYREF = type(C.byref(C.c_int()))
+
+
+class Memory:
+    """The known allocations of one plan; `word(v)` is the one rule that makes a value address-independent."""
+
+    def __init__(self):
+        self.starts, self.ends, self.ords = [], [], []
+        self.n = 0
+        self.tables = {}          # data_ptr of a kept uint8 table -> tensor
+        self.ids = {}             # id() of a Buf -> ordinal of its allocation; other identities: first seen
+
+    def add(self, base, nbytes, obj_id=None):
+        o = self.n
+        self.n += 1
+        if obj_id is not None:
+            self.ids[obj_id] = ('a', o)
+        if nbytes <= 0:
+            return o
+        i = bisect.bisect_right(self.starts, base)
+        if (i > 0 and self.ends[i - 1] > base) or (i < len(self.starts) and self.starts[i] < base + nbytes):
+            return o              # inside / across an earlier allocation (a view of a flat buffer): the earlier one names these bytes
+        self.starts.insert(i, base); self.ends.insert(i, base + nbytes); self.ords.insert(i, o)
+        return o
+
+    def add_tensor(self, t):
+        if isinstance(t, torch.Tensor) and t.numel():
+            self.add(t.data_ptr(), t.numel() * t.element_size())
+
+    def word(self, v):
+        i = bisect.bisect_right(self.starts, v) - 1
+        if i >= 0 and v < self.ends[i]:
+            return ('@', self.ords[i], v - self.starts[i])
+        return v
+
+    def ident(self, v):
+        if v not in self.ids:
+            w = self.word(v)
+            if w is not v:
+                return w
+            self.ids[v] = ('id', sum(1 for k in self.ids.values() if k[0] == 'id'))
+        return self.ids[v]
+
+    def blob(self, data):
+        """bytes -> bytes with every 8-byte-aligned word that is an address replaced by 1 << 63 | ordinal << 40 | offset"""
+        data = bytes(data)
+        data += b'\0' * (-len(data) % 8)
+        w = np.frombuffer(data, dtype=np.uint64).copy()
+        if not self.starts or not len(w):
+            return w.tobytes()
+        st, en = np.asarray(self.starts, dtype=np.uint64), np.asarray(self.ends, dtype=np.uint64)
+        i = np.searchsorted(st, w, side='right').astype(np.int64) - 1
+        ok = i >= 0
+        ic = np.where(ok, i, 0)
+        ok &= w < en[ic]
+        off = w - st[ic]
+        assert not bool((off[ok] >> np.uint64(40)).any())
+        enc = np.uint64(1 << 63) | (np.asarray(self.ords, dtype=np.uint64)[ic] << np.uint64(40)) | off
+        return np.where(ok, enc, w).tobytes()
+
+
+def _arg(mem, a, P):
+    if a is None or isinstance(a, (float, str)):
+        return a
+    if isinstance(a, bool):
+        return int(a)
+    if isinstance(a, int):
+        if a in mem.tables:                                   # a table of argument structs / descriptors: its bytes, not its address
+            return ('table', hashlib.sha256(mem.blob(mem.tables[a].numpy().tobytes())).hexdigest())
+        return mem.word(a)
+    if isinstance(a, _BYREF):
+        a = a._obj
+    if isinstance(a, (C.Structure, C.Array)):
+        return (type(a).__name__, hashlib.sha256(mem.blob(bytes(a))).hexdigest())
+    if isinstance(a, torch.Tensor):
+        return ('tensor', mem.word(a.data_ptr()), tuple(a.shape), str(a.dtype))
+    if isinstance(a, P.LateVec):
+        return ('late', a.n, a.f64, mem.word(a.ptr) if a.buf is not None else None)
+    if isinstance(a, P.InRef):
+        return ('inref', tuple(a.shape))
+    return type(a).__name__
+
+
+def _records(mem, lst, P):
+    out = []
+    for c in lst:
+        reg = lambda rs: [(mem.ident(k[0]), k[1], k[2]) for k in rs]      # noqa: E731
+        pay = c.payload
+        out.append((c.name, c.tag, sorted(c.tags) if c.tags is not None else None, c.members, c.stream, tuple(c.waits), c.event is not None,
+                    c.bkey, type(pay).__name__, _arg(mem, pay, P) if isinstance(pay, (C.Structure, P.LateVec)) else None,
+                    reg(c.rd), reg(c.wr), [_arg(mem, a, P) for a in c.args]))
+    return out
+
+
+def _memory(g, extra):
+    mem = Memory()
+    for b in g._bufs:
+        mem.add(b.ptr, 4 * max(b.n, 4), id(b))
+    for p in g.params:
+        mem.add_tensor(p)
+    for p in g.params:
+        mem.add_tensor(g.pgrad.get(p))
+    for t in g.keep:
+        if isinstance(t, torch.Tensor):
+            mem.add_tensor(t)
+            if t.dtype == torch.uint8:
+                mem.tables[t.data_ptr()] = t
+    for t in extra:
+        mem.add_tensor(t)
+    return mem
+
+
+def _fingerprint(g, lists, extra, dump, label):
+    import addk.plan as P
+    mem = _memory(g, extra)
+    res = {'nbytes': int(g.nbytes), 'bufs': len(g._bufs), 'buf_sizes': hashlib.sha256(repr([b.n for b in g._bufs]).encode()).hexdigest(),
+           'packs': len(g._packs), 'lists': {}}
+    for name, lst in lists:
+        recs = _records(mem, lst, P)
+        text = '\n'.join(repr(r) for r in recs)
+        res['lists'][name] = {'sha256': hashlib.sha256(text.encode()).hexdigest(), 'commands': len(recs),
+                              'names': dict(sorted(collections.Counter(c.name for c in lst).items()))}
+        if dump:
+            with open(os.path.join(dump, '%s.%s.txt' % (label.replace('/', '.'), name)), 'w') as f:
+                f.write(text + '\n')
+    return res
+
+
+# ---------------------------------------------------------------- the plans
+def _model(F, sync=False, train=True):
+    from _util import ARCH_C2, GENOTYPE_AUTODEEPLAB, make_args
+    from addk.modeling.ADD import ADD
+    m = ADD(ARCH_C2['network_arch'], ARCH_C2['C_index'], GENOTYPE_AUTODEEPLAB, 19, make_args(F, sync_bn=sync), ARCH_C2['low_level_layer'])
+    return m.train(train)
+
+
+def _tensors(*objs):
+    """every tensor an object of the plan's front end holds (one level of attributes, lists, dicts)"""
+    out = []
+    for o in objs:
+        vals = list(vars(o).values()) if hasattr(o, '__dict__') else [o]
+        for v in vals:
+            for t in (v if isinstance(v, (list, tuple)) else v.values() if isinstance(v, dict) else [v]):
+                if isinstance(t, torch.Tensor):
+                    out.append(t)
+                elif hasattr(t, 'y') and isinstance(getattr(t, 'y'), torch.Tensor):     # OutRef
+                    out.append(t.y)
+    return out
+
+
+def _train_step(F, shape, sync=False):
+    """the fused train step as bench.py builds it (flat gradient views, fused up-sampling + loss)"""
+    import addk.train as T
+    comm = None
+    if sync:                       # the forced exchange at world 1 without a process group: arena binding, packed all-reduces, gradient buckets
+        from addk import parallel
+        comm = object.__new__(parallel.SyncBNComm)
+        comm.group, comm.force, comm.size, comm.rank, comm.calls, comm.log, comm.small, comm._small_tried = None, True, 1, 0, 0, None, None, True
+    m = _model(F, sync)
+    ts = T.TrainStep(m, shape, sync_comm=comm, use_graph=False, nstreams=2)
+    g = ts.g
+    extra = _tensors(ts, ts.inref, *ts.outs) + list(m.buffers())
+    return g, [('fwd', g.fwd), ('bwd', g.bwd)], extra, (ts, m)
+
+
+def _module_plan(F, shape, train):
+    """the nn.Module front end: model(x) (and loss.backward() in training) builds the plan"""
+    m = _model(F, train=train)
+    with torch.set_grad_enabled(train):
+        m(torch.empty(*shape))
+    plan = next(iter(m._plans().values()))
+    g = plan.g
+    extra = _tensors(*[o for _, o in plan.outs if not isinstance(o, int)], *plan.inrefs) + list(m.buffers())
+    return g, [('fwd', g.fwd), ('bwd', g.bwd)], extra, (plan, m)
+
+
+def _dynamic(F, shape):
+    """the gated inference plan and every segment it replays (trunk to the gate, early head, remainder)"""
+    from addk.modeling.ADD import EDM
+    m = _model(F, train=False)
+    edm = EDM().eval()
+    x = torch.empty(*shape)
+    plan = m._dynamic_plan(x, edm)
+    segs = [(0, plan.trunk_end[0]), plan.head_rng[0], (plan.head_rng[0][1], -1)]
+    with torch.no_grad():
+        for i0, i1 in segs:
+            plan._seg(i0, i1)
+    g = plan.g
+    lists = [('fwd', g.fwd)] + [('seg%d' % k, plan.segs[(i0, i1 if i1 >= 0 else len(g.fwd))]) for k, (i0, i1) in enumerate(segs)]
+    extra = _tensors(plan, plan.inref, *plan.conf, *plan.heads, plan.final) + list(m.buffers()) + list(edm.buffers())
+    return g, lists, extra, (plan, m, edm)
+
+
+PLANS = (
+    ('c2_train_step', lambda: _train_step(20, (2, 3, 1024, 2048))),          # the flagship: config 2, F = 20, want_grad
+    ('c2_inference', lambda: _module_plan(20, (1, 3, 1024, 2048), False)),
+    ('c2_module_train', lambda: _module_plan(4, (2, 3, 65, 129), True)),      # autograd front end: logits resize and its backward as launches
+    ('f40_train_step', lambda: _train_step(40, (2, 3, 1024, 2048))),
+    ('syncbn_forced_train_step', lambda: _train_step(4, (2, 3, 65, 129), sync=True)),
+    ('dynamic_segments', lambda: _dynamic(20, (1, 3, 65, 129))),
+)
+
+
+class _dry:
+    """Stub the launches and accept CPU tensors, as the dry-run tests do; restores everything on exit."""
+
+    late = []
+
+    def __enter__(self):
+        import addk.plan as P
+        self.P, self.saved = P, (P.Graph.run, P.require_device, P.current_stream, P.LateVec.__init__)
+        P.Graph.run = lambda self, cmds, stream: None
+        # a LateVec's region key is its identity, and the merged all-reduce of a level outlives the vectors it replaced: they are kept
+        # alive here so that no later object is given the address (= identity) of a dead one
+        late, init = self.late, P.LateVec.__init__
+        P.LateVec.__init__ = lambda s, *a, **k: (init(s, *a, **k), late.append(s))[0]
+        P.require_device = lambda x: None
+        P.current_stream = lambda: 0
+        return self
+
+    def __exit__(self, *exc):
+        self.P.Graph.run, self.P.require_device, self.P.current_stream, self.P.LateVec.__init__ = self.saved
+
+
+def fingerprints(only=None, dump=None):
+    """{plan/environment: fingerprint} of every plan of PLANS (or of the names in `only`) under every environment of ENVS, built
+    in f16x3 arithmetic with every fast path on (config 2's defaults on the MI355X)."""
+    import addk
+    from addk import _lib as L
+    lib = addk.load()
+    mode, fast = lib.addk_get_conv_precision(), lib.addk_get_fast_paths()
+    out = {}
+    try:
+        L.check(lib.addk_set_conv_precision(1), 'set_conv_precision')
+        lib.addk_set_fast_paths(31)
+        with _dry():
+            for pname, build in PLANS:
+                if only and pname not in only:
+                    continue
+                for ename, env in ENVS:
+                    old = {k: os.environ.get(k) for k in env}
+                    os.environ.update(env)
+                    try:
+                        g, lists, extra, hold = build()
+                        label = '%s/%s' % (pname, ename)
+                        out[label] = _fingerprint(g, lists, extra, dump, label)
+                    finally:
+                        for k, v in old.items():
+                            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+                    del g, lists, extra, hold, _dry.late[:]
+                    gc.collect()
+    finally:
+        lib.addk_set_conv_precision(mode)
+        lib.addk_set_fast_paths(fast)
+    return out
+
+
+def differences(got, want):
+    """human-readable list of what differs between two results of fingerprints()"""
+    diff = []
+    for label in sorted(set(got) | set(want)):
+        a, b = got.get(label), want.get(label)
+        if a is None or b is None:
+            diff.append('%s: %s' % (label, 'missing' if a is None else 'not in the fixture'))
+            continue
+        for k in ('nbytes', 'bufs', 'buf_sizes', 'packs'):
+            if a[k] != b[k]:
+                diff.append('%s: %s %s, fixture %s' % (label, k, a[k], b[k]))
+        for name in sorted(set(a['lists']) | set(b['lists'])):
+            x, y = a['lists'].get(name), b['lists'].get(name)
+            if x != y:
+                cnt = '' if x is None or y is None else ' names differ: %s' % sorted(
+                    (n, x['names'].get(n, 0), y['names'].get(n, 0)) for n in set(x['names']) | set(y['names']) if x['names'].get(n) != y['names'].get(n))
+                diff.append('%s/%s: launch list differs from the fixture%s' % (label, name, cnt))
+    return diff
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--check', action='store_true')
+    ap.add_argument('--dump')
+    ap.add_argument('--out', default=OUT)
+    ap.add_argument('--only', nargs='*')
+    a = ap.parse_args()
+    if a.dump:
+        os.makedirs(a.dump, exist_ok=True)
+    got = fingerprints(a.only, a.dump)
+    if a.check:
+        with open(a.out) as f:
+            want = json.load(f)
+        if a.only:
+            want = {k: v for k, v in want.items() if k.split('/')[0] in a.only}
+        diff = differences(got, want)
+        print('\n'.join(diff) if diff else 'plan fingerprints equal the fixture (%d plans)' % len(got))
+        return 1 if diff else 0
+    with open(a.out, 'w') as f:
+        json.dump(got, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('wrote %s (%d plans)' % (a.out, len(got)))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
