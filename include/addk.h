@@ -145,9 +145,9 @@ int addk_set_split_min_channels(int c);
  * initial value. */
 #define ADDK_FAST_PW      1   /* register-stationary 1x1 convolution (pw.hip) */
 #define ADDK_FAST_CONV3   2   /* halo-patch 3x3 stride-1 forward / data gradient (conv3.hip; needs wpack) */
-#define ADDK_FAST_WGRAD3  4   /* halo-patch 3x3 stride-1 weight gradient (wgrad.hip) */
+#define ADDK_FAST_WGRAD3  4   /* halo-patch 3x3 stride-1 weight gradient (wgrad_h3.hip) */
 #define ADDK_FAST_DWTILE  8   /* LDS-tiled depthwise forward / backward, tiled logits-upsample backward */
-#define ADDK_FAST_WGRAD_RS 16  /* register-streaming weight gradient of the narrow cell convs (wgrad.hip) */
+#define ADDK_FAST_WGRAD_RS 16  /* register-streaming weight gradient of the narrow cell convs (wgrad_rs.hip, wgrad_hk.hip, wgrad_pix.hip: wgrad_st_kernel) */
 int addk_set_fast_paths(int mask);
 int addk_get_fast_paths(void);
 int addk_get_conv_precision(void);

@@ -1,5 +1,5 @@
-"""GPU tests of the specialised 3x3 kernels (conv3.hip halo-patch forward / data gradient, wgrad.hip halo-patch weight
-gradient) through the C ABI: each launch is compared with an fp64 PyTorch reference of the same operation
+"""GPU tests of the specialised 3x3 kernels (conv3.hip halo-patch forward / data gradient, wgrad_h3.hip / wgrad_hk.hip halo-patch and
+wgrad_rs.hip / wgrad_pix.hip register-streaming weight gradients) through the C ABI: each launch is compared with an fp64 PyTorch reference of the same operation
 (relu(a*x+b) -> conv2d -> batch statistics, and its autograd) and with the generic kernels on identical buffers.
 The whole-network parity tests use maps too small to reach these kernels (they need >= 8192 pixels), so they are pinned
 here.  Tolerance: 2e-5 of the reference's max-abs for fp32 products with fp32 accumulation over K <= 2736.  Shapes cover the wide heads (3x3, dilation 1-18, 64/128-channel column blocks) and

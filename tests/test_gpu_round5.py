@@ -5,7 +5,7 @@
    the real `modeling.ADD` in double precision), relative to the live fp32 oracle's error — the backward of the headline step held to a
    number instead of to the chaos argument;
  * the wide 1x1 weight gradient with 128 output channels (a shape both the split-bf16 head kernel and the register-streaming kernel accept:
-   ADVICE r04, wgrad.hip wg_fill) against fp64, with the launch geometry the chosen kernel expects."""
+   ADVICE r04; wgrad.hip wg_choose / wg_fill, kernel in wgrad_h3.hip) against fp64, with the launch geometry the chosen kernel expects."""
 import ctypes as C
 import os
 

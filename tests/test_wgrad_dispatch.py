@@ -1,13 +1,20 @@
-"""Host-side choice of the weight-gradient kernel (wgrad.hip), no GPU: the library is called with aligned placeholder pointers (nothing is
+"""Host-side choice of the weight-gradient kernel (csrc/wgrad.hip: wg_choose, wg_fill and the dispatch over the kernel families in
+wgrad_pix.hip, wgrad_h3.hip, wgrad_hk.hip and wgrad_rs.hip), no GPU: the library is called with aligned placeholder pointers (nothing is
 dereferenced before a launch).  For every shape x precision mode x fast-path mask: the launch key addk_conv_wgrad_config reports is the one a
 batch of that conv carries, and a workspace of exactly addk_conv_wgrad_ws floats passes the checked batch prepare.  The shapes of the GPU
-kernel tests get the kinds those tests assert."""
+kernel tests get the kinds those tests assert, and every (case, mode) of the bit-for-bit fixture (tests/tools/make_wgrad_bits.py) its launch key."""
 import ctypes as C
+import importlib.util
+import os
 
 import pytest
 
 import addk
 from addk import _lib as L
+
+_spec = importlib.util.spec_from_file_location('make_wgrad_bits', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tools', 'make_wgrad_bits.py'))
+bits = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(bits)
 
 MODES = {'fp32': 0, 'f16x3': 1, 'bf16x6': 2, 'tail_x3': 3}
 PTR = {'dy': 0x10000000, 'x': 0x20000000, 'a': 0x30000000, 'b': 0x30001000, 'dw': 0x40000000, 'ws': 0x50000000}      # 16-byte aligned
@@ -114,3 +121,23 @@ def test_halo_shapes_get_halo_kinds(lib, mode):
                 assert (kind == 5) == bool(fast & 4), (shape[0], fast, kind)
             elif Ci >= 16 and Cout <= 160 and d <= 2:
                 assert (kind == 7) == bool(fast & 16), (shape[0], fast, kind)
+
+
+def test_bit_fixture_cases_get_their_launch_keys(lib):
+    """Every (case, mode) of tests/tools/make_wgrad_bits.CASES gets the (kind, cty, ctz) it lists, and between them the cases reach every
+    kernel family, NT and NG in {1, 2} of the halo kernels in both split modes (NP = 2 and 3), the three tap / tile forms of the cells'
+    halo kernels, the four lane layouts of the register-streaming kernel, and kind 9 in the split modes only."""
+    seen = set()
+    for case in bits.CASES:
+        lib.addk_set_fast_paths(case[2])
+        for mode, key in case[5].items():
+            L.check(lib.addk_set_conv_precision(bits.MODES[mode]), 'set_conv_precision')
+            wa = bits.wgrad_args(L, case, PTR)
+            assert tuple(_config(lib, wa)[:3]) == key, (case[0], mode)
+            seen.add((mode,) + key)
+        assert set(case[5]) == set(bits.MODES) or case[5][next(iter(case[5]))][0] == 9, case[0]
+    want = {(m, 0, 2, 1) for m in bits.MODES} | {(m, 0, 3, 3) for m in bits.MODES} | {(m, k, t, u) for m in bits.MODES for k, t, u in ((1, 8, 4), (2, 6, 6), (3, 4, 4), (8, 4, 2))}
+    want |= {('fp32', 5, 4, 1), ('fp32', 5, 8, 1)} | {(m, 5, t, g) for m in ('f16x3', 'bf16x6') for t in (4, 8) for g in (1, 2)}
+    want |= {(m, 9, 8, 4) for m in ('f16x3', 'bf16x6')}
+    want |= {(m, 7, t, k) for m in bits.MODES for t, k in ((3, 3), (3, 5), (5, 3))} | {(m, 6, la, lb) for m in bits.MODES for la in (3, 4) for lb in (3, 4)}
+    assert want <= seen, sorted(want - seen)
