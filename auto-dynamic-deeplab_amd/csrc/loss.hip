@@ -306,6 +306,128 @@ bool ceu_ok(int N, int H, int W, int OH, int OW, int C) {
   return true;
 }
 
+// ---- fused logits up-sampling + scoring of a validation pass (decoder.py:28 + train.py:268-285) --------------------------
+// Confusion matrix, loss and entropy of one exit from the low-resolution NHWC logits, as a GATHER: a wave owns 64 consecutive
+// columns X of the high-resolution grid and walks SCU_R rows; a thread keeps the two W-interpolated rows t0 = lw0*v(h0,w0) +
+// lw1*v(h0,w1), t1 = (same on h1) of its column in registers and reloads them only when the (wave-uniform) pair (h0, h1)
+// changes, so at the x8 of config 2 the four neighbours are read once per 8 pixels and a pixel costs 19 x 3 flops of
+// interpolation — z = lh0*t0 + lh1*t1 is the expression of resize_fwd_nchw_kernel / ce_up_kernel, operation for operation.
+// One max/arg-max sweep, one exp sweep (Σe, Σe·d) serves loss and entropy.  HBM traffic: the target (coalesced 512 B per wave
+// row) and the optional uint8 map; the logits (5 MB at config 2) stay in L2.  Counts go to a 361-entry LDS histogram (a thread
+// merges the run of equal (gt, pred) keys of its column first), flushed once per workgroup with 64-bit integer atomics:
+// order-independent, exact.  Loss and entropy leave the workgroup as two partials reduced in a fixed order.
+constexpr int SCU_W = 64, SCU_WAVES = 4, SCU_R = 8;      // tile: 64 columns x (4 waves x 8 rows)
+
+struct ScoreUpK {
+  const float* x; int ld; int N, H, W, OH, OW;
+  const int64_t* target; const float* cw; int ignore;
+  unsigned long long* cm; uint8_t* pred;
+  float* ws; int nblk;
+};
+
+// VEC: 16-byte loads of a pixel's CP channels (host check: ld % 4 == 0, ld >= CP, aligned base); a compile-time switch, so that no
+// register array crosses a branch merge (the run-time form of ce_up_kernel keeps 40 bytes of scratch per lane for it)
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) score_up_kernel(const ScoreUpK p) {
+  constexpr int CP = (CC + 3) / 4 * 4;
+  __shared__ unsigned hist[CC * CC];
+  __shared__ float shs[4];
+  const int t = threadIdx.x, lane = t & (SCU_W - 1), wv = t / SCU_W;
+  for (int i = t; i < CC * CC; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const int X = blockIdx.x * SCU_W + lane, n = blockIdx.z;
+  const int ybeg = (blockIdx.y * SCU_WAVES + wv) * SCU_R;
+  const int yend = ybeg + SCU_R < p.OH ? ybeg + SCU_R : p.OH;
+  const float sh = (float)p.H / (float)p.OH, sw = (float)p.W / (float)p.OW;
+  const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
+  const gfloat* cw = (const gfloat*)p.cw;
+  auto load_px = [](const float* q, float (&v)[CP]) {
+    if constexpr (VEC) {
+#pragma unroll
+      for (int c = 0; c < CP; c += 4) { const float4 f = ld4(q + c); v[c] = f.x; v[c + 1] = f.y; v[c + 2] = f.z; v[c + 3] = f.w; }
+    } else {
+#pragma unroll
+      for (int c = 0; c < CC; ++c) v[c] = ((const gfloat*)q)[c];
+    }
+  };
+  float lsum = 0.f, esum = 0.f;
+  if (X < p.OW) {
+    int w0, w1; float lw0, lw1;
+    ce_src_index(X, sw, p.W, w0, w1, lw0, lw1);
+    float t0[CC], t1[CC];
+    int ph0 = -1, ph1 = -1;
+    int key = -1; unsigned run = 0;                              // pending (gt, pred) run of this column
+    for (int Y = ybeg; Y < yend; ++Y) {
+      int h0, h1; float lh0, lh1;
+      ce_src_index(Y, sh, p.H, h0, h1, lh0, lh1);
+      if (h0 != ph0 || h1 != ph1) {                              // wave-uniform: Y is
+        const float* r0 = p.x + ((long)(n * p.H + h0) * p.W) * p.ld;
+        const float* r1 = p.x + ((long)(n * p.H + h1) * p.W) * p.ld;
+        float a[CP], b[CP];
+        load_px(r0 + (long)w0 * p.ld, a); load_px(r0 + (long)w1 * p.ld, b);
+#pragma unroll
+        for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
+        load_px(r1 + (long)w0 * p.ld, a); load_px(r1 + (long)w1 * p.ld, b);
+#pragma unroll
+        for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
+        ph0 = h0; ph1 = h1;
+      }
+      const long pix = ((long)n * p.OH + Y) * p.OW + X;
+      const long tg = tgt[pix];
+      const bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+      float z[CC];
+      float mx = -INFINITY, zt = 0.f; int am = 0;
+#pragma unroll
+      for (int c = 0; c < CC; ++c) {
+        z[c] = lh0 * t0[c] + lh1 * t1[c];
+        if (z[c] > mx) { mx = z[c]; am = c; }                    // strict: a tie keeps the lowest channel
+        if (c == tg) zt = z[c];
+      }
+      float se = 0.f, sx = 0.f;
+#pragma unroll
+      for (int c = 0; c < CC; ++c) { const float d = z[c] - mx; const float e = __expf(d); se += e; sx += e * d; }
+      const float lse = logf(se);
+      if (valid) lsum += (cw ? cw[tg] : 1.f) * (lse + mx - zt);
+      esum += lse - sx / se;
+      if (p.pred) p.pred[pix] = (uint8_t)am;
+      const int k = (tg >= 0 && tg < CC) ? (int)tg * CC + am : -1;   // the evaluator's mask: labels in [0, C), whatever ignore_index is
+      if (k != key) {
+        if (key >= 0) atomicAdd(&hist[key], run);
+        key = k; run = 0;
+      }
+      ++run;
+    }
+    if (key >= 0) atomicAdd(&hist[key], run);
+  }
+  lsum = block_sum(lsum, shs);
+  esum = block_sum(esum, shs);
+  const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (t == 0) { ((gfloat*)p.ws)[blk] = lsum; ((gfloat*)p.ws)[p.nblk + blk] = esum; }
+  __syncthreads();
+  for (int i = t; i < CC * CC; i += 256) {
+    const unsigned v = hist[i];
+    if (v) atomicAdd(&p.cm[i], (unsigned long long)v);
+  }
+}
+
+// second stage of score_up_kernel: block 0 finishes the loss (scale / wsum), block 1 the entropy, each in a fixed order
+__global__ void __launch_bounds__(256) score_sum_kernel(const float* ws, int n, float scale, const float* wsum, float* loss_out, float* ent_out) {
+  __shared__ float sh[4];
+  const float* w = ws + (long)blockIdx.x * n;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += w[i];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) {
+    if (blockIdx.x == 0) *loss_out += s * scale / *wsum;
+    else *ent_out += s;
+  }
+}
+
+bool scu_ok(int N, int H, int W, int OH, int OW, int C) {
+  if (C != 19 || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return false;
+  return N <= 65535 && cdiv(OH, SCU_WAVES * SCU_R) <= 65535 && (long)N * cdiv(OH, SCU_WAVES * SCU_R) * cdiv(OW, SCU_W) < (1L << 30);
+}
+
 int ce_blocks(long total) { long b = cdiv(total, 256 * 4); if (b < 1) b = 1; if (b > 1024) b = 1024; return (int)b; }
 
 }  // namespace
@@ -362,6 +484,33 @@ extern "C" int addk_ce_upsample_fwd_bwd(const addk_ce_upsample_args* a, void* st
   if (rc) return rc;
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, a->ws, (int)(grid.x * grid.y * grid.z), a->scale, a->wsum, a->loss_out, 1);
   return addk_check_launch("ce_upsample_sum");
+}
+
+extern "C" int addk_score_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return scu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_score_upsample_ws_floats(int32_t N, int32_t OH, int32_t OW) {
+  return 2 * (int64_t)N * cdiv(OH, SCU_WAVES * SCU_R) * cdiv(OW, SCU_W);
+}
+extern "C" int addk_score_upsample(const addk_score_upsample_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->target && a->wsum && a->loss_out && a->ent_out && a->cm && a->ws, "score_upsample: null pointer");
+  ADDK_REQUIRE(a->ld >= a->C, "score_upsample: short stride");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "score_upsample: unsupported shape (19 classes)");
+  const dim3 grid(cdiv(a->OW, SCU_W), cdiv(a->OH, SCU_WAVES * SCU_R), a->N);
+  ScoreUpK k;
+  k.x = a->logits; k.ld = a->ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
+  k.target = a->target; k.cw = a->class_w; k.ignore = a->ignore_index;
+  k.cm = reinterpret_cast<unsigned long long*>(a->cm); k.pred = a->pred_out;
+  k.ws = a->ws; k.nblk = (int)(grid.x * grid.y * grid.z);
+  hipStream_t st = (hipStream_t)stream;
+  if (a->ld % 4 == 0 && a->ld >= 20 && aligned16(a->logits))
+    hipLaunchKernelGGL((score_up_kernel<19, true>), grid, dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL((score_up_kernel<19, false>), grid, dim3(256), 0, st, k);
+  int rc = addk_check_launch("score_upsample");
+  if (rc) return rc;
+  hipLaunchKernelGGL(score_sum_kernel, dim3(2), dim3(256), 0, st, a->ws, k.nblk, a->scale, a->wsum, a->loss_out, a->ent_out);
+  return addk_check_launch("score_upsample_sum");
 }
 
 extern "C" int addk_entropy_sum(const float* logits, int32_t N, int32_t C, int64_t HW, float* out1, float* ws, void* stream) {

@@ -17,6 +17,13 @@ def argmax_logits(logits):
     return out
 
 
+def mean_iou(cm):
+    """utils/metrics.py:24-30 on a confusion matrix, as a 0-dim tensor on the matrix's device (no host sync)."""
+    cm = cm.float()
+    d = torch.diag(cm)
+    return Evaluator.torch_nanmean(d / (cm.sum(dim=1) + cm.sum(dim=0) - d))
+
+
 class Evaluator(object):
     def __init__(self, num_class, device='cuda'):
         self.num_class = num_class
@@ -33,6 +40,11 @@ class Evaluator(object):
         pr = pre_image.to(self._cm.device).long().contiguous()
         L.check(lib.addk_confusion(gt.data_ptr(), pr.data_ptr(), gt.numel(), self.num_class, self._cm.data_ptr(),
                                    _plan.current_stream()), 'confusion')
+
+    def add_confusion(self, cm):
+        """Add a [num_class, num_class] int64 matrix counted elsewhere on the device (validate.ValidationStep.result())."""
+        assert tuple(cm.shape) == tuple(self._cm.shape) and cm.dtype == torch.int64
+        self._cm.add_(cm.to(self._cm.device))
 
     def reset(self):
         self._cm.zero_()
@@ -51,9 +63,7 @@ class Evaluator(object):
         return self.torch_nanmean(torch.diag(cm) / cm.sum(dim=1))
 
     def Mean_Intersection_over_Union(self):
-        cm = self.confusion_matrix
-        d = torch.diag(cm)
-        return self.torch_nanmean(d / (cm.sum(dim=1) + cm.sum(dim=0) - d)).item()
+        return mean_iou(self._cm).item()
 
     def Frequency_Weighted_Intersection_over_Union(self):
         cm = self.confusion_matrix

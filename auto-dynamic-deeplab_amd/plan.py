@@ -372,6 +372,8 @@ class Graph:
         self.pgrad_views = None       # param -> view of a flat gradient buffer to use as its gradient (train.TrainStep)
         self.reorder = False          # level-order and batch the lists although this is not a training plan (set before finalize)
         self.fuse_ce = False          # logits outputs feed the fused up-sampling + cross-entropy launch (train.TrainStep)
+        self.fuse_score = False       # logits outputs of an inference plan feed the fused up-sampling + scoring launch (validate.ValidationStep)
+        self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted (fuse_score)
         self.pginit = set()
         self._pcols = {}
         self.params = []              # ordered unique params touched
@@ -442,6 +444,9 @@ class Graph:
     def finalize(self, nstreams=1):
         """Emit the backward list (reverse op order), schedule both lists on `nstreams` streams and allocate one wgrad
         scratch per stream (launches of one stream are ordered, so they can share it)."""
+        for em in self._fwd_late:
+            em()
+        self._fwd_late = []
         for em in reversed(self._bwd_emitters):
             em()
         self._bwd_emitters = []
@@ -1302,6 +1307,8 @@ class Graph:
                           rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
             self._bwd_emitters.append(emit_ce)
             return out
+        if self.fuse_score and not self.want_grad:
+            return self._score_head(src, OH, OW)
         y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=self.device)
         self.nbytes += y.numel() * 4
         ar = L.ResizeArgs()
@@ -1327,6 +1334,64 @@ class Graph:
                 out.bwd_args = ba
                 self._add(self.bwd, 'resize_nchw_bwd', lib.addk_resize_bwd, C.byref(ba), rd=self.lz(src), wr=[gs])
             self._bwd_emitters.append(emit_bwd)
+        return out
+
+    def _score_head(self, src, OH, OW):
+        """Logits output of a validation plan (`self.fuse_score`, set by validate.ValidationStep): nobody reads the full-resolution
+        logits, so no resize is emitted and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `score` slot the step
+        binds (target, class weights, wsum and the per-exit loss / entropy / confusion / prediction tensors); finalize() then appends
+        ONE `score_upsample` launch per exit to the forward list (`addk_score_upsample`).  Where the library does not take the shape
+        (`addk_score_upsample_supported` == 0, e.g. C != 19) the same quantities come from the stand-alone kernels inside this plan:
+        resize + ce_fwd_bwd without a gradient + argmax_nchw + confusion + entropy_sum."""
+        lib = self.lib
+        N, H, W, Cc = src.N, src.H, src.W, src.C
+        out = OutRef(None)
+        out.fused_score, out.shape, out.score = True, (N, Cc, OH, OW), None
+        tag = self.tag
+
+        def emit_score():
+            sc = out.score
+            assert sc is not None, 'fused logits output without a score binding'
+            first = len(self.fwd)
+            tgt, wsum, loss, ent, cm, pred = sc['target'], sc['wsum'], sc['loss'], sc['entropy'], sc['confusion'], sc.get('pred')
+            if lib.addk_score_upsample_supported(N, H, W, OH, OW, Cc) == 1:
+                a = L.ScoreUpsampleArgs()
+                s = self.src(src)
+                a.logits, a.ld = s.x, s.ld
+                a.N, a.H, a.W, a.C, a.OH, a.OW = N, H, W, Cc, OH, OW
+                a.target, a.class_w, a.ignore_index = tgt.data_ptr(), sc['class_w'], sc['ignore_index']
+                a.wsum, a.scale = wsum.data_ptr(), sc['scale']
+                a.loss_out, a.ent_out, a.cm = loss.data_ptr(), ent.data_ptr(), cm.data_ptr()
+                a.pred_out = pred.data_ptr() if pred is not None else None
+                ws = torch.zeros(int(lib.addk_score_upsample_ws_floats(N, OH, OW)), dtype=torch.float32, device=self.device)
+                a.ws = ws.data_ptr()
+                self.keep += [a, ws]
+                self._add(self.fwd, 'score_upsample', lib.addk_score_upsample, C.byref(a),
+                          rd=self.lz(src) + [tgt, wsum], wr=[loss, ent, cm, pred, ws])
+            else:
+                y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=self.device)
+                am = torch.empty((N, OH, OW), dtype=torch.int64, device=self.device)
+                ws = torch.zeros(int(lib.addk_ce_ws_floats(N, OH * OW)), dtype=torch.float32, device=self.device)
+                self.nbytes += y.numel() * 4 + am.numel() * 8
+                ar = L.ResizeArgs()
+                ar.src = self.src(src)
+                ar.N, ar.H, ar.W, ar.OH, ar.OW = N, H, W, OH, OW
+                ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
+                self.keep += [ar, y, am, ws]
+                self._add(self.fwd, 'resize_nchw', lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])
+                self._add(self.fwd, 'ce_fwd_bwd', lib.addk_ce_fwd_bwd, y.data_ptr(), tgt.data_ptr(), N, Cc, OH * OW, sc['class_w'],
+                          sc['ignore_index'], wsum.data_ptr(), sc['scale'], loss.data_ptr(), None, ws.data_ptr(),
+                          rd=[y, tgt, wsum], wr=[loss, ws])
+                self._add(self.fwd, 'argmax_nchw', lib.addk_argmax_nchw, y.data_ptr(), N, Cc, OH * OW, am.data_ptr(), rd=[y], wr=[am])
+                self._add(self.fwd, 'confusion', lib.addk_confusion, tgt.data_ptr(), am.data_ptr(), N * OH * OW, Cc, cm.data_ptr(),
+                          rd=[tgt, am], wr=[cm])
+                # addk_entropy_sum overwrites its output: the step zeroes `ent` before every pass, which makes that the same thing
+                self._add(self.fwd, 'entropy_sum', lib.addk_entropy_sum, y.data_ptr(), N, Cc, OH * OW, ent.data_ptr(), ws.data_ptr(),
+                          rd=[y], wr=[ent, ws])
+                sc['pred_i64'] = am                    # the map of this path is int64: ValidationStep.predictions() narrows it
+            for c in self.fwd[first:]:
+                c.tag = tag
+        self._fwd_late.append(emit_score)
         return out
 
     def gap(self, src, relu_in=False):
@@ -1476,6 +1541,7 @@ class OutRef:
         self.dy_ptr, self.dy_scale, self.dynamic = None, None, True
         self.bwd_args = None     # ResizeBwdArgs (logits path)
         self.fused_ce = False    # logits consumed by the fused up-sampling + cross-entropy launch (train.TrainStep): y is None
+        self.fused_score = False  # logits consumed by the scoring launch of a validation plan (validate.ValidationStep): y is None
         self.bwd_cmd = None      # generic nhwc path
 
     def set_grad(self, gy):

@@ -507,6 +507,35 @@ int addk_ce_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int3
 int64_t addk_ce_upsample_ws_floats(int32_t N, int32_t H, int32_t W);
 int addk_ce_upsample_fwd_bwd(const addk_ce_upsample_args* a, void* stream);
 
+/* Scoring head of a validation pass (train.py:250-322, eval.py:165-193): what the evaluator, the criterion and the entropy
+ * meter need of one exit, in ONE pass over the high-resolution pixel grid, straight from the LOW-resolution NHWC logits
+ * [N,H,W,C] (bilinear, align_corners=False, the arithmetic of addk_resize_fwd bit for bit) — the [N,C,OH,OW] tensor is never
+ * materialised:
+ *   cm[gt*C + pred] += 1          int64 [C,C]; pred = arg-max over channels (ties: lowest channel); labels outside [0,C) skipped
+ *   loss_out[0]     += scale * sum_valid w[t]*nll / wsum          (definition of addk_ce_upsample_fwd_bwd)
+ *   ent_out[0]      += sum_pixels (log sum e - sum e*d / sum e)   (un-normalised, as addk_entropy_sum)
+ *   pred_out[n,y,x]  = pred       uint8 [N,OH,OW], optional (NULL: not written)
+ * Deterministic: integer atomics for the matrix, fixed-order two-stage sums for the two scalars.  It is a gather (one thread
+ * per high-resolution pixel), so the 16-rows-per-input-row limit of addk_ce_upsample_supported does NOT apply here:
+ * addk_score_upsample_supported() is 0 only for C != 19, non-positive sizes or a grid beyond 65535 x 32 rows / 65535 images. */
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
+  int32_t N, H, W, C, OH, OW;
+  const int64_t* target;             /* [N,OH,OW] */
+  const float* class_w;              /* [C] or NULL */
+  int32_t ignore_index;
+  const float* wsum;                 /* device scalar from addk_ce_count */
+  float scale;
+  float* loss_out;                   /* device scalar, accumulated */
+  float* ent_out;                    /* device scalar, accumulated */
+  int64_t* cm;                       /* [C,C], accumulated */
+  uint8_t* pred_out;                 /* [N,OH,OW] or NULL */
+  float* ws;                         /* addk_score_upsample_ws_floats() floats */
+} addk_score_upsample_args;
+int addk_score_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+int64_t addk_score_upsample_ws_floats(int32_t N, int32_t OH, int32_t OW);
+int addk_score_upsample(const addk_score_upsample_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Fused SGD (torch.optim.SGD(momentum, weight_decay, nesterov), train.py:126) on a flat buffer.
  *   d = g*gscale + wd*p;  buf = first ? d : mom*buf + d;  p -= lr*(nesterov ? d + mom*buf : buf)
