@@ -1,5 +1,6 @@
-// Pointwise (1x1, stride 1) convolution with register-stationary weights — the pointwise halves of SepConv and the
-// 40/80/160-channel glue convs, forward and data gradient.  These launches are far too small to amortise the LDS
+// Pointwise (1x1, stride 1) convolution with register-stationary weights — the 40/80/160-channel 1x1 convs of the cell
+// body, forward and data gradient (a SepConv half fused with its depthwise conv is sepf.hip / sepb.hip, not this file).
+// Further down: the streaming-K 1x1 (pwk_kernel), stem0 and the classifier's data gradient (k1s_dgrad_kernel).  These launches are far too small to amortise the LDS
 // staging + two barriers per 32-channel chunk of the general implicit-GEMM kernel (measured: 25-30 us each against an
 // HBM-ideal 5-10 us).  Here there is NO LDS and NO barrier in the main loop:
 //   * a wave keeps its whole weight panel as MFMA A-fragments in registers (K <= 160, <= 3 column tiles of 16),
@@ -28,14 +29,11 @@ struct PwK {
   addk_src dst; int accumulate;          // dgrad epilogue
   int P; int ntiles16; int rows;       // rows: slab rows the caller allocated (>= gx; the extra rows are zero-filled)
   int gx, gy;                          // grid of this launch (a batched launch runs several descriptors on one larger grid)
-  // fused SepConv half (SEP = 3 / 5): depthwise K x K in front of the pointwise conv, computed while the B fragment is built
-  const float* dww; int H, W;          // depthwise weights [C][K*K]; image geometry (stride 1, dilation 1, pad K/2)
-  float* t; int ldt;                   // optional copy of the depthwise output (training: the backward pass reads it)
-  const float* ea; const float* eb;    // inference epilogue: y = ea*acc + eb + sum of terms
-  int nterm; addk_src term[ADDK_MAX_TERMS];
   // RS (forward only): src.x is an [N, RH, RW] map sampled bilinearly onto this launch's [N, H, W] pixel grid (addk_src.rs_hw);
   // rs_y: optional materialised copy of the interpolated input (training: the backward pass reads it)
-  int RH, RW; float* rs_y; int rs_ldy;
+  // gap0 / gap1 are never read: they keep (gx, gy), (H, W) and (RH, RW, rs_y) in separate scalar loads, as in the builds every
+  // measurement of this file was taken on — next to each other the loads merge and the RS kernels' registers move (profiles/pw_epilogue_isa.txt)
+  const void* gap0; int H, W; const void* gap1; int RH, RW; float* rs_y; int rs_ldy;
 };
 
 // These launches are latency chains (kernel arguments -> weight panel -> one or two pixel tiles -> store -> statistics)
@@ -43,16 +41,12 @@ struct PwK {
 // is kept under 128 (KG=3) / 168 (KG=5) registers for 4 / 3 waves per SIMD: no prefetch buffer (occupancy hides the
 // latency) and, for maps of >= 4096 pixels, per-lane statistics in fp32 (a lane sums at most a handful of values; the
 // cross-lane / cross-wave / cross-block sums stay fp64).
-// SEP > 0 (forward only): the B operand is not x but depthwise_SEPxSEP(relu?(a*x+b)) — every lane builds its fragment
-// (pixel li, channels 16g + 4kq + {0..3}) from the SEP*SEP neighbouring pixels, all loads unconditional and independent (L1/L2 hits:
-// neighbouring lanes share them), zero padding after the prologue as in the reference; tap weights sit in LDS as [tap][channel].
-// No barrier in the main loop and no round trip of the depthwise output through HBM (operations.py:51-53: ReLU, dw, pw in one launch).
 // RS: the B operand is the bilinear interpolation (align_corners = False) of a map of another size, taken while the fragment is loaded —
 // four 16-byte loads per channel group instead of one (neighbouring lanes share them: L1 / L2 hits), the resize.hip expressions
 // (common.h: src_index, lerp4) in the same order, so the result is bit-identical to addk_resize_fwd followed by the plain launch
 // (ADD.py:76-77,84-90: F.interpolate in front of `preprocess` / `pre_preprocess`; the resized tensor is never written at inference).
-template <int CT, int KG, int MODE, bool RED32, int SEP = 0, bool RS = false>     // CT column tiles of 16, KG groups of 16 reduction channels
-__device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2], const float* dwl = nullptr, float* patch = nullptr, const float* abl = nullptr) {
+template <int CT, int KG, int MODE, bool RED32, bool RS = false>     // CT column tiles of 16, KG groups of 16 reduction channels
+__device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2]) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int li = lane & 15, kq = lane >> 4;
   const int n0 = blockIdx.y * (CT * 16);
@@ -80,7 +74,7 @@ __device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2],
         wf[i][g] = v;
       }
   };
-  if (!SEP) load_panel();        // fused form: the panel is fetched after the depthwise phase (its registers are needed there)
+  load_panel();
   // lazy prologue coefficients of this lane's k slots
   const bool relu = p.src.relu != 0;
   const bool pro = relu || p.src.a != nullptr;
@@ -140,82 +134,10 @@ __device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2],
       x[g] = v;
     }
   };
-  // Fused SepConv half, LDS-tiled: the block owns 64 consecutive pixels of one image row; it stages the haloed input patch
-  // [SEP rows][64 + SEP - 1 px][channels] once (all loads independent, BatchNorm/ReLU applied on the way in, zero padding
-  // after it), and every lane then builds its B fragment — the depthwise output of (pixel 16 wave + li, channels 16g + 4kq ..)
-  // — from SEP*SEP 16-byte LDS reads per group.  The pixel stride KP = 16 KG + 4 floats makes the 16 pixel lanes of a
-  // fragment read hit 16 distinct 4-bank groups (52 and 84 are = 4 * odd mod 64).
-  constexpr int SEPX = SEP ? SEP : 1, PWX = 64 + SEPX - 1, KP = KG * 16 + 4, KQ = KG * 4;
-  constexpr int NSLOT = (SEPX * PWX * KQ + 255) / 256;
-  auto stage_patch = [&](int n, int oh, int ow0) {
-    constexpr int HK = SEPX / 2;
-    constexpr int NB = 8;                                               // independent loads per thread in flight
-#pragma unroll 1
-    for (int b0 = 0; b0 < NSLOT; b0 += NB) {
-      float4 rv[NB];
-      unsigned okm = 0;
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int slot = t + 256 * (b0 + u);
-        const int r = slot / (PWX * KQ), rem = slot - r * (PWX * KQ), px = rem / KQ, q = rem - px * KQ;
-        const int ih = oh - HK + r, iw = ow0 - HK + px;
-        const bool ok = b0 + u < NSLOT && r < SEPX && 4 * q < p.K && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-        okm |= (ok ? 1u : 0u) << u;
-        rv[u] = ld4(p.src.x + (ok ? ((long)(n * p.H + ih) * p.W + iw) * p.src.ld + 4 * q : 0));
-      }
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const int slot = t + 256 * (b0 + u);
-        const int r = slot / (PWX * KQ), rem = slot - r * (PWX * KQ), px = rem / KQ, q = rem - px * KQ;
-        float4 v = rv[u];
-        if (pro) {
-          const float4 av = lds_ld4(abl + 4 * q), bv = lds_ld4(abl + KG * 16 + 4 * q);
-          v.x = fmaf(av.x, v.x, bv.x); v.y = fmaf(av.y, v.y, bv.y); v.z = fmaf(av.z, v.z, bv.z); v.w = fmaf(av.w, v.w, bv.w);
-          if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        }
-        const bool ok = (okm >> u) & 1u;
-        v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-        if (b0 + u < NSLOT && r < SEPX) lds_st4(patch + (r * PWX + px) * KP + 4 * q, v);
-      }
-    }
-  };
-  auto dw_from_patch = [&](float4 (&x)[KG]) {
-    const float* pb0 = patch + (16 * wave + li) * KP + 4 * kq;
-#pragma unroll
-    for (int g = 0; g < KG; ++g) x[g] = zero4();
-#pragma unroll
-    for (int kh = 0; kh < SEPX; ++kh)
-#pragma unroll
-      for (int kw = 0; kw < SEPX; ++kw)
-#pragma unroll
-        for (int g = 0; g < KG; ++g) {
-          const float4 v = lds_ld4(pb0 + (kh * PWX + kw) * KP + 16 * g);
-          const float4 w4 = lds_ld4(dwl + (kh * SEPX + kw) * (KG * 16) + 16 * g + 4 * kq);
-          x[g].x = fmaf(w4.x, v.x, x[g].x); x[g].y = fmaf(w4.y, v.y, x[g].y); x[g].z = fmaf(w4.z, v.z, x[g].z); x[g].w = fmaf(w4.w, v.w, x[g].w);
-        }
-  };
-  const int spr = SEP ? (p.W + 63) / 64 : 1;
-  for (int tile = SEP ? (int)blockIdx.x : blockIdx.x * 4 + wave; tile < p.ntiles16; tile += SEP ? p.gx : wstride) {
-    int pp; bool pin;
-    if (SEP) {            // tile = row segment (n, oh, 64 px): block-wide staging, then per-wave fragments
-      const int rowid = tile / spr, sx = tile - rowid * spr;
-      const int n = rowid / p.H, oh = rowid - n * p.H, ow = sx * 64 + 16 * wave + li;
-      if (tile != (int)blockIdx.x) __syncthreads();          // every wave is done with the previous segment's patch
-      if (KG <= 3 && tile == (int)blockIdx.x) load_panel();  // in the same round trip as the patch
-      stage_patch(n, oh, sx * 64);
-      __syncthreads();
-      dw_from_patch(xf);
-      pin = ow < p.W;
-      pp = rowid * p.W + ow;
-      if (p.t && pin) {
-#pragma unroll
-        for (int g = 0; g < KG; ++g) { const int k = 16 * g + 4 * kq; if (k < p.K) st4(p.t + (long)pp * p.ldt + k, xf[g]); }
-      }
-    } else {
-      load_tile(tile, xf);
-      pp = tile * 16 + li;
-      pin = pp < p.P;
-    }
+  for (int tile = blockIdx.x * 4 + wave; tile < p.ntiles16; tile += wstride) {
+    load_tile(tile, xf);
+    const int pp = tile * 16 + li;
+    const bool pin = pp < p.P;
     // [r4] data gradient: the epilogue's operands (the forward input for the ReLU mask and the (dA, dB) sums, the gradient to
     // accumulate into) do not depend on the matrix product — they are requested with the tile, not after it: one dependent
     // round trip per tile instead of two or three (these launches are latency chains: 2 TB/s of their algorithmic bytes before)
@@ -230,7 +152,7 @@ __device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2],
         if (p.accumulate) dop[i] = ld4g(p.y + (pin ? (long)pp * p.ldy + c : 0), nrem, true);
       }
     }
-    if (pro && !SEP) {
+    if (pro) {
 #pragma unroll
       for (int g = 0; g < KG; ++g) {
         float4 v = xf[g];
@@ -246,21 +168,11 @@ __device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2],
     for (int i = 0; i < CT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int g = 0; g < KG; ++g) {
-      if (SEP && KG > 3) {          // wide fused form: the weight fragments of one group at a time (L1 hits), not the whole 25-quad panel
-#pragma unroll
-        for (int i = 0; i < CT; ++i) {
-          const int n = n0 + i * 16 + li, k = 16 * g + 4 * kq;
-          const bool ok = n < p.Cn && k < p.K;
-          float4 v = ld4(ok ? p.w + (long)n * p.ldw + p.w_off + k : p.w);
-          v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-          wf[i][0] = v;
-        }
-      }
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int i = 0; i < CT; ++i)
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(get4(wf[i][(SEP && KG > 3) ? 0 : g], e), get4(xf[g], e), acc[i], 0, 0, 0);
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(get4(wf[i][g], e), get4(xf[g], e), acc[i], 0, 0, 0);
     }
     // ---- epilogue: lane holds channels n0 + i*16 + kq*4 + {0..3} of pixel pp ----
     if (pin) {
@@ -272,17 +184,6 @@ __device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2],
         float4 v = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
         if (MODE == PW_FWD) {
           if (p.bias) { float4 b = ld4g(p.bias + c, nrem, false); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-          if (SEP) {            // inference epilogue: own frozen BatchNorm, then the other branches of the cell block
-            if (p.ea) {
-              const float4 ea = ld4g(p.ea + c, nrem, true), eb = ld4g(p.eb + c, nrem, true);
-              v.x = fmaf(ea.x, v.x, eb.x); v.y = fmaf(ea.y, v.y, eb.y); v.z = fmaf(ea.z, v.z, eb.z); v.w = fmaf(ea.w, v.w, eb.w);
-            }
-            for (int ti = 0; ti < p.nterm; ++ti) {
-              const addk_src& T = p.term[ti];
-              const float4 u = prologue4(ld4g(T.x + (long)pp * T.ld + c, nrem, true), T.a, T.b, c, nrem, T.relu != 0, true);
-              v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-            }
-          }
           st4g(p.y + (long)pp * p.ldy + c, v, nrem, true);
           if (p.slab) {
 #pragma unroll
@@ -334,7 +235,7 @@ __device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2],
 template <int CT, int KG, int MODE, bool RED32, bool RS = false>
 __global__ void __launch_bounds__(256, (KG <= 3 && !RS && MODE == PW_FWD ? 4 : 3)) pw_kernel(const PwK p) {
   __shared__ double red[4][CT * 16][2];
-  pw_body<CT, KG, MODE, RED32, 0, RS>(p, red);
+  pw_body<CT, KG, MODE, RED32, RS>(p, red);
 }
 // several independent pointwise convs of one dependency level in ONE launch: block (x, y, z) runs descriptor z
 template <int CT, int KG, int MODE, bool RED32, bool RS = false>
@@ -342,7 +243,7 @@ __global__ void __launch_bounds__(256, (KG <= 3 && !RS && MODE == PW_FWD ? 4 : 3
   __shared__ double red[4][CT * 16][2];
   const PwK p = tab[blockIdx.z];
   if ((int)blockIdx.x >= p.gx || (int)blockIdx.y >= p.gy) return;
-  pw_body<CT, KG, MODE, RED32, 0, RS>(p, red);
+  pw_body<CT, KG, MODE, RED32, RS>(p, red);
 }
 
 // Streaming-K pointwise forward for the 1x1 convs the register-stationary kernel does not take: many input channels
@@ -517,41 +418,51 @@ static bool pw_config(PwK& k, int rows, PwCfg& c) {
   return true;
 }
 
-template <int MODE>
-int pw_launch(const ConvChoice& c, const PwK& k, hipStream_t st) {
-  const int ct = c.v[0], kg = c.v[1], rs = c.v[2], red32 = c.v[3];
-  dim3 grid(c.gx, c.gy);          // (round 1 measured far fewer, fatter workgroups slower, 14 -> 36 us: the grid keeps >= ~500 workgroups on the large maps)
+// one variant, as a lone launch (one) or as a batch (tab: block z runs descriptor z)
+template <int CT, int KG, int MODE, bool RED32, bool RS>
+int pw_go(dim3 grid, hipStream_t st, const PwK* one, const PwK* tab) {
+  if (tab) hipLaunchKernelGGL((pw_batch_kernel<CT, KG, MODE, RED32, RS>), grid, dim3(256), 0, st, tab);
+  else hipLaunchKernelGGL((pw_kernel<CT, KG, MODE, RED32, RS>), grid, dim3(256), 0, st, *one);
+  return addk_check_launch(tab ? "pw_conv_batch" : "pw_conv");
+}
+// the (CT, KG) x mode x RS x red32 table; RS is a forward form only
+// (round 1 measured far fewer, fatter workgroups slower, 14 -> 36 us: the grid keeps >= ~500 workgroups on the large maps)
+int pw_dispatch(const PwCfg& c, int mode, dim3 grid, hipStream_t st, const PwK* one, const PwK* tab) {
+#define ADDK_PW_GO(CT_, KG_, MODE_, RS_) \
+  (c.red32 ? pw_go<CT_, KG_, MODE_, true, RS_>(grid, st, one, tab) : pw_go<CT_, KG_, MODE_, false, RS_>(grid, st, one, tab))
 #define ADDK_PW(CT_, KG_) \
-  if (ct == CT_ && kg == KG_) { \
-    if (MODE == PW_FWD && rs) { \
-      if (red32) hipLaunchKernelGGL((pw_kernel<CT_, KG_, PW_FWD, true, true>), grid, dim3(256), 0, st, k); \
-      else hipLaunchKernelGGL((pw_kernel<CT_, KG_, PW_FWD, false, true>), grid, dim3(256), 0, st, k); \
-    } else if (red32) hipLaunchKernelGGL((pw_kernel<CT_, KG_, MODE, true>), grid, dim3(256), 0, st, k); \
-    else hipLaunchKernelGGL((pw_kernel<CT_, KG_, MODE, false>), grid, dim3(256), 0, st, k); \
-    return addk_check_launch("pw_conv"); }
+  if (c.ct == CT_ && c.kg == KG_) { \
+    if (mode == PW_DGRAD) return ADDK_PW_GO(CT_, KG_, PW_DGRAD, false); \
+    return c.rs ? ADDK_PW_GO(CT_, KG_, PW_FWD, true) : ADDK_PW_GO(CT_, KG_, PW_FWD, false); }
   ADDK_PW(1, 3) ADDK_PW(2, 3) ADDK_PW(3, 3)
   ADDK_PW(1, 5) ADDK_PW(2, 5)
 #undef ADDK_PW
-  addk_set_error("pw_conv: no instantiation");
+#undef ADDK_PW_GO
+  addk_set_error(tab ? "pw_batch: no instantiation" : "pw_conv: no instantiation");
   return ADDK_ERR_UNSUPPORTED;
 }
 
-template <int MODE>
-int pw_batch_launch(const PwK* tab, int n, int ct, int kg, int red32, int rs, int gx, int gy, hipStream_t st) {
-  dim3 grid(gx, gy, n);
-#define ADDK_PW(CT_, KG_) \
-  if (ct == CT_ && kg == KG_) { \
-    if (MODE == PW_FWD && rs) { \
-      if (red32) hipLaunchKernelGGL((pw_batch_kernel<CT_, KG_, PW_FWD, true, true>), grid, dim3(256), 0, st, tab); \
-      else hipLaunchKernelGGL((pw_batch_kernel<CT_, KG_, PW_FWD, false, true>), grid, dim3(256), 0, st, tab); \
-    } else if (red32) hipLaunchKernelGGL((pw_batch_kernel<CT_, KG_, MODE, true>), grid, dim3(256), 0, st, tab); \
-    else hipLaunchKernelGGL((pw_batch_kernel<CT_, KG_, MODE, false>), grid, dim3(256), 0, st, tab); \
-    return addk_check_launch("pw_conv_batch"); }
-  ADDK_PW(1, 3) ADDK_PW(2, 3) ADDK_PW(3, 3)
-  ADDK_PW(1, 5) ADDK_PW(2, 5)
-#undef ADDK_PW
-  addk_set_error("pw_batch: no instantiation");
+template <int CT, bool RED32, bool RS>
+int pwk_go(dim3 grid, hipStream_t st, const PwkK& k) {
+  hipLaunchKernelGGL((pwk_kernel<CT, RED32, RS>), grid, dim3(256), 0, st, k);
+  return addk_check_launch("pwk_conv");
+}
+int pwk_dispatch(int ct, int rs, int red32, dim3 grid, hipStream_t st, const PwkK& k) {
+#define ADDK_PWK(CT_) \
+  if (ct == CT_) { \
+    if (rs) return red32 ? pwk_go<CT_, true, true>(grid, st, k) : pwk_go<CT_, false, true>(grid, st, k); \
+    return red32 ? pwk_go<CT_, true, false>(grid, st, k) : pwk_go<CT_, false, false>(grid, st, k); }
+  ADDK_PWK(1) ADDK_PWK(2) ADDK_PWK(3)
+#undef ADDK_PWK
+  addk_set_error("pwk_conv: no instantiation");
   return ADDK_ERR_UNSUPPORTED;
+}
+
+// what the forward descriptors (PwK, PwkK, StemK) share: the statistics slab and the pixel count
+template <typename K>
+void fwd_slab_pixels(const addk_conv_args* a, K& k) {
+  k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
+  k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16);
 }
 
 bool pw_fill_fwd(const addk_conv_args* a, PwK& k) {
@@ -563,8 +474,7 @@ bool pw_fill_fwd(const addk_conv_args* a, PwK& k) {
   k = PwK{};
   k.src = s; k.K = s.C; k.Cn = a->Cout; k.w = a->w; k.ldw = a->ldw; k.w_off = a->w_choff;
   k.y = a->y; k.ldy = a->ldy; k.bias = a->bias;
-  k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
-  k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16);
+  fwd_slab_pixels(a, k);
   k.H = a->OH; k.W = a->OW;
   if (s.rs_hw) {                      // the input is sampled from an [N, RH, RW] map (addk_src.rs_hw)
     k.RH = s.rs_hw >> 16; k.RW = s.rs_hw & 0xffff;
@@ -586,7 +496,11 @@ bool pw_fill_dgrad(const addk_conv_dgrad_args* a, PwK& k) {
   k.P = a->N * a->H * a->W; k.ntiles16 = cdiv(k.P, 16);
   return true;
 }
+// the batch key of a CK_PW launch: its template variant (launches with equal keys can share a batch; the grid travels beside it)
 inline int pw_key(const PwCfg& c, int mode) { return (mode << 12) | (c.ct << 8) | (c.kg << 4) | (c.rs << 1) | c.red32; }
+inline void pw_key_decode(int key, PwCfg& c, int& mode) {
+  mode = key >> 12; c.ct = (key >> 8) & 15; c.kg = (key >> 4) & 15; c.rs = (key >> 1) & 1; c.red32 = key & 1;
+}
 void pw_choice(ConvChoice& c, const PwCfg& g, int mode) {
   c.kind = CK_PW; c.v[0] = g.ct; c.v[1] = g.kg; c.v[2] = g.rs; c.v[3] = g.red32; c.gx = g.gx; c.gy = g.gy; c.key = pw_key(g, mode);
 }
@@ -708,7 +622,6 @@ bool stem0_covers(const addk_conv_args* a) {
   if (!aligned16(a->y) || a->ldy % 4 || a->ldy < 64) return false;
   return a->OH == (a->H + 2 - 3) / 2 + 1 && a->OW == (a->W + 2 - 3) / 2 + 1;
 }
-}  // namespace
 
 // Data gradient of a 1x1 convolution with FEW output channels into a wide input — the classifier (decoder.py last_conv, 256 -> 19 classes):
 // 0.6 GF against 2 x 67 MB at config 2.  On the generic implicit-GEMM kernel (LDS tiles, 32-channel chunks with 19 live k slots) it took 110 us;
@@ -783,12 +696,13 @@ __global__ void __launch_bounds__(256) k1s_dgrad_kernel(const K1sK p) {
     }
   }
 }
-static bool k1s_covers(const addk_conv_dgrad_args* a) {
+bool k1s_covers(const addk_conv_dgrad_args* a) {
   if (a->KH != 1 || a->KW != 1 || a->stride != 1 || a->pad != 0 || a->H != a->OH || a->W != a->OW) return false;
   if (a->Cout > 32 || a->dst.C < 128 || a->dst.C > 256 || a->dst.C % 4) return false;
   if (!src_vec_ok(a->dst) || !aligned16(a->g) || a->ldg % 4 || !aligned16(a->w) || a->ldw % 4 || a->w_choff % 4) return false;
   return !a->dst.a || (aligned16(a->dst.a) && aligned16(a->dst.b));
 }
+}  // namespace
 
 bool pw_choose_fwd(const addk_conv_args* a, ConvChoice& c) {
   const long P = (long)a->N * a->OH * a->OW;
@@ -820,17 +734,16 @@ bool pw_choose_dgrad(const addk_conv_dgrad_args* a, ConvChoice& c) {
 
 int pw_run_fwd(const ConvChoice& c, const addk_conv_args* a, hipStream_t st) {
   if (c.kind == CK_PW) {
-    PwK k;
-    pw_fill_fwd(a, k); pw_desc(c, k);
-    return pw_launch<PW_FWD>(c, k, st);
+    PwK k; PwCfg g; int mode;
+    pw_fill_fwd(a, k); pw_desc(c, k); pw_key_decode(c.key, g, mode);
+    return pw_dispatch(g, mode, dim3(c.gx, c.gy), st, &k, nullptr);
   }
   if (c.kind == CK_STEM0) {
     const addk_src& s = a->src[0];
     StemK k{};
     k.x = s.x; k.ld = s.ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
     k.w = a->w; k.ldw = a->ldw; k.y = a->y; k.ldy = a->ldy;
-    k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
-    k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16); k.rows = c.rows; k.gx = c.gx;
+    fwd_slab_pixels(a, k); k.rows = c.rows; k.gx = c.gx;
     if (c.v[1]) hipLaunchKernelGGL((stem0_kernel<4, true>), dim3(c.gx), dim3(256), 0, st, k);
     else hipLaunchKernelGGL((stem0_kernel<4, false>), dim3(c.gx), dim3(256), 0, st, k);
     return addk_check_launch("stem0");
@@ -839,30 +752,16 @@ int pw_run_fwd(const ConvChoice& c, const addk_conv_args* a, hipStream_t st) {
   for (int i = 0; i < a->nsrc; ++i) k.src[i] = a->src[i];
   k.nsrc = a->nsrc; k.Cn = a->Cout; k.w = a->w; k.ldw = a->ldw; k.w_off = a->w_choff;
   k.y = a->y; k.ldy = a->ldy; k.bias = a->bias;
-  k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
-  k.P = a->N * a->OH * a->OW; k.ntiles16 = cdiv(k.P, 16); k.rows = c.rows;
+  fwd_slab_pixels(a, k); k.rows = c.rows;
   k.H = a->OH; k.W = a->OW; k.rs_y = a->rs_y; k.rs_ldy = a->rs_ldy;
   k.gx = c.gx;
-  const int ct = c.v[0], rs = c.v[1], red32 = c.v[2];
-  dim3 grid(c.gx, c.gy);
-#define ADDK_PWK(CT_) \
-  if (ct == CT_) { \
-    if (rs) { \
-      if (red32) hipLaunchKernelGGL((pwk_kernel<CT_, true, true>), grid, dim3(256), 0, st, k); \
-      else hipLaunchKernelGGL((pwk_kernel<CT_, false, true>), grid, dim3(256), 0, st, k); \
-    } else if (red32) hipLaunchKernelGGL((pwk_kernel<CT_, true>), grid, dim3(256), 0, st, k); \
-    else hipLaunchKernelGGL((pwk_kernel<CT_, false>), grid, dim3(256), 0, st, k); \
-    return addk_check_launch("pwk_conv"); }
-  ADDK_PWK(1) ADDK_PWK(2) ADDK_PWK(3)
-#undef ADDK_PWK
-  addk_set_error("pwk_conv: no instantiation");
-  return ADDK_ERR_UNSUPPORTED;
+  return pwk_dispatch(c.v[0], c.v[1], c.v[2], dim3(c.gx, c.gy), st, k);
 }
 int pw_run_dgrad(const ConvChoice& c, const addk_conv_dgrad_args* a, hipStream_t st) {
   if (c.kind == CK_PW) {
-    PwK k;
-    pw_fill_dgrad(a, k); pw_desc(c, k);
-    return pw_launch<PW_DGRAD>(c, k, st);
+    PwK k; PwCfg g; int mode;
+    pw_fill_dgrad(a, k); pw_desc(c, k); pw_key_decode(c.key, g, mode);
+    return pw_dispatch(g, mode, dim3(c.gx, c.gy), st, &k, nullptr);
   }
   K1sK k{};
   k.dy = a->dy; k.lddy = a->lddy; k.K = a->Cout; k.w = a->w; k.ldw = a->ldw; k.w_off = a->w_choff;
@@ -912,8 +811,7 @@ extern "C" int64_t addk_conv_dgrad_batch_prepare(const addk_conv_dgrad_args* a, 
 }
 extern "C" int addk_conv_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
   ADDK_REQUIRE(dev_blob && meta && meta[1] > 0 && meta[2] > 0 && meta[3] > 0, "conv_batch_run: bad args");
-  const int key = (int)meta[0], mode = key >> 12, ct = (key >> 8) & 15, kg = (key >> 4) & 15, red32 = key & 1, rs = (key >> 1) & 1;
-  const PwK* tab = reinterpret_cast<const PwK*>(dev_blob);
-  if (mode == PW_FWD) return pw_batch_launch<PW_FWD>(tab, (int)meta[1], ct, kg, red32, rs, (int)meta[2], (int)meta[3], (hipStream_t)stream);
-  return pw_batch_launch<PW_DGRAD>(tab, (int)meta[1], ct, kg, red32, 0, (int)meta[2], (int)meta[3], (hipStream_t)stream);
+  PwCfg g; int mode;
+  pw_key_decode((int)meta[0], g, mode);
+  return pw_dispatch(g, mode, dim3((unsigned)meta[2], (unsigned)meta[3], (unsigned)meta[1]), (hipStream_t)stream, nullptr, reinterpret_cast<const PwK*>(dev_blob));
 }
