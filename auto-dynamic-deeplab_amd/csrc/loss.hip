@@ -1,8 +1,11 @@
 // Softmax cross-entropy on NCHW logits (nn.CrossEntropyLoss(weight, ignore_index=255), train.py:70,231),
 // normalised Shannon entropy of the prediction (operations.py:161-170), argmax and the confusion matrix
-// of the evaluator (utils/metrics.py:34-43).  One thread per pixel; channel planes are contiguous along
+// of the evaluator (utils/metrics.py:34-43), and the entropy / top-probability gates of dynamic inference
+// (operations.py:161-180) from the low-resolution logits.  One thread per pixel; channel planes are contiguous along
 // W so every per-channel access of a wave is one coalesced 256-B segment.
+#include <math.h>
 #include "common.h"
+#include "bnfin.h"
 
 namespace {
 
@@ -428,6 +431,114 @@ bool scu_ok(int N, int H, int W, int OH, int OW, int C) {
   return N <= 65535 && cdiv(OH, SCU_WAVES * SCU_R) <= 65535 && (long)N * cdiv(OH, SCU_WAVES * SCU_R) * cdiv(OW, SCU_W) < (1L << 30);
 }
 
+// ---- fused logits up-sampling + early-exit gate (decoder.py:28 + operations.py:161-180) -----------------------------------
+// The two gates of dynamic inference that need no trained EDM: the normalised Shannon entropy of the up-sampled prediction and the
+// share of pixels whose top softmax probability passes a threshold.  The walk is score_up_kernel's (same tile, same interpolation
+// z = lh0*t0 + lh1*t1, one max sweep, one exp sweep) without target, histogram, loss and map.  Per pixel: se = Σe, sx = Σe·d with
+// d = z - max, entropy term log se - sx/se, top probability pmax = 1/se (the largest e is exp(0) = 1), counted when pmax > *max_thr.
+// A workgroup leaves one fp32 entropy partial and one count, write-through; the workgroup that arrives LAST (csrc/bnfin.h ticket, as
+// csrc/edm.hip) adds each image's partials in a FIXED order (fp64; the counts are integers), writes (entropy, share) to `out` and to
+// the pinned host words the gate reads, and puts the ticket back to zero: one launch, bit-reproducible, graph-replayable, nothing spins.
+struct GateUpK {
+  const float* x; int ld; int N, H, W, OH, OW;
+  const float* thr;
+  float* out; float* out_host;
+  unsigned* counter; float* part; unsigned* cnt;          // ws: [ticket, 16 bytes][nblk floats][nblk counts], image-major
+  int nblk_img;
+  double npix, ent_div;                                    // OH*OW and log(C) * OH*OW
+};
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) gate_up_kernel(const GateUpK p) {
+  constexpr int CP = (CC + 3) / 4 * 4;
+  __shared__ float shs[4];
+  __shared__ unsigned shc[4];
+  __shared__ double shd[4];
+  __shared__ unsigned long long shl[4];
+  __shared__ unsigned flag;
+  const int t = threadIdx.x, lane = t & (SCU_W - 1), wv = t / SCU_W;
+  const int X = blockIdx.x * SCU_W + lane, n = blockIdx.z;
+  const int ybeg = (blockIdx.y * SCU_WAVES + wv) * SCU_R;
+  const int yend = ybeg + SCU_R < p.OH ? ybeg + SCU_R : p.OH;
+  const float sh = (float)p.H / (float)p.OH, sw = (float)p.W / (float)p.OW;
+  const float thr = *(const gfloat*)p.thr;
+  auto load_px = [](const float* q, float (&v)[CP]) {
+    if constexpr (VEC) {
+#pragma unroll
+      for (int c = 0; c < CP; c += 4) { const float4 f = ld4(q + c); v[c] = f.x; v[c + 1] = f.y; v[c + 2] = f.z; v[c + 3] = f.w; }
+    } else {
+#pragma unroll
+      for (int c = 0; c < CC; ++c) v[c] = ((const gfloat*)q)[c];
+    }
+  };
+  float esum = 0.f; unsigned hit = 0u;
+  if (X < p.OW) {
+    int w0, w1; float lw0, lw1;
+    ce_src_index(X, sw, p.W, w0, w1, lw0, lw1);
+    float t0[CC], t1[CC];
+    int ph0 = -1, ph1 = -1;
+    for (int Y = ybeg; Y < yend; ++Y) {
+      int h0, h1; float lh0, lh1;
+      ce_src_index(Y, sh, p.H, h0, h1, lh0, lh1);
+      if (h0 != ph0 || h1 != ph1) {                              // wave-uniform: Y is
+        const float* r0 = p.x + ((long)(n * p.H + h0) * p.W) * p.ld;
+        const float* r1 = p.x + ((long)(n * p.H + h1) * p.W) * p.ld;
+        float a[CP], b[CP];
+        load_px(r0 + (long)w0 * p.ld, a); load_px(r0 + (long)w1 * p.ld, b);
+#pragma unroll
+        for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
+        load_px(r1 + (long)w0 * p.ld, a); load_px(r1 + (long)w1 * p.ld, b);
+#pragma unroll
+        for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
+        ph0 = h0; ph1 = h1;
+      }
+      float z[CC];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < CC; ++c) { z[c] = lh0 * t0[c] + lh1 * t1[c]; mx = fmaxf(mx, z[c]); }
+      float se = 0.f, sx = 0.f;
+#pragma unroll
+      for (int c = 0; c < CC; ++c) { const float d = z[c] - mx; const float e = __expf(d); se += e; sx += e * d; }
+      esum += logf(se) - sx / se;
+      hit += (1.f / se > thr) ? 1u : 0u;
+    }
+  }
+  esum = block_sum(esum, shs);
+  for (int m = 32; m > 0; m >>= 1) hit += __shfl_xor(hit, m);
+  if (lane == 0) shc[wv] = hit;
+  __syncthreads();
+  const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (t == 0) {
+    __hip_atomic_store((gu32*)(p.part + blk), __float_as_uint(esum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store((gu32*)(p.cnt + blk), shc[0] + shc[1] + shc[2] + shc[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (!bnfin_arrive(p.counter, gridDim.x * gridDim.y * gridDim.z, &flag)) return;
+  // ---- the last workgroup: thread t adds partials t, t + 256, ... of an image, then lanes and waves in a fixed order ----
+  for (int img = 0; img < p.N; ++img) {
+    double s = 0.0; unsigned long long k = 0ull;
+    const long base = (long)img * p.nblk_img;
+    for (int i = t; i < p.nblk_img; i += 256) {
+      s += (double)__uint_as_float(__hip_atomic_load((gu32*)(p.part + base + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      k += __hip_atomic_load((gu32*)(p.cnt + base + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int m = 32; m > 0; m >>= 1) { s += __shfl_xor(s, m); k += __shfl_xor(k, m); }
+    if (lane == 0) { shd[wv] = s; shl[wv] = k; }
+    __syncthreads();
+    if (t == 0) {
+      const double es = ((shd[0] + shd[1]) + shd[2]) + shd[3];
+      const unsigned long long ks = shl[0] + shl[1] + shl[2] + shl[3];
+      const float ent = (float)(es / p.ent_div), share = (float)((double)ks / p.npix);
+      ((gfloat*)p.out)[2 * img] = ent; ((gfloat*)p.out)[2 * img + 1] = share;
+      if (p.out_host) { p.out_host[2 * img] = ent; p.out_host[2 * img + 1] = share; }
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (p.out_host) __threadfence_system();
+    __hip_atomic_store((gu32*)p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 int ce_blocks(long total) { long b = cdiv(total, 256 * 4); if (b < 1) b = 1; if (b > 1024) b = 1024; return (int)b; }
 
 }  // namespace
@@ -511,6 +622,34 @@ extern "C" int addk_score_upsample(const addk_score_upsample_args* a, void* stre
   if (rc) return rc;
   hipLaunchKernelGGL(score_sum_kernel, dim3(2), dim3(256), 0, st, a->ws, k.nblk, a->scale, a->wsum, a->loss_out, a->ent_out);
   return addk_check_launch("score_upsample_sum");
+}
+
+extern "C" int addk_gate_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return scu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_gate_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW) {
+  if (N <= 0 || OH <= 0 || OW <= 0) return 0;
+  return 16 + 8 * (int64_t)N * cdiv(OH, SCU_WAVES * SCU_R) * cdiv(OW, SCU_W);
+}
+extern "C" int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->max_thr && a->out && a->ws, "gate_upsample: null pointer");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(a->ld >= a->C, "gate_upsample: short stride");
+  const dim3 grid(cdiv(a->OW, SCU_W), cdiv(a->OH, SCU_WAVES * SCU_R), a->N);
+  GateUpK k;
+  k.x = a->logits; k.ld = a->ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
+  k.thr = a->max_thr; k.out = a->out; k.out_host = a->out_host;
+  k.nblk_img = (int)(grid.x * grid.y);
+  k.counter = (unsigned*)a->ws;
+  k.part = (float*)((char*)a->ws + 16);
+  k.cnt = (unsigned*)(k.part + (long)a->N * k.nblk_img);
+  k.npix = (double)a->OH * (double)a->OW; k.ent_div = log(19.0) * k.npix;
+  hipStream_t st = (hipStream_t)stream;
+  if (a->ld % 4 == 0 && a->ld >= 20 && aligned16(a->logits))
+    hipLaunchKernelGGL((gate_up_kernel<19, true>), grid, dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL((gate_up_kernel<19, false>), grid, dim3(256), 0, st, k);
+  return addk_check_launch("gate_upsample");
 }
 
 extern "C" int addk_entropy_sum(const float* logits, int32_t N, int32_t C, int64_t HW, float* out1, float* ws, void* stream) {

@@ -1,8 +1,19 @@
-"""EDM-gated dynamic inference (reference ADD.dynamic_inference, ADD.py:379-438; eval.py:195-230).
+"""Gated dynamic inference (reference ADD.dynamic_inference, ADD.py:379-488; eval.py:195-230 `--confidence {edm,entropy,max}`).
 
 The gate stays on the host and only selects which exit's kernels fire (north_star): the trunk is emitted
-once into a single launch list that is cut into segments — [stems+cells up to gate k + EDM] and, per gate,
-[early head k]; the last segment is [remaining cells + final head].  All segments share one buffer set."""
+once into a single launch list that is cut into segments.  All segments share one buffer set.
+
+DynamicPlan ('edm', ADD.py:379-438): [stems+cells up to gate k + EDM] and, per gate, [early head k]; the last segment is
+[remaining cells + final head].
+
+GatePlan ('entropy' / 'max', operations.py:161-180; the reference's own branch ADD.py:440-488 is broken, SURVEY Q6, so the
+semantics are this project's): the gate judges exit k's PREDICTION, so head k runs before the decision —
+[trunk up to exit k] [head k down to the decoder's low-resolution logits + the gate launch] [resize of head k to NCHW] ...
+[remaining cells + final head + its resize].  The gate launch (csrc/loss.hip gate_up_kernel) takes the entropy / top-probability
+share of the x8 up-sampled prediction straight from the low-resolution logits and writes them to pinned host words; the full-size
+logits are written only for the image that leaves.  Exit k's logits are forward()'s (`model(x)[k]`): aspp_size from 2^-(last+2)
+and conv_aspp[k] when the level differs; no EDM runs, so its in-place ReLU (Q3) does not happen.  The 2^-last size (Q5) is a
+quirk of the working 'edm' path and stays only there: the heads training optimises are forward()'s."""
 import torch
 
 from .module import ensure_layout
@@ -62,6 +73,10 @@ class DynamicPlan:
                     it += 1                                           # ADD.py:422 increments on every passed gate
                 else:
                     self.final = model._head(g, y, low, size, aspp_size, it, model.network_arch[i], resize=False, adapt=False)
+        self._finish(x)
+
+    def _finish(self, x):
+        g = self.g
         g.finalize()
         self.params = list(g.params)
         self.ptrs = [p.data_ptr() for p in self.params]
@@ -124,3 +139,81 @@ class DynamicPlan:
                 return self.heads[k].y, 1, conf
             self._seg(pos, -1)
         return self.final.y, 0, conf
+
+
+KINDS = ('entropy', 'max')
+
+
+class GatePlan(DynamicPlan):
+    """Dynamic inference gated by the entropy ('entropy') or the top-probability share ('max') of each early exit's prediction."""
+
+    def __init__(self, model, x, kind):
+        from .modeling.ADD import _aspp_size
+        if kind not in KINDS:
+            raise ValueError('confidence must be one of %s (got %r)' % (('edm',) + KINDS, kind))
+        for p in model.parameters():
+            ensure_layout(p)
+        if x.shape[0] != 1:              # the same decision as DynamicPlan: one image per gate
+            raise RuntimeError('dynamic_inference gates one image at a time (got batch size %d): the reference\'s '
+                               '`if confidence_value > threshold` is ambiguous for more than one value' % x.shape[0])
+        self.kind = kind
+        self.g = g = Graph(x.device, False, False, None)
+        # (entropy, share) of the gated exit travel through pinned host memory: the gate launch writes them there itself; on the
+        # stand-alone path an asynchronous 8-byte copy does.  Either way the host waits on ONE event, not on the whole device
+        self._conf_host = torch.zeros(2, dtype=torch.float32)
+        self._conf_evt = None
+        self._thr = torch.zeros(1, dtype=torch.float32, device=x.device)      # the word the 'max' gate compares against
+        if x.is_cuda:
+            self._conf_host = self._conf_host.pin_memory()
+            self._conf_evt = torch.cuda.Event()
+        a, self.inref = g.input_nchw(x)
+        size = (a.H, a.W)
+        aspp_size = _aspp_size(size, model.network_arch[-1] + 2)       # forward()'s (ADD.emit)
+        self.trunk_end, self.head_rng, self.heads = [], [], []
+        self.final, it = None, 0
+        for i, y, low in model._trunk(g, a):
+            lvl = model.network_arch[i]
+            if i in model.C_index and i != model.num_net - 1:
+                self.trunk_end.append(len(g.fwd))
+                g.gate = {'kind': kind, 'host': self._conf_host if x.is_cuda else None, 'thr': self._thr}
+                h = model._head(g, y, low, size, aspp_size, it, lvl)
+                g.gate = None
+                self.heads.append(h)
+                self.head_rng.append((h.gate_cut, len(g.fwd)))          # [trunk_end, gate_cut): head + gate; [gate_cut, end): resize
+            elif i == model.num_net - 1:
+                self.final = model._head(g, y, low, size, aspp_size, it, lvl)
+            else:
+                continue
+            if lvl != model.network_arch[-1]:
+                it += 1                                                  # ADD.emit: conv_aspp is indexed by the adapted exits
+        self._finish(x)
+
+    def run(self, x, threshold):
+        """-> (logits, earlier_exit, gate value).  The image leaves at the first exit whose entropy is BELOW the threshold
+        ('entropy'), or whose share of pixels with top probability above the threshold is ABOVE it ('max': the same number plays
+        both roles, ADD.py:476,481)."""
+        self.calls += 1
+        self.x_static.copy_(x)
+        thr = float(threshold)
+        # a finite word for the kernel: every top probability lies in (0, 1], so clamping an infinite threshold changes no comparison
+        self._thr.fill_(min(max(thr, -1.0), 2.0))
+        pos, value = 0, None
+        col = 0 if self.kind == 'entropy' else 1
+        with torch.no_grad():
+            for k, end in enumerate(self.trunk_end):
+                h = self.heads[k]
+                cut, hend = self.head_rng[k]
+                self._seg(pos, cut)
+                if not h.gate_fused:
+                    self._conf_host.copy_(h.gate_out.reshape(-1)[:2], non_blocking=True)
+                if self._conf_evt is not None:
+                    self._conf_evt.record()
+                    self._conf_evt.synchronize()                      # the host waits for these two words only
+                value = float(self._conf_host[col]) * (h.gate_scale if col == 0 else 1.0)
+                if (value < thr) if self.kind == 'entropy' else (value > thr):
+                    if hend > cut:
+                        self._seg(cut, hend)
+                    return h.y, 1, value
+                pos = hend
+            self._seg(pos, -1)
+        return self.final.y, 0, value

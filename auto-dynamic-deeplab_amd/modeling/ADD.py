@@ -290,16 +290,36 @@ class ADD(AddkModule):
         return out, feat
 
     def dynamic_inference(self, x, threshold=1.0, confidence='edm', edm=False):
-        """reference ADD.py:379-438 (working 'edm' gate only).  Three plan segments share one buffer
-        set: trunk up to the gate + EDM, the early head, and the remaining cells + final head; the host reads the
-        EDM scalar (one D2H sync, as in the reference's `if confidence_value > threshold`) and launches one."""
+        """reference ADD.py:379-488 -> (y, earlier_exit, seconds, confidence_value).
+
+        confidence='edm' (ADD.py:379-438, the reference's working gate): three plan segments share one buffer set — trunk up to the
+        gate + EDM, the early head, and the remaining cells + final head; the host reads the EDM scalar (one D2H sync, as in the
+        reference's `if confidence_value > threshold`) and launches one.  The exit's aspp_size is 2^-last (Q5) and the EDM's in-place
+        ReLU reaches the trunk (Q3), as in the reference.
+
+        confidence='entropy' | 'max' (operations.py:161-180; `edm` is ignored): the gates that need no trained EDM.  The reference's
+        own branch (ADD.py:440-488) is broken, so the semantics are decided here: exit k's logits are forward()'s,
+        `model(x)[k]` (aspp_size from 2^-(last+2), conv_aspp[k] when the level differs; no EDM, so no in-place ReLU) — the heads
+        training optimises are the ones an entropy gate must judge; Q5's size stays a quirk of the 'edm' path only.  For every early
+        exit in order: trunk up to it, head k down to the decoder's low-resolution logits, the gate value of the full-resolution
+        prediction softmax(interpolate(logits_k, size, bilinear, align_corners=False)) in one launch (csrc/loss.hip), decision on
+        the host.  'entropy': value = mean over pixels of -sum p log p / log 19, the image leaves when value < threshold.  'max':
+        value = share of pixels with max_c p > threshold, the image leaves when value > threshold (one number in both roles,
+        ADD.py:476,481).  On exit y = exit k's [1,19,H,W] logits and earlier_exit = 1; after the last gate fails the final head's
+        logits come back with earlier_exit = 0.  confidence_value is a Python float: the last gate evaluated.
+
+        A batch of more than one image raises RuntimeError on every path; any other `confidence` raises ValueError."""
         if confidence != 'edm':
-            raise NotImplementedError("only confidence='edm' is a working reference path (ADD.py:465-488 return features)")
-        torch.cuda.synchronize()
+            from ..dynamic import KINDS
+            if confidence not in KINDS:
+                raise ValueError("confidence must be 'edm', 'entropy' or 'max' (got %r)" % (confidence,))
+        if x.is_cuda:
+            torch.cuda.synchronize()
         tic = time.perf_counter()
-        plan = self._dynamic_plan(x, edm)
+        plan = self._dynamic_plan(x, edm) if confidence == 'edm' else self._gate_plan(x, confidence)
         y, earlier_exit, conf = plan.run(x, threshold)
-        torch.cuda.synchronize()
+        if x.is_cuda:
+            torch.cuda.synchronize()
         return y, earlier_exit, time.perf_counter() - tic, conf
 
     def _dynamic_plan(self, x, edm):
@@ -309,6 +329,15 @@ class ADD(AddkModule):
         p = plans.get(key)
         if p is None or not p.check_params():
             p = plans[key] = DynamicPlan(self, edm, x)
+        return p
+
+    def _gate_plan(self, x, kind):
+        from ..dynamic import GatePlan
+        key = ('dyn', kind, tuple(x.shape), int(L.load().addk_get_conv_precision()))
+        plans = self._plans()
+        p = plans.get(key)
+        if p is None or not p.check_params():
+            p = plans[key] = GatePlan(self, x, kind)
         return p
 
 

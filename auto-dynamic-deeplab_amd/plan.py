@@ -11,6 +11,7 @@ the producing BatchNorm; consumers apply it while staging their tiles, so BatchN
 never cost a pass over HBM.
 """
 import collections
+import math
 import os
 import ctypes as C
 
@@ -373,6 +374,7 @@ class Graph:
         self.reorder = False          # level-order and batch the lists although this is not a training plan (set before finalize)
         self.fuse_ce = False          # logits outputs feed the fused up-sampling + cross-entropy launch (train.TrainStep)
         self.fuse_score = False       # logits outputs of an inference plan feed the fused up-sampling + scoring launch (validate.ValidationStep)
+        self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}
         self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted (fuse_score)
         self.pginit = set()
         self._pcols = {}
@@ -1309,6 +1311,8 @@ class Graph:
             return out
         if self.fuse_score and not self.want_grad:
             return self._score_head(src, OH, OW)
+        if self.gate is not None and not self.want_grad:
+            return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'])
         y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=self.device)
         self.nbytes += y.numel() * 4
         ar = L.ResizeArgs()
@@ -1392,6 +1396,58 @@ class Graph:
             for c in self.fwd[first:]:
                 c.tag = tag
         self._fwd_late.append(emit_score)
+        return out
+
+    def gate_head(self, src, OH, OW, host_out, thr, kind='entropy'):
+        """Logits output of a gated early exit (`self.gate`, set by dynamic.GatePlan): the gate value of the exit's full-resolution
+        prediction (modeling/operations.py:161-180) and, separately, the resize that writes the [N,C,OH,OW] logits.  Fused form: ONE
+        `gate_upsample` launch (`addk_gate_upsample`, csrc/loss.hip) reads the decoder's low-resolution NHWC logits and writes (entropy,
+        share) to the OutRef's `gate_out` [N,2] and to the pinned words `host_out`; the `resize_nchw` launch FOLLOWS it, so a plan cut
+        at `gate_cut` replays the resize only for an image that leaves here.  `thr`: the device word the 'max' gate compares against.
+        Where the library does not take the shape (`addk_gate_upsample_supported` == 0, e.g. C != 19) or with ADDK_FUSE_GATE=0, the same
+        plan uses the stand-alone kernels on the materialised logits — `resize_nchw` first, then `entropy_sum` ('entropy': gate_out[0, 0]
+        holds the un-normalised sum, `gate_scale` the factor the host applies) or a count in torch ops ('max': gate_out[0, 1]); nothing
+        is left behind the cut and the host copies `gate_out` itself (`gate_fused` False)."""
+        lib = self.lib
+        assert src.bn is None and not src.relu
+        N, H, W, Cc = src.N, src.H, src.W, src.C
+        y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=self.device)
+        gout = torch.zeros((N, 2), dtype=torch.float32, device=self.device)
+        self.nbytes += y.numel() * 4
+        ar = L.ResizeArgs()
+        ar.src = self.src(src)
+        ar.N, ar.H, ar.W, ar.OH, ar.OW = N, H, W, OH, OW
+        ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
+        self.keep += [ar, gout, thr, host_out]
+        out = OutRef(y)
+        out.gate_out, out.gate_scale = gout, 1.0
+        out.gate_fused = _on('ADDK_FUSE_GATE') and lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
+
+        def emit_resize():
+            self._add(self.fwd, 'resize_nchw', lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])
+        if out.gate_fused:
+            a = L.GateUpsampleArgs()
+            s = self.src(src)
+            a.logits, a.ld = s.x, s.ld
+            a.N, a.H, a.W, a.C, a.OH, a.OW = N, H, W, Cc, OH, OW
+            ws = self.buf((int(lib.addk_gate_upsample_ws_bytes(N, OH, OW)) + 3) // 4, zero=True)
+            a.max_thr, a.out, a.ws = thr.data_ptr(), gout.data_ptr(), ws.ptr
+            a.out_host = host_out.data_ptr() if host_out is not None else None
+            self.keep.append(a)
+            self._add(self.fwd, 'gate_upsample', lib.addk_gate_upsample, C.byref(a), rd=self.lz(src) + [thr], wr=[gout, ws])
+            out.gate_cut = len(self.fwd)
+            emit_resize()
+            return out
+        emit_resize()
+        if kind == 'entropy':
+            ws = torch.zeros(int(lib.addk_ce_ws_floats(N, OH * OW)), dtype=torch.float32, device=self.device)
+            self.keep.append(ws)
+            self._add(self.fwd, 'entropy_sum', lib.addk_entropy_sum, y.data_ptr(), N, Cc, OH * OW, gout.data_ptr(), ws.data_ptr(),
+                      rd=[y], wr=[gout, ws])
+            out.gate_scale = 1.0 / (math.log(19.0) * OH * OW)
+        else:
+            self._add(self.fwd, 'gate_count_torch', _gate_count_torch, y, thr, gout, rd=[y, thr], wr=[gout], pin=True)
+        out.gate_cut = len(self.fwd)
         return out
 
     def gap(self, src, relu_in=False):
@@ -1514,6 +1570,14 @@ def require_device(x):
 
 def current_stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def _gate_count_torch(y, thr, gout, stream):
+    """Cold path of Graph.gate_head ('max' gate on materialised logits): share of pixels with 1 / sum_c exp(z_c - max z) > thr, in torch
+    ops on the current stream (the command is pinned to the plan's main stream, which is the current one in eager runs and captures)."""
+    se = (y - y.amax(1, keepdim=True)).exp_().sum(1)
+    gout[:, 1] = (se.reciprocal_() > thr).flatten(1).float().mean(1)
+    return 0
 
 
 def _in_stage(lib, inref, N, Cc, HW, ptr, ld, stream):

@@ -536,6 +536,31 @@ int addk_score_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, i
 int64_t addk_score_upsample_ws_floats(int32_t N, int32_t OH, int32_t OW);
 int addk_score_upsample(const addk_score_upsample_args* a, void* stream);
 
+/* Early-exit gates that need no trained EDM (modeling/operations.py:161-180; eval.py --confidence entropy|max), on the
+ * full-resolution prediction softmax(interpolate(logits, (OH,OW), bilinear, align_corners=False)) straight from the
+ * LOW-resolution NHWC logits [N,H,W,C] (the arithmetic of addk_resize_fwd bit for bit; the [N,C,OH,OW] tensor is never
+ * materialised), in ONE launch:
+ *   out[2n]     = sum_pixels (log sum e - sum e*d / sum e) / (log C * OH*OW)     normalised Shannon entropy of image n
+ *   out[2n + 1] = #{pixels: pmax > *max_thr} / (OH*OW),  pmax = 1 / sum_c exp(z_c - max_c z)   (operations.py:172-180)
+ * max_thr is read from memory when the launch runs, so a captured graph serves every threshold.  out_host: optional
+ * host-mapped (pinned) [N][2] words that receive the same bits — the host gate then needs no device-to-host copy, only
+ * the completion of the launch.  ws: addk_gate_upsample_ws_bytes() bytes, ZERO-initialised once (the kernel leaves its
+ * ticket word at zero: replayable from a hipGraph).  Deterministic: the last-arriving workgroup adds the per-workgroup
+ * partials in a fixed order.  addk_gate_upsample_supported() is 0 for C != 19, non-positive sizes or a grid beyond
+ * 65535 x 32 rows / 65535 images (the limits of addk_score_upsample_supported); addk_gate_upsample then returns
+ * ADDK_ERR_INVALID without launching. */
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
+  int32_t N, H, W, C, OH, OW;
+  const float* max_thr;              /* device-readable word: threshold of the 'max' gate */
+  float* out;                        /* device [N][2]: (entropy, share) */
+  float* out_host;                   /* pinned host [N][2] or NULL */
+  void* ws;                          /* addk_gate_upsample_ws_bytes() zero-initialised bytes */
+} addk_gate_upsample_args;
+int addk_gate_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+int64_t addk_gate_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW);
+int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Fused SGD (torch.optim.SGD(momentum, weight_decay, nesterov), train.py:126) on a flat buffer.
  *   d = g*gscale + wd*p;  buf = first ? d : mom*buf + d;  p -= lr*(nesterov ? d + mom*buf : buf)
