@@ -10,8 +10,9 @@
 //     pointwise weights wait in LDS as ready A fragments — and drops the result into the LDS patch [pixel][KP] whose stride
 //     KP = 8 (mod 16) makes the tap reads of stage 2 conflict-free (sepf.hip);
 //   * stage 2: lane (li, kq) owns R input pixels x 4 channels of group g: per kernel row it reads KS shifted dt quads, feeds dz
-//     and the KS weight-gradient products, and reduces the latter over the 16 pixel lanes with four DPP row adds (fixed
-//     order: bit-reproducible); the four row bands' partials meet in LDS, one row [C][KS*KS] of the weight-gradient workspace and one row
+//     and the KS weight-gradient products, and reduces the latter over the 16 pixel lanes with four DPP row adds per value, all 4 * KS
+//     values of the kernel row in one interleaved block (fixed order: bit-reproducible); the fp64 (dA, dB) sums of an item take the same
+//     tree by DPP moves; the four row bands' partials meet in LDS, one row [C][KS*KS] of the weight-gradient workspace and one row
 //     [C][2] of the (dA, dB) slab per workgroup.
 // The pointwise WEIGHT gradient stays with the batched register-streaming kernel (wgrad.hip), which reads dy and the stored
 // depthwise output.
@@ -33,25 +34,79 @@ struct SepbK {
 __device__ __forceinline__ float4 fma4b(float4 w, float4 v, float4 a) {
   return make_float4(fmaf(w.x, v.x, a.x), fmaf(w.y, v.y, a.y), fmaf(w.z, v.z, a.z), fmaf(w.w, v.w, a.w));
 }
-// sum over the 16 lanes of a DPP row (= the 16 pixel lanes li of one channel quad), same value in every lane, fixed order
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
+// the same four FMAs as two explicit 2-vectors: the weight-gradient products end in the scalar operands of the reduction block below,
+// which the SLP vectoriser takes as a reason to leave their FMAs scalar; written as vectors they stay v_pk_fma_f32
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+struct F4pk { f32x2 lo, hi; };
+__device__ __forceinline__ F4pk fma4pk(float4 w, float4 v, F4pk a) {
+  a.lo = __builtin_elementwise_fma((f32x2){w.x, w.y}, (f32x2){v.x, v.y}, a.lo);
+  a.hi = __builtin_elementwise_fma((f32x2){w.z, w.w}, (f32x2){v.z, v.w}, a.hi);
+  return a;
+}
+// Sums over the 16 lanes of a DPP row (= the 16 pixel lanes li of one channel quad) of all 4 * KS products of a kernel row at once, the same
+// value in every lane, in the fixed tree (((x0+x1)+(x2+x3)) + ((x4+x5)+(x6+x7))) + (((x8+x9)+(x10+x11)) + ((x12+x13)+(x14+x15))): four levels
+// (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror), each ONE v_add_f32_dpp per value.  Written per component with
+// __builtin_amdgcn_update_dpp, the SLP vectoriser pairs the adds into v_pk_add_f32, which cannot carry the DPP control: every level then
+// costs v_mov_b32_dpp x2 + v_pk_add_f32 + hazard no-ops, 6 VALU per value per tree where 4 suffice.
+// Hazards: a DPP read of a VGPR that the VALU wrote needs two wait states and the compiler's hazard recogniser does not look inside inline
+// assembly, so the spacing holds by construction: ONE asm statement, level by level over the 12 or 20 independent chains, so an add reads
+// what the instruction 12 / 20 places before it wrote; the only no-op inside is the `s_nop 1` that opens the block, for the FMA that may
+// have written the first operands just before it (in front of an asm statement the compiler may add its own fixed one-state pad, an
+// `s_nop 0`: two no-ops per kernel row at the most, where the per-component form had 10-22).  volatile: the block is cross-lane and must
+// stay where every lane of the row is active.
+// an empty statement that the values pass through: what computes them stays above it, so the patch quads die before the reduction block
+__device__ __forceinline__ void pin4(F4pk& v) { asm volatile("" : "+v"(v.lo), "+v"(v.hi)); }
+#define SEPB_DPP(i, ctl) "v_add_f32_dpp %" #i ", %" #i ", %" #i " " ctl " row_mask:0xf bank_mask:0xf\n\t"
+#define SEPB_LVL12(ctl) SEPB_DPP(0, ctl) SEPB_DPP(1, ctl) SEPB_DPP(2, ctl) SEPB_DPP(3, ctl) SEPB_DPP(4, ctl) SEPB_DPP(5, ctl) \
+  SEPB_DPP(6, ctl) SEPB_DPP(7, ctl) SEPB_DPP(8, ctl) SEPB_DPP(9, ctl) SEPB_DPP(10, ctl) SEPB_DPP(11, ctl)
+#define SEPB_LVL20(ctl) SEPB_LVL12(ctl) SEPB_DPP(12, ctl) SEPB_DPP(13, ctl) SEPB_DPP(14, ctl) SEPB_DPP(15, ctl) SEPB_DPP(16, ctl) \
+  SEPB_DPP(17, ctl) SEPB_DPP(18, ctl) SEPB_DPP(19, ctl)
+#define SEPB_TREE(LVL) "s_nop 1\n\t" LVL("quad_perm:[1,0,3,2]") LVL("quad_perm:[2,3,0,1]") LVL("row_half_mirror") LVL("row_mirror")
+#define SEPB_V4(d) "+v"((d).x), "+v"((d).y), "+v"((d).z), "+v"((d).w)
+__device__ __forceinline__ void row_sum16_taps(float4 (&d)[3]) {
+  asm volatile(SEPB_TREE(SEPB_LVL12) : SEPB_V4(d[0]), SEPB_V4(d[1]), SEPB_V4(d[2]));
+}
+__device__ __forceinline__ void row_sum16_taps(float4 (&d)[5]) {
+  asm volatile(SEPB_TREE(SEPB_LVL20) : SEPB_V4(d[0]), SEPB_V4(d[1]), SEPB_V4(d[2]), SEPB_V4(d[3]), SEPB_V4(d[4]));
+}
+#undef SEPB_V4
+#undef SEPB_TREE
+#undef SEPB_LVL20
+#undef SEPB_LVL12
+#undef SEPB_DPP
+
+// One level of the same tree for the fp64 (dA, dB) sums: v + (v of the partner lane), the partner's two halves fetched by DPP moves (DPP on
+// 64-bit arithmetic is limited to row_newbcast on this ISA); no LDS round trip, unlike __shfl_xor on a double.  Plain builtins: the compiler
+// keeps the hazard spacing of these itself.
+template <int CTL>
+__device__ __forceinline__ double dpp_add_f64(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTL, 0xF, 0xF, true);
+  return v + __hiloint2double(hi, lo);
+}
+template <int N>
+__device__ __forceinline__ void row_sum16_f64(double (&s)[N]) {      // all N chains level by level: N independent adds in flight
+#pragma unroll
+  for (int i = 0; i < N; ++i) s[i] = dpp_add_f64<0xB1>(s[i]);         // quad_perm [1,0,3,2]
+#pragma unroll
+  for (int i = 0; i < N; ++i) s[i] = dpp_add_f64<0x4E>(s[i]);         // quad_perm [2,3,0,1]
+#pragma unroll
+  for (int i = 0; i < N; ++i) s[i] = dpp_add_f64<0x141>(s[i]);        // row_half_mirror
+#pragma unroll
+  for (int i = 0; i < N; ++i) s[i] = dpp_add_f64<0x140>(s[i]);        // row_mirror
 }
 
 // waves per workgroup.  Stage 1 hands the 16-pixel tiles of the patch and stage 2 the 4 * KG (row band, channel group) items round-robin to
 // NW waves; the arithmetic of a tile / an item does not depend on which wave runs it.  A tile is one workgroup and the grid is one or two
 // workgroups per CU (sep.h), so NW sets the waves per SIMD: 16 waves for the 80-channel tiles (one workgroup per CU), 8 for the 40-channel
-// 3x3 (two per CU), both 4 waves per SIMD within 128 VGPRs; the 40-channel 5x5 needs ~146 VGPRs and stays at 4 waves.
-template <int KS, int KG>
-struct SepbWaves { static constexpr int NW = KG == 5 ? 16 : KS == 3 ? 8 : 4, WPS = NW == 4 ? 2 : 4; };
+// tiles config 2 runs (two per CU), all 4 waves per SIMD within 128 VGPRs; the 40-channel 5x5 at R = 1 (not run by config 2, not
+// measured) stays at 4 waves.
+template <int KS, int KG, int R>
+struct SepbWaves { static constexpr int NW = KG == 5 ? 16 : (KS == 3 || R == 2) ? 8 : 4, WPS = NW == 4 ? 2 : 4; };
 
 template <int KS, int KG, int KP, int R>
 struct SepbGeo {
-  static constexpr int NW = SepbWaves<KS, KG>::NW, NTHR = 64 * NW, WPS = SepbWaves<KS, KG>::WPS;   // waves, threads, waves per SIMD the launch bounds ask for
+  static constexpr int NW = SepbWaves<KS, KG, R>::NW, NTHR = 64 * NW, WPS = SepbWaves<KS, KG, R>::WPS;   // waves, threads, waves per SIMD the launch bounds ask for
   static constexpr int CT = KG, PH = 4 * R + KS - 1, PW = 16 + KS - 1, NPIX = PH * PW, KQ = KP / 4, NT16 = (NPIX + 15) / 16;
   static constexpr int PATCH = NT16 * 16 * KP + 8;
   static constexpr int DWL = KS * KS * KG * 16, PWL = KG * CT * 64 * 4;
@@ -178,19 +233,15 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
   double (*rd)[KG * 16][2] = reinterpret_cast<double (*)[KG * 16][2]>(red);
   // real loops over the channel group and the kernel row: fully unrolled, hipcc hoists every LDS read of the 15 (group, row)
   // bodies to the top (234-256 VGPRs and scratch spills for KS = 5); one body at a time needs ~100
-  // [r4] the operands of this wave's NEXT item (input values, the gradient to accumulate into) are requested at the top of an item's
-  // body and arrive under its LDS / VALU work: the loop used to open with a dependent round trip per group and close with another
-  float4 xn[R], on[R];
+  // [r4] the input values of this wave's NEXT item and the gradient THIS item accumulates into are requested at the top of an item's body and
+  // arrive under its LDS / VALU work: the loop used to open with a dependent round trip per group and close with another.  (The accumulate
+  // operand is not read until the item's end, so it need not be asked for an item earlier: R quads fewer live across the kernel-row loop.)
+  float4 xn[R];
   auto pre = [&](int g) {
     const int q = 4 * g + kq;
     const bool cok = g < KG && 4 * q < C;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const bool okx = pin[r] && cok;
-      xn[r] = ld4(p.src.x + (okx ? (long)pp[r] * p.src.ld + 4 * q : 0));
-      on[r] = zero4();
-      if (p.g && p.accumulate) on[r] = ld4(p.g + (okx ? (long)pp[r] * p.ldg + 4 * q : 0));
-    }
+    for (int r = 0; r < R; ++r) xn[r] = ld4(p.src.x + ((pin[r] && cok) ? (long)pp[r] * p.src.ld + 4 * q : 0));
   };
   pre(wave >> 2);
 #pragma unroll 1
@@ -200,9 +251,13 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
     const bool cok = 4 * q < C;
     float4 av = make_float4(1.f, 1.f, 1.f, 1.f), bv = zero4();
     if (p.src.a && cok) { av = ld4(p.src.a + 4 * q); bv = ld4(p.src.b + 4 * q); }
-    float4 x[R], z[R], dz[R], oacc[R]; bool m[R][4];
+    float4 x[R], z[R], oacc[R]; F4pk dz[R]; bool m[R][4];
 #pragma unroll
-    for (int r = 0; r < R; ++r) { x[r] = xn[r]; oacc[r] = on[r]; }
+    for (int r = 0; r < R; ++r) {
+      x[r] = xn[r];
+      oacc[r] = zero4();
+      if (p.g && p.accumulate) oacc[r] = ld4(p.g + ((pin[r] && cok) ? (long)pp[r] * p.ldg + 4 * q : 0));
+    }
     pre(g + NW / 4);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -212,40 +267,44 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
       for (int e = 0; e < 4; ++e) m[r][e] = okx && (!relu || get4(zp, e) > 0.f);
       z[r] = make_float4(m[r][0] ? zp.x : 0.f, m[r][1] ? zp.y : 0.f, m[r][2] ? zp.z : 0.f, m[r][3] ? zp.w : 0.f);
       if (!relu) z[r] = make_float4(okx ? zp.x : 0.f, okx ? zp.y : 0.f, okx ? zp.z : 0.f, okx ? zp.w : 0.f);
-      dz[r] = zero4();
+      dz[r].lo = dz[r].hi = (f32x2){0.f, 0.f};
     }
     const float* pb = patch + ((rb * R) * PW + li) * KP + 4 * qr;
 #pragma unroll 1
     for (int fr = 0; fr < KS; ++fr) {                    // flipped kernel row: patch row i = fr + r feeds input row r
-      float4 wr[KS], dwa[KS];
+      float4 wr[KS], dwa[KS]; F4pk dwp[KS];
 #pragma unroll
-      for (int dx = 0; dx < KS; ++dx) { wr[dx] = lds_ld4(dwl + (fr * KS + dx) * (KG * 16) + 4 * q); dwa[dx] = zero4(); }
+      for (int dx = 0; dx < KS; ++dx) { wr[dx] = lds_ld4(dwl + (fr * KS + dx) * (KG * 16) + 4 * q); dwp[dx].lo = dwp[dx].hi = (f32x2){0.f, 0.f}; }
 #pragma unroll
       for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int dx = 0; dx < KS; ++dx) {
           const float4 v = lds_ld4(pb + ((fr + r) * PW + dx) * KP);
-          dz[r] = fma4b(wr[dx], v, dz[r]);
-          dwa[dx] = fma4b(v, z[r], dwa[dx]);
+          dz[r] = fma4pk(wr[dx], v, dz[r]);
+          dwp[dx] = fma4pk(v, z[r], dwp[dx]);
         }
 #pragma unroll
-      for (int dx = 0; dx < KS; ++dx) {
-        float4 s;
-        s.x = row_sum16(dwa[dx].x); s.y = row_sum16(dwa[dx].y); s.z = row_sum16(dwa[dx].z); s.w = row_sum16(dwa[dx].w);
-        if (li == 0) lds_st4(mydws + (fr * KS + dx) * (KG * 16) + 4 * q, s);     // flipped tap index f = fr*KS + dx
+      for (int r = 0; r < R; ++r) pin4(dz[r]);
+#pragma unroll
+      for (int dx = 0; dx < KS; ++dx) dwa[dx] = make_float4(dwp[dx].lo.x, dwp[dx].lo.y, dwp[dx].hi.x, dwp[dx].hi.y);
+      row_sum16_taps(dwa);
+      if (li == 0) {
+#pragma unroll
+        for (int dx = 0; dx < KS; ++dx) lds_st4(mydws + (fr * KS + dx) * (KG * 16) + 4 * q, dwa[dx]);     // flipped tap index f = fr*KS + dx
       }
     }
-    double sA[4], sB[4];
+    double sAB[8];                                       // sA[e] = sAB[2 e], sB[e] = sAB[2 e + 1]
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { sA[e] = 0.0; sB[e] = 0.0; }
+    for (int e = 0; e < 8; ++e) sAB[e] = 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
+      const float4 dzr = make_float4(dz[r].lo.x, dz[r].lo.y, dz[r].hi.x, dz[r].hi.y);
       float4 gm;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float d = m[r][e] ? get4(dz[r], e) : 0.f;
+        const float d = m[r][e] ? get4(dzr, e) : 0.f;
         set4(gm, e, d);
-        sA[e] += (double)d * (double)get4(x[r], e); sB[e] += (double)d;
+        sAB[2 * e] += (double)d * (double)get4(x[r], e); sAB[2 * e + 1] += (double)d;
       }
       if (p.g && pin[r] && cok) {
         float4 gv = make_float4(gm.x * av.x, gm.y * av.y, gm.z * av.z, gm.w * av.w);
@@ -255,12 +314,10 @@ __device__ __forceinline__ void sepb_body(const SepbK& p, float* sm) {
       }
     }
     if (p.dab) {
+      row_sum16_f64(sAB);
+      if (li == 0) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        double a2 = sA[e], b2 = sB[e];
-#pragma unroll
-        for (int mk = 1; mk < 16; mk <<= 1) { a2 += __shfl_xor(a2, mk); b2 += __shfl_xor(b2, mk); }
-        if (li == 0) { rd[rb][4 * q + e][0] = a2; rd[rb][4 * q + e][1] = b2; }
+        for (int e = 0; e < 4; ++e) { rd[rb][4 * q + e][0] = sAB[2 * e]; rd[rb][4 * q + e][1] = sAB[2 * e + 1]; }
       }
     }
   }
