@@ -138,23 +138,35 @@ __global__ void confusion_kernel(const int64_t* gt, const int64_t* pred, long n,
 // atomics and no second pass over the 1.3 GB/exit of full-resolution logits and gradients the three-kernel form wrote and re-read.
 // A block owns 31 output columns x HB output rows; it re-walks one band above (for the carry) and one column to the left
 // (for A1): (HB+1)/HB * 32/31 redundant softmax work, counted once in the loss (own bands, xl >= 1).
-struct CeUpK {
-  const float* x; int ld; int N, H, W, OH, OW;
+//
+// What the three heads on the low-resolution logits share (this one, the scoring head and the exit gate below): the argument prefix
+// UpSrc, the pixel loader load_px and its vector-load predicate px_vec_ok; the two gather heads also share their walk, scu_walk.
+struct UpSrc { const float* x; int ld; int N, H, W, OH, OW; };      // NHWC logits, pixel stride ld, (H, W) -> (OH, OW)
+template <class A> UpSrc up_src(const A* a) { return UpSrc{a->logits, a->ld, a->N, a->H, a->W, a->OH, a->OW}; }
+
+constexpr int cpad(int cc) { return (cc + 3) / 4 * 4; }              // channels incl. the padding of a 16-byte-aligned pixel row
+// 16-byte loads of a pixel's cpad(CC) channels: stride and base keep every pixel aligned and the padding exists.  The host's
+// choice of a VEC kernel; ce_up_kernel evaluates the same three terms on the device
+template <int CC> bool px_vec_ok(const float* x, int ld) { return ld % 4 == 0 && ld >= cpad(CC) && aligned16(x); }
+// vec is a run-time value in ce_up_kernel and a compile-time constant in scu_walk, where the other branch folds away
+template <int CC>
+__device__ __forceinline__ void load_px(const float* q, float (&v)[cpad(CC)], bool vec) {
+  if (vec) {
+#pragma unroll
+    for (int c = 0; c < cpad(CC); c += 4) { const float4 f = ld4(q + c); v[c] = f.x; v[c + 1] = f.y; v[c + 2] = f.z; v[c + 3] = f.w; }
+  } else {
+#pragma unroll
+    for (int c = 0; c < CC; ++c) v[c] = ((const gfloat*)q)[c];
+  }
+}
+
+struct CeUpK : UpSrc {
   const int64_t* target; const float* cw; int ignore;
   const float* wsum; float scale;
   float* g; int ldg; int accumulate;
   float* ws; int HB;
 };
 
-__device__ __forceinline__ void ce_src_index(int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
-  float s = scale * ((float)dst + 0.5f) - 0.5f;
-  if (s < 0.f) s = 0.f;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-  l1 = s - (float)i0;
-  l0 = 1.f - l1;
-}
 __host__ __device__ __forceinline__ int ce_idx0(int dst, float scale, int in) {
   float s = scale * ((float)dst + 0.5f) - 0.5f;
   if (s < 0.f) s = 0.f;
@@ -177,7 +189,7 @@ constexpr int CEU_MAXBAND = 16;            // high-resolution rows per low-resol
 
 template <int CC>
 __global__ void __launch_bounds__(256) ce_up_kernel(const CeUpK p) {
-  constexpr int CP = (CC + 3) / 4 * 4;     // channels incl. the padding of a 16-byte-aligned pixel row
+  constexpr int CP = cpad(CC);
   constexpr int NOUT = ((CEU_X - 1) * CC + 255) / 256;
   __shared__ float S0[CEU_R * CEU_X * CC], S1[CEU_R * CEU_X * CC];
   __shared__ float shs[4];
@@ -190,18 +202,9 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const CeUpK p) {
   if (x >= 0 && x < p.W) { xlo = ce_first_out(x, sw, p.W, p.OW); xhi = (x + 1 < p.W) ? ce_first_out(x + 1, sw, p.W, p.OW) : p.OW; }
   const bool xlast = x == p.W - 1;
   const int x1 = x + (x < p.W - 1 ? 1 : 0);
-  const bool vec = (p.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0) && p.ld >= CP;
+  const bool vec = (p.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0) && p.ld >= CP;      // px_vec_ok
   const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
   const gfloat* cw = (const gfloat*)p.cw;
-  auto load_px = [&](const float* q, float (&v)[CP]) {
-    if (vec) {
-#pragma unroll
-      for (int c = 0; c < CP; c += 4) { const float4 f = ld4(q + c); v[c] = f.x; v[c + 1] = f.y; v[c + 2] = f.z; v[c + 3] = f.w; }
-    } else {
-#pragma unroll
-      for (int c = 0; c < CC; ++c) v[c] = ((const gfloat*)q)[c];
-    }
-  };
   float lsum = 0.f;
   float carry[NOUT];
 #pragma unroll
@@ -223,16 +226,16 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const CeUpK p) {
       float lh0 = 0.f, lh1 = 0.f;
       if (Y < yhi && xhi > xlo) {
         int h0, h1;
-        ce_src_index(Y, sh, p.H, h0, h1, lh0, lh1);
+        src_index(Y, sh, p.H, h0, h1, lh0, lh1);
         const float* r0 = p.x + ((long)(n * p.H + h0) * p.W) * p.ld;
         const float* r1 = p.x + ((long)(n * p.H + h1) * p.W) * p.ld;
         float v00[CP], v01[CP], v10[CP], v11[CP];
-        load_px(r0 + (long)x * p.ld, v00); load_px(r0 + (long)x1 * p.ld, v01);
-        load_px(r1 + (long)x * p.ld, v10); load_px(r1 + (long)x1 * p.ld, v11);
+        load_px<CC>(r0 + (long)x * p.ld, v00, vec); load_px<CC>(r0 + (long)x1 * p.ld, v01, vec);
+        load_px<CC>(r1 + (long)x * p.ld, v10, vec); load_px<CC>(r1 + (long)x1 * p.ld, v11, vec);
         const int64_t __attribute__((address_space(1)))* tp = tgt + ((long)n * p.OH + Y) * p.OW;
         for (int X = xlo; X < xhi; ++X) {
           int w0, w1; float lw0, lw1;
-          ce_src_index(X, sw, p.W, w0, w1, lw0, lw1);
+          src_index(X, sw, p.W, w0, w1, lw0, lw1);
           const long tg = tp[X];
           const bool valid = tg != p.ignore && tg >= 0 && tg < CC;
           const float w = valid ? (cw ? cw[tg] : 1.f) : 0.f;
@@ -321,87 +324,90 @@ bool ceu_ok(int N, int H, int W, int OH, int OW, int C) {
 // order-independent, exact.  Loss and entropy leave the workgroup as two partials reduced in a fixed order.
 constexpr int SCU_W = 64, SCU_WAVES = 4, SCU_R = 8;      // tile: 64 columns x (4 waves x 8 rows)
 
-struct ScoreUpK {
-  const float* x; int ld; int N, H, W, OH, OW;
+// The walk of a thread: its column X of the tile, SCU_R rows; pixel(pix, z) gets the flat index of each high-resolution pixel
+// and its CC interpolated logits.  VEC: the loader's 16-byte form (host check px_vec_ok); a compile-time switch, so that no
+// register array crosses a branch merge (the run-time form of ce_up_kernel keeps 40 bytes of scratch per lane for it)
+template <int CC, bool VEC, class F>
+__device__ __forceinline__ void scu_walk(const UpSrc& p, F&& pixel) {
+  const int lane = threadIdx.x & (SCU_W - 1), wv = threadIdx.x / SCU_W;
+  const int X = blockIdx.x * SCU_W + lane, n = blockIdx.z;
+  if (X >= p.OW) return;
+  const int ybeg = (blockIdx.y * SCU_WAVES + wv) * SCU_R;
+  const int yend = ybeg + SCU_R < p.OH ? ybeg + SCU_R : p.OH;
+  const float sh = (float)p.H / (float)p.OH, sw = (float)p.W / (float)p.OW;
+  int w0, w1; float lw0, lw1;
+  src_index(X, sw, p.W, w0, w1, lw0, lw1);
+  float t0[CC], t1[CC];
+  int ph0 = -1, ph1 = -1;
+  for (int Y = ybeg; Y < yend; ++Y) {
+    int h0, h1; float lh0, lh1;
+    src_index(Y, sh, p.H, h0, h1, lh0, lh1);
+    if (h0 != ph0 || h1 != ph1) {                                // wave-uniform: Y is
+      const float* r0 = p.x + ((long)(n * p.H + h0) * p.W) * p.ld;
+      const float* r1 = p.x + ((long)(n * p.H + h1) * p.W) * p.ld;
+      float a[cpad(CC)], b[cpad(CC)];
+      load_px<CC>(r0 + (long)w0 * p.ld, a, VEC); load_px<CC>(r0 + (long)w1 * p.ld, b, VEC);
+#pragma unroll
+      for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
+      load_px<CC>(r1 + (long)w0 * p.ld, a, VEC); load_px<CC>(r1 + (long)w1 * p.ld, b, VEC);
+#pragma unroll
+      for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
+      ph0 = h0; ph1 = h1;
+    }
+    float z[CC];
+#pragma unroll
+    for (int c = 0; c < CC; ++c) z[c] = lh0 * t0[c] + lh1 * t1[c];
+    pixel(((long)n * p.OH + Y) * p.OW + X, z);
+  }
+}
+// se = Σe, sx = Σe·d over d = z - mx, e = exp(d): loss (log se) and entropy (log se - sx/se) of a pixel from one sweep
+template <int CC>
+__device__ __forceinline__ void exp_sweep(const float (&z)[CC], float mx, float& se, float& sx) {
+  se = 0.f; sx = 0.f;
+#pragma unroll
+  for (int c = 0; c < CC; ++c) { const float d = z[c] - mx; const float e = __expf(d); se += e; sx += e * d; }
+}
+
+struct ScoreUpK : UpSrc {
   const int64_t* target; const float* cw; int ignore;
   unsigned long long* cm; uint8_t* pred;
   float* ws; int nblk;
 };
 
-// VEC: 16-byte loads of a pixel's CP channels (host check: ld % 4 == 0, ld >= CP, aligned base); a compile-time switch, so that no
-// register array crosses a branch merge (the run-time form of ce_up_kernel keeps 40 bytes of scratch per lane for it)
 template <int CC, bool VEC>
 __global__ void __launch_bounds__(256) score_up_kernel(const ScoreUpK p) {
-  constexpr int CP = (CC + 3) / 4 * 4;
   __shared__ unsigned hist[CC * CC];
   __shared__ float shs[4];
-  const int t = threadIdx.x, lane = t & (SCU_W - 1), wv = t / SCU_W;
+  const int t = threadIdx.x;
   for (int i = t; i < CC * CC; i += 256) hist[i] = 0u;
   __syncthreads();
-  const int X = blockIdx.x * SCU_W + lane, n = blockIdx.z;
-  const int ybeg = (blockIdx.y * SCU_WAVES + wv) * SCU_R;
-  const int yend = ybeg + SCU_R < p.OH ? ybeg + SCU_R : p.OH;
-  const float sh = (float)p.H / (float)p.OH, sw = (float)p.W / (float)p.OW;
   const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
   const gfloat* cw = (const gfloat*)p.cw;
-  auto load_px = [](const float* q, float (&v)[CP]) {
-    if constexpr (VEC) {
-#pragma unroll
-      for (int c = 0; c < CP; c += 4) { const float4 f = ld4(q + c); v[c] = f.x; v[c + 1] = f.y; v[c + 2] = f.z; v[c + 3] = f.w; }
-    } else {
-#pragma unroll
-      for (int c = 0; c < CC; ++c) v[c] = ((const gfloat*)q)[c];
-    }
-  };
   float lsum = 0.f, esum = 0.f;
-  if (X < p.OW) {
-    int w0, w1; float lw0, lw1;
-    ce_src_index(X, sw, p.W, w0, w1, lw0, lw1);
-    float t0[CC], t1[CC];
-    int ph0 = -1, ph1 = -1;
-    int key = -1; unsigned run = 0;                              // pending (gt, pred) run of this column
-    for (int Y = ybeg; Y < yend; ++Y) {
-      int h0, h1; float lh0, lh1;
-      ce_src_index(Y, sh, p.H, h0, h1, lh0, lh1);
-      if (h0 != ph0 || h1 != ph1) {                              // wave-uniform: Y is
-        const float* r0 = p.x + ((long)(n * p.H + h0) * p.W) * p.ld;
-        const float* r1 = p.x + ((long)(n * p.H + h1) * p.W) * p.ld;
-        float a[CP], b[CP];
-        load_px(r0 + (long)w0 * p.ld, a); load_px(r0 + (long)w1 * p.ld, b);
+  int key = -1; unsigned run = 0;                                // pending (gt, pred) run of this column
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
+    const long tg = tgt[pix];
+    const bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+    float mx = -INFINITY, zt = 0.f; int am = 0;
 #pragma unroll
-        for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
-        load_px(r1 + (long)w0 * p.ld, a); load_px(r1 + (long)w1 * p.ld, b);
-#pragma unroll
-        for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
-        ph0 = h0; ph1 = h1;
-      }
-      const long pix = ((long)n * p.OH + Y) * p.OW + X;
-      const long tg = tgt[pix];
-      const bool valid = tg != p.ignore && tg >= 0 && tg < CC;
-      float z[CC];
-      float mx = -INFINITY, zt = 0.f; int am = 0;
-#pragma unroll
-      for (int c = 0; c < CC; ++c) {
-        z[c] = lh0 * t0[c] + lh1 * t1[c];
-        if (z[c] > mx) { mx = z[c]; am = c; }                    // strict: a tie keeps the lowest channel
-        if (c == tg) zt = z[c];
-      }
-      float se = 0.f, sx = 0.f;
-#pragma unroll
-      for (int c = 0; c < CC; ++c) { const float d = z[c] - mx; const float e = __expf(d); se += e; sx += e * d; }
-      const float lse = logf(se);
-      if (valid) lsum += (cw ? cw[tg] : 1.f) * (lse + mx - zt);
-      esum += lse - sx / se;
-      if (p.pred) p.pred[pix] = (uint8_t)am;
-      const int k = (tg >= 0 && tg < CC) ? (int)tg * CC + am : -1;   // the evaluator's mask: labels in [0, C), whatever ignore_index is
-      if (k != key) {
-        if (key >= 0) atomicAdd(&hist[key], run);
-        key = k; run = 0;
-      }
-      ++run;
+    for (int c = 0; c < CC; ++c) {
+      if (z[c] > mx) { mx = z[c]; am = c; }                      // strict: a tie keeps the lowest channel
+      if (c == tg) zt = z[c];
     }
-    if (key >= 0) atomicAdd(&hist[key], run);
-  }
+    float se, sx;
+    exp_sweep<CC>(z, mx, se, sx);
+    const float lse = logf(se);
+    if (valid) lsum += (cw ? cw[tg] : 1.f) * (lse + mx - zt);
+    esum += lse - sx / se;
+    if (p.pred) p.pred[pix] = (uint8_t)am;
+    const int k = (tg >= 0 && tg < CC) ? (int)tg * CC + am : -1;     // the evaluator's mask: labels in [0, C), whatever ignore_index is
+    if (k != key) {
+      if (key >= 0) atomicAdd(&hist[key], run);
+      key = k; run = 0;
+    }
+    ++run;
+  });
+  if (key >= 0) atomicAdd(&hist[key], run);
   lsum = block_sum(lsum, shs);
   esum = block_sum(esum, shs);
   const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
@@ -426,21 +432,23 @@ __global__ void __launch_bounds__(256) score_sum_kernel(const float* ws, int n, 
   }
 }
 
+// the launch grid of the two gather heads (one workgroup per tile and image) and its workgroup count, which sizes their workspaces
+dim3 scu_grid(int N, int OH, int OW) { return dim3(cdiv(OW, SCU_W), cdiv(OH, SCU_WAVES * SCU_R), N); }
+long scu_blocks(int N, int OH, int OW) { const dim3 g = scu_grid(N, OH, OW); return (long)(int)g.z * (int)g.y * (int)g.x; }
 bool scu_ok(int N, int H, int W, int OH, int OW, int C) {
   if (C != 19 || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return false;
-  return N <= 65535 && cdiv(OH, SCU_WAVES * SCU_R) <= 65535 && (long)N * cdiv(OH, SCU_WAVES * SCU_R) * cdiv(OW, SCU_W) < (1L << 30);
+  return N <= 65535 && scu_grid(N, OH, OW).y <= 65535 && scu_blocks(N, OH, OW) < (1L << 30);
 }
 
 // ---- fused logits up-sampling + early-exit gate (decoder.py:28 + operations.py:161-180) -----------------------------------
 // The two gates of dynamic inference that need no trained EDM: the normalised Shannon entropy of the up-sampled prediction and the
-// share of pixels whose top softmax probability passes a threshold.  The walk is score_up_kernel's (same tile, same interpolation
-// z = lh0*t0 + lh1*t1, one max sweep, one exp sweep) without target, histogram, loss and map.  Per pixel: se = Σe, sx = Σe·d with
+// share of pixels whose top softmax probability passes a threshold.  The walk is scu_walk (same tile, same interpolation
+// z = lh0*t0 + lh1*t1), then one max sweep and the exp sweep; no target, histogram, loss or map.  Per pixel: se = Σe, sx = Σe·d with
 // d = z - max, entropy term log se - sx/se, top probability pmax = 1/se (the largest e is exp(0) = 1), counted when pmax > *max_thr.
 // A workgroup leaves one fp32 entropy partial and one count, write-through; the workgroup that arrives LAST (csrc/bnfin.h ticket, as
 // csrc/edm.hip) adds each image's partials in a FIXED order (fp64; the counts are integers), writes (entropy, share) to `out` and to
 // the pinned host words the gate reads, and puts the ticket back to zero: one launch, bit-reproducible, graph-replayable, nothing spins.
-struct GateUpK {
-  const float* x; int ld; int N, H, W, OH, OW;
+struct GateUpK : UpSrc {
   const float* thr;
   float* out; float* out_host;
   unsigned* counter; float* part; unsigned* cnt;          // ws: [ticket, 16 bytes][nblk floats][nblk counts], image-major
@@ -450,59 +458,23 @@ struct GateUpK {
 
 template <int CC, bool VEC>
 __global__ void __launch_bounds__(256) gate_up_kernel(const GateUpK p) {
-  constexpr int CP = (CC + 3) / 4 * 4;
   __shared__ float shs[4];
   __shared__ unsigned shc[4];
   __shared__ double shd[4];
   __shared__ unsigned long long shl[4];
   __shared__ unsigned flag;
   const int t = threadIdx.x, lane = t & (SCU_W - 1), wv = t / SCU_W;
-  const int X = blockIdx.x * SCU_W + lane, n = blockIdx.z;
-  const int ybeg = (blockIdx.y * SCU_WAVES + wv) * SCU_R;
-  const int yend = ybeg + SCU_R < p.OH ? ybeg + SCU_R : p.OH;
-  const float sh = (float)p.H / (float)p.OH, sw = (float)p.W / (float)p.OW;
   const float thr = *(const gfloat*)p.thr;
-  auto load_px = [](const float* q, float (&v)[CP]) {
-    if constexpr (VEC) {
-#pragma unroll
-      for (int c = 0; c < CP; c += 4) { const float4 f = ld4(q + c); v[c] = f.x; v[c + 1] = f.y; v[c + 2] = f.z; v[c + 3] = f.w; }
-    } else {
-#pragma unroll
-      for (int c = 0; c < CC; ++c) v[c] = ((const gfloat*)q)[c];
-    }
-  };
   float esum = 0.f; unsigned hit = 0u;
-  if (X < p.OW) {
-    int w0, w1; float lw0, lw1;
-    ce_src_index(X, sw, p.W, w0, w1, lw0, lw1);
-    float t0[CC], t1[CC];
-    int ph0 = -1, ph1 = -1;
-    for (int Y = ybeg; Y < yend; ++Y) {
-      int h0, h1; float lh0, lh1;
-      ce_src_index(Y, sh, p.H, h0, h1, lh0, lh1);
-      if (h0 != ph0 || h1 != ph1) {                              // wave-uniform: Y is
-        const float* r0 = p.x + ((long)(n * p.H + h0) * p.W) * p.ld;
-        const float* r1 = p.x + ((long)(n * p.H + h1) * p.W) * p.ld;
-        float a[CP], b[CP];
-        load_px(r0 + (long)w0 * p.ld, a); load_px(r0 + (long)w1 * p.ld, b);
+  scu_walk<CC, VEC>(p, [&](long, const float (&z)[CC]) {
+    float mx = -INFINITY;
 #pragma unroll
-        for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
-        load_px(r1 + (long)w0 * p.ld, a); load_px(r1 + (long)w1 * p.ld, b);
-#pragma unroll
-        for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
-        ph0 = h0; ph1 = h1;
-      }
-      float z[CC];
-      float mx = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < CC; ++c) { z[c] = lh0 * t0[c] + lh1 * t1[c]; mx = fmaxf(mx, z[c]); }
-      float se = 0.f, sx = 0.f;
-#pragma unroll
-      for (int c = 0; c < CC; ++c) { const float d = z[c] - mx; const float e = __expf(d); se += e; sx += e * d; }
-      esum += logf(se) - sx / se;
-      hit += (1.f / se > thr) ? 1u : 0u;
-    }
-  }
+    for (int c = 0; c < CC; ++c) mx = fmaxf(mx, z[c]);
+    float se, sx;
+    exp_sweep<CC>(z, mx, se, sx);
+    esum += logf(se) - sx / se;
+    hit += (1.f / se > thr) ? 1u : 0u;
+  });
   esum = block_sum(esum, shs);
   for (int m = 32; m > 0; m >>= 1) hit += __shfl_xor(hit, m);
   if (lane == 0) shc[wv] = hit;
@@ -585,7 +557,7 @@ extern "C" int addk_ce_upsample_fwd_bwd(const addk_ce_upsample_args* a, void* st
   ADDK_REQUIRE(a->ld >= a->C && a->ldg >= a->C, "ce_upsample: short stride");
   ADDK_REQUIRE(ceu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "ce_upsample: unsupported shape (19 classes, at most %d output rows per input row)", CEU_MAXBAND);
   CeUpK k;
-  k.x = a->logits; k.ld = a->ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
+  static_cast<UpSrc&>(k) = up_src(a);
   k.target = a->target; k.cw = a->class_w; k.ignore = a->ignore_index; k.wsum = a->wsum; k.scale = a->scale;
   k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate; k.ws = a->ws; k.HB = ceu_hb(a->H);
   hipStream_t st = (hipStream_t)stream;
@@ -601,20 +573,20 @@ extern "C" int addk_score_upsample_supported(int32_t N, int32_t H, int32_t W, in
   return scu_ok(N, H, W, OH, OW, C) ? 1 : 0;
 }
 extern "C" int64_t addk_score_upsample_ws_floats(int32_t N, int32_t OH, int32_t OW) {
-  return 2 * (int64_t)N * cdiv(OH, SCU_WAVES * SCU_R) * cdiv(OW, SCU_W);
+  return 2 * scu_blocks(N, OH, OW);
 }
 extern "C" int addk_score_upsample(const addk_score_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->target && a->wsum && a->loss_out && a->ent_out && a->cm && a->ws, "score_upsample: null pointer");
   ADDK_REQUIRE(a->ld >= a->C, "score_upsample: short stride");
   ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "score_upsample: unsupported shape (19 classes)");
-  const dim3 grid(cdiv(a->OW, SCU_W), cdiv(a->OH, SCU_WAVES * SCU_R), a->N);
+  const dim3 grid = scu_grid(a->N, a->OH, a->OW);
   ScoreUpK k;
-  k.x = a->logits; k.ld = a->ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
+  static_cast<UpSrc&>(k) = up_src(a);
   k.target = a->target; k.cw = a->class_w; k.ignore = a->ignore_index;
   k.cm = reinterpret_cast<unsigned long long*>(a->cm); k.pred = a->pred_out;
-  k.ws = a->ws; k.nblk = (int)(grid.x * grid.y * grid.z);
+  k.ws = a->ws; k.nblk = (int)scu_blocks(a->N, a->OH, a->OW);
   hipStream_t st = (hipStream_t)stream;
-  if (a->ld % 4 == 0 && a->ld >= 20 && aligned16(a->logits))
+  if (px_vec_ok<19>(a->logits, a->ld))
     hipLaunchKernelGGL((score_up_kernel<19, true>), grid, dim3(256), 0, st, k);
   else
     hipLaunchKernelGGL((score_up_kernel<19, false>), grid, dim3(256), 0, st, k);
@@ -629,15 +601,15 @@ extern "C" int addk_gate_upsample_supported(int32_t N, int32_t H, int32_t W, int
 }
 extern "C" int64_t addk_gate_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW) {
   if (N <= 0 || OH <= 0 || OW <= 0) return 0;
-  return 16 + 8 * (int64_t)N * cdiv(OH, SCU_WAVES * SCU_R) * cdiv(OW, SCU_W);
+  return 16 + 8 * scu_blocks(N, OH, OW);
 }
 extern "C" int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->max_thr && a->out && a->ws, "gate_upsample: null pointer");
   ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample: unsupported shape (19 classes)");
   ADDK_REQUIRE(a->ld >= a->C, "gate_upsample: short stride");
-  const dim3 grid(cdiv(a->OW, SCU_W), cdiv(a->OH, SCU_WAVES * SCU_R), a->N);
+  const dim3 grid = scu_grid(a->N, a->OH, a->OW);
   GateUpK k;
-  k.x = a->logits; k.ld = a->ld; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
+  static_cast<UpSrc&>(k) = up_src(a);
   k.thr = a->max_thr; k.out = a->out; k.out_host = a->out_host;
   k.nblk_img = (int)(grid.x * grid.y);
   k.counter = (unsigned*)a->ws;
@@ -645,7 +617,7 @@ extern "C" int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream
   k.cnt = (unsigned*)(k.part + (long)a->N * k.nblk_img);
   k.npix = (double)a->OH * (double)a->OW; k.ent_div = log(19.0) * k.npix;
   hipStream_t st = (hipStream_t)stream;
-  if (a->ld % 4 == 0 && a->ld >= 20 && aligned16(a->logits))
+  if (px_vec_ok<19>(a->logits, a->ld))
     hipLaunchKernelGGL((gate_up_kernel<19, true>), grid, dim3(256), 0, st, k);
   else
     hipLaunchKernelGGL((gate_up_kernel<19, false>), grid, dim3(256), 0, st, k);

@@ -1279,65 +1279,79 @@ class Graph:
         return res
 
     def resize_to_nchw(self, src, OH, OW):
-        """Final logits resize (decoder.py:28) into a contiguous [N,C,OH,OW] tensor.  Returns an OutRef.
-        In a fused training step (`self.fuse_ce`, set by train.TrainStep) nobody reads the full-resolution logits: the
-        resize is not emitted at all and the OutRef carries what the fused up-sampling + cross-entropy launch needs
-        (`addk_ce_upsample_fwd_bwd`, placed at the head of the backward list with the loss parameters TrainStep binds)."""
-        lib = self.lib
+        """Final logits resize (decoder.py:28).  Returns an OutRef.  The plan chooses who consumes the low-resolution logits: the loss head
+        of a fused training step (_ce_head), the scoring head of a validation plan (_score_head), the gate of an early exit (gate_head),
+        or nobody: the resize into a contiguous [N,C,OH,OW] tensor, and its backward."""
         assert src.bn is None and not src.relu
-        N, H, W, Cc = src.N, src.H, src.W, src.C
         if (self.fuse_ce and self.want_grad and src.needs_grad
-                and lib.addk_ce_upsample_supported(N, H, W, OH, OW, Cc) == 1):
-            out = OutRef(None)
-            out.fused_ce, out.shape, out.ce = True, (N, Cc, OH, OW), None
-
-            def emit_ce():
-                assert out.ce is not None, 'fused logits output without a loss binding'
-                a = L.CeUpsampleArgs()
-                s = self.src(src)
-                a.logits, a.ld = s.x, s.ld
-                a.N, a.H, a.W, a.C, a.OH, a.OW = N, H, W, Cc, OH, OW
-                ce = out.ce
-                a.target, a.class_w, a.ignore_index = ce['target'].data_ptr(), ce['class_w'], ce['ignore_index']
-                a.wsum, a.scale, a.loss_out = ce['wsum'].data_ptr(), ce['scale'], ce['loss'].data_ptr()
-                gs, a.accumulate, _ = self._grad_into(src)
-                a.g, a.ldg = gs.ptr, gs.ld
-                ws = torch.zeros(int(lib.addk_ce_upsample_ws_floats(N, H, W)), dtype=torch.float32, device=self.device)
-                a.ws = ws.data_ptr()
-                self.keep += [a, ws]
-                self._add(self.bwd, 'ce_upsample', lib.addk_ce_upsample_fwd_bwd, C.byref(a),
-                          rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
-            self._bwd_emitters.append(emit_ce)
-            return out
+                and self.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1):
+            return self._ce_head(src, OH, OW)
         if self.fuse_score and not self.want_grad:
             return self._score_head(src, OH, OW)
         if self.gate is not None and not self.want_grad:
             return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'])
-        y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=self.device)
-        self.nbytes += y.numel() * 4
-        ar = L.ResizeArgs()
-        ar.src = self.src(src)
-        ar.N, ar.H, ar.W, ar.OH, ar.OW = N, H, W, OH, OW
-        ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
-        self.keep.append(ar)
-        self._add(self.fwd, 'resize_nchw', lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])
+        y, emit_resize = self._logits_resize(src, OH, OW)
+        emit_resize()
         out = OutRef(y)
         if self.want_grad and src.needs_grad:
             def emit_bwd():
                 if out.dy_ptr is None and not out.dynamic:
                     return
                 ba = L.ResizeBwdArgs()
-                ba.dy = out.dy_ptr
-                ba.lddy, ba.nchw_in = 0, 1
-                ba.dy_scale = out.dy_scale
+                ba.dy, ba.lddy, ba.nchw_in, ba.dy_scale = out.dy_ptr, 0, 1, out.dy_scale
                 ba.src = self.src(src)
-                ba.N, ba.H, ba.W, ba.OH, ba.OW = N, H, W, OH, OW
+                ba.N, ba.H, ba.W, ba.OH, ba.OW = src.N, src.H, src.W, OH, OW
                 gs, ba.accumulate, _ = self._grad_into(src)
                 ba.g, ba.ldg = gs.ptr, gs.ld
                 self.keep.append(ba)
                 out.bwd_args = ba
-                self._add(self.bwd, 'resize_nchw_bwd', lib.addk_resize_bwd, C.byref(ba), rd=self.lz(src), wr=[gs])
+                self._add(self.bwd, 'resize_nchw_bwd', self.lib.addk_resize_bwd, C.byref(ba), rd=self.lz(src), wr=[gs])
             self._bwd_emitters.append(emit_bwd)
+        return out
+
+    def _logits_resize(self, src, OH, OW):
+        """The full-resolution logits: (y [N,C,OH,OW], emit); emit() appends the `resize_nchw` launch that writes y, now or later."""
+        y = torch.empty((src.N, src.C, OH, OW), dtype=torch.float32, device=self.device)
+        self.nbytes += y.numel() * 4
+        ar = L.ResizeArgs()
+        ar.src = self.src(src)
+        ar.N, ar.H, ar.W, ar.OH, ar.OW = src.N, src.H, src.W, OH, OW
+        ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
+        self.keep.append(ar)
+        return y, lambda: self._add(self.fwd, 'resize_nchw', self.lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])
+
+    def _up_args(self, cls, src, OH, OW):
+        """A *UpsampleArgs struct with the prefix the three share filled in: the low-resolution NHWC logits and the two grids."""
+        a, s = cls(), self.src(src)
+        a.logits, a.ld, a.N, a.H, a.W, a.C, a.OH, a.OW = s.x, s.ld, src.N, src.H, src.W, src.C, OH, OW
+        return a
+
+    @staticmethod
+    def _bind_loss(a, b):
+        """The loss binding a step attached to an OutRef (`ce` / `score`) into the loss head's or the scoring head's arguments."""
+        a.target, a.class_w, a.ignore_index = b['target'].data_ptr(), b['class_w'], b['ignore_index']
+        a.wsum, a.scale, a.loss_out = b['wsum'].data_ptr(), b['scale'], b['loss'].data_ptr()
+
+    def _ce_head(self, src, OH, OW):
+        """Logits output of a fused training step (`self.fuse_ce`, set by train.TrainStep): nobody reads the full-resolution logits, so
+        the resize is not emitted at all and the OutRef carries `shape` and the `ce` slot TrainStep binds; finalize() then places ONE
+        fused up-sampling + cross-entropy launch (`addk_ce_upsample_fwd_bwd`) at the head of the backward list."""
+        out = OutRef(None)
+        out.fused_ce, out.shape = True, (src.N, src.C, OH, OW)
+
+        def emit_ce():
+            ce = out.ce
+            assert ce is not None, 'fused logits output without a loss binding'
+            a = self._up_args(L.CeUpsampleArgs, src, OH, OW)
+            self._bind_loss(a, ce)
+            gs, a.accumulate, _ = self._grad_into(src)
+            a.g, a.ldg = gs.ptr, gs.ld
+            ws = torch.zeros(int(self.lib.addk_ce_upsample_ws_floats(src.N, src.H, src.W)), dtype=torch.float32, device=self.device)
+            a.ws = ws.data_ptr()
+            self.keep += [a, ws]
+            self._add(self.bwd, 'ce_upsample', self.lib.addk_ce_upsample_fwd_bwd, C.byref(a),
+                      rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
+        self._bwd_emitters.append(emit_ce)
         return out
 
     def _score_head(self, src, OH, OW):
@@ -1350,39 +1364,29 @@ class Graph:
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
         out = OutRef(None)
-        out.fused_score, out.shape, out.score = True, (N, Cc, OH, OW), None
+        out.fused_score, out.shape = True, (N, Cc, OH, OW)
         tag = self.tag
 
         def emit_score():
-            sc = out.score
+            sc, first = out.score, len(self.fwd)
             assert sc is not None, 'fused logits output without a score binding'
-            first = len(self.fwd)
             tgt, wsum, loss, ent, cm, pred = sc['target'], sc['wsum'], sc['loss'], sc['entropy'], sc['confusion'], sc.get('pred')
             if lib.addk_score_upsample_supported(N, H, W, OH, OW, Cc) == 1:
-                a = L.ScoreUpsampleArgs()
-                s = self.src(src)
-                a.logits, a.ld = s.x, s.ld
-                a.N, a.H, a.W, a.C, a.OH, a.OW = N, H, W, Cc, OH, OW
-                a.target, a.class_w, a.ignore_index = tgt.data_ptr(), sc['class_w'], sc['ignore_index']
-                a.wsum, a.scale = wsum.data_ptr(), sc['scale']
-                a.loss_out, a.ent_out, a.cm = loss.data_ptr(), ent.data_ptr(), cm.data_ptr()
-                a.pred_out = pred.data_ptr() if pred is not None else None
+                a = self._up_args(L.ScoreUpsampleArgs, src, OH, OW)
+                self._bind_loss(a, sc)
+                a.ent_out, a.cm, a.pred_out = ent.data_ptr(), cm.data_ptr(), pred.data_ptr() if pred is not None else None
                 ws = torch.zeros(int(lib.addk_score_upsample_ws_floats(N, OH, OW)), dtype=torch.float32, device=self.device)
                 a.ws = ws.data_ptr()
                 self.keep += [a, ws]
                 self._add(self.fwd, 'score_upsample', lib.addk_score_upsample, C.byref(a),
                           rd=self.lz(src) + [tgt, wsum], wr=[loss, ent, cm, pred, ws])
             else:
-                y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=self.device)
+                y, emit_resize = self._logits_resize(src, OH, OW)
                 am = torch.empty((N, OH, OW), dtype=torch.int64, device=self.device)
                 ws = torch.zeros(int(lib.addk_ce_ws_floats(N, OH * OW)), dtype=torch.float32, device=self.device)
-                self.nbytes += y.numel() * 4 + am.numel() * 8
-                ar = L.ResizeArgs()
-                ar.src = self.src(src)
-                ar.N, ar.H, ar.W, ar.OH, ar.OW = N, H, W, OH, OW
-                ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
-                self.keep += [ar, y, am, ws]
-                self._add(self.fwd, 'resize_nchw', lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])
+                self.nbytes += am.numel() * 8
+                self.keep += [y, am, ws]
+                emit_resize()
                 self._add(self.fwd, 'ce_fwd_bwd', lib.addk_ce_fwd_bwd, y.data_ptr(), tgt.data_ptr(), N, Cc, OH * OW, sc['class_w'],
                           sc['ignore_index'], wsum.data_ptr(), sc['scale'], loss.data_ptr(), None, ws.data_ptr(),
                           rd=[y, tgt, wsum], wr=[loss, ws])
@@ -1399,37 +1403,25 @@ class Graph:
         return out
 
     def gate_head(self, src, OH, OW, host_out, thr, kind='entropy'):
-        """Logits output of a gated early exit (`self.gate`, set by dynamic.GatePlan): the gate value of the exit's full-resolution
-        prediction (modeling/operations.py:161-180) and, separately, the resize that writes the [N,C,OH,OW] logits.  Fused form: ONE
-        `gate_upsample` launch (`addk_gate_upsample`, csrc/loss.hip) reads the decoder's low-resolution NHWC logits and writes (entropy,
-        share) to the OutRef's `gate_out` [N,2] and to the pinned words `host_out`; the `resize_nchw` launch FOLLOWS it, so a plan cut
-        at `gate_cut` replays the resize only for an image that leaves here.  `thr`: the device word the 'max' gate compares against.
+        """Logits output of a gated early exit (`self.gate`, set by dynamic.GatePlan): the exit's gate value (modeling/operations.py:161-180)
+        and, separately, the resize that writes the [N,C,OH,OW] logits.  Fused form: ONE `gate_upsample` launch (`addk_gate_upsample`)
+        reads the low-resolution NHWC logits and writes (entropy, share) to the OutRef's `gate_out` [N,2] and to the pinned words `host_out`;
+        the `resize_nchw` launch FOLLOWS it, so a plan cut at `gate_cut` replays the resize only for an image that leaves here.  `thr`: the
+        device word the 'max' gate compares against.
         Where the library does not take the shape (`addk_gate_upsample_supported` == 0, e.g. C != 19) or with ADDK_FUSE_GATE=0, the same
         plan uses the stand-alone kernels on the materialised logits — `resize_nchw` first, then `entropy_sum` ('entropy': gate_out[0, 0]
         holds the un-normalised sum, `gate_scale` the factor the host applies) or a count in torch ops ('max': gate_out[0, 1]); nothing
         is left behind the cut and the host copies `gate_out` itself (`gate_fused` False)."""
         lib = self.lib
-        assert src.bn is None and not src.relu
         N, H, W, Cc = src.N, src.H, src.W, src.C
-        y = torch.empty((N, Cc, OH, OW), dtype=torch.float32, device=self.device)
+        y, emit_resize = self._logits_resize(src, OH, OW)
         gout = torch.zeros((N, 2), dtype=torch.float32, device=self.device)
-        self.nbytes += y.numel() * 4
-        ar = L.ResizeArgs()
-        ar.src = self.src(src)
-        ar.N, ar.H, ar.W, ar.OH, ar.OW = N, H, W, OH, OW
-        ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
-        self.keep += [ar, gout, thr, host_out]
+        self.keep += [gout, thr, host_out]
         out = OutRef(y)
-        out.gate_out, out.gate_scale = gout, 1.0
+        out.gate_out = gout
         out.gate_fused = _on('ADDK_FUSE_GATE') and lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
-
-        def emit_resize():
-            self._add(self.fwd, 'resize_nchw', lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])
         if out.gate_fused:
-            a = L.GateUpsampleArgs()
-            s = self.src(src)
-            a.logits, a.ld = s.x, s.ld
-            a.N, a.H, a.W, a.C, a.OH, a.OW = N, H, W, Cc, OH, OW
+            a = self._up_args(L.GateUpsampleArgs, src, OH, OW)
             ws = self.buf((int(lib.addk_gate_upsample_ws_bytes(N, OH, OW)) + 3) // 4, zero=True)
             a.max_thr, a.out, a.ws = thr.data_ptr(), gout.data_ptr(), ws.ptr
             a.out_host = host_out.data_ptr() if host_out is not None else None
@@ -1601,12 +1593,19 @@ class OutRef:
     """A plan output: tensor + how its incoming gradient pointer is patched per backward call."""
 
     def __init__(self, y):
-        self.y = y
+        self.y = y               # [N,C,OH,OW] logits; None where a head consumes the low-resolution logits instead
         self.dy_ptr, self.dy_scale, self.dynamic = None, None, True
         self.bwd_args = None     # ResizeBwdArgs (logits path)
-        self.fused_ce = False    # logits consumed by the fused up-sampling + cross-entropy launch (train.TrainStep): y is None
-        self.fused_score = False  # logits consumed by the scoring launch of a validation plan (validate.ValidationStep): y is None
         self.bwd_cmd = None      # generic nhwc path
+        self.shape = None        # (N, C, OH, OW) of the logits a fused head stands for (y is None)
+        self.fused_ce = False    # logits consumed by the fused up-sampling + cross-entropy launch (train.TrainStep): y is None
+        self.ce = None           # its loss binding, set by TrainStep: target, class_w, ignore_index, wsum, scale, loss
+        self.fused_score = False  # logits consumed by the scoring launch of a validation plan (validate.ValidationStep): y is None
+        self.score = None        # its binding, set by ValidationStep: the loss binding + entropy, confusion, pred
+        self.gate_out = None     # [N,2] device tensor of a gated exit: (entropy, share of pixels above the threshold)
+        self.gate_scale = 1.0    # factor the host applies to gate_out[:, 0] (the stand-alone entropy kernel leaves a sum)
+        self.gate_fused = False  # the gate launch writes the pinned host words itself; else the host copies gate_out
+        self.gate_cut = None     # index in the forward list behind the gate: what follows runs only for an image that leaves here
 
     def set_grad(self, gy):
         gy = gy.contiguous()

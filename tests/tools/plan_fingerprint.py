@@ -168,10 +168,10 @@ def _fingerprint(g, lists, extra, dump, label):
 
 
 # ---------------------------------------------------------------- the plans
-def _model(F, sync=False, train=True):
+def _model(F, sync=False, train=True, classes=19):
     from _util import ARCH_C2, GENOTYPE_AUTODEEPLAB, make_args
     from addk.modeling.ADD import ADD
-    m = ADD(ARCH_C2['network_arch'], ARCH_C2['C_index'], GENOTYPE_AUTODEEPLAB, 19, make_args(F, sync_bn=sync), ARCH_C2['low_level_layer'])
+    m = ADD(ARCH_C2['network_arch'], ARCH_C2['C_index'], GENOTYPE_AUTODEEPLAB, classes, make_args(F, sync_bn=sync), ARCH_C2['low_level_layer'])
     return m.train(train)
 
 
@@ -232,6 +232,37 @@ def _dynamic(F, shape):
     return g, lists, extra, (plan, m, edm)
 
 
+def _validation(F, shape, classes=19):
+    """the validation pass: one scoring head per exit (7 classes: the stand-alone kernels inside the plan), class weights and maps"""
+    from addk.validate import ValidationStep
+    m = _model(F, classes=classes)
+    vs = ValidationStep(m, shape, class_weight=torch.ones(classes), keep_predictions=True, use_graph=False, nstreams=2)
+    g = vs.g
+    extra = _tensors(vs, vs.inref) + list(m.buffers())
+    return g, [('fwd', g.fwd)], extra, (vs, m)
+
+
+def _gate(F, shape, kind, env=None):
+    """dynamic inference gated by entropy / top-probability share, and the segments it replays (trunk + head + gate, resize, remainder)"""
+    old = {k: os.environ.get(k) for k in env or {}}
+    os.environ.update(env or {})
+    try:
+        m = _model(F, train=False)
+        plan = m._gate_plan(torch.empty(*shape), kind)
+        segs = [(0, plan.head_rng[0][0]), plan.head_rng[0], (plan.head_rng[0][1], -1)]
+        segs = [s for s in segs if s[0] != s[1]]              # the stand-alone form leaves nothing behind the cut
+        with torch.no_grad():
+            for i0, i1 in segs:
+                plan._seg(i0, i1)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    g = plan.g
+    lists = [('fwd', g.fwd)] + [('seg%d' % k, plan.segs[(i0, i1 if i1 >= 0 else len(g.fwd))]) for k, (i0, i1) in enumerate(segs)]
+    extra = _tensors(plan, plan.inref, *plan.heads, plan.final) + list(m.buffers())
+    return g, lists, extra, (plan, m)
+
+
 PLANS = (
     ('c2_train_step', lambda: _train_step(20, (2, 3, 1024, 2048))),          # the flagship: config 2, F = 20, want_grad
     ('c2_inference', lambda: _module_plan(20, (1, 3, 1024, 2048), False)),
@@ -239,6 +270,12 @@ PLANS = (
     ('f40_train_step', lambda: _train_step(40, (2, 3, 1024, 2048))),
     ('syncbn_forced_train_step', lambda: _train_step(4, (2, 3, 65, 129), sync=True)),
     ('dynamic_segments', lambda: _dynamic(20, (1, 3, 65, 129))),
+    ('validation_step', lambda: _validation(4, (2, 3, 65, 129))),             # the scoring head: one score_upsample per exit
+    ('validation_7_classes', lambda: _validation(4, (1, 3, 33, 65), 7)),      # addk_score_upsample_supported == 0: the stand-alone kernels
+    ('gate_entropy', lambda: _gate(20, (1, 3, 65, 129), 'entropy')),          # the exit gate: gate_upsample, then the resize behind the cut
+    ('gate_max', lambda: _gate(20, (1, 3, 65, 129), 'max')),
+    ('gate_entropy_unfused', lambda: _gate(20, (1, 3, 65, 129), 'entropy', {'ADDK_FUSE_GATE': '0'})),
+    ('gate_max_unfused', lambda: _gate(20, (1, 3, 65, 129), 'max', {'ADDK_FUSE_GATE': '0'})),
 )
 
 
