@@ -73,6 +73,11 @@ class GateUpsampleArgs(C.Structure):
                 ('max_thr', vp), ('out', vp), ('out_host', vp), ('ws', vp)]
 
 
+class ProfileUpsampleArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
+                ('target', vp), ('thr', vp), ('nthr', i32), ('ent_out', vp), ('share_out', vp), ('cm', vp), ('pred_out', vp), ('ws', vp)]
+
+
 class DwArgs(C.Structure):
     _fields_ = [('src', Src), ('N', i32), ('H', i32), ('W', i32), ('OH', i32), ('OW', i32), ('KH', i32), ('KW', i32),
                 ('stride', i32), ('pad', i32), ('dil', i32), ('w', vp), ('y', vp), ('ldy', i32)]
@@ -246,6 +251,9 @@ _SIGS = {
     'addk_gate_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_gate_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_gate_upsample': (i32, [C.POINTER(GateUpsampleArgs), vp]),
+    'addk_profile_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
+    'addk_profile_upsample_ws_bytes': (i64, [i32, i32, i32]),
+    'addk_profile_upsample': (i32, [C.POINTER(ProfileUpsampleArgs), vp]),
     'addk_sgd_step': (i32, [vp, vp, vp, i64, vp, f32, f32, i32, i32, f32, vp]),
     'addk_fill': (i32, [vp, i64, f32, vp]),
     'addk_entropy_sum': (i32, [vp, i32, i32, i64, vp, vp, vp]),

@@ -1,7 +1,7 @@
 // Softmax cross-entropy on NCHW logits (nn.CrossEntropyLoss(weight, ignore_index=255), train.py:70,231),
 // normalised Shannon entropy of the prediction (operations.py:161-170), argmax and the confusion matrix
-// of the evaluator (utils/metrics.py:34-43), and the entropy / top-probability gates of dynamic inference
-// (operations.py:161-180) from the low-resolution logits.  One thread per pixel; channel planes are contiguous along
+// of the evaluator (utils/metrics.py:34-43), the entropy / top-probability gates of dynamic inference
+// (operations.py:161-180) and the per-image exit profile (eval.py:195-230) from the low-resolution logits.  One thread per pixel; channel planes are contiguous along
 // W so every per-channel access of a wave is one coalesced 256-B segment.
 #include <math.h>
 #include "common.h"
@@ -456,16 +456,74 @@ struct GateUpK : UpSrc {
   double npix, ent_div;                                    // OH*OW and log(C) * OH*OW
 };
 
-template <int CC, bool VEC>
-__global__ void __launch_bounds__(256) gate_up_kernel(const GateUpK p) {
+// What a workgroup of a gate-style head does after its walk, shared by gate_up_kernel (NK = 1) and profile_up_kernel (NK = 16): its
+// entropy partial (block_sum) and its first nk of NK pixel counts (wave shuffle, then LDS) leave write-through to part[blk] and
+// cnt[blk * NK + j]; the workgroup that takes the LAST ticket adds each image's partials in a FIXED order — thread t the partials
+// t, t + 256, ... in fp64, then lanes, then the four waves in order; the counts are integers — and calls write(img, es, ks) from thread 0;
+// it then puts the ticket back to zero, after a system-scope fence when the writer stored to host memory.
+template <int NK, class Wr>
+__device__ __forceinline__ void up_finish(float esum, const unsigned (&hit)[NK], int nk, unsigned* counter, float* part, unsigned* cnt,
+                                          int N, int nblk_img, bool host_fence, Wr&& write) {
   __shared__ float shs[4];
-  __shared__ unsigned shc[4];
+  __shared__ unsigned shc[4 * NK];
   __shared__ double shd[4];
-  __shared__ unsigned long long shl[4];
+  __shared__ unsigned long long shl[4 * NK];
   __shared__ unsigned flag;
   const int t = threadIdx.x, lane = t & (SCU_W - 1), wv = t / SCU_W;
+  esum = block_sum(esum, shs);
+#pragma unroll
+  for (int j = 0; j < NK; ++j) {
+    if (j < nk) {
+      unsigned h = hit[j];
+      for (int m = 32; m > 0; m >>= 1) h += __shfl_xor(h, m);
+      if (lane == 0) shc[wv * NK + j] = h;
+    }
+  }
+  __syncthreads();
+  const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (t == 0) __hip_atomic_store((gu32*)(part + blk), __float_as_uint(esum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (t < nk)
+    __hip_atomic_store((gu32*)(cnt + (long)blk * NK + t), shc[t] + shc[NK + t] + shc[2 * NK + t] + shc[3 * NK + t], __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  if (!bnfin_arrive(counter, gridDim.x * gridDim.y * gridDim.z, &flag)) return;
+  // ---- the last workgroup: thread t adds partials t, t + 256, ... of an image, then lanes and waves in a fixed order ----
+  for (int img = 0; img < N; ++img) {
+    double s = 0.0; unsigned long long k[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) k[j] = 0ull;
+    const long base = (long)img * nblk_img;
+    for (int i = t; i < nblk_img; i += 256) {
+      s += (double)__uint_as_float(__hip_atomic_load((gu32*)(part + base + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+      for (int j = 0; j < NK; ++j)
+        if (j < nk) k[j] += __hip_atomic_load((gu32*)(cnt + (base + i) * NK + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+    if (lane == 0) shd[wv] = s;
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+      if (j < nk) {
+        for (int m = 32; m > 0; m >>= 1) k[j] += __shfl_xor(k[j], m);
+        if (lane == 0) shl[wv * NK + j] = k[j];
+      }
+    }
+    __syncthreads();
+    if (t == 0) {
+      const double es = ((shd[0] + shd[1]) + shd[2]) + shd[3];
+      write(img, es, [&](int j) { return shl[j] + shl[NK + j] + shl[2 * NK + j] + shl[3 * NK + j]; });
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (host_fence) __threadfence_system();
+    __hip_atomic_store((gu32*)counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) gate_up_kernel(const GateUpK p) {
   const float thr = *(const gfloat*)p.thr;
-  float esum = 0.f; unsigned hit = 0u;
+  float esum = 0.f; unsigned hit[1] = {0u};
   scu_walk<CC, VEC>(p, [&](long, const float (&z)[CC]) {
     float mx = -INFINITY;
 #pragma unroll
@@ -473,42 +531,75 @@ __global__ void __launch_bounds__(256) gate_up_kernel(const GateUpK p) {
     float se, sx;
     exp_sweep<CC>(z, mx, se, sx);
     esum += logf(se) - sx / se;
-    hit += (1.f / se > thr) ? 1u : 0u;
+    hit[0] += (1.f / se > thr) ? 1u : 0u;
   });
-  esum = block_sum(esum, shs);
-  for (int m = 32; m > 0; m >>= 1) hit += __shfl_xor(hit, m);
-  if (lane == 0) shc[wv] = hit;
+  up_finish<1>(esum, hit, 1, p.counter, p.part, p.cnt, p.N, p.nblk_img, p.out_host != nullptr, [&](int img, double es, auto&& count) {
+    const float ent = (float)(es / p.ent_div), share = (float)((double)count(0) / p.npix);
+    ((gfloat*)p.out)[2 * img] = ent; ((gfloat*)p.out)[2 * img + 1] = share;
+    if (p.out_host) { p.out_host[2 * img] = ent; p.out_host[2 * img + 1] = share; }
+  });
+}
+
+// ---- fused logits up-sampling + per-image exit profile (decoder.py:28 + eval.py:195-230) --------------------------------------
+// What the early-exit operating curve needs of one exit, PER IMAGE (grid z), in one walk: the gate kernel's normalised entropy, its
+// share of pixels with top probability 1/se > thr[j] for up to PRU_NT thresholds at once (one register counter each: no atomics), and
+// the scoring kernel's confusion matrix (same arg-max sweep, same LDS histogram, flushed into the image's own [CC,CC] block) and
+// optional uint8 map.  No loss.  The per-pixel values are the two parents' operation for operation — the strict `>` sweep leaves the
+// max that fmaxf leaves — and the tail is the gate's (up_finish), so entropy and shares carry the gate's bits and the matrix the scorer's.
+constexpr int PRU_NT = 16;
+struct ProfileUpK : UpSrc {
+  const int64_t* target; const float* thr; int nthr;
+  float* ent; float* share; unsigned long long* cm; uint8_t* pred;
+  unsigned* counter; float* part; unsigned* cnt;          // ws: [ticket, 16 bytes][nblk floats][nblk x PRU_NT counts], image-major
+  int nblk_img;
+  double npix, ent_div;
+};
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) profile_up_kernel(const ProfileUpK p) {
+  __shared__ unsigned hist[CC * CC];
+  const int t = threadIdx.x;
+  for (int i = t; i < CC * CC; i += 256) hist[i] = 0u;
   __syncthreads();
-  const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  if (t == 0) {
-    __hip_atomic_store((gu32*)(p.part + blk), __float_as_uint(esum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store((gu32*)(p.cnt + blk), shc[0] + shc[1] + shc[2] + shc[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!bnfin_arrive(p.counter, gridDim.x * gridDim.y * gridDim.z, &flag)) return;
-  // ---- the last workgroup: thread t adds partials t, t + 256, ... of an image, then lanes and waves in a fixed order ----
-  for (int img = 0; img < p.N; ++img) {
-    double s = 0.0; unsigned long long k = 0ull;
-    const long base = (long)img * p.nblk_img;
-    for (int i = t; i < p.nblk_img; i += 256) {
-      s += (double)__uint_as_float(__hip_atomic_load((gu32*)(p.part + base + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      k += __hip_atomic_load((gu32*)(p.cnt + base + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
+  float thr[PRU_NT];                                             // wave-uniform; an unused slot never counts (1/se <= 1)
+#pragma unroll
+  for (int j = 0; j < PRU_NT; ++j) thr[j] = j < p.nthr ? ((const gfloat*)p.thr)[j] : INFINITY;
+  float esum = 0.f; unsigned hit[PRU_NT];
+#pragma unroll
+  for (int j = 0; j < PRU_NT; ++j) hit[j] = 0u;
+  int key = -1; unsigned run = 0;                                // pending (gt, pred) run of this column
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
+    const long tg = tgt[pix];
+    float mx = -INFINITY; int am = 0;
+#pragma unroll
+    for (int c = 0; c < CC; ++c)
+      if (z[c] > mx) { mx = z[c]; am = c; }                      // strict: a tie keeps the lowest channel
+    float se, sx;
+    exp_sweep<CC>(z, mx, se, sx);
+    esum += logf(se) - sx / se;
+    const float pmax = 1.f / se;
+#pragma unroll
+    for (int j = 0; j < PRU_NT; ++j) hit[j] += (pmax > thr[j]) ? 1u : 0u;
+    if (p.pred) p.pred[pix] = (uint8_t)am;
+    const int k = (tg >= 0 && tg < CC) ? (int)tg * CC + am : -1;     // the evaluator's mask: labels in [0, C), whatever ignore_index is
+    if (k != key) {
+      if (key >= 0) atomicAdd(&hist[key], run);
+      key = k; run = 0;
     }
-    for (int m = 32; m > 0; m >>= 1) { s += __shfl_xor(s, m); k += __shfl_xor(k, m); }
-    if (lane == 0) { shd[wv] = s; shl[wv] = k; }
-    __syncthreads();
-    if (t == 0) {
-      const double es = ((shd[0] + shd[1]) + shd[2]) + shd[3];
-      const unsigned long long ks = shl[0] + shl[1] + shl[2] + shl[3];
-      const float ent = (float)(es / p.ent_div), share = (float)((double)ks / p.npix);
-      ((gfloat*)p.out)[2 * img] = ent; ((gfloat*)p.out)[2 * img + 1] = share;
-      if (p.out_host) { p.out_host[2 * img] = ent; p.out_host[2 * img + 1] = share; }
-    }
-    __syncthreads();
+    ++run;
+  });
+  if (key >= 0) atomicAdd(&hist[key], run);
+  __syncthreads();
+  unsigned long long* cm = p.cm + (long)blockIdx.z * (CC * CC);
+  for (int i = t; i < CC * CC; i += 256) {
+    const unsigned v = hist[i];
+    if (v) atomicAdd(&cm[i], (unsigned long long)v);
   }
-  if (t == 0) {
-    if (p.out_host) __threadfence_system();
-    __hip_atomic_store((gu32*)p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  up_finish<PRU_NT>(esum, hit, p.nthr, p.counter, p.part, p.cnt, p.N, p.nblk_img, false, [&](int img, double es, auto&& count) {
+    ((gfloat*)p.ent)[img] = (float)(es / p.ent_div);
+    for (int j = 0; j < p.nthr; ++j) ((gfloat*)p.share)[(long)img * p.nthr + j] = (float)((double)count(j) / p.npix);
+  });
 }
 
 int ce_blocks(long total) { long b = cdiv(total, 256 * 4); if (b < 1) b = 1; if (b > 1024) b = 1024; return (int)b; }
@@ -622,6 +713,37 @@ extern "C" int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream
   else
     hipLaunchKernelGGL((gate_up_kernel<19, false>), grid, dim3(256), 0, st, k);
   return addk_check_launch("gate_upsample");
+}
+
+extern "C" int addk_profile_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C, int32_t nthr) {
+  return scu_ok(N, H, W, OH, OW, C) && nthr >= 0 && nthr <= PRU_NT ? 1 : 0;
+}
+extern "C" int64_t addk_profile_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW) {
+  if (N <= 0 || OH <= 0 || OW <= 0) return 0;
+  return 16 + (4 + 4 * PRU_NT) * scu_blocks(N, OH, OW);
+}
+extern "C" int addk_profile_upsample(const addk_profile_upsample_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->target && a->ent_out && a->cm && a->ws, "profile_upsample: null pointer");
+  ADDK_REQUIRE(addk_profile_upsample_supported(a->N, a->H, a->W, a->OH, a->OW, a->C, a->nthr) == 1,
+               "profile_upsample: unsupported shape (19 classes, at most %d thresholds)", PRU_NT);
+  ADDK_REQUIRE(a->nthr == 0 || (a->thr && a->share_out), "profile_upsample: null pointer");
+  ADDK_REQUIRE(a->ld >= a->C, "profile_upsample: short stride");
+  const dim3 grid = scu_grid(a->N, a->OH, a->OW);
+  ProfileUpK k;
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.target = a->target; k.thr = a->thr; k.nthr = a->nthr;
+  k.ent = a->ent_out; k.share = a->share_out; k.cm = reinterpret_cast<unsigned long long*>(a->cm); k.pred = a->pred_out;
+  k.nblk_img = (int)(grid.x * grid.y);
+  k.counter = (unsigned*)a->ws;
+  k.part = (float*)((char*)a->ws + 16);
+  k.cnt = (unsigned*)(k.part + (long)a->N * k.nblk_img);
+  k.npix = (double)a->OH * (double)a->OW; k.ent_div = log(19.0) * k.npix;
+  hipStream_t st = (hipStream_t)stream;
+  if (px_vec_ok<19>(a->logits, a->ld))
+    hipLaunchKernelGGL((profile_up_kernel<19, true>), grid, dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL((profile_up_kernel<19, false>), grid, dim3(256), 0, st, k);
+  return addk_check_launch("profile_upsample");
 }
 
 extern "C" int addk_entropy_sum(const float* logits, int32_t N, int32_t C, int64_t HW, float* out1, float* ws, void* stream) {

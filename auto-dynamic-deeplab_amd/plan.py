@@ -374,8 +374,9 @@ class Graph:
         self.reorder = False          # level-order and batch the lists although this is not a training plan (set before finalize)
         self.fuse_ce = False          # logits outputs feed the fused up-sampling + cross-entropy launch (train.TrainStep)
         self.fuse_score = False       # logits outputs of an inference plan feed the fused up-sampling + scoring launch (validate.ValidationStep)
+        self.profile = False          # logits outputs of an inference plan feed the per-image exit-profile launch (exit_profile.ExitProfile)
         self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}
-        self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted (fuse_score)
+        self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted (fuse_score, profile)
         self.pginit = set()
         self._pcols = {}
         self.params = []              # ordered unique params touched
@@ -1280,14 +1281,16 @@ class Graph:
 
     def resize_to_nchw(self, src, OH, OW):
         """Final logits resize (decoder.py:28).  Returns an OutRef.  The plan chooses who consumes the low-resolution logits: the loss head
-        of a fused training step (_ce_head), the scoring head of a validation plan (_score_head), the gate of an early exit (gate_head),
-        or nobody: the resize into a contiguous [N,C,OH,OW] tensor, and its backward."""
+        of a fused training step (_ce_head), the scoring head of a validation plan (_score_head), the per-image profile of an exit-profile
+        plan (_profile_head), the gate of an early exit (gate_head), or nobody: the resize into a contiguous [N,C,OH,OW] tensor, and its backward."""
         assert src.bn is None and not src.relu
         if (self.fuse_ce and self.want_grad and src.needs_grad
                 and self.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1):
             return self._ce_head(src, OH, OW)
         if self.fuse_score and not self.want_grad:
             return self._score_head(src, OH, OW)
+        if self.profile and not self.want_grad:
+            return self._profile_head(src, OH, OW)
         if self.gate is not None and not self.want_grad:
             return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'])
         y, emit_resize = self._logits_resize(src, OH, OW)
@@ -1400,6 +1403,37 @@ class Graph:
             for c in self.fwd[first:]:
                 c.tag = tag
         self._fwd_late.append(emit_score)
+        return out
+
+    def _profile_head(self, src, OH, OW):
+        """Logits output of an exit-profile plan (`self.profile`, set by exit_profile.ExitProfile): as in _score_head no resize is emitted
+        and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `profile` slot the step binds (target, the device array of
+        top-probability thresholds and its length, and this exit's per-image entropy [N], share [N,nthr], confusion [N,C,C] and optional
+        prediction tensors); finalize() then appends ONE `profile_upsample` launch per exit (`addk_profile_upsample`).  There is no
+        stand-alone form: a shape the library does not take is an error."""
+        lib = self.lib
+        N, H, W, Cc = src.N, src.H, src.W, src.C
+        out = OutRef(None)
+        out.fused_profile, out.shape = True, (N, Cc, OH, OW)
+        tag = self.tag
+
+        def emit_profile():
+            pr = out.profile
+            assert pr is not None, 'fused logits output without a profile binding'
+            tgt, thr, nthr, ent, share, cm, pred = pr['target'], pr['thr'], pr['nthr'], pr['entropy'], pr['share'], pr['confusion'], pr.get('pred')
+            if lib.addk_profile_upsample_supported(N, H, W, OH, OW, Cc, nthr) != 1:
+                raise L.AddkError('the exit profile takes 19 classes and at most 16 thresholds (got %d classes, %d thresholds, '
+                                  '[%d,%d,%d] -> %dx%d)' % (Cc, nthr, N, H, W, OH, OW))
+            a = self._up_args(L.ProfileUpsampleArgs, src, OH, OW)
+            a.target, a.thr, a.nthr = tgt.data_ptr(), thr.data_ptr() if nthr else None, nthr
+            a.ent_out, a.share_out, a.cm = ent.data_ptr(), share.data_ptr() if nthr else None, cm.data_ptr()
+            a.pred_out = pred.data_ptr() if pred is not None else None
+            ws = torch.zeros(int(lib.addk_profile_upsample_ws_bytes(N, OH, OW)), dtype=torch.uint8, device=self.device)
+            a.ws = ws.data_ptr()
+            self.keep += [a, ws]
+            self._add(self.fwd, 'profile_upsample', lib.addk_profile_upsample, C.byref(a),
+                      rd=self.lz(src) + [tgt, thr], wr=[ent, share, cm, pred, ws]).tag = tag
+        self._fwd_late.append(emit_profile)
         return out
 
     def gate_head(self, src, OH, OW, host_out, thr, kind='entropy'):
@@ -1602,6 +1636,8 @@ class OutRef:
         self.ce = None           # its loss binding, set by TrainStep: target, class_w, ignore_index, wsum, scale, loss
         self.fused_score = False  # logits consumed by the scoring launch of a validation plan (validate.ValidationStep): y is None
         self.score = None        # its binding, set by ValidationStep: the loss binding + entropy, confusion, pred
+        self.fused_profile = False  # logits consumed by the per-image profile launch of an exit-profile plan (exit_profile.ExitProfile): y is None
+        self.profile = None      # its binding, set by ExitProfile: target, thr, nthr, entropy, share, confusion, pred
         self.gate_out = None     # [N,2] device tensor of a gated exit: (entropy, share of pixels above the threshold)
         self.gate_scale = 1.0    # factor the host applies to gate_out[:, 0] (the stand-alone entropy kernel leaves a sum)
         self.gate_fused = False  # the gate launch writes the pinned host words itself; else the host copies gate_out

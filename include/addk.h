@@ -561,6 +561,35 @@ int addk_gate_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, in
 int64_t addk_gate_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW);
 int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream);
 
+/* Exit profile of a validation pass (eval.py:195-230): what the early-exit operating curve needs of one exit, PER IMAGE, in
+ * ONE launch over the LOW-resolution NHWC logits [N,H,W,C] (the walk and the arithmetic of the two heads above):
+ *   ent_out[n]            = normalised Shannon entropy of image n: the bits of addk_gate_upsample's out[2n]
+ *   share_out[n*nthr + j] = #{pixels of image n: pmax > thr[j]} / (OH*OW): the bits of addk_gate_upsample's out[2n + 1]
+ *                           launched with *max_thr == thr[j]; 0 <= nthr <= 16 (nthr == 0: thr and share_out may be NULL)
+ *   cm[n][gt*C + pred]   += 1     int64 [N,C,C], the rule of addk_score_upsample (labels outside [0,C) skipped, ties: lowest
+ *                                 channel); ADDED to what cm holds: the caller zeroes it
+ *   pred_out[n,y,x]       = pred  uint8 [N,OH,OW], optional (NULL: not written)
+ * No loss.  thr is read from memory when the launch runs, so a captured graph serves every threshold set of one length.
+ * ws: addk_profile_upsample_ws_bytes() bytes, ZERO-initialised once (the ticket word is left at zero).  Deterministic: integer
+ * atomics for the matrix, the gate's fixed-order sum by the last-arriving workgroup for the rest.
+ * addk_profile_upsample_supported() is 0 where addk_score_upsample_supported() is, and for nthr outside [0, 16];
+ * addk_profile_upsample then returns ADDK_ERR_INVALID without launching. */
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
+  int32_t N, H, W, C, OH, OW;
+  const int64_t* target;             /* [N,OH,OW] */
+  const float* thr;                  /* device [nthr]: thresholds of the top probability */
+  int32_t nthr;
+  float* ent_out;                    /* device [N] */
+  float* share_out;                  /* device [N][nthr] */
+  int64_t* cm;                       /* device [N][C,C], accumulated */
+  uint8_t* pred_out;                 /* [N,OH,OW] or NULL */
+  void* ws;                          /* addk_profile_upsample_ws_bytes() zero-initialised bytes */
+} addk_profile_upsample_args;
+int addk_profile_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C, int32_t nthr);
+int64_t addk_profile_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW);
+int addk_profile_upsample(const addk_profile_upsample_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Fused SGD (torch.optim.SGD(momentum, weight_decay, nesterov), train.py:126) on a flat buffer.
  *   d = g*gscale + wd*p;  buf = first ? d : mom*buf + d;  p -= lr*(nesterov ? d + mom*buf : buf)
