@@ -73,6 +73,15 @@ class GateUpsampleArgs(C.Structure):
                 ('max_thr', vp), ('out', vp), ('out_host', vp), ('ws', vp)]
 
 
+class LabelUpsampleArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
+                ('lut256', vp), ('labels', vp)]
+
+
+class GateLabelUpsampleArgs(C.Structure):
+    _fields_ = [('gate', GateUpsampleArgs), ('lut256', vp), ('labels', vp)]
+
+
 class ProfileUpsampleArgs(C.Structure):
     _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
                 ('target', vp), ('thr', vp), ('nthr', i32), ('ent_out', vp), ('share_out', vp), ('cm', vp), ('pred_out', vp), ('ws', vp)]
@@ -251,6 +260,9 @@ _SIGS = {
     'addk_gate_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_gate_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_gate_upsample': (i32, [C.POINTER(GateUpsampleArgs), vp]),
+    'addk_label_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
+    'addk_label_upsample': (i32, [C.POINTER(LabelUpsampleArgs), vp]),
+    'addk_gate_label_upsample': (i32, [C.POINTER(GateLabelUpsampleArgs), vp]),
     'addk_profile_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
     'addk_profile_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_profile_upsample': (i32, [C.POINTER(ProfileUpsampleArgs), vp]),

@@ -440,6 +440,29 @@ bool scu_ok(int N, int H, int W, int OH, int OW, int C) {
   return N <= 65535 && scu_grid(N, OH, OW).y <= 65535 && scu_blocks(N, OH, OW) < (1L << 30);
 }
 
+// ---- fused logits up-sampling + label map (decoder.py:28 + eval.py:218-221) ------------------------------------------------------
+// What inference keeps of an exit: the arg-max of the up-sampled logits, one byte per high-resolution pixel.  The walk is scu_walk
+// (same tile, same interpolation), then the strict `>` arg-max sweep of score_up_kernel (a tie keeps the lowest channel) and one
+// byte store — the class index, or lut[class] (train id -> Cityscapes labelId).  No exp, no LDS, no workspace; a wave row stores 64
+// consecutive bytes.  label_px is also the store of the gate launch that leaves the map (gate_up_kernel<.., LABELS = true>).
+typedef __attribute__((address_space(1))) uint8_t gu8;
+__device__ __forceinline__ void label_px(const uint8_t* lut, uint8_t* labels, long pix, int am) {
+  ((gu8*)labels)[pix] = lut ? ((const gu8*)lut)[am] : (uint8_t)am;
+}
+
+struct LabelUpK : UpSrc { const uint8_t* lut; uint8_t* labels; };
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) label_up_kernel(const LabelUpK p) {
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
+    float mx = -INFINITY; int am = 0;
+#pragma unroll
+    for (int c = 0; c < CC; ++c)
+      if (z[c] > mx) { mx = z[c]; am = c; }                      // strict: a tie keeps the lowest channel
+    label_px(p.lut, p.labels, pix, am);
+  });
+}
+
 // ---- fused logits up-sampling + early-exit gate (decoder.py:28 + operations.py:161-180) -----------------------------------
 // The two gates of dynamic inference that need no trained EDM: the normalised Shannon entropy of the up-sampled prediction and the
 // share of pixels whose top softmax probability passes a threshold.  The walk is scu_walk (same tile, same interpolation
@@ -520,14 +543,28 @@ __device__ __forceinline__ void up_finish(float esum, const unsigned (&hit)[NK],
   }
 }
 
-template <int CC, bool VEC>
-__global__ void __launch_bounds__(256) gate_up_kernel(const GateUpK p) {
+// LABELS: the launch also leaves the label map of label_up_kernel, speculatively, for every image (one byte per pixel): the max sweep
+// becomes the strict `>` arg-max sweep, which leaves the max that fmaxf leaves, so `out` / `out_host` carry the bits of the plain gate
+struct GateLabelUpK : GateUpK { const uint8_t* lut; uint8_t* labels; };
+template <bool LABELS> struct GateUpArg { typedef GateUpK type; };
+template <> struct GateUpArg<true> { typedef GateLabelUpK type; };
+
+template <int CC, bool VEC, bool LABELS = false>
+__global__ void __launch_bounds__(256) gate_up_kernel(const typename GateUpArg<LABELS>::type p) {
   const float thr = *(const gfloat*)p.thr;
   float esum = 0.f; unsigned hit[1] = {0u};
-  scu_walk<CC, VEC>(p, [&](long, const float (&z)[CC]) {
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
     float mx = -INFINITY;
+    if constexpr (LABELS) {
+      int am = 0;
 #pragma unroll
-    for (int c = 0; c < CC; ++c) mx = fmaxf(mx, z[c]);
+      for (int c = 0; c < CC; ++c)
+        if (z[c] > mx) { mx = z[c]; am = c; }                    // strict: a tie keeps the lowest channel
+      label_px(p.lut, p.labels, pix, am);
+    } else {
+#pragma unroll
+      for (int c = 0; c < CC; ++c) mx = fmaxf(mx, z[c]);
+    }
     float se, sx;
     exp_sweep<CC>(z, mx, se, sx);
     esum += logf(se) - sx / se;
@@ -600,6 +637,18 @@ __global__ void __launch_bounds__(256) profile_up_kernel(const ProfileUpK p) {
     ((gfloat*)p.ent)[img] = (float)(es / p.ent_div);
     for (int j = 0; j < p.nthr; ++j) ((gfloat*)p.share)[(long)img * p.nthr + j] = (float)((double)count(j) / p.npix);
   });
+}
+
+// the gate launch's arguments behind the UpSrc prefix (both of its forms): outputs, workspace layout, normalisation
+void gate_up_fill(GateUpK& k, const addk_gate_upsample_args* a) {
+  const dim3 grid = scu_grid(a->N, a->OH, a->OW);
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.thr = a->max_thr; k.out = a->out; k.out_host = a->out_host;
+  k.nblk_img = (int)(grid.x * grid.y);
+  k.counter = (unsigned*)a->ws;
+  k.part = (float*)((char*)a->ws + 16);
+  k.cnt = (unsigned*)(k.part + (long)a->N * k.nblk_img);
+  k.npix = (double)a->OH * (double)a->OW; k.ent_div = log(19.0) * k.npix;
 }
 
 int ce_blocks(long total) { long b = cdiv(total, 256 * 4); if (b < 1) b = 1; if (b > 1024) b = 1024; return (int)b; }
@@ -698,21 +747,48 @@ extern "C" int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream
   ADDK_REQUIRE(a && a->logits && a->max_thr && a->out && a->ws, "gate_upsample: null pointer");
   ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample: unsupported shape (19 classes)");
   ADDK_REQUIRE(a->ld >= a->C, "gate_upsample: short stride");
-  const dim3 grid = scu_grid(a->N, a->OH, a->OW);
   GateUpK k;
-  static_cast<UpSrc&>(k) = up_src(a);
-  k.thr = a->max_thr; k.out = a->out; k.out_host = a->out_host;
-  k.nblk_img = (int)(grid.x * grid.y);
-  k.counter = (unsigned*)a->ws;
-  k.part = (float*)((char*)a->ws + 16);
-  k.cnt = (unsigned*)(k.part + (long)a->N * k.nblk_img);
-  k.npix = (double)a->OH * (double)a->OW; k.ent_div = log(19.0) * k.npix;
+  gate_up_fill(k, a);
   hipStream_t st = (hipStream_t)stream;
   if (px_vec_ok<19>(a->logits, a->ld))
-    hipLaunchKernelGGL((gate_up_kernel<19, true>), grid, dim3(256), 0, st, k);
+    hipLaunchKernelGGL((gate_up_kernel<19, true>), scu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, k);
   else
-    hipLaunchKernelGGL((gate_up_kernel<19, false>), grid, dim3(256), 0, st, k);
+    hipLaunchKernelGGL((gate_up_kernel<19, false>), scu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, k);
   return addk_check_launch("gate_upsample");
+}
+extern "C" int addk_gate_label_upsample(const addk_gate_label_upsample_args* b, void* stream) {
+  ADDK_REQUIRE(b, "gate_label_upsample: null pointer");
+  const addk_gate_upsample_args* a = &b->gate;
+  ADDK_REQUIRE(a->logits && a->max_thr && a->out && a->ws && b->labels, "gate_label_upsample: null pointer");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_label_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(a->ld >= a->C, "gate_label_upsample: short stride");
+  GateLabelUpK k;
+  gate_up_fill(k, a);
+  k.lut = b->lut256; k.labels = b->labels;
+  hipStream_t st = (hipStream_t)stream;
+  if (px_vec_ok<19>(a->logits, a->ld))
+    hipLaunchKernelGGL((gate_up_kernel<19, true, true>), scu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL((gate_up_kernel<19, false, true>), scu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, k);
+  return addk_check_launch("gate_label_upsample");
+}
+
+extern "C" int addk_label_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return scu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int addk_label_upsample(const addk_label_upsample_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->labels, "label_upsample: null pointer");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "label_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(a->ld >= a->C, "label_upsample: short stride");
+  LabelUpK k;
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.lut = a->lut256; k.labels = a->labels;
+  hipStream_t st = (hipStream_t)stream;
+  if (px_vec_ok<19>(a->logits, a->ld))
+    hipLaunchKernelGGL((label_up_kernel<19, true>), scu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL((label_up_kernel<19, false>), scu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, k);
+  return addk_check_launch("label_upsample");
 }
 
 extern "C" int addk_profile_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C, int32_t nthr) {

@@ -40,6 +40,14 @@ def encode_segmap_lut(ignore_index=255):
     return m.astype(np.uint8)
 
 
+def decode_segmap_lut():
+    """The inverse of encode_segmap_lut as a 256-entry table for the label heads (`label_lut`): train id i < 19 -> VALID_CLASSES[i], the
+    Cityscapes labelId a submission holds; every other entry -> 0 ("unlabeled")."""
+    m = np.zeros(256, dtype=np.uint8)
+    m[:len(VALID_CLASSES)] = VALID_CLASSES
+    return m
+
+
 def _sinc(x):
     if x == 0.0:
         return 1.0

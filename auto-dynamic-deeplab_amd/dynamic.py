@@ -13,16 +13,32 @@ semantics are this project's): the gate judges exit k's PREDICTION, so head k ru
 share of the x8 up-sampled prediction straight from the low-resolution logits and writes them to pinned host words; the full-size
 logits are written only for the image that leaves.  Exit k's logits are forward()'s (`model(x)[k]`): aspp_size from 2^-(last+2)
 and conv_aspp[k] when the level differs; no EDM runs, so its in-place ReLU (Q3) does not happen.  The 2^-last size (Q5) is a
-quirk of the working 'edm' path and stays only there: the heads training optimises are forward()'s."""
+quirk of the working 'edm' path and stays only there: the heads training optimises are forward()'s.
+
+output='labels' (both plans): every exit ends in a label head instead (plan.Graph.labels) and returns the plan-owned uint8 [1,H,W]
+arg-max map of its logits; no [N,C,H,W] buffer exists.  'edm': [early head k] and the final head end in one `label_upsample` launch.
+'entropy' / 'max': the gate launch leaves the map as well (`gate_label_upsample`), so nothing is left to replay for the image that
+leaves — [trunk up to exit k] [head k + the gate-and-labels launch] ... [remaining cells + final head + its `label_upsample`]."""
 import torch
 
 from .module import ensure_layout
-from .plan import Act, Graph
+from .plan import Act, Graph, label_lut as _label_lut
+
+OUTPUTS = ('logits', 'labels')
+
+
+def _label_mode(output, label_lut, device):
+    """Graph.labels of a dynamic plan: None for output='logits', else {'lut': uint8[256] device tensor or None}."""
+    if output not in OUTPUTS:
+        raise ValueError('output must be one of %s (got %r)' % (OUTPUTS, output))
+    lut = _label_lut(label_lut, device)
+    return {'lut': lut} if output == 'labels' else None
 
 
 class DynamicPlan:
-    def __init__(self, model, edm, x):
+    def __init__(self, model, edm, x, output='logits', label_lut=None):
         from .modeling.ADD import _aspp_size
+        labels = _label_mode(output, label_lut, x.device)
         for p in list(model.parameters()) + list(edm.parameters()):
             ensure_layout(p)
         if x.shape[0] != 1:
@@ -31,6 +47,7 @@ class DynamicPlan:
             raise RuntimeError('dynamic_inference gates one image at a time (got batch size %d): the reference\'s '
                                '`if confidence_value > threshold` is ambiguous for more than one value' % x.shape[0])
         self.g = g = Graph(x.device, False, False, None)
+        g.labels = labels
         # the gate scalar travels through pinned host memory: the fused EDM head (csrc/edm.hip) writes it there itself; on the generic path an
         # asynchronous 4-byte copy does.  Either way the host waits on ONE event, not on the whole device (ADD.py:421 does
         # `if confidence_value > threshold`, a blocking read)
@@ -147,10 +164,11 @@ KINDS = ('entropy', 'max')
 class GatePlan(DynamicPlan):
     """Dynamic inference gated by the entropy ('entropy') or the top-probability share ('max') of each early exit's prediction."""
 
-    def __init__(self, model, x, kind):
+    def __init__(self, model, x, kind, output='logits', label_lut=None):
         from .modeling.ADD import _aspp_size
         if kind not in KINDS:
             raise ValueError('confidence must be one of %s (got %r)' % (('edm',) + KINDS, kind))
+        labels = _label_mode(output, label_lut, x.device)
         for p in model.parameters():
             ensure_layout(p)
         if x.shape[0] != 1:              # the same decision as DynamicPlan: one image per gate
@@ -158,6 +176,7 @@ class GatePlan(DynamicPlan):
                                '`if confidence_value > threshold` is ambiguous for more than one value' % x.shape[0])
         self.kind = kind
         self.g = g = Graph(x.device, False, False, None)
+        g.labels = labels
         # (entropy, share) of the gated exit travel through pinned host memory: the gate launch writes them there itself; on the
         # stand-alone path an asynchronous 8-byte copy does.  Either way the host waits on ONE event, not on the whole device
         self._conf_host = torch.zeros(2, dtype=torch.float32)
@@ -179,7 +198,7 @@ class GatePlan(DynamicPlan):
                 h = model._head(g, y, low, size, aspp_size, it, lvl)
                 g.gate = None
                 self.heads.append(h)
-                self.head_rng.append((h.gate_cut, len(g.fwd)))          # [trunk_end, gate_cut): head + gate; [gate_cut, end): resize
+                self.head_rng.append((h.gate_cut, len(g.fwd)))          # [trunk_end, gate_cut): head + gate; [gate_cut, end): resize (labels: empty)
             elif i == model.num_net - 1:
                 self.final = model._head(g, y, low, size, aspp_size, it, lvl)
             else:
@@ -189,7 +208,7 @@ class GatePlan(DynamicPlan):
         self._finish(x)
 
     def run(self, x, threshold):
-        """-> (logits, earlier_exit, gate value).  The image leaves at the first exit whose entropy is BELOW the threshold
+        """-> (logits or label map, earlier_exit, gate value).  The image leaves at the first exit whose entropy is BELOW the threshold
         ('entropy'), or whose share of pixels with top probability above the threshold is ABOVE it ('max': the same number plays
         both roles, ADD.py:476,481)."""
         self.calls += 1

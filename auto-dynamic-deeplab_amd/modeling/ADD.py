@@ -289,7 +289,27 @@ class ADD(AddkModule):
         out, feat = self.run_plan(self._emit_get_feature, (x,), tag='get_feature')
         return out, feat
 
-    def dynamic_inference(self, x, threshold=1.0, confidence='edm', edm=False):
+    def _emit_exit(self, g, x, k):
+        """forward()'s exit k alone (segment.Segmenter): the trunk only up to that exit's cell, then emit()'s head for it — aspp_size
+        from 2^-(last+2), conv_aspp indexed by the adapted exits before it."""
+        size = (x.H, x.W)
+        aspp_size = _aspp_size(size, self.network_arch[-1] + 2)
+        it, n = 0, 0
+        for i, y, low in self._trunk(g, x):
+            if i in self.C_index or i == self.num_net - 1:
+                lvl = self.network_arch[i]
+                if n == k:
+                    return self._head(g, y, low, size, aspp_size, it, lvl)       # the generator stops here: no later cell is emitted
+                n += 1
+                if lvl != self.network_arch[-1]:
+                    it += 1
+        raise IndexError('exit %d of %d' % (k, n))
+
+    def num_exits(self):
+        """length of forward()'s output list"""
+        return len(set(self.C_index) | {self.num_net - 1})
+
+    def dynamic_inference(self, x, threshold=1.0, confidence='edm', edm=False, output='logits', label_lut=None):
         """reference ADD.py:379-488 -> (y, earlier_exit, seconds, confidence_value).
 
         confidence='edm' (ADD.py:379-438, the reference's working gate): three plan segments share one buffer set — trunk up to the
@@ -308,36 +328,56 @@ class ADD(AddkModule):
         ADD.py:476,481).  On exit y = exit k's [1,19,H,W] logits and earlier_exit = 1; after the last gate fails the final head's
         logits come back with earlier_exit = 0.  confidence_value is a Python float: the last gate evaluated.
 
-        A batch of more than one image raises RuntimeError on every path; any other `confidence` raises ValueError."""
-        if confidence != 'edm':
-            from ..dynamic import KINDS
-            if confidence not in KINDS:
-                raise ValueError("confidence must be 'edm', 'entropy' or 'max' (got %r)" % (confidence,))
+        output='labels' (all three gates): y is the plan-owned uint8 [1,H,W] arg-max map of those logits (ties: lowest channel) — the
+        class index, or label_lut[class] with a 256-entry uint8 table such as data.decode_segmap_lut() — written by a label head
+        straight from the decoder's low-resolution logits: no [1,19,H,W] tensor is written or kept, and for 'entropy' / 'max' the gate
+        launch leaves the map itself.  earlier_exit, seconds and confidence_value are those of output='logits'.  Like the logits, the
+        map belongs to the cached plan and is overwritten by the next call of the same shape and mode.
+
+        A batch of more than one image raises RuntimeError on every path; any other `confidence` or `output`, or a `label_lut` that
+        is not 256 uint8 entries, raises ValueError."""
+        from ..dynamic import KINDS, OUTPUTS
+        if confidence != 'edm' and confidence not in KINDS:
+            raise ValueError("confidence must be 'edm', 'entropy' or 'max' (got %r)" % (confidence,))
+        if output not in OUTPUTS:
+            raise ValueError("output must be 'logits' or 'labels' (got %r)" % (output,))
+        from ..plan import label_lut as _label_lut
+        lut = _label_lut(label_lut, 'cpu')
+        mode = (output, None if lut is None else bytes(lut.numpy().tobytes())) if output == 'labels' else ()
         if x.is_cuda:
             torch.cuda.synchronize()
         tic = time.perf_counter()
-        plan = self._dynamic_plan(x, edm) if confidence == 'edm' else self._gate_plan(x, confidence)
+        plan = self._dynamic_plan(x, edm, *mode) if confidence == 'edm' else self._gate_plan(x, confidence, *mode)
         y, earlier_exit, conf = plan.run(x, threshold)
         if x.is_cuda:
             torch.cuda.synchronize()
         return y, earlier_exit, time.perf_counter() - tic, conf
 
-    def _dynamic_plan(self, x, edm):
+    @staticmethod
+    def _lut_from_key(lut):
+        return None if lut is None else torch.frombuffer(bytearray(lut), dtype=torch.uint8)
+
+    def _dynamic_plan(self, x, edm, output='logits', lut=None):
+        """`lut`: the 256 table bytes or None.  The logits plan keeps the key it always had; a labels plan adds (output, lut) to it."""
         from ..dynamic import DynamicPlan
         key = ('dyn', tuple(x.shape), id(edm), int(L.load().addk_get_conv_precision()))
+        if output != 'logits':
+            key += (output, lut)
         plans = self._plans()
         p = plans.get(key)
         if p is None or not p.check_params():
-            p = plans[key] = DynamicPlan(self, edm, x)
+            p = plans[key] = DynamicPlan(self, edm, x, output, self._lut_from_key(lut))
         return p
 
-    def _gate_plan(self, x, kind):
+    def _gate_plan(self, x, kind, output='logits', lut=None):
         from ..dynamic import GatePlan
         key = ('dyn', kind, tuple(x.shape), int(L.load().addk_get_conv_precision()))
+        if output != 'logits':
+            key += (output, lut)
         plans = self._plans()
         p = plans.get(key)
         if p is None or not p.check_params():
-            p = plans[key] = GatePlan(self, x, kind)
+            p = plans[key] = GatePlan(self, x, kind, output, self._lut_from_key(lut))
         return p
 
 

@@ -376,6 +376,7 @@ class Graph:
         self.fuse_score = False       # logits outputs of an inference plan feed the fused up-sampling + scoring launch (validate.ValidationStep)
         self.profile = False          # logits outputs of an inference plan feed the per-image exit-profile launch (exit_profile.ExitProfile)
         self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}
+        self.labels = None            # logits outputs of an inference plan end in the label head (dynamic plans, segment.Segmenter): {'lut': uint8[256] or None}
         self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted (fuse_score, profile)
         self.pginit = set()
         self._pcols = {}
@@ -1282,7 +1283,8 @@ class Graph:
     def resize_to_nchw(self, src, OH, OW):
         """Final logits resize (decoder.py:28).  Returns an OutRef.  The plan chooses who consumes the low-resolution logits: the loss head
         of a fused training step (_ce_head), the scoring head of a validation plan (_score_head), the per-image profile of an exit-profile
-        plan (_profile_head), the gate of an early exit (gate_head), or nobody: the resize into a contiguous [N,C,OH,OW] tensor, and its backward."""
+        plan (_profile_head), the gate of an early exit (gate_head), the label head of a label-map plan (_label_head), or nobody: the resize
+        into a contiguous [N,C,OH,OW] tensor, and its backward."""
         assert src.bn is None and not src.relu
         if (self.fuse_ce and self.want_grad and src.needs_grad
                 and self.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1):
@@ -1293,6 +1295,8 @@ class Graph:
             return self._profile_head(src, OH, OW)
         if self.gate is not None and not self.want_grad:
             return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'])
+        if self.labels is not None and not self.want_grad:
+            return self._label_head(src, OH, OW)
         y, emit_resize = self._logits_resize(src, OH, OW)
         emit_resize()
         out = OutRef(y)
@@ -1436,6 +1440,44 @@ class Graph:
         self._fwd_late.append(emit_profile)
         return out
 
+    def _label_map(self, src, OH, OW):
+        """The plan-owned uint8 [N,OH,OW] label map of a label head and its OutRef (`shape`: the logits it stands for)."""
+        lab = torch.zeros((src.N, OH, OW), dtype=torch.uint8, device=self.device)
+        self.nbytes += lab.numel()
+        out = OutRef(lab)
+        out.labels, out.shape = True, (src.N, src.C, OH, OW)
+        return lab, out
+
+    def _label_head(self, src, OH, OW):
+        """Logits output of a label-map plan (`self.labels`, set by dynamic.DynamicPlan / GatePlan and segment.Segmenter): what inference
+        keeps of an exit is the arg-max of its up-sampled logits (eval.py:218-221), so no resize is emitted and no [N,C,OH,OW] buffer exists.
+        ONE `label_upsample` launch (`addk_label_upsample`) writes the OutRef's `y`, a plan-owned uint8 [N,OH,OW] map: the class index, or
+        lut[class] with `self.labels['lut']`.  Where the library does not take the shape (`addk_label_upsample_supported` == 0, e.g.
+        C != 19) the same plan uses the stand-alone kernels: resize + argmax_nchw + a cast in torch ops (_labels_cold)."""
+        lib = self.lib
+        lab, out = self._label_map(src, OH, OW)
+        lut = self.labels.get('lut')
+        if lib.addk_label_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1:
+            a = self._up_args(L.LabelUpsampleArgs, src, OH, OW)
+            a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
+            self.keep += [a, lut]
+            self._add(self.fwd, 'label_upsample', lib.addk_label_upsample, C.byref(a), rd=self.lz(src) + [lut], wr=[lab])
+        else:
+            y, emit_resize = self._logits_resize(src, OH, OW)
+            emit_resize()
+            self._labels_cold(y, lab, lut)
+        return out
+
+    def _labels_cold(self, y, lab, lut):
+        """Cold path of the two label heads: the map from materialised logits y [N,C,OH,OW] — `argmax_nchw`, then the cast / table look-up
+        to uint8 in torch ops."""
+        N, Cc, OH, OW = y.shape
+        am = torch.empty((N, OH, OW), dtype=torch.int64, device=self.device)
+        self.nbytes += am.numel() * 8
+        self.keep += [y, am, lut]
+        self._add(self.fwd, 'argmax_nchw', self.lib.addk_argmax_nchw, y.data_ptr(), N, Cc, OH * OW, am.data_ptr(), rd=[y], wr=[am])
+        self._add(self.fwd, 'label_cast_torch', _label_cast_torch, am, lut, lab, rd=[am, lut], wr=[lab], pin=True)
+
     def gate_head(self, src, OH, OW, host_out, thr, kind='entropy'):
         """Logits output of a gated early exit (`self.gate`, set by dynamic.GatePlan): the exit's gate value (modeling/operations.py:161-180)
         and, separately, the resize that writes the [N,C,OH,OW] logits.  Fused form: ONE `gate_upsample` launch (`addk_gate_upsample`)
@@ -1445,15 +1487,37 @@ class Graph:
         Where the library does not take the shape (`addk_gate_upsample_supported` == 0, e.g. C != 19) or with ADDK_FUSE_GATE=0, the same
         plan uses the stand-alone kernels on the materialised logits — `resize_nchw` first, then `entropy_sum` ('entropy': gate_out[0, 0]
         holds the un-normalised sum, `gate_scale` the factor the host applies) or a count in torch ops ('max': gate_out[0, 1]); nothing
-        is left behind the cut and the host copies `gate_out` itself (`gate_fused` False)."""
+        is left behind the cut and the host copies `gate_out` itself (`gate_fused` False).
+        In a label-map plan (`self.labels`) the OutRef's `y` is the uint8 [N,OH,OW] map of _label_head.  Fused form: ONE
+        `gate_label_upsample` launch (`addk_gate_label_upsample`) leaves the gate value AND the map, for every image; nothing follows the
+        cut and no [N,C,OH,OW] buffer exists.  Stand-alone form: the stand-alone gate above, then, behind the cut, _labels_cold."""
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
-        y, emit_resize = self._logits_resize(src, OH, OW)
+        fused = _on('ADDK_FUSE_GATE') and lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
+        if self.labels is None or not fused:
+            y, emit_resize = self._logits_resize(src, OH, OW)
         gout = torch.zeros((N, 2), dtype=torch.float32, device=self.device)
         self.keep += [gout, thr, host_out]
-        out = OutRef(y)
+        if self.labels is not None:
+            lab, out = self._label_map(src, OH, OW)
+            lut = self.labels.get('lut')
+        if self.labels is not None and fused:
+            out.gate_out, out.gate_fused = gout, True
+            a = L.GateLabelUpsampleArgs()
+            a.gate = self._up_args(L.GateUpsampleArgs, src, OH, OW)
+            ws = self.buf((int(lib.addk_gate_upsample_ws_bytes(N, OH, OW)) + 3) // 4, zero=True)
+            a.gate.max_thr, a.gate.out, a.gate.ws = thr.data_ptr(), gout.data_ptr(), ws.ptr
+            a.gate.out_host = host_out.data_ptr() if host_out is not None else None
+            a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
+            self.keep += [a, lut]
+            self._add(self.fwd, 'gate_label_upsample', lib.addk_gate_label_upsample, C.byref(a), rd=self.lz(src) + [thr, lut],
+                      wr=[gout, ws, lab])
+            out.gate_cut = len(self.fwd)
+            return out
+        if self.labels is None:
+            out = OutRef(y)
         out.gate_out = gout
-        out.gate_fused = _on('ADDK_FUSE_GATE') and lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
+        out.gate_fused = fused
         if out.gate_fused:
             a = self._up_args(L.GateUpsampleArgs, src, OH, OW)
             ws = self.buf((int(lib.addk_gate_upsample_ws_bytes(N, OH, OW)) + 3) // 4, zero=True)
@@ -1474,6 +1538,8 @@ class Graph:
         else:
             self._add(self.fwd, 'gate_count_torch', _gate_count_torch, y, thr, gout, rd=[y, thr], wr=[gout], pin=True)
         out.gate_cut = len(self.fwd)
+        if self.labels is not None:
+            self._labels_cold(y, lab, lut)           # behind the cut: only for an image that leaves here
         return out
 
     def gap(self, src, relu_in=False):
@@ -1606,6 +1672,24 @@ def _gate_count_torch(y, thr, gout, stream):
     return 0
 
 
+def _label_cast_torch(am, lut, lab, stream):
+    """Cold path of the label heads: the int64 arg-max map as uint8, through the table where there is one; torch ops on the current
+    stream (pinned to the plan's main stream, as _gate_count_torch)."""
+    lab.copy_(am if lut is None else lut[am])
+    return 0
+
+
+def label_lut(lut, device):
+    """`label_lut` of the public label-map calls as what the plan binds: None, or a uint8 [256] tensor on `device`.  Anything that is
+    not 256 uint8 entries is a ValueError."""
+    if lut is None:
+        return None
+    t = lut if isinstance(lut, torch.Tensor) else torch.as_tensor(lut)
+    if t.dtype != torch.uint8 or tuple(t.shape) != (256,):
+        raise ValueError('label_lut must be 256 uint8 entries (got %s %s)' % (t.dtype, tuple(t.shape)))
+    return t.detach().to(device).contiguous().clone()
+
+
 def _in_stage(lib, inref, N, Cc, HW, ptr, ld, stream):
     return lib.addk_nchw_to_nhwc(inref.ptr, N, Cc, HW, ptr, ld, stream)
 
@@ -1627,7 +1711,7 @@ class OutRef:
     """A plan output: tensor + how its incoming gradient pointer is patched per backward call."""
 
     def __init__(self, y):
-        self.y = y               # [N,C,OH,OW] logits; None where a head consumes the low-resolution logits instead
+        self.y = y               # [N,C,OH,OW] logits; None where a head consumes the low-resolution logits instead; the uint8 [N,OH,OW] map of a label head
         self.dy_ptr, self.dy_scale, self.dynamic = None, None, True
         self.bwd_args = None     # ResizeBwdArgs (logits path)
         self.bwd_cmd = None      # generic nhwc path
@@ -1638,6 +1722,7 @@ class OutRef:
         self.score = None        # its binding, set by ValidationStep: the loss binding + entropy, confusion, pred
         self.fused_profile = False  # logits consumed by the per-image profile launch of an exit-profile plan (exit_profile.ExitProfile): y is None
         self.profile = None      # its binding, set by ExitProfile: target, thr, nthr, entropy, share, confusion, pred
+        self.labels = False      # y is the label map of a label-map plan (Graph.labels): no logits exist
         self.gate_out = None     # [N,2] device tensor of a gated exit: (entropy, share of pixels above the threshold)
         self.gate_scale = 1.0    # factor the host applies to gate_out[:, 0] (the stand-alone entropy kernel leaves a sum)
         self.gate_fused = False  # the gate launch writes the pinned host words itself; else the host copies gate_out

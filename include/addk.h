@@ -561,6 +561,34 @@ int addk_gate_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, in
 int64_t addk_gate_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW);
 int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream);
 
+/* Label head of an inference exit (decoder.py:28 + eval.py:218-221): the arg-max over channels of the up-sampled logits, one
+ * byte per high-resolution pixel, straight from the LOW-resolution NHWC logits [N,H,W,C] (the arithmetic of addk_resize_fwd
+ * bit for bit; the [N,C,OH,OW] tensor is never materialised), in ONE launch:
+ *   labels[n,y,x] = pred, or lut256[pred];  pred = arg-max over channels (ties: lowest channel) — the bytes of
+ *                   addk_score_upsample's pred_out and of addk_argmax_nchw on addk_resize_fwd's NCHW output
+ * No workspace, no atomics: deterministic.  addk_label_upsample_supported() == addk_score_upsample_supported(); where it is 0
+ * addk_label_upsample returns ADDK_ERR_INVALID without launching. */
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
+  int32_t N, H, W, C, OH, OW;
+  const uint8_t* lut256;             /* NULL: the class index; else lut256[class] (e.g. train id -> Cityscapes labelId) */
+  uint8_t* labels;                   /* [N,OH,OW] */
+} addk_label_upsample_args;
+int addk_label_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+int addk_label_upsample(const addk_label_upsample_args* a, void* stream);
+
+/* The gate launch that also leaves the label map: addk_gate_upsample and addk_label_upsample in ONE walk.  out / out_host
+ * receive the bits of addk_gate_upsample on the same input with the same *max_thr, labels the bytes of addk_label_upsample;
+ * the map is written for every image, whatever the host then decides (one byte per pixel).  gate.ws: the workspace of
+ * addk_gate_upsample (addk_gate_upsample_ws_bytes() zero-initialised bytes, ticket word left at zero: replayable from a
+ * hipGraph).  Supported exactly where addk_gate_upsample_supported() is 1; otherwise ADDK_ERR_INVALID without launching. */
+typedef struct {
+  addk_gate_upsample_args gate;
+  const uint8_t* lut256;             /* NULL: the class index; else lut256[class] */
+  uint8_t* labels;                   /* [N,OH,OW] */
+} addk_gate_label_upsample_args;
+int addk_gate_label_upsample(const addk_gate_label_upsample_args* a, void* stream);
+
 /* Exit profile of a validation pass (eval.py:195-230): what the early-exit operating curve needs of one exit, PER IMAGE, in
  * ONE launch over the LOW-resolution NHWC logits [N,H,W,C] (the walk and the arithmetic of the two heads above):
  *   ent_out[n]            = normalised Shannon entropy of image n: the bits of addk_gate_upsample's out[2n]
