@@ -15,49 +15,29 @@ logits are written only for the image that leaves.  Exit k's logits are forward(
 and conv_aspp[k] when the level differs; no EDM runs, so its in-place ReLU (Q3) does not happen.  The 2^-last size (Q5) is a
 quirk of the working 'edm' path and stays only there: the heads training optimises are forward()'s.
 
-output='labels' (both plans): every exit ends in a label head instead (plan.Graph.labels) and returns the plan-owned uint8 [1,H,W]
+output='labels' (both plans): every exit ends in a label head instead (plan.Graph.head 'labels') and returns the plan-owned uint8 [1,H,W]
 arg-max map of its logits; no [N,C,H,W] buffer exists.  'edm': [early head k] and the final head end in one `label_upsample` launch.
 'entropy' / 'max': the gate launch leaves the map as well (`gate_label_upsample`), so nothing is left to replay for the image that
 leaves — [trunk up to exit k] [head k + the gate-and-labels launch] ... [remaining cells + final head + its `label_upsample`]."""
+import os
+
 import torch
 
 from .module import ensure_layout
-from .plan import Act, Graph, label_lut as _label_lut
+from .plan import Act, Graph, OutRef, env_graph_infer, env_streams, label_lut as _label_lut
 
 OUTPUTS = ('logits', 'labels')
-
-
-def _label_mode(output, label_lut, device):
-    """Graph.labels of a dynamic plan: None for output='logits', else {'lut': uint8[256] device tensor or None}."""
-    if output not in OUTPUTS:
-        raise ValueError('output must be one of %s (got %r)' % (OUTPUTS, output))
-    lut = _label_lut(label_lut, device)
-    return {'lut': lut} if output == 'labels' else None
 
 
 class DynamicPlan:
     def __init__(self, model, edm, x, output='logits', label_lut=None):
         from .modeling.ADD import _aspp_size
-        labels = _label_mode(output, label_lut, x.device)
-        for p in list(model.parameters()) + list(edm.parameters()):
-            ensure_layout(p)
-        if x.shape[0] != 1:
-            # ADD.py:421 `if confidence_value > threshold` on a [bs, 1] tensor raises for bs > 1 ("Boolean value of Tensor with more
-            # than one value is ambiguous"): the gate is a per-image decision (eval.py:195-230 runs bs = 1); same error class here
-            raise RuntimeError('dynamic_inference gates one image at a time (got batch size %d): the reference\'s '
-                               '`if confidence_value > threshold` is ambiguous for more than one value' % x.shape[0])
-        self.g = g = Graph(x.device, False, False, None)
-        g.labels = labels
         # the gate scalar travels through pinned host memory: the fused EDM head (csrc/edm.hip) writes it there itself; on the generic path an
         # asynchronous 4-byte copy does.  Either way the host waits on ONE event, not on the whole device (ADD.py:421 does
         # `if confidence_value > threshold`, a blocking read)
-        self._conf_host = torch.zeros(1, dtype=torch.float32)
-        self._conf_evt = None
-        if x.is_cuda:                                   # (dry-run planning on CPU in tests/test_plan_dryrun.py builds plans without a device)
-            self._conf_host = self._conf_host.pin_memory()
-            self._conf_evt = torch.cuda.Event()
+        a = self._begin((model, edm), x, output, label_lut, 1)
+        g = self.g
         self.conf_fused = []
-        a, self.inref = g.input_nchw(x)
         size = (a.H, a.W)
         aspp_size = _aspp_size(size, model.network_arch[-1])          # 2^-last (SURVEY Q5)
         self.trunk_end, self.head_rng, self.conf, self.heads = [], [], [], []
@@ -76,7 +56,6 @@ class DynamicPlan:
                     ca = edm.emit(g, y, host_out=self._conf_host if x.is_cuda else None)
                     self.conf_fused.append(bool(g.edm_fused))
                     if g.edm_fused:                                   # the head wrote [N,1,1,1] itself (and the pinned word): no layout launch
-                        from .plan import OutRef
                         conf = OutRef(ca.raw.view().permute(0, 3, 1, 2))
                     else:
                         conf = g.output_nchw(ca)                      # EDM applies ReLU to y in place (Q3) ...
@@ -92,6 +71,31 @@ class DynamicPlan:
                     self.final = model._head(g, y, low, size, aspp_size, it, model.network_arch[i], resize=False, adapt=False)
         self._finish(x)
 
+    def _begin(self, modules, x, output, label_lut, words):
+        """What both plans start with: the checks, the inference Graph with its label mode, `words` pinned host words the gate value
+        travels through and the event the host waits on, and the input -> its activation."""
+        if output not in OUTPUTS:
+            raise ValueError('output must be one of %s (got %r)' % (OUTPUTS, output))
+        lut = _label_lut(label_lut, x.device)
+        for m in modules:
+            for p in m.parameters():
+                ensure_layout(p)
+        if x.shape[0] != 1:
+            # ADD.py:421 `if confidence_value > threshold` on a [bs, 1] tensor raises for bs > 1 ("Boolean value of Tensor with more
+            # than one value is ambiguous"): the gate is a per-image decision (eval.py:195-230 runs bs = 1); same error class here
+            raise RuntimeError('dynamic_inference gates one image at a time (got batch size %d): the reference\'s '
+                               '`if confidence_value > threshold` is ambiguous for more than one value' % x.shape[0])
+        self.g = g = Graph(x.device, False, False, None)
+        if output == 'labels':
+            g.head, g.lut = 'labels', lut
+        self._conf_host = torch.zeros(words, dtype=torch.float32)
+        self._conf_evt = None
+        if x.is_cuda:                                   # (dry-run planning on CPU in tests/test_plan_dryrun.py builds plans without a device)
+            self._conf_host = self._conf_host.pin_memory()
+            self._conf_evt = torch.cuda.Event()
+        a, self.inref = g.input_nchw(x)
+        return a
+
     def _finish(self, x):
         g = self.g
         g.finalize()
@@ -101,8 +105,7 @@ class DynamicPlan:
         self.inref.bind(self.x_static)
         self.graphs = {}          # (begin, end) -> hipGraph of that launch-list segment
         self.segs = {}            # (begin, end) -> that segment's launch list, level-ordered / batched / scheduled on two streams
-        import os
-        g.nstreams = int(os.environ.get('ADDK_STREAMS', '2'))
+        g.nstreams = env_streams()
         self.calls = 0
 
     def check_params(self):
@@ -111,7 +114,6 @@ class DynamicPlan:
     def _seg(self, i0, i1):
         """Run launch-list segment [i0, i1): eagerly the first two calls, then as a captured hipGraph (each segment —
         trunk up to a gate, an exit head, the remainder — is its own graph; the host gate picks which ones replay)."""
-        import os
         g = self.g
         if i1 < 0:
             i1 = len(g.fwd)
@@ -122,7 +124,7 @@ class DynamicPlan:
                 g.level_batch(cmds)
             g.place(cmds)
             self.segs[(i0, i1)] = cmds
-        if self.calls < 3 or os.environ.get('ADDK_GRAPH_INFER', '1') != '1':
+        if self.calls < 3 or not env_graph_infer():
             g.run_parallel(cmds, None)
             return
         gr = self.graphs.get((i0, i1))
@@ -168,43 +170,25 @@ class GatePlan(DynamicPlan):
         from .modeling.ADD import _aspp_size
         if kind not in KINDS:
             raise ValueError('confidence must be one of %s (got %r)' % (('edm',) + KINDS, kind))
-        labels = _label_mode(output, label_lut, x.device)
-        for p in model.parameters():
-            ensure_layout(p)
-        if x.shape[0] != 1:              # the same decision as DynamicPlan: one image per gate
-            raise RuntimeError('dynamic_inference gates one image at a time (got batch size %d): the reference\'s '
-                               '`if confidence_value > threshold` is ambiguous for more than one value' % x.shape[0])
         self.kind = kind
-        self.g = g = Graph(x.device, False, False, None)
-        g.labels = labels
         # (entropy, share) of the gated exit travel through pinned host memory: the gate launch writes them there itself; on the
         # stand-alone path an asynchronous 8-byte copy does.  Either way the host waits on ONE event, not on the whole device
-        self._conf_host = torch.zeros(2, dtype=torch.float32)
-        self._conf_evt = None
+        a = self._begin((model,), x, output, label_lut, 2)
+        g = self.g
         self._thr = torch.zeros(1, dtype=torch.float32, device=x.device)      # the word the 'max' gate compares against
-        if x.is_cuda:
-            self._conf_host = self._conf_host.pin_memory()
-            self._conf_evt = torch.cuda.Event()
-        a, self.inref = g.input_nchw(x)
         size = (a.H, a.W)
         aspp_size = _aspp_size(size, model.network_arch[-1] + 2)       # forward()'s (ADD.emit)
-        self.trunk_end, self.head_rng, self.heads = [], [], []
-        self.final, it = None, 0
-        for i, y, low in model._trunk(g, a):
-            lvl = model.network_arch[i]
-            if i in model.C_index and i != model.num_net - 1:
+        self.trunk_end, self.head_rng, self.heads, self.final = [], [], [], None
+        for i, y, low, it, lvl in model._exits(g, a):
+            if i == model.num_net - 1:
+                self.final = model._head(g, y, low, size, aspp_size, it, lvl)
+            else:
                 self.trunk_end.append(len(g.fwd))
                 g.gate = {'kind': kind, 'host': self._conf_host if x.is_cuda else None, 'thr': self._thr}
                 h = model._head(g, y, low, size, aspp_size, it, lvl)
                 g.gate = None
                 self.heads.append(h)
                 self.head_rng.append((h.gate_cut, len(g.fwd)))          # [trunk_end, gate_cut): head + gate; [gate_cut, end): resize (labels: empty)
-            elif i == model.num_net - 1:
-                self.final = model._head(g, y, low, size, aspp_size, it, lvl)
-            else:
-                continue
-            if lvl != model.network_arch[-1]:
-                it += 1                                                  # ADD.emit: conv_aspp is indexed by the adapted exits
         self._finish(x)
 
     def run(self, x, threshold):

@@ -4,8 +4,8 @@ The reference runs every validation image through the gated network at one thres
 the average confidence; a sweep repeats the whole set per threshold.  For the 'entropy' and 'max' gates (dynamic.GatePlan) none of
 what the gate reads depends on the threshold of the DECISION: exit k's prediction is forward()'s `model(x)[k]`, its entropy is one
 number per image, and its top-probability share is one number per image and per top-probability threshold.  ExitProfile therefore runs
-the static, batched inference plan of validate.ValidationStep and ends every exit in one `addk_profile_upsample` launch
-(plan.Graph.profile, csrc/loss.hip profile_up_kernel) that leaves, PER IMAGE, the entropy, the share at each of `max_thresholds` and the
+the static, batched inference plan of resident.InferenceStep and ends every exit in one `addk_profile_upsample` launch
+(plan.Graph.head 'profile', csrc/loss.hip profile_up_kernel) that leaves, PER IMAGE, the entropy, the share at each of `max_thresholds` and the
 confusion matrix.  Every point of the curve follows on the host (exit_curve) by GatePlan.run's own decision rule.
 
     prof = ExitProfile(model, (N, 3, H, W), max_thresholds=(0.5, 0.9, 0.99))
@@ -16,16 +16,12 @@ confusion matrix.  Every point of the curve follows on the host (exit_curve) by 
     pts = prof.curve('max')                  # at max_thresholds
 
 The 'edm' gate is out of reach of this pass: its early head is not forward()'s."""
-import os
-
 import torch
 
 from . import _lib as L
-from . import plan as _plan
 from .dynamic import KINDS
 from .metrics import mean_iou
-from .module import ensure_layout
-from .plan import Graph
+from .resident import InferenceStep
 
 MAX_THRESHOLDS = 16
 
@@ -97,30 +93,18 @@ def exit_curve(entropy, share, confusion, kind, thresholds, max_thresholds=None,
     return points
 
 
-class ExitProfile:
+class ExitProfile(InferenceStep):
+    head = 'profile'
+
     def __init__(self, model, batch_shape, max_thresholds=(0.5, 0.9, 0.99), ignore_index=255, keep_predictions=False,
                  use_graph=None, nstreams=None):
-        self.lib = L.load()
-        p0 = next(model.parameters())
-        _plan.require_device(p0)
-        self.model, self.dev = model, p0.device
-        self.batch_shape = tuple(int(v) for v in batch_shape)
-        N, _, H, W = self.batch_shape
         self.max_thresholds = _check_thresholds(max_thresholds)
+        super().__init__(model, batch_shape, use_graph, nstreams)
         # the evaluator counts every label in [0, classes) (utils/metrics.py:34-43); ignore_index is what the loader paints elsewhere
         self.ignore_index = int(ignore_index)
         self.keep_predictions = bool(keep_predictions)
-        self.x = torch.zeros(self.batch_shape, dtype=torch.float32, device=self.dev)
-        self.target = torch.zeros((N, H, W), dtype=torch.int64, device=self.dev)
         self.thr = torch.zeros(max(len(self.max_thresholds), 1), dtype=torch.float32, device=self.dev)
         self._write_thresholds()
-        if nstreams is None:
-            nstreams = int(os.environ.get('ADDK_STREAMS', '2'))
-        self.nstreams = nstreams
-        if use_graph is None:
-            use_graph = self.dev.type == 'cuda' and os.environ.get('ADDK_GRAPH_INFER', '1') == '1'
-        self.use_graph = use_graph
-        self.nex = 0
         self._build()
         self.reset()
 
@@ -140,58 +124,27 @@ class ExitProfile:
         self.reset()
 
     # ---------------- plan ----------------
-    def _build(self):
-        """Emit the plan for the model's CURRENT parameter storage (see ValidationStep._build)."""
-        lib, dev, model = self.lib, self.dev, self.model
+    def _emit(self, g, a):
+        dev = self.dev
         N, _, H, W = self.batch_shape
         NT = len(self.max_thresholds)
-        for p in model.parameters():
-            ensure_layout(p)
-        # an inference plan whatever model.training says: mode, parameters, running statistics and num_batches_tracked are left alone
-        g = self.g = Graph(dev, False, False, None)
-        g.profile = True
-        g.reorder = True
-        a, self.inref = g.input_nchw(self.x)
-        self.inref.bind(self.x)
-        outs = model.emit(g, a)
-        outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
-        assert all(getattr(o, 'fused_profile', False) for o in outs), 'the model did not end in Graph.resize_to_nchw'
-        nex, ncls = len(outs), outs[0].shape[1]
-        assert all(tuple(o.shape) == (N, ncls, H, W) for o in outs)
+        outs, first = self._emit_exits(g, a)
+        nex, ncls = self.nex, self.ncls
         if 0 <= self.ignore_index < ncls:
             raise ValueError('ExitProfile: ignore_index %d is one of the %d classes the evaluator counts' % (self.ignore_index, ncls))
-        if self.nex == 0:
-            self.nex, self.ncls = nex, ncls
+        if first:
             self.ent = torch.zeros((nex, N), dtype=torch.float32, device=dev)             # this batch, per exit and image
             self.share = torch.zeros((nex, N, NT), dtype=torch.float32, device=dev)
             self.cm = torch.zeros((nex, N, ncls, ncls), dtype=torch.int64, device=dev)
             self.pred = torch.zeros((nex, N, H, W), dtype=torch.uint8, device=dev) if self.keep_predictions else None
-        assert (nex, ncls) == (self.nex, self.ncls)
         # the launch adds into the matrices: zero bits of int64 written as twice as many fp32 zeros
-        g._add(g.fwd, 'profile_zero', lib.addk_fill, self.cm.data_ptr(), 2 * self.cm.numel(), 0.0, wr=[self.cm])
+        g._add(g.fwd, 'profile_zero', self.lib.addk_fill, self.cm.data_ptr(), 2 * self.cm.numel(), 0.0, wr=[self.cm])
         for i, o in enumerate(outs):
-            o.profile = dict(target=self.target, thr=self.thr, nthr=NT, entropy=self.ent[i], share=self.share[i], confusion=self.cm[i],
+            o.binding = dict(target=self.target, thr=self.thr, nthr=NT, entropy=self.ent[i], share=self.share[i], confusion=self.cm[i],
                              pred=self.pred[i] if self.pred is not None else None)
         self.outs = outs
-        g.finalize(self.nstreams)
-        assert not g.bwd and not g.nbt
-        self._ptrs = self._storage()
-        self.nbytes = g.nbytes
-        self.graph, self.calls = None, 0
-
-    def _storage(self):
-        bufs = [b for n, b in self.model.named_buffers() if not n.endswith('num_batches_tracked')]
-        return [t.data_ptr() for t in list(self.g.params) + bufs]
 
     # ---------------- replay ----------------
-    def _run(self):
-        main = torch.cuda.current_stream() if self.dev.type == 'cuda' else None
-        self.g.run_parallel(self.g.fwd, main)
-
-    def load_batch(self, images, targets):
-        self.x.copy_(images, non_blocking=True)
-        self.target.copy_(targets, non_blocking=True)
-
     def step(self, images=None, targets=None, count=None):
         """Profiles the resident batch (or `images` / `targets` if given) and appends the rows of its first `count` images (default: all N;
         a short last batch passes fewer and the rest is dropped) to the device-side logs.  No host synchronisation, except once when the
@@ -200,21 +153,9 @@ class ExitProfile:
         count = N if count is None else int(count)
         if not 0 <= count <= N:
             raise ValueError('count must lie in [0, %d] (got %d)' % (N, count))
-        if self._storage() != self._ptrs:
-            self._build()
         if images is not None:
             self.load_batch(images, targets)
-        self.calls += 1
-        if self.use_graph and self.calls >= 3:
-            if self.graph is None:             # the list has run eagerly twice; the capture itself executes nothing
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                    self._run()
-                self.graph = graph
-            self.graph.replay()
-        else:
-            self._run()
+        self._replay()
         # outside the captured region, ordered behind it on the same stream: copies of the batch's rows
         self._log.append((self.ent[:, :count].clone(), self.share[:, :count].clone(), self.cm[:, :count].clone()))
         self.batches += 1
@@ -256,8 +197,3 @@ class ExitProfile:
         if not self.keep_predictions:
             raise L.AddkError('ExitProfile was built without keep_predictions=True')
         return [self.pred[i].clone() for i in range(self.nex)]
-
-    def close(self):
-        if self.dev.type == 'cuda':
-            torch.cuda.synchronize()
-        self.graph = None

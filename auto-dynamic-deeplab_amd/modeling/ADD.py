@@ -260,18 +260,23 @@ class ADD(AddkModule):
         g.tag = 'decoder'
         return self.decoder.emit(g, y, low, size)
 
+    def _exits(self, g, x):
+        """forward()'s exits in order, over _trunk: (cell index, y, low, it, level) as _head takes them.  The exit cells are C_index plus the
+        last cell; `it` indexes conv_aspp by the adapted exits (level != the last cell's) before this one.  A caller that stops iterating
+        stops the trunk: no later cell is emitted."""
+        it = 0
+        for i, y, low in self._trunk(g, x):
+            if i in self.C_index or i == self.num_net - 1:
+                lvl = self.network_arch[i]
+                yield i, y, low, it, lvl
+                if lvl != self.network_arch[-1]:
+                    it += 1
+
     def emit(self, g, x):
         """reference ADD.py:277-325."""
         size = (x.H, x.W)
         aspp_size = _aspp_size(size, self.network_arch[-1] + 2)
-        it, out = 0, []
-        for i, y, low in self._trunk(g, x):
-            if i in self.C_index or i == self.num_net - 1:
-                lvl = self.network_arch[i]
-                out.append(self._head(g, y, low, size, aspp_size, it, lvl))
-                if lvl != self.network_arch[-1]:
-                    it += 1
-        return out
+        return [self._head(g, y, low, size, aspp_size, it, lvl) for _, y, low, it, lvl in self._exits(g, x)]
 
     def forward(self, x):
         return self.run_plan(self.emit, (x,))
@@ -290,20 +295,13 @@ class ADD(AddkModule):
         return out, feat
 
     def _emit_exit(self, g, x, k):
-        """forward()'s exit k alone (segment.Segmenter): the trunk only up to that exit's cell, then emit()'s head for it — aspp_size
-        from 2^-(last+2), conv_aspp indexed by the adapted exits before it."""
+        """forward()'s exit k alone (segment.Segmenter): the trunk only up to that exit's cell, then emit()'s head for it."""
         size = (x.H, x.W)
         aspp_size = _aspp_size(size, self.network_arch[-1] + 2)
-        it, n = 0, 0
-        for i, y, low in self._trunk(g, x):
-            if i in self.C_index or i == self.num_net - 1:
-                lvl = self.network_arch[i]
-                if n == k:
-                    return self._head(g, y, low, size, aspp_size, it, lvl)       # the generator stops here: no later cell is emitted
-                n += 1
-                if lvl != self.network_arch[-1]:
-                    it += 1
-        raise IndexError('exit %d of %d' % (k, n))
+        for n, (_, y, low, it, lvl) in enumerate(self._exits(g, x)):
+            if n == k:
+                return self._head(g, y, low, size, aspp_size, it, lvl)       # the generator stops here: no later cell is emitted
+        raise IndexError('exit %d of %d' % (k, n + 1))
 
     def num_exits(self):
         """length of forward()'s output list"""

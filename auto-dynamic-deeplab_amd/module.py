@@ -73,8 +73,7 @@ class Plan:
                 raise TypeError('emit returned %r' % type(r))
         # whole lists are always replayed front to back here: level-ordered, batched and on two streams like the fused train step
         g.reorder = True
-        import os
-        g.finalize(int(os.environ.get('ADDK_STREAMS', '2')))
+        g.finalize(_plan.env_streams())
         self.params = list(g.params)
         self.param_ptrs = [p.data_ptr() for p in self.params]
         self.serial = 0
@@ -100,7 +99,7 @@ class Plan:
         if not inputs[0].is_cuda:
             return False
         if not (self.g.want_grad or self.g.training):
-            return os.environ.get('ADDK_GRAPH_INFER', '1') == '1'
+            return _plan.env_graph_infer()
         if os.environ.get('ADDK_GRAPH_MODULE', '1') != '1':
             return False
         if getattr(self, '_has_coll', None) is None:

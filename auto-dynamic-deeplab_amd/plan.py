@@ -32,6 +32,16 @@ def _env_int(name, default):
     return int(os.environ.get(name, default))
 
 
+def env_streams():
+    """ADDK_STREAMS: the HIP streams a plan is scheduled on where its caller names no number."""
+    return _env_int('ADDK_STREAMS', '2')
+
+
+def env_graph_infer():
+    """ADDK_GRAPH_INFER: inference plans are replayed as hipGraphs (0 = the eager launch loop)."""
+    return _on('ADDK_GRAPH_INFER')
+
+
 def _ptr(x):
     return None if x is None else x.ptr
 
@@ -359,6 +369,9 @@ BATCHED = {'bn_finalize': _Table('addk_bn_finalize_batch', 'C'), 'bn_bwd': _Tabl
            'allreduce': _Arena()}
 
 
+HEADS = (None, 'ce', 'score', 'profile', 'labels')     # Graph.head / OutRef.head
+
+
 class Graph:
     def __init__(self, device, training, want_grad, world=None):
         self.lib = L.load()
@@ -372,12 +385,13 @@ class Graph:
         self.pgrad = {}               # param -> grad tensor
         self.pgrad_views = None       # param -> view of a flat gradient buffer to use as its gradient (train.TrainStep)
         self.reorder = False          # level-order and batch the lists although this is not a training plan (set before finalize)
-        self.fuse_ce = False          # logits outputs feed the fused up-sampling + cross-entropy launch (train.TrainStep)
-        self.fuse_score = False       # logits outputs of an inference plan feed the fused up-sampling + scoring launch (validate.ValidationStep)
-        self.profile = False          # logits outputs of an inference plan feed the per-image exit-profile launch (exit_profile.ExitProfile)
-        self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}
-        self.labels = None            # logits outputs of an inference plan end in the label head (dynamic plans, segment.Segmenter): {'lut': uint8[256] or None}
-        self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted (fuse_score, profile)
+        # who consumes the decoder's low-resolution logits (resize_to_nchw): None = nobody, the resize writes [N,C,OH,OW]; 'ce' = the fused
+        # up-sampling + cross-entropy launch (train.TrainStep); 'score' = the scoring launch (validate.ValidationStep); 'profile' = the
+        # per-image exit-profile launch (exit_profile.ExitProfile); 'labels' = the label head (dynamic plans, segment.Segmenter)
+        self.head = None
+        self.lut = None               # 'labels': the uint8 [256] device table the class indices go through, or None
+        self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}; with head None or 'labels'
+        self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted ('score', 'profile')
         self.pginit = set()
         self._pcols = {}
         self.params = []              # ordered unique params touched
@@ -1285,17 +1299,18 @@ class Graph:
         of a fused training step (_ce_head), the scoring head of a validation plan (_score_head), the per-image profile of an exit-profile
         plan (_profile_head), the gate of an early exit (gate_head), the label head of a label-map plan (_label_head), or nobody: the resize
         into a contiguous [N,C,OH,OW] tensor, and its backward."""
-        assert src.bn is None and not src.relu
-        if (self.fuse_ce and self.want_grad and src.needs_grad
-                and self.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1):
-            return self._ce_head(src, OH, OW)
-        if self.fuse_score and not self.want_grad:
+        assert src.bn is None and not src.relu and self.head in HEADS
+        if self.want_grad:
+            if (self.head == 'ce' and src.needs_grad
+                    and self.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1):
+                return self._ce_head(src, OH, OW)
+        elif self.head == 'score':
             return self._score_head(src, OH, OW)
-        if self.profile and not self.want_grad:
+        elif self.head == 'profile':
             return self._profile_head(src, OH, OW)
-        if self.gate is not None and not self.want_grad:
+        elif self.gate is not None:
             return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'])
-        if self.labels is not None and not self.want_grad:
+        elif self.head == 'labels':
             return self._label_head(src, OH, OW)
         y, emit_resize = self._logits_resize(src, OH, OW)
         emit_resize()
@@ -1333,22 +1348,34 @@ class Graph:
         a.logits, a.ld, a.N, a.H, a.W, a.C, a.OH, a.OW = s.x, s.ld, src.N, src.H, src.W, src.C, OH, OW
         return a
 
+    def _late_head(self, head, src, OH, OW, lst, emitters, emit):
+        """The OutRef of a head whose step binds its tensors only after the module tree was emitted: no resize, no [N,C,OH,OW] buffer, `y`
+        is None and `shape` says what the logits would be.  finalize() runs `emitters`; by then `binding` must be there, and
+        `emit(binding)` appends the head's launches to `lst` under the tag of the exit."""
+        out = OutRef(None)
+        out.head, out.shape = head, (src.N, src.C, OH, OW)
+        tag = self.tag
+
+        def late():
+            assert out.binding is not None, 'fused logits output without a %s binding' % head
+            first = len(lst)
+            emit(out.binding)
+            for c in lst[first:]:
+                c.tag = tag
+        emitters.append(late)
+        return out
+
     @staticmethod
     def _bind_loss(a, b):
-        """The loss binding a step attached to an OutRef (`ce` / `score`) into the loss head's or the scoring head's arguments."""
+        """The loss binding a step attached to an OutRef ('ce' / 'score') into the loss head's or the scoring head's arguments."""
         a.target, a.class_w, a.ignore_index = b['target'].data_ptr(), b['class_w'], b['ignore_index']
         a.wsum, a.scale, a.loss_out = b['wsum'].data_ptr(), b['scale'], b['loss'].data_ptr()
 
     def _ce_head(self, src, OH, OW):
-        """Logits output of a fused training step (`self.fuse_ce`, set by train.TrainStep): nobody reads the full-resolution logits, so
-        the resize is not emitted at all and the OutRef carries `shape` and the `ce` slot TrainStep binds; finalize() then places ONE
+        """Logits output of a fused training step (head 'ce', set by train.TrainStep): nobody reads the full-resolution logits, so
+        the resize is not emitted at all and the OutRef carries `shape` and the `binding` TrainStep sets; finalize() then places ONE
         fused up-sampling + cross-entropy launch (`addk_ce_upsample_fwd_bwd`) at the head of the backward list."""
-        out = OutRef(None)
-        out.fused_ce, out.shape = True, (src.N, src.C, OH, OW)
-
-        def emit_ce():
-            ce = out.ce
-            assert ce is not None, 'fused logits output without a loss binding'
+        def emit_ce(ce):
             a = self._up_args(L.CeUpsampleArgs, src, OH, OW)
             self._bind_loss(a, ce)
             gs, a.accumulate, _ = self._grad_into(src)
@@ -1358,25 +1385,19 @@ class Graph:
             self.keep += [a, ws]
             self._add(self.bwd, 'ce_upsample', self.lib.addk_ce_upsample_fwd_bwd, C.byref(a),
                       rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
-        self._bwd_emitters.append(emit_ce)
-        return out
+        return self._late_head('ce', src, OH, OW, self.bwd, self._bwd_emitters, emit_ce)
 
     def _score_head(self, src, OH, OW):
-        """Logits output of a validation plan (`self.fuse_score`, set by validate.ValidationStep): nobody reads the full-resolution
-        logits, so no resize is emitted and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `score` slot the step
-        binds (target, class weights, wsum and the per-exit loss / entropy / confusion / prediction tensors); finalize() then appends
+        """Logits output of a validation plan (head 'score', set by validate.ValidationStep): nobody reads the full-resolution
+        logits, so no resize is emitted and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step
+        sets (target, class weights, wsum and the per-exit loss / entropy / confusion / prediction tensors); finalize() then appends
         ONE `score_upsample` launch per exit to the forward list (`addk_score_upsample`).  Where the library does not take the shape
         (`addk_score_upsample_supported` == 0, e.g. C != 19) the same quantities come from the stand-alone kernels inside this plan:
         resize + ce_fwd_bwd without a gradient + argmax_nchw + confusion + entropy_sum."""
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
-        out = OutRef(None)
-        out.fused_score, out.shape = True, (N, Cc, OH, OW)
-        tag = self.tag
 
-        def emit_score():
-            sc, first = out.score, len(self.fwd)
-            assert sc is not None, 'fused logits output without a score binding'
+        def emit_score(sc):
             tgt, wsum, loss, ent, cm, pred = sc['target'], sc['wsum'], sc['loss'], sc['entropy'], sc['confusion'], sc.get('pred')
             if lib.addk_score_upsample_supported(N, H, W, OH, OW, Cc) == 1:
                 a = self._up_args(L.ScoreUpsampleArgs, src, OH, OW)
@@ -1404,26 +1425,18 @@ class Graph:
                 self._add(self.fwd, 'entropy_sum', lib.addk_entropy_sum, y.data_ptr(), N, Cc, OH * OW, ent.data_ptr(), ws.data_ptr(),
                           rd=[y], wr=[ent, ws])
                 sc['pred_i64'] = am                    # the map of this path is int64: ValidationStep.predictions() narrows it
-            for c in self.fwd[first:]:
-                c.tag = tag
-        self._fwd_late.append(emit_score)
-        return out
+        return self._late_head('score', src, OH, OW, self.fwd, self._fwd_late, emit_score)
 
     def _profile_head(self, src, OH, OW):
-        """Logits output of an exit-profile plan (`self.profile`, set by exit_profile.ExitProfile): as in _score_head no resize is emitted
-        and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `profile` slot the step binds (target, the device array of
+        """Logits output of an exit-profile plan (head 'profile', set by exit_profile.ExitProfile): as in _score_head no resize is emitted
+        and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step sets (target, the device array of
         top-probability thresholds and its length, and this exit's per-image entropy [N], share [N,nthr], confusion [N,C,C] and optional
         prediction tensors); finalize() then appends ONE `profile_upsample` launch per exit (`addk_profile_upsample`).  There is no
         stand-alone form: a shape the library does not take is an error."""
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
-        out = OutRef(None)
-        out.fused_profile, out.shape = True, (N, Cc, OH, OW)
-        tag = self.tag
 
-        def emit_profile():
-            pr = out.profile
-            assert pr is not None, 'fused logits output without a profile binding'
+        def emit_profile(pr):
             tgt, thr, nthr, ent, share, cm, pred = pr['target'], pr['thr'], pr['nthr'], pr['entropy'], pr['share'], pr['confusion'], pr.get('pred')
             if lib.addk_profile_upsample_supported(N, H, W, OH, OW, Cc, nthr) != 1:
                 raise L.AddkError('the exit profile takes 19 classes and at most 16 thresholds (got %d classes, %d thresholds, '
@@ -1436,27 +1449,26 @@ class Graph:
             a.ws = ws.data_ptr()
             self.keep += [a, ws]
             self._add(self.fwd, 'profile_upsample', lib.addk_profile_upsample, C.byref(a),
-                      rd=self.lz(src) + [tgt, thr], wr=[ent, share, cm, pred, ws]).tag = tag
-        self._fwd_late.append(emit_profile)
-        return out
+                      rd=self.lz(src) + [tgt, thr], wr=[ent, share, cm, pred, ws])
+        return self._late_head('profile', src, OH, OW, self.fwd, self._fwd_late, emit_profile)
 
     def _label_map(self, src, OH, OW):
         """The plan-owned uint8 [N,OH,OW] label map of a label head and its OutRef (`shape`: the logits it stands for)."""
         lab = torch.zeros((src.N, OH, OW), dtype=torch.uint8, device=self.device)
         self.nbytes += lab.numel()
         out = OutRef(lab)
-        out.labels, out.shape = True, (src.N, src.C, OH, OW)
+        out.head, out.shape = 'labels', (src.N, src.C, OH, OW)
         return lab, out
 
     def _label_head(self, src, OH, OW):
-        """Logits output of a label-map plan (`self.labels`, set by dynamic.DynamicPlan / GatePlan and segment.Segmenter): what inference
+        """Logits output of a label-map plan (head 'labels', set by dynamic.DynamicPlan / GatePlan and segment.Segmenter): what inference
         keeps of an exit is the arg-max of its up-sampled logits (eval.py:218-221), so no resize is emitted and no [N,C,OH,OW] buffer exists.
         ONE `label_upsample` launch (`addk_label_upsample`) writes the OutRef's `y`, a plan-owned uint8 [N,OH,OW] map: the class index, or
-        lut[class] with `self.labels['lut']`.  Where the library does not take the shape (`addk_label_upsample_supported` == 0, e.g.
+        lut[class] with the table `self.lut`.  Where the library does not take the shape (`addk_label_upsample_supported` == 0, e.g.
         C != 19) the same plan uses the stand-alone kernels: resize + argmax_nchw + a cast in torch ops (_labels_cold)."""
         lib = self.lib
         lab, out = self._label_map(src, OH, OW)
-        lut = self.labels.get('lut')
+        lut = self.lut
         if lib.addk_label_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1:
             a = self._up_args(L.LabelUpsampleArgs, src, OH, OW)
             a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
@@ -1488,20 +1500,20 @@ class Graph:
         plan uses the stand-alone kernels on the materialised logits — `resize_nchw` first, then `entropy_sum` ('entropy': gate_out[0, 0]
         holds the un-normalised sum, `gate_scale` the factor the host applies) or a count in torch ops ('max': gate_out[0, 1]); nothing
         is left behind the cut and the host copies `gate_out` itself (`gate_fused` False).
-        In a label-map plan (`self.labels`) the OutRef's `y` is the uint8 [N,OH,OW] map of _label_head.  Fused form: ONE
+        In a label-map plan (head 'labels') the OutRef's `y` is the uint8 [N,OH,OW] map of _label_head.  Fused form: ONE
         `gate_label_upsample` launch (`addk_gate_label_upsample`) leaves the gate value AND the map, for every image; nothing follows the
         cut and no [N,C,OH,OW] buffer exists.  Stand-alone form: the stand-alone gate above, then, behind the cut, _labels_cold."""
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
         fused = _on('ADDK_FUSE_GATE') and lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
-        if self.labels is None or not fused:
+        labels, lut = self.head == 'labels', self.lut
+        if not labels or not fused:
             y, emit_resize = self._logits_resize(src, OH, OW)
         gout = torch.zeros((N, 2), dtype=torch.float32, device=self.device)
         self.keep += [gout, thr, host_out]
-        if self.labels is not None:
+        if labels:
             lab, out = self._label_map(src, OH, OW)
-            lut = self.labels.get('lut')
-        if self.labels is not None and fused:
+        if labels and fused:
             out.gate_out, out.gate_fused = gout, True
             a = L.GateLabelUpsampleArgs()
             a.gate = self._up_args(L.GateUpsampleArgs, src, OH, OW)
@@ -1514,7 +1526,7 @@ class Graph:
                       wr=[gout, ws, lab])
             out.gate_cut = len(self.fwd)
             return out
-        if self.labels is None:
+        if not labels:
             out = OutRef(y)
         out.gate_out = gout
         out.gate_fused = fused
@@ -1538,7 +1550,7 @@ class Graph:
         else:
             self._add(self.fwd, 'gate_count_torch', _gate_count_torch, y, thr, gout, rd=[y, thr], wr=[gout], pin=True)
         out.gate_cut = len(self.fwd)
-        if self.labels is not None:
+        if labels:
             self._labels_cold(y, lab, lut)           # behind the cut: only for an image that leaves here
         return out
 
@@ -1716,13 +1728,10 @@ class OutRef:
         self.bwd_args = None     # ResizeBwdArgs (logits path)
         self.bwd_cmd = None      # generic nhwc path
         self.shape = None        # (N, C, OH, OW) of the logits a fused head stands for (y is None)
-        self.fused_ce = False    # logits consumed by the fused up-sampling + cross-entropy launch (train.TrainStep): y is None
-        self.ce = None           # its loss binding, set by TrainStep: target, class_w, ignore_index, wsum, scale, loss
-        self.fused_score = False  # logits consumed by the scoring launch of a validation plan (validate.ValidationStep): y is None
-        self.score = None        # its binding, set by ValidationStep: the loss binding + entropy, confusion, pred
-        self.fused_profile = False  # logits consumed by the per-image profile launch of an exit-profile plan (exit_profile.ExitProfile): y is None
-        self.profile = None      # its binding, set by ExitProfile: target, thr, nthr, entropy, share, confusion, pred
-        self.labels = False      # y is the label map of a label-map plan (Graph.labels): no logits exist
+        self.head = None         # Graph.head of the head that consumed the logits; None: y is the real logits.  'labels': y is the label map
+        # what the step binds to a 'ce' / 'score' / 'profile' head before finalize() — 'ce': target, class_w, ignore_index, wsum, scale, loss;
+        # 'score': those + entropy, confusion, pred; 'profile': target, thr, nthr, entropy, share, confusion, pred
+        self.binding = None
         self.gate_out = None     # [N,2] device tensor of a gated exit: (entropy, share of pixels above the threshold)
         self.gate_scale = 1.0    # factor the host applies to gate_out[:, 0] (the stand-alone entropy kernel leaves a sum)
         self.gate_fused = False  # the gate launch writes the pinned host words itself; else the host copies gate_out

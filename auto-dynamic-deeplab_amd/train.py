@@ -60,13 +60,13 @@ class TrainStep:
         g = self.g = Graph(dev, True, True, sync_comm)
         g.pgrad_views = gviews
         # the step never hands out full-resolution logits: up-sampling + loss + their backward run as one launch per exit
-        g.fuse_ce = os.environ.get('ADDK_FUSE_CE', '1') == '1'
+        g.head = 'ce' if os.environ.get('ADDK_FUSE_CE', '1') == '1' else None
         a, self.inref = g.input_nchw(self.x)
         self.inref.bind(self.x)
         outs = model.emit(g, a)
         self.outs = outs
         nex = len(outs)
-        ncls = outs[0].shape[1] if outs[0].fused_ce else outs[0].y.shape[1]
+        ncls = outs[0].shape[1] if outs[0].head == 'ce' else outs[0].y.shape[1]
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.wsum = torch.zeros(1, dtype=torch.float32, device=dev)
         ws = torch.zeros(int(lib.addk_ce_ws_floats(N, H * W)), dtype=torch.float32, device=dev)
@@ -78,8 +78,8 @@ class TrainStep:
                self.wsum.data_ptr(), ws.data_ptr(), rd=[self.target], wr=[self.wsum, ws])
         self.dlogits = []
         for o in outs:
-            if o.fused_ce:
-                o.ce = dict(target=self.target, class_w=cwp, ignore_index=ignore_index, wsum=self.wsum, scale=1.0 / nex, loss=self.loss)
+            if o.head == 'ce':
+                o.binding = dict(target=self.target, class_w=cwp, ignore_index=ignore_index, wsum=self.wsum, scale=1.0 / nex, loss=self.loss)
                 self.dlogits.append(None)
                 continue
             d = torch.empty_like(o.y)
@@ -98,7 +98,7 @@ class TrainStep:
             # two HIP streams: independent branches of the cell DAG overlap (-4 ms of 82 at config 2, eager or captured);
             # 3, 4 and 6 streams measure the same or slightly worse (68.5 / 68.7 / 69.8 / 69.7 ms).  The SyncBN path
             # keeps its collectives on one stream.
-            nstreams = int(os.environ.get('ADDK_STREAMS', '2'))
+            nstreams = _plan.env_streams()
         g.finalize(nstreams)
         self.nbt = NbtCounter(g.nbt)
         self.nbt.bump(); self.nbt.flat.sub_(self.nbt.inc)      # flatten now (pointers must be fixed before graph capture)

@@ -60,7 +60,7 @@ def test_one_profile_launch_per_exit_and_no_full_resolution_logits(dry, arch, ne
     assert names['profile_zero'] == 1 and order.index('profile_zero') < order.index('profile_upsample')
     assert names['bn_eval_affine_batch'] == 1 and names['bn_finalize'] == 0   # inference form
     assert not prof.g.bwd
-    assert all(o.y is None and o.fused_profile and o.profile is not None and tuple(o.shape) == (2, 19, 65, 129) for o in prof.outs)
+    assert all(o.y is None and o.head == 'profile' and o.binding is not None and tuple(o.shape) == (2, 19, 65, 129) for o in prof.outs)
     assert not _has_full_resolution_buffer(prof.g, (2, 19, 65, 129))
     launches = [c for c in prof.g.fwd if c.name == 'profile_upsample']
     assert all(c.tag == 'decoder' for c in launches)                          # tagged like the scoring launch
@@ -120,7 +120,7 @@ def test_plain_eval_plan_keeps_its_resizes(dry):
     plan = next(iter(m._plans().values()))
     names = collections.Counter(c.name for c in plan.g.fwd)
     assert names['resize_nchw'] == 2 and names['profile_upsample'] == 0
-    assert P.Graph(torch.device('cpu'), False, False).profile is False
+    assert P.Graph(torch.device('cpu'), False, False).head is None
 
 
 def test_unsupported_class_count_is_an_error(dry):
@@ -140,6 +140,12 @@ def test_rebuilds_when_the_parameters_move(dry):
     p.data = p.data.clone()
     prof.step()
     assert prof.g is not g0 and prof.batches == 2 and prof.records()['entropy'].shape[1] == 4
+    # after a capture: the rebuild drops the captured graph with the plan it replayed and starts the eager calls again
+    prof = ExitProfile(m, SHAPE, use_graph=True)
+    g0, prof.graph, prof.calls = prof.g, object(), 7
+    p.data = p.data.clone()
+    prof.step()
+    assert prof.g is not g0 and prof.graph is None and prof.calls == 1 and prof.batches == 1
 
 
 def test_profile_abi_declared_and_exported():

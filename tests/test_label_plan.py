@@ -133,7 +133,7 @@ def test_gate_plan_with_labels(dry, arch, gates):
     assert names['resize_nchw'] == 0 and names['gate_upsample'] == 0
     assert names['gate_label_upsample'] == gates and names['label_upsample'] == 1
     for h in plan.heads + [plan.final]:
-        assert h.y.dtype == torch.uint8 and tuple(h.y.shape) == (1,) + HW and h.labels
+        assert h.y.dtype == torch.uint8 and tuple(h.y.shape) == (1,) + HW and h.head == 'labels'
     assert not _has_logits_buffer(g)
     assert g.nbytes <= ref.g.nbytes - (gates + 1) * (19 * 4 - 1) * HW[0] * HW[1]
     # the plan without the mode, built next to it, is what it was
@@ -186,7 +186,7 @@ def test_logits_and_labels_plans_coexist_in_the_cache(dry):
     lut = decode_segmap_lut()
     m.dynamic_inference(x, 0.5, confidence='max', output='labels', label_lut=lut)
     withlut = m._gate_plan(x, 'max', 'labels', lut.tobytes())
-    assert withlut is not m._gate_plan(x, 'max', 'labels') and withlut.g.labels['lut'].tolist() == lut.tolist()
+    assert withlut is not m._gate_plan(x, 'max', 'labels') and withlut.g.lut.tolist() == lut.tolist()
     y, ex, _, conf = m.dynamic_inference(x, 1.0, confidence='edm', edm=edm, output='labels')
     assert y.dtype == torch.uint8 and m._dynamic_plan(x, edm, 'labels') is not m._dynamic_plan(x, edm)
     assert _count(m._dynamic_plan(x, edm).g)['resize_nchw'] == 2
@@ -253,6 +253,12 @@ def test_segmenter_rebuilds_when_the_parameters_move(dry):
     p.data = p.data.clone()
     seg.step()
     assert seg.g is not g0 and seg.calls == 1
+    # after a capture: the rebuild drops the captured graph with the plan it replayed and starts the eager calls again
+    seg = Segmenter(m, (2, 3) + HW, use_graph=True)
+    g0, seg.graph, seg.calls = seg.g, object(), 7
+    p.data = p.data.clone()
+    seg.step()
+    assert seg.g is not g0 and seg.graph is None and seg.calls == 1
 
 
 # ---------------- error paths ----------------

@@ -58,7 +58,7 @@ def test_validation_step_scores_every_exit_without_full_resolution_logits(dry):
     assert names['ce_count'] == 1 and names['score_zero'] == 1               # one target count shared by the exits
     assert names['bn_eval_affine_batch'] == 1 and names['bn_finalize'] == 0   # inference form
     assert not vs.g.bwd
-    assert all(o.y is None and o.fused_score and tuple(o.shape) == (2, 19, 65, 129) for o in vs.outs)
+    assert all(o.y is None and o.head == 'score' and tuple(o.shape) == (2, 19, 65, 129) for o in vs.outs)
     assert not _has_full_resolution_buffer(vs.g, (2, 19, 65, 129))
     # every scoring launch follows the zeroing of its scalars and the shared count in the scheduled list
     order = [c.name for c in vs.g.fwd]
@@ -96,7 +96,7 @@ def test_plain_eval_plan_keeps_its_resizes(dry):
     plan = next(iter(m._plans().values()))
     names = collections.Counter(c.name for c in plan.g.fwd)
     assert names['resize_nchw'] == 2 and names['score_upsample'] == 0
-    assert P.Graph(torch.device('cpu'), False, False).fuse_score is False
+    assert P.Graph(torch.device('cpu'), False, False).head is None
 
 
 def test_unsupported_class_count_falls_back_inside_the_plan(dry):
@@ -127,6 +127,12 @@ def test_rebuilds_when_the_parameters_move(dry):
     p.data = p.data.clone()
     vs.step()
     assert vs.g is not g0 and vs.batches == 2
+    # after a capture: the rebuild drops the captured graph with the plan it replayed and starts the eager calls again
+    vs = ValidationStep(m, SHAPE, use_graph=True)
+    g0, vs.graph, vs.calls = vs.g, object(), 7
+    p.data = p.data.clone()
+    vs.step()
+    assert vs.g is not g0 and vs.graph is None and vs.calls == 1 and vs.batches == 1
 
 
 def test_score_abi_declared_and_exported():

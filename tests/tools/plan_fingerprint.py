@@ -215,13 +215,14 @@ def _module_plan(F, shape, train):
     return g, [('fwd', g.fwd), ('bwd', g.bwd)], extra, (plan, m)
 
 
-def _dynamic(F, shape):
-    """the gated inference plan and every segment it replays (trunk to the gate, early head, remainder)"""
+def _dynamic(F, shape, *mode):
+    """the gated inference plan and every segment it replays (trunk to the gate, early head, remainder); `mode`: ('labels', table bytes
+    or None) for the label-map form"""
     from addk.modeling.ADD import EDM
     m = _model(F, train=False)
     edm = EDM().eval()
     x = torch.empty(*shape)
-    plan = m._dynamic_plan(x, edm)
+    plan = m._dynamic_plan(x, edm, *mode)
     segs = [(0, plan.trunk_end[0]), plan.head_rng[0], (plan.head_rng[0][1], -1)]
     with torch.no_grad():
         for i0, i1 in segs:
@@ -242,13 +243,34 @@ def _validation(F, shape, classes=19):
     return g, [('fwd', g.fwd)], extra, (vs, m)
 
 
-def _gate(F, shape, kind, env=None):
-    """dynamic inference gated by entropy / top-probability share, and the segments it replays (trunk + head + gate, resize, remainder)"""
+def _exit_profile(F, shape):
+    """the exit profile: one profile_upsample per exit, three top-probability thresholds, prediction maps"""
+    from addk.exit_profile import ExitProfile
+    m = _model(F)
+    prof = ExitProfile(m, shape, max_thresholds=(0.5, 0.9, 0.99), keep_predictions=True, use_graph=False, nstreams=2)
+    g = prof.g
+    extra = _tensors(prof, prof.inref) + list(m.buffers())
+    return g, [('fwd', g.fwd)], extra, (prof, m)
+
+
+def _segmenter(F, shape, exit, lut=None):
+    """static label-map inference of one exit: the trunk up to that exit's cell and one label_upsample"""
+    from addk.segment import Segmenter
+    m = _model(F)
+    seg = Segmenter(m, shape, exit=exit, label_lut=lut, use_graph=False, nstreams=2)
+    g = seg.g
+    extra = _tensors(seg, seg.inref) + list(m.buffers())
+    return g, [('fwd', g.fwd)], extra, (seg, m)
+
+
+def _gate(F, shape, kind, env=None, mode=()):
+    """dynamic inference gated by entropy / top-probability share, and the segments it replays (trunk + head + gate, resize, remainder);
+    `mode` as in _dynamic"""
     old = {k: os.environ.get(k) for k in env or {}}
     os.environ.update(env or {})
     try:
         m = _model(F, train=False)
-        plan = m._gate_plan(torch.empty(*shape), kind)
+        plan = m._gate_plan(torch.empty(*shape), kind, *mode)
         segs = [(0, plan.head_rng[0][0]), plan.head_rng[0], (plan.head_rng[0][1], -1)]
         segs = [s for s in segs if s[0] != s[1]]              # the stand-alone form leaves nothing behind the cut
         with torch.no_grad():
@@ -276,6 +298,12 @@ PLANS = (
     ('gate_max', lambda: _gate(20, (1, 3, 65, 129), 'max')),
     ('gate_entropy_unfused', lambda: _gate(20, (1, 3, 65, 129), 'entropy', {'ADDK_FUSE_GATE': '0'})),
     ('gate_max_unfused', lambda: _gate(20, (1, 3, 65, 129), 'max', {'ADDK_FUSE_GATE': '0'})),
+    ('exit_profile', lambda: _exit_profile(4, (2, 3, 65, 129))),
+    ('segmenter_final_lut', lambda: _segmenter(4, (2, 3, 65, 129), -1, torch.arange(255, -1, -1, dtype=torch.uint8))),
+    ('segmenter_exit0', lambda: _segmenter(4, (2, 3, 65, 129), 0)),            # the trunk stops at the first exit
+    ('dynamic_labels', lambda: _dynamic(20, (1, 3, 65, 129), 'labels', None)),
+    ('gate_entropy_labels', lambda: _gate(20, (1, 3, 65, 129), 'entropy', mode=('labels', None))),     # gate_label_upsample, nothing behind the cut
+    ('gate_max_labels_unfused', lambda: _gate(20, (1, 3, 65, 129), 'max', {'ADDK_FUSE_GATE': '0'}, ('labels', None))),   # _labels_cold behind the cut
 )
 
 
