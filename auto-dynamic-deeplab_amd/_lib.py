@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ADDK_LIB') or os.path.join(_HERE, 'libaddk.so')      # ADDK_LIB: an A/B or diagnostic build of the same sources (scripts/*.sh)
 
 MAX_SRC, MAX_SLAB, MAX_TERMS = 12, 32, 4
+MAX_VIEWS = 8
 fp = C.POINTER(C.c_float)
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -80,6 +81,15 @@ class LabelUpsampleArgs(C.Structure):
 
 class GateLabelUpsampleArgs(C.Structure):
     _fields_ = [('gate', GateUpsampleArgs), ('lut256', vp), ('labels', vp)]
+
+
+class View(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('n0', i32), ('H', i32), ('W', i32), ('mirror', i32), ('weight', f32)]
+
+
+class LabelViewsArgs(C.Structure):
+    _fields_ = [('view', View * MAX_VIEWS), ('nview', i32), ('N', i32), ('C', i32), ('OH', i32), ('OW', i32),
+                ('lut256', vp), ('labels', vp)]
 
 
 class ProfileUpsampleArgs(C.Structure):
@@ -263,6 +273,8 @@ _SIGS = {
     'addk_label_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_label_upsample': (i32, [C.POINTER(LabelUpsampleArgs), vp]),
     'addk_gate_label_upsample': (i32, [C.POINTER(GateLabelUpsampleArgs), vp]),
+    'addk_label_views_upsample_supported': (i32, [i32, i32, i32, i32, i32]),
+    'addk_label_views_upsample': (i32, [C.POINTER(LabelViewsArgs), vp]),
     'addk_profile_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
     'addk_profile_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_profile_upsample': (i32, [C.POINTER(ProfileUpsampleArgs), vp]),

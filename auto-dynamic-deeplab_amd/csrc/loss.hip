@@ -463,6 +463,89 @@ __global__ void __launch_bounds__(256) label_up_kernel(const LabelUpK p) {
   });
 }
 
+// ---- fused multi-view label map: up-sample, softmax, weighted sum over views, arg-max (multi-scale + flip inference) -----------------
+// What a multi-scale submission keeps: the arg-max of the weighted mean of the class probabilities of up to 8 views of one image —
+// low-resolution NHWC maps of different sizes, some of them horizontally mirrored — one byte per high-resolution pixel.  A wave owns
+// 64 consecutive output columns and LVU_R rows; a thread owns one column X.  The view loop is outermost (run-time count, descriptors
+// from the argument block: wave-uniform).  Within a view the thread samples column Xv = mirror ? OW-1-X : X with the walk of scu_walk:
+// the two W-interpolated rows t0 / t1 stay in registers and are reloaded only when the wave-uniform row pair changes, z = lh0*t0 +
+// lh1*t1 carries the bits addk_resize_fwd writes at (Y, Xv).  Then max, exp sweep, acc[r][c] += (weight / Σe) * e[c]; acc[LVU_R][CC]
+// lives in registers (the row loop is fully unrolled: nothing is indexed at run time).  After the last view: the strict `>` arg-max of
+// acc and label_px.  No LDS, no atomics, no workspace; the maps (a few MB) stay in L2, HBM sees the one byte per pixel.
+constexpr int LVU_W = 64, LVU_WAVES = 4, LVU_R = 4;      // tile: 64 columns x (4 waves x 4 rows)
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) label_views_kernel(const addk_label_views_args p) {
+  const int lane = threadIdx.x & (LVU_W - 1), wv = threadIdx.x / LVU_W;
+  const int X = blockIdx.x * LVU_W + lane, n = blockIdx.z;
+  if (X >= p.OW) return;
+  const int ybeg = (blockIdx.y * LVU_WAVES + wv) * LVU_R;
+  float acc[LVU_R][CC];
+#pragma unroll
+  for (int r = 0; r < LVU_R; ++r)
+#pragma unroll
+    for (int c = 0; c < CC; ++c) acc[r][c] = 0.f;
+  for (int v = 0; v < p.nview; ++v) {
+    const float* x = p.view[v].logits;
+    const int ld = p.view[v].ld, H = p.view[v].H, W = p.view[v].W;
+    const long img = (long)(p.view[v].n0 + n) * H;
+    const float wt = p.view[v].weight;
+    const float sh = (float)H / (float)p.OH, sw = (float)W / (float)p.OW;
+    int w0, w1; float lw0, lw1;
+    src_index(p.view[v].mirror ? p.OW - 1 - X : X, sw, W, w0, w1, lw0, lw1);
+    float t0[CC], t1[CC];
+    int ph0 = -1, ph1 = -1;
+#pragma unroll
+    for (int r = 0; r < LVU_R; ++r) {
+      const int Y = ybeg + r;
+      if (Y < p.OH) {                                              // wave-uniform
+        int h0, h1; float lh0, lh1;
+        src_index(Y, sh, H, h0, h1, lh0, lh1);
+        if (h0 != ph0 || h1 != ph1) {                              // wave-uniform
+          const float* r0 = x + ((img + h0) * W) * ld;
+          const float* r1 = x + ((img + h1) * W) * ld;
+          float a[cpad(CC)], b[cpad(CC)];
+          load_px<CC>(r0 + (long)w0 * ld, a, VEC); load_px<CC>(r0 + (long)w1 * ld, b, VEC);
+#pragma unroll
+          for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
+          load_px<CC>(r1 + (long)w0 * ld, a, VEC); load_px<CC>(r1 + (long)w1 * ld, b, VEC);
+#pragma unroll
+          for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
+          ph0 = h0; ph1 = h1;
+        }
+        float e[CC];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < CC; ++c) { e[c] = lh0 * t0[c] + lh1 * t1[c]; mx = fmaxf(mx, e[c]); }
+        float se = 0.f;
+#pragma unroll
+        for (int c = 0; c < CC; ++c) { e[c] = __expf(e[c] - mx); se += e[c]; }
+        const float s = wt / se;
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[r][c] += s * e[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < LVU_R; ++r) {
+    const int Y = ybeg + r;
+    if (Y < p.OH) {
+      float mx = -INFINITY; int am = 0;
+#pragma unroll
+      for (int c = 0; c < CC; ++c)
+        if (acc[r][c] > mx) { mx = acc[r][c]; am = c; }            // strict: a tie keeps the lowest channel
+      label_px(p.lut256, p.labels, ((long)n * p.OH + Y) * p.OW + X, am);
+    }
+  }
+}
+
+dim3 lvu_grid(int N, int OH, int OW) { return dim3(cdiv(OW, LVU_W), cdiv(OH, LVU_WAVES * LVU_R), N); }
+bool lvu_ok(int nview, int N, int OH, int OW, int C) {
+  if (nview < 1 || nview > ADDK_MAX_VIEWS || C != 19 || N <= 0 || OH <= 0 || OW <= 0) return false;
+  const dim3 g = lvu_grid(N, OH, OW);
+  return N <= 65535 && g.y <= 65535 && (long)(int)g.z * (int)g.y * (int)g.x < (1L << 30);
+}
+
 // ---- fused logits up-sampling + early-exit gate (decoder.py:28 + operations.py:161-180) -----------------------------------
 // The two gates of dynamic inference that need no trained EDM: the normalised Shannon entropy of the up-sampled prediction and the
 // share of pixels whose top softmax probability passes a threshold.  The walk is scu_walk (same tile, same interpolation
@@ -789,6 +872,28 @@ extern "C" int addk_label_upsample(const addk_label_upsample_args* a, void* stre
   else
     hipLaunchKernelGGL((label_up_kernel<19, false>), scu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, k);
   return addk_check_launch("label_upsample");
+}
+
+extern "C" int addk_label_views_upsample_supported(int32_t nview, int32_t N, int32_t OH, int32_t OW, int32_t C) {
+  return lvu_ok(nview, N, OH, OW, C) ? 1 : 0;
+}
+extern "C" int addk_label_views_upsample(const addk_label_views_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->labels, "label_views_upsample: null pointer");
+  ADDK_REQUIRE(lvu_ok(a->nview, a->N, a->OH, a->OW, a->C), "label_views_upsample: unsupported shape (1..%d views, 19 classes)", ADDK_MAX_VIEWS);
+  bool vec = true;
+  for (int v = 0; v < a->nview; ++v) {
+    const addk_view& w = a->view[v];
+    ADDK_REQUIRE(w.logits, "label_views_upsample: null pointer (view %d)", v);
+    ADDK_REQUIRE(w.H > 0 && w.W > 0 && w.n0 >= 0 && w.ld >= a->C, "label_views_upsample: bad size, image offset or stride (view %d)", v);
+    ADDK_REQUIRE(w.weight > 0.f && isfinite(w.weight), "label_views_upsample: a weight must be positive and finite (view %d)", v);
+    vec = vec && px_vec_ok<19>(w.logits, w.ld);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (vec)                                                         // 16-byte pixel loads only where every view allows them
+    hipLaunchKernelGGL((label_views_kernel<19, true>), lvu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, *a);
+  else
+    hipLaunchKernelGGL((label_views_kernel<19, false>), lvu_grid(a->N, a->OH, a->OW), dim3(256), 0, st, *a);
+  return addk_check_launch("label_views_upsample");
 }
 
 extern "C" int addk_profile_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C, int32_t nthr) {

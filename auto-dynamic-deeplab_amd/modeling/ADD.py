@@ -105,8 +105,8 @@ class Cell(AddkModule):
             s1 = g.resize(s1, scale_dimension(s1.H, 2), scale_dimension(s1.W, 2))
         s1 = self.preprocess.emit(g, s1)
 
-        def fit(t):                         # ADD.py:84-85,89-90 compare H only
-            return g.resize(t, s1.H, s1.W) if t.H != s1.H else t
+        def fit(t):                         # ADD.py:84-85,89-90 compare H only, and torch.cat then refuses a map that agrees in H and not in W
+            return g.resize(t, s1.H, s1.W) if (t.H, t.W) != (s1.H, s1.W) else t      # (48x96: 3x6 beside 3x5); wherever the reference runs, the same resizes
 
         if self.dense_in:
             parts = [self.pre_preprocess[i].emit(g, fit(t)) for i, t in enumerate(prev_prev_input)]

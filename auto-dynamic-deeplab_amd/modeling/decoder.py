@@ -23,7 +23,7 @@ class Decoder(AddkModule):
             conv2d(256, n_class, 1, stride=1, bias=True))
 
     def emit(self, g, x, low_level, size):
-        if x.H != low_level.H:                      # decoder.py:24-25 compares H only
+        if (x.H, x.W) != (low_level.H, low_level.W):     # decoder.py:24-25 compares H only and cannot concatenate maps that then differ in W (5x9)
             x = g.resize(x, low_level.H, low_level.W)
         c = self._conv
         y = g.conv_bn([x, low_level], c[1], c[2], relu_in=True, post_relu=True)

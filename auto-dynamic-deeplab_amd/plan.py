@@ -369,7 +369,7 @@ BATCHED = {'bn_finalize': _Table('addk_bn_finalize_batch', 'C'), 'bn_bwd': _Tabl
            'allreduce': _Arena()}
 
 
-HEADS = (None, 'ce', 'score', 'profile', 'labels')     # Graph.head / OutRef.head
+HEADS = (None, 'ce', 'score', 'profile', 'labels', 'views')     # Graph.head / OutRef.head
 
 
 class Graph:
@@ -387,9 +387,13 @@ class Graph:
         self.reorder = False          # level-order and batch the lists although this is not a training plan (set before finalize)
         # who consumes the decoder's low-resolution logits (resize_to_nchw): None = nobody, the resize writes [N,C,OH,OW]; 'ce' = the fused
         # up-sampling + cross-entropy launch (train.TrainStep); 'score' = the scoring launch (validate.ValidationStep); 'profile' = the
-        # per-image exit-profile launch (exit_profile.ExitProfile); 'labels' = the label head (dynamic plans, segment.Segmenter)
+        # per-image exit-profile launch (exit_profile.ExitProfile); 'labels' = the label head (dynamic plans, segment.Segmenter); 'views' =
+        # the multi-view label head: every logits output of the plan is one or more views of ONE label map (segment.MultiViewSegmenter)
         self.head = None
-        self.lut = None               # 'labels': the uint8 [256] device table the class indices go through, or None
+        self.lut = None               # 'labels' / 'views': the uint8 [256] device table the class indices go through, or None
+        self.view_outs = []           # 'views': the OutRefs of the plan's logits outputs, in emission order (= kernel order of their views)
+        self.view_labels = None       # 'views': the plan-owned uint8 [N,OH,OW] map, allocated by finalize()
+        self._views_tag = ''          # 'views': segment tag of the last output, stamped on the one launch
         self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}; with head None or 'labels'
         self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted ('score', 'profile')
         self.pginit = set()
@@ -1297,8 +1301,8 @@ class Graph:
     def resize_to_nchw(self, src, OH, OW):
         """Final logits resize (decoder.py:28).  Returns an OutRef.  The plan chooses who consumes the low-resolution logits: the loss head
         of a fused training step (_ce_head), the scoring head of a validation plan (_score_head), the per-image profile of an exit-profile
-        plan (_profile_head), the gate of an early exit (gate_head), the label head of a label-map plan (_label_head), or nobody: the resize
-        into a contiguous [N,C,OH,OW] tensor, and its backward."""
+        plan (_profile_head), the gate of an early exit (gate_head), the label head of a label-map plan (_label_head), the multi-view label head that all outputs
+        of a multi-view plan share (_views_head), or nobody: the resize into a contiguous [N,C,OH,OW] tensor, and its backward."""
         assert src.bn is None and not src.relu and self.head in HEADS
         if self.want_grad:
             if (self.head == 'ce' and src.needs_grad
@@ -1312,6 +1316,8 @@ class Graph:
             return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'])
         elif self.head == 'labels':
             return self._label_head(src, OH, OW)
+        elif self.head == 'views':
+            return self._views_head(src, OH, OW)
         y, emit_resize = self._logits_resize(src, OH, OW)
         emit_resize()
         out = OutRef(y)
@@ -1479,6 +1485,47 @@ class Graph:
             emit_resize()
             self._labels_cold(y, lab, lut)
         return out
+
+    def _views_head(self, src, OH, OW):
+        """Logits output of a multi-view plan (head 'views', set by segment.MultiViewSegmenter): the plan emits the model several times —
+        once per input scale, at batch 2N where the mirrored images ride along — and ALL its logits outputs end in one label map.  Nothing is
+        emitted here and no [N,C,OH,OW] buffer exists: the OutRef keeps the low-resolution source (`src`), `shape`, and the `binding` the step
+        sets — {'N': images per view, 'size': (OH, OW) of the map, 'views': [(n0, mirror, weight), ...]}, the views this output holds (n0:
+        its first image in the batch).  The (OH, OW) passed here, the size the model would up-sample this output to, only goes into `shape`.
+        finalize() then appends ONE `label_views_upsample` launch (`addk_label_views_upsample`) that reads every view's source and writes
+        `view_labels`, the plan-owned uint8 [N,OH,OW] map.  There is no stand-alone form: C != 19 or more than 8 views is an error."""
+        if src.C != 19:
+            raise L.AddkError('the multi-view label head takes 19 classes (got %d)' % src.C)
+        out = OutRef(None)
+        out.head, out.shape, out.src = 'views', (src.N, src.C, OH, OW), src
+        if not self.view_outs:
+            self._fwd_late.append(self._emit_views)
+        self.view_outs.append(out)
+        self._views_tag = self.tag
+        return out
+
+    def _emit_views(self):
+        lib, outs = self.lib, self.view_outs
+        assert all(o.binding is not None for o in outs), 'multi-view logits output without a views binding'
+        views = [(o, v) for o in outs for v in o.binding['views']]
+        b0, Cc = outs[0].binding, outs[0].shape[1]
+        N, (OH, OW) = b0['N'], b0['size']
+        assert all(o.binding['N'] == N and tuple(o.binding['size']) == (OH, OW) and o.shape[1] == Cc for o in outs)
+        assert all(0 <= n0 and n0 + N <= o.shape[0] for o, (n0, _, _) in views)
+        if len(views) > L.MAX_VIEWS or lib.addk_label_views_upsample_supported(len(views), N, OH, OW, Cc) != 1:
+            raise L.AddkError('the multi-view label head takes 1..%d views of 19 classes (got %d views, %d classes, %d x %dx%d)'
+                              % (L.MAX_VIEWS, len(views), Cc, N, OH, OW))
+        lab = self.view_labels = torch.zeros((N, OH, OW), dtype=torch.uint8, device=self.device)
+        self.nbytes += lab.numel()
+        a, lut, rd = L.LabelViewsArgs(), self.lut, []
+        for i, (o, (n0, mirror, weight)) in enumerate(views):
+            s, v = self.src(o.src), a.view[i]
+            v.logits, v.ld, v.n0, v.H, v.W, v.mirror, v.weight = s.x, s.ld, n0, o.src.H, o.src.W, int(bool(mirror)), weight
+            rd += self.lz(o.src)
+        a.nview, a.N, a.C, a.OH, a.OW = len(views), N, Cc, OH, OW
+        a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
+        self.keep += [a, lut]
+        self._add(self.fwd, 'label_views_upsample', lib.addk_label_views_upsample, C.byref(a), rd=rd + [lut], wr=[lab]).tag = self._views_tag
 
     def _labels_cold(self, y, lab, lut):
         """Cold path of the two label heads: the map from materialised logits y [N,C,OH,OW] — `argmax_nchw`, then the cast / table look-up
@@ -1729,8 +1776,9 @@ class OutRef:
         self.bwd_cmd = None      # generic nhwc path
         self.shape = None        # (N, C, OH, OW) of the logits a fused head stands for (y is None)
         self.head = None         # Graph.head of the head that consumed the logits; None: y is the real logits.  'labels': y is the label map
+        self.src = None          # 'views': the lazy activation of the decoder's low-resolution logits this output stands for
         # what the step binds to a 'ce' / 'score' / 'profile' head before finalize() — 'ce': target, class_w, ignore_index, wsum, scale, loss;
-        # 'score': those + entropy, confusion, pred; 'profile': target, thr, nthr, entropy, share, confusion, pred
+        # 'score': those + entropy, confusion, pred; 'profile': target, thr, nthr, entropy, share, confusion, pred; 'views': N, views
         self.binding = None
         self.gate_out = None     # [N,2] device tensor of a gated exit: (entropy, share of pixels above the threshold)
         self.gate_scale = 1.0    # factor the host applies to gate_out[:, 0] (the stand-alone entropy kernel leaves a sum)

@@ -589,6 +589,32 @@ typedef struct {
 } addk_gate_label_upsample_args;
 int addk_gate_label_upsample(const addk_gate_label_upsample_args* a, void* stream);
 
+/* Multi-view label head (multi-scale + flip inference): the arg-max of the weighted mean of the class probabilities of up to
+ * ADDK_MAX_VIEWS views of the same N images, each a LOW-resolution NHWC logits map of its own size (H, W) — larger or smaller
+ * than (OH, OW) — in ONE launch; no [N,C,OH,OW] tensor exists for any view.  For output pixel (n, Y, X), views in order:
+ *   Xv   = mirror ? OW-1-X : X
+ *   z_v  = bilinear sample (align_corners=False) of image n0 + n of the view at (Y, Xv): the bits addk_resize_fwd writes there
+ *   p_v  = softmax(z_v) in fp32 (max subtracted);  acc[c] += weight * p_v[c]
+ *   labels[n,Y,X] = am, or lut256[am];  am = arg-max of acc (strict >: a tie keeps the lowest channel)
+ * The mirrored half of a batch-2N logits tensor is addressed with n0 = N.  No workspace, no atomics: deterministic.
+ * addk_label_views_upsample_supported() is 0 for nview outside 1..ADDK_MAX_VIEWS, C != 19, non-positive sizes or a grid beyond
+ * 65535 x 16 rows / 65535 images; addk_label_views_upsample then returns ADDK_ERR_INVALID without launching, as it does for a
+ * null pointer, a view with a non-positive size or a stride below C, and a weight that is not positive and finite. */
+#define ADDK_MAX_VIEWS 8
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C; this view's image n is logits[n0 + n] */
+  int32_t n0, H, W, mirror;
+  float weight;
+} addk_view;
+typedef struct {
+  addk_view view[ADDK_MAX_VIEWS];
+  int32_t nview, N, C, OH, OW;
+  const uint8_t* lut256;             /* NULL: the class index; else lut256[class] */
+  uint8_t* labels;                   /* [N,OH,OW] */
+} addk_label_views_args;
+int addk_label_views_upsample_supported(int32_t nview, int32_t N, int32_t OH, int32_t OW, int32_t C);
+int addk_label_views_upsample(const addk_label_views_args* a, void* stream);
+
 /* Exit profile of a validation pass (eval.py:195-230): what the early-exit operating curve needs of one exit, PER IMAGE, in
  * ONE launch over the LOW-resolution NHWC logits [N,H,W,C] (the walk and the arithmetic of the two heads above):
  *   ent_out[n]            = normalised Shannon entropy of image n: the bits of addk_gate_upsample's out[2n]
