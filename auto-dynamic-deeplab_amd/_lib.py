@@ -63,6 +63,16 @@ class CeUpsampleArgs(C.Structure):
                 ('g', vp), ('ldg', i32), ('accumulate', i32), ('ws', vp)]
 
 
+class OhemSelectArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
+                ('target', vp), ('class_w', vp), ('ignore_index', i32), ('thresh', f32), ('min_kept_total', i64), ('pix_loss', vp),
+                ('tau', vp), ('wsum_kept', vp), ('counts', vp), ('ws', vp)]
+
+
+class CeUpsampleOhemArgs(C.Structure):
+    _fields_ = [('ce', CeUpsampleArgs), ('pix_loss', vp), ('tau', vp)]
+
+
 class ScoreUpsampleArgs(C.Structure):
     _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
                 ('target', vp), ('class_w', vp), ('ignore_index', i32), ('wsum', vp), ('scale', f32), ('loss_out', vp),
@@ -264,6 +274,10 @@ _SIGS = {
     'addk_ce_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_ce_upsample_ws_floats': (i64, [i32, i32, i32]),
     'addk_ce_upsample_fwd_bwd': (i32, [C.POINTER(CeUpsampleArgs), vp]),
+    'addk_ohem_select_supported': (i32, [i32, i32, i32, i32, i32, i32]),
+    'addk_ohem_select_ws_bytes': (i64, [i32, i32, i32]),
+    'addk_ohem_select': (i32, [C.POINTER(OhemSelectArgs), vp]),
+    'addk_ce_upsample_ohem_fwd_bwd': (i32, [C.POINTER(CeUpsampleOhemArgs), vp]),
     'addk_score_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_score_upsample_ws_floats': (i64, [i32, i32, i32]),
     'addk_score_upsample': (i32, [C.POINTER(ScoreUpsampleArgs), vp]),

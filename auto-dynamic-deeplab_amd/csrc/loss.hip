@@ -187,8 +187,15 @@ __host__ __device__ __forceinline__ int ce_first_out(int i, float scale, int in,
 constexpr int CEU_R = 8, CEU_X = 32;       // rows per pass / lanes per row (31 output columns + the left neighbour)
 constexpr int CEU_MAXBAND = 16;            // high-resolution rows per low-resolution row the kernel takes (host check)
 
-template <int CC>
-__global__ void __launch_bounds__(256) ce_up_kernel(const CeUpK p) {
+// OHEM (online hard example mining, addk_ce_upsample_ohem_fwd_bwd): the launch also gets the per-pixel loss map and the device word tau of
+// addk_ohem_select; a pixel whose stored loss is below tau counts as not valid (weight 0), and p.wsum points at the kept weight sum.  The
+// keep decision is READ, never recomputed: invalid pixels carry -1 in the map and tau >= 0.  OHEM = false is the plain kernel, token for token.
+struct CeUpOhemK : CeUpK { const float* lmap; const float* tau; };
+template <bool OHEM> struct CeUpArg { typedef CeUpK type; };
+template <> struct CeUpArg<true> { typedef CeUpOhemK type; };
+
+template <int CC, bool OHEM = false>
+__global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM>::type p) {
   constexpr int CP = cpad(CC);
   constexpr int NOUT = ((CEU_X - 1) * CC + 255) / 256;
   __shared__ float S0[CEU_R * CEU_X * CC], S1[CEU_R * CEU_X * CC];
@@ -205,6 +212,8 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const CeUpK p) {
   const bool vec = (p.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0) && p.ld >= CP;      // px_vec_ok
   const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
   const gfloat* cw = (const gfloat*)p.cw;
+  float tau = 0.f;
+  if constexpr (OHEM) tau = *(const gfloat*)p.tau;
   float lsum = 0.f;
   float carry[NOUT];
 #pragma unroll
@@ -237,7 +246,8 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const CeUpK p) {
           int w0, w1; float lw0, lw1;
           src_index(X, sw, p.W, w0, w1, lw0, lw1);
           const long tg = tp[X];
-          const bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+          bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+          if constexpr (OHEM) valid = valid && ((const gfloat*)p.lmap)[((long)n * p.OH + Y) * p.OW + X] >= tau;
           const float w = valid ? (cw ? cw[tg] : 1.f) : 0.f;
           float z[CC];
           float mx = -INFINITY, zt = 0.f;
@@ -734,6 +744,181 @@ void gate_up_fill(GateUpK& k, const addk_gate_upsample_args* a) {
   k.npix = (double)a->OH * (double)a->OW; k.ent_div = log(19.0) * k.npix;
 }
 
+// ---- online hard example mining for the fused loss head (addk_ohem_select) -------------------------------------------------------------
+// Per exit: the per-pixel loss l = max(0, logsumexp(z) - z[target]) of every valid full-resolution pixel, the EXACT order statistic
+// l_(min(K, n)) of the batch and tau = min(-log theta, l_(k)), all on the stream.  l >= 0, so its fp32 bit pattern orders like l: a
+// three-pass most-significant-first radix select on the bits (11 + 11 + 10) finds the pattern of the k-th largest value.
+//   ohem_loss_kernel     the walk of scu_walk (same tile, same interpolation); writes l (or -1: not valid) to the [N,OH,OW] map and bins
+//                        bits 31..21 into a 2048-bin LDS histogram (a thread merges the run of equal bins of its column first), flushed
+//                        with 32-bit integer atomics: order-independent, exact.
+//   ohem_scan_kernel     ONE workgroup between the passes: walks a histogram from the top bin down to the bin that holds rank k, appends
+//                        its index to the selected prefix and leaves the rank within that bin.  A launch of its own, not a scan at the
+//                        top of every workgroup of the next pass: the refinement kernels stay pure streaming loops (no 8 KB histogram
+//                        re-read and no block scan in ~1000 workgroups), at the price of three 1-workgroup launches per exit.
+//   ohem_refine_kernel   streams the STORED map: pixels whose leading bits equal the prefix are binned on the next 11 / 10 bits.
+//   ohem_keep_kernel     streams the stored map against tau: per workgroup the count of kept pixels and the sum of their weights;
+//   ohem_keep_sum_kernel one workgroup adds the partials in a fixed order (the float sum as sum_partials_kernel does).
+// Workspace (32-bit words): [0..2047] hist of pass 0, [2048..4095] pass 1, [4096..5119] pass 2, [5120] prefix, [5121] rank, then
+// OHEM_KEEP_BLOCKS float weight partials and as many kept counts.  The first 5122 words are cleared by the launch sequence itself.
+constexpr int OHEM_B0 = 2048, OHEM_B2 = 1024;
+constexpr int OHEM_SEL = 2 * OHEM_B0 + OHEM_B2, OHEM_PART = OHEM_SEL + 2;
+constexpr int OHEM_KEEP_BLOCKS = 1024;
+constexpr unsigned OHEM_NONE = 0xffffffffu;                       // prefix of an empty selection (n == 0): no bit pattern matches it
+
+__global__ void __launch_bounds__(256) ohem_clear_kernel(unsigned* ws) {
+  for (int i = threadIdx.x; i < OHEM_PART; i += 256) ((gu32*)ws)[i] = 0u;
+}
+
+struct OhemLossK : UpSrc { const int64_t* target; int ignore; float* lmap; unsigned* hist; };
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) ohem_loss_kernel(const OhemLossK p) {
+  __shared__ unsigned hist[OHEM_B0];
+  const int t = threadIdx.x;
+  for (int i = t; i < OHEM_B0; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
+  int key = -1; unsigned run = 0;                                // pending run of equal bins of this column
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
+    const long tg = tgt[pix];
+    const bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+    float mx = -INFINITY, zt = 0.f;
+#pragma unroll
+    for (int c = 0; c < CC; ++c) {
+      mx = fmaxf(mx, z[c]);
+      if (c == tg) zt = z[c];
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < CC; ++c) se += __expf(z[c] - mx);
+    const float l = valid ? fmaxf(0.f, logf(se) + mx - zt) : -1.f;
+    ((gfloat*)p.lmap)[pix] = l;
+    const int k = valid ? (int)(__float_as_uint(l) >> 21) : -1;
+    if (k != key) {
+      if (key >= 0) atomicAdd(&hist[key], run);
+      key = k; run = 0;
+    }
+    ++run;
+  });
+  if (key >= 0) atomicAdd(&hist[key], run);
+  __syncthreads();
+  for (int i = t; i < OHEM_B0; i += 256) {
+    const unsigned v = hist[i];
+    if (v) atomicAdd(&p.hist[i], v);
+  }
+}
+
+// One workgroup.  hist: NBIN = 256 * per counters of the pass; sel = {prefix, rank}.  pass 0 takes rank = min(K, n) with n the histogram's
+// total (also written to counts[0]); the last pass turns the completed 32-bit pattern into tau = min(tau_theta, l_(k)).
+__global__ void __launch_bounds__(256) ohem_scan_kernel(const unsigned* hist, int per, int bits, int pass, unsigned* sel, unsigned long long kmin,
+                                                        float tau_theta, float* tau, long long* counts) {
+  __shared__ unsigned sc[256];
+  const int t = threadIdx.x, nbin = 256 * per;
+  const gu32* h = (const gu32*)hist;
+  // thread t owns the bins nbin-1 - t*per ... nbin - (t+1)*per, largest first
+  unsigned c = 0;
+  for (int j = 0; j < per; ++j) c += h[nbin - 1 - (t * per + j)];
+  sc[t] = c;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {                            // inclusive scan over the threads
+    const unsigned add = t >= d ? sc[t - d] : 0u;
+    __syncthreads();
+    sc[t] += add;
+    __syncthreads();
+  }
+  const unsigned total = sc[255], above = sc[t] - c;
+  unsigned prefix = 0u, k;
+  if (pass == 0) {
+    k = kmin < (unsigned long long)total ? (unsigned)kmin : total;
+    if (t == 0) ((__attribute__((address_space(1))) long long*)counts)[0] = (long long)total;
+  } else {
+    prefix = ((const gu32*)sel)[0]; k = ((const gu32*)sel)[1];
+  }
+  __syncthreads();                                               // every thread has read sel before one rewrites it
+  if (k == 0u || prefix == OHEM_NONE) {                          // nothing to select: n == 0
+    if (t == 0) {
+      ((gu32*)sel)[0] = OHEM_NONE; ((gu32*)sel)[1] = 0u;
+      if (tau) *(gfloat*)tau = tau_theta;
+    }
+    return;
+  }
+  if (above < k && k <= above + c) {                             // exactly one thread: 1 <= k <= total
+    unsigned a = above; int b = nbin - 1 - t * per;
+    for (int j = 0; j < per; ++j, --b) {
+      const unsigned v = h[b];
+      if (k <= a + v) break;
+      a += v;
+    }
+    const unsigned np = (prefix << bits) | (unsigned)b;
+    ((gu32*)sel)[0] = np; ((gu32*)sel)[1] = k - a;
+    if (tau) *(gfloat*)tau = fminf(tau_theta, __uint_as_float(np));
+  }
+}
+
+// pixels of the stored map whose bits >> PS equal the selected prefix are binned on (bits >> BS) & (NBIN - 1)
+template <int PS, int BS, int NBIN>
+__global__ void __launch_bounds__(256) ohem_refine_kernel(const float* lmap, long n, const unsigned* sel, unsigned* hist) {
+  __shared__ unsigned sh[NBIN];
+  const int t = threadIdx.x;
+  for (int i = t; i < NBIN; i += 256) sh[i] = 0u;
+  __syncthreads();
+  const unsigned prefix = ((const gu32*)sel)[0];
+  if (prefix == OHEM_NONE) return;                               // uniform over the grid
+  const gu32* m = (const gu32*)lmap;
+  for (long i = (long)blockIdx.x * 256 + t; i < n; i += (long)gridDim.x * 256) {
+    const unsigned b = m[i];
+    if ((b >> PS) == prefix) atomicAdd(&sh[(b >> BS) & (NBIN - 1)], 1u);
+  }
+  __syncthreads();
+  for (int i = t; i < NBIN; i += 256) {
+    const unsigned v = sh[i];
+    if (v) atomicAdd(&hist[i], v);
+  }
+}
+
+__global__ void __launch_bounds__(256) ohem_keep_kernel(const float* lmap, const int64_t* target, const float* cw, long n, const float* tau,
+                                                        float* wpart, unsigned* kpart) {
+  __shared__ float shs[4];
+  __shared__ unsigned shk[4];
+  const int t = threadIdx.x;
+  const float ta = *(const gfloat*)tau;
+  const gfloat* m = (const gfloat*)lmap;
+  const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)target;
+  float s = 0.f; unsigned k = 0u;
+  for (long i = (long)blockIdx.x * 256 + t; i < n; i += (long)gridDim.x * 256) {
+    if (m[i] >= ta) {                                            // not valid: -1 < 0 <= tau
+      ++k;
+      s += cw ? ((const gfloat*)cw)[tgt[i]] : 1.f;
+    }
+  }
+  s = block_sum(s, shs);
+  for (int mk = 32; mk > 0; mk >>= 1) k += __shfl_xor(k, mk);
+  if ((t & 63) == 0) shk[t >> 6] = k;
+  __syncthreads();
+  if (t == 0) { ((gfloat*)wpart)[blockIdx.x] = s; ((gu32*)kpart)[blockIdx.x] = shk[0] + shk[1] + shk[2] + shk[3]; }
+}
+
+__global__ void __launch_bounds__(256) ohem_keep_sum_kernel(const float* wpart, const unsigned* kpart, int n, float* wsum, long long* counts) {
+  __shared__ float shs[4];
+  __shared__ unsigned long long shk[4];
+  const int t = threadIdx.x;
+  float s = 0.f; unsigned long long k = 0ull;
+  for (int i = t; i < n; i += 256) { s += ((const gfloat*)wpart)[i]; k += ((const gu32*)kpart)[i]; }
+  s = block_sum(s, shs);
+  for (int mk = 32; mk > 0; mk >>= 1) k += __shfl_xor(k, mk);
+  if ((t & 63) == 0) shk[t >> 6] = k;
+  __syncthreads();
+  if (t == 0) {
+    *(gfloat*)wsum = s;
+    ((__attribute__((address_space(1))) long long*)counts)[1] = (long long)(shk[0] + shk[1] + shk[2] + shk[3]);
+  }
+}
+
+bool ohem_ok(int N, int H, int W, int OH, int OW, int C) {
+  return scu_ok(N, H, W, OH, OW, C) && (long)N * OH * OW < (1L << 31);
+}
+int ohem_stream_blocks(long n) { long b = cdiv(n, 256 * 16); if (b < 1) b = 1; if (b > OHEM_KEEP_BLOCKS) b = OHEM_KEEP_BLOCKS; return (int)b; }
+
 int ce_blocks(long total) { long b = cdiv(total, 256 * 4); if (b < 1) b = 1; if (b > 1024) b = 1024; return (int)b; }
 
 }  // namespace
@@ -790,6 +975,67 @@ extern "C" int addk_ce_upsample_fwd_bwd(const addk_ce_upsample_args* a, void* st
   if (rc) return rc;
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, a->ws, (int)(grid.x * grid.y * grid.z), a->scale, a->wsum, a->loss_out, 1);
   return addk_check_launch("ce_upsample_sum");
+}
+
+extern "C" int addk_ce_upsample_ohem_fwd_bwd(const addk_ce_upsample_ohem_args* b, void* stream) {
+  ADDK_REQUIRE(b, "ce_upsample_ohem: null pointer");
+  const addk_ce_upsample_args* a = &b->ce;
+  ADDK_REQUIRE(a->logits && a->target && a->wsum && a->loss_out && a->g && a->ws && b->pix_loss && b->tau, "ce_upsample_ohem: null pointer");
+  ADDK_REQUIRE(a->ld >= a->C && a->ldg >= a->C, "ce_upsample_ohem: short stride");
+  ADDK_REQUIRE(ceu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "ce_upsample_ohem: unsupported shape (19 classes, at most %d output rows per input row)", CEU_MAXBAND);
+  CeUpOhemK k;
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.target = a->target; k.cw = a->class_w; k.ignore = a->ignore_index; k.wsum = a->wsum; k.scale = a->scale;
+  k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate; k.ws = a->ws; k.HB = ceu_hb(a->H);
+  k.lmap = b->pix_loss; k.tau = b->tau;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(cdiv(a->W, CEU_X - 1), cdiv(a->H, k.HB), a->N);
+  hipLaunchKernelGGL((ce_up_kernel<19, true>), grid, dim3(256), 0, st, k);
+  int rc = addk_check_launch("ce_upsample_ohem");
+  if (rc) return rc;
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, a->ws, (int)(grid.x * grid.y * grid.z), a->scale, a->wsum, a->loss_out, 1);
+  return addk_check_launch("ce_upsample_ohem_sum");
+}
+
+extern "C" int addk_ohem_select_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return ohem_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_ohem_select_ws_bytes(int32_t N, int32_t OH, int32_t OW) {
+  if (N <= 0 || OH <= 0 || OW <= 0) return 0;
+  return 4 * (int64_t)(OHEM_PART + 2 * OHEM_KEEP_BLOCKS);
+}
+extern "C" int addk_ohem_select(const addk_ohem_select_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->target && a->pix_loss && a->tau && a->wsum_kept && a->counts && a->ws, "ohem_select: null pointer");
+  ADDK_REQUIRE(a->thresh > 0.f && a->thresh <= 1.f, "ohem_select: thresh must lie in (0, 1]");
+  ADDK_REQUIRE(a->min_kept_total >= 1, "ohem_select: min_kept_total must be at least 1");
+  ADDK_REQUIRE(a->ld >= a->C, "ohem_select: short stride");
+  ADDK_REQUIRE(ohem_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "ohem_select: unsupported shape (19 classes, fewer than 2^31 pixels)");
+  unsigned* w = (unsigned*)a->ws;
+  unsigned* sel = w + OHEM_SEL;
+  float* wpart = (float*)(w + OHEM_PART);
+  unsigned* kpart = w + OHEM_PART + OHEM_KEEP_BLOCKS;
+  const float tau_theta = a->thresh >= 1.f ? 0.f : (float)(-log((double)a->thresh));
+  const long npix = (long)a->N * a->OH * a->OW;
+  const int nb = ohem_stream_blocks(npix);
+  long long* counts = (long long*)a->counts;
+  OhemLossK k;
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.target = a->target; k.ignore = a->ignore_index; k.lmap = a->pix_loss; k.hist = w;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 one(1), blk(256);
+  hipLaunchKernelGGL(ohem_clear_kernel, one, blk, 0, st, w);
+  if (px_vec_ok<19>(a->logits, a->ld))
+    hipLaunchKernelGGL((ohem_loss_kernel<19, true>), scu_grid(a->N, a->OH, a->OW), blk, 0, st, k);
+  else
+    hipLaunchKernelGGL((ohem_loss_kernel<19, false>), scu_grid(a->N, a->OH, a->OW), blk, 0, st, k);
+  hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w, OHEM_B0 / 256, 11, 0, sel, (unsigned long long)a->min_kept_total, tau_theta, (float*)nullptr, counts);
+  hipLaunchKernelGGL((ohem_refine_kernel<21, 10, OHEM_B0>), dim3(nb), blk, 0, st, a->pix_loss, npix, sel, w + OHEM_B0);
+  hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w + OHEM_B0, OHEM_B0 / 256, 11, 1, sel, 0ull, tau_theta, (float*)nullptr, counts);
+  hipLaunchKernelGGL((ohem_refine_kernel<10, 0, OHEM_B2>), dim3(nb), blk, 0, st, a->pix_loss, npix, sel, w + 2 * OHEM_B0);
+  hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w + 2 * OHEM_B0, OHEM_B2 / 256, 10, 2, sel, 0ull, tau_theta, a->tau, counts);
+  hipLaunchKernelGGL(ohem_keep_kernel, dim3(nb), blk, 0, st, a->pix_loss, a->target, a->class_w, npix, a->tau, wpart, kpart);
+  hipLaunchKernelGGL(ohem_keep_sum_kernel, one, blk, 0, st, wpart, kpart, nb, a->wsum_kept, counts);
+  return addk_check_launch("ohem_select");
 }
 
 extern "C" int addk_score_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {

@@ -1380,8 +1380,12 @@ class Graph:
     def _ce_head(self, src, OH, OW):
         """Logits output of a fused training step (head 'ce', set by train.TrainStep): nobody reads the full-resolution logits, so
         the resize is not emitted at all and the OutRef carries `shape` and the `binding` TrainStep sets; finalize() then places ONE
-        fused up-sampling + cross-entropy launch (`addk_ce_upsample_fwd_bwd`) at the head of the backward list."""
+        fused up-sampling + cross-entropy launch (`addk_ce_upsample_fwd_bwd`) at the head of the backward list.  A binding with
+        `ohem = (thresh, min_kept_total)` mines hard examples (include/addk.h, addk_ohem_select): `ohem_select` leaves this exit's own
+        per-pixel loss map, tau and kept weight sum, and `ce_upsample_ohem` is the loss head that reads them; the binding gets the
+        tensors back as `ohem_state` (TrainStep.ohem_stats)."""
         def emit_ce(ce):
+            ohem = ce.get('ohem')
             a = self._up_args(L.CeUpsampleArgs, src, OH, OW)
             self._bind_loss(a, ce)
             gs, a.accumulate, _ = self._grad_into(src)
@@ -1389,8 +1393,31 @@ class Graph:
             ws = torch.zeros(int(self.lib.addk_ce_upsample_ws_floats(src.N, src.H, src.W)), dtype=torch.float32, device=self.device)
             a.ws = ws.data_ptr()
             self.keep += [a, ws]
-            self._add(self.bwd, 'ce_upsample', self.lib.addk_ce_upsample_fwd_bwd, C.byref(a),
-                      rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
+            if not ohem:
+                self._add(self.bwd, 'ce_upsample', self.lib.addk_ce_upsample_fwd_bwd, C.byref(a),
+                          rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
+                return
+            if self.lib.addk_ohem_select_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
+                raise L.AddkError('hard example mining takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
+                                  % (src.C, src.N, src.H, src.W, OH, OW))
+            f32 = dict(dtype=torch.float32, device=self.device)
+            lmap, tau, wkept = torch.zeros((src.N, OH, OW), **f32), torch.zeros(1, **f32), torch.zeros(1, **f32)
+            counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+            sws = torch.zeros(int(self.lib.addk_ohem_select_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=self.device)
+            self.nbytes += lmap.numel() * 4
+            s = self._up_args(L.OhemSelectArgs, src, OH, OW)
+            s.target, s.class_w, s.ignore_index = a.target, a.class_w, a.ignore_index
+            s.thresh, s.min_kept_total = ohem
+            s.pix_loss, s.tau, s.wsum_kept, s.counts, s.ws = lmap.data_ptr(), tau.data_ptr(), wkept.data_ptr(), counts.data_ptr(), sws.data_ptr()
+            b = L.CeUpsampleOhemArgs()
+            b.ce = a                                   # a copy: the head's arguments with the kept weight sum as the normaliser
+            b.ce.wsum, b.pix_loss, b.tau = wkept.data_ptr(), lmap.data_ptr(), tau.data_ptr()
+            ce['ohem_state'] = dict(pix_loss=lmap, tau=tau, wsum_kept=wkept, counts=counts)
+            self.keep += [s, b, lmap, tau, wkept, counts, sws]
+            self._add(self.bwd, 'ohem_select', self.lib.addk_ohem_select, C.byref(s),
+                      rd=self.lz(src) + [ce['target']], wr=[lmap, tau, wkept, counts, sws])
+            self._add(self.bwd, 'ce_upsample_ohem', self.lib.addk_ce_upsample_ohem_fwd_bwd, C.byref(b),
+                      rd=self.lz(src) + [ce['target'], lmap, tau, wkept], wr=[gs, ce['loss'], ws])
         return self._late_head('ce', src, OH, OW, self.bwd, self._bwd_emitters, emit_ce)
 
     def _score_head(self, src, OH, OW):

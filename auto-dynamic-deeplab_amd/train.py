@@ -33,10 +33,30 @@ def _flat_views(params, device):
     return flat_p, flat_g, gviews
 
 
+def _check_ohem(ohem, N):
+    """(thresh, min_kept per image) -> (thresh, min_kept * N), or None; ValueError for what the library would refuse."""
+    if ohem is None:
+        return None
+    if os.environ.get('ADDK_FUSE_CE', '1') != '1':
+        raise ValueError('ohem needs the fused loss head (ADDK_FUSE_CE=1): there is no form over full-resolution logits')
+    try:
+        thresh, min_kept = ohem
+        thresh, min_kept = float(thresh), int(min_kept)
+    except (TypeError, ValueError):
+        raise ValueError('ohem must be (thresh, min_kept), got %r' % (ohem,))
+    if not (0.0 < thresh <= 1.0) or min_kept < 1 or min_kept != ohem[1]:
+        raise ValueError('ohem: thresh must lie in (0, 1] and min_kept must be a positive integer, got %r' % (ohem,))
+    return thresh, min_kept * N
+
+
 class TrainStep:
     def __init__(self, model, batch_shape, lr=0.05, momentum=0.9, weight_decay=4e-5, nesterov=True, class_weight=None,
-                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None):
+                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None, ohem=None):
+        """ohem = (thresh, min_kept): online hard example mining in every exit's loss head (include/addk.h, addk_ohem_select) — per exit
+        and per process, a pixel counts when its target-class probability is below `thresh`, and never fewer than `min_kept` pixels per
+        image (min_kept * N of the batch) count.  Only the fused loss head has this form: ValueError otherwise."""
         lib = self.lib = L.load()
+        self.ohem = _check_ohem(ohem, batch_shape[0])
         dev = next(model.parameters()).device
         _plan.require_device(next(model.parameters()))
         self.model, self.dev = model, dev
@@ -66,6 +86,8 @@ class TrainStep:
         outs = model.emit(g, a)
         self.outs = outs
         nex = len(outs)
+        if self.ohem is not None and any(o.head != 'ce' for o in outs):
+            raise ValueError('ohem: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
         ncls = outs[0].shape[1] if outs[0].head == 'ce' else outs[0].y.shape[1]
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.wsum = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -74,12 +96,15 @@ class TrainStep:
         self._keep = [ws, cw]
         cwp = cw.data_ptr() if cw is not None else None
         g._add(g.fwd, 'loss_zero', lib.addk_fill, self.loss.data_ptr(), 1, 0.0, wr=[self.loss])
-        g._add(g.fwd, 'ce_count', lib.addk_ce_count, self.target.data_ptr(), N * H * W, cwp, ignore_index, ncls,
-               self.wsum.data_ptr(), ws.data_ptr(), rd=[self.target], wr=[self.wsum, ws])
+        if self.ohem is None:             # a mining head normalises by its own kept weight sum
+            g._add(g.fwd, 'ce_count', lib.addk_ce_count, self.target.data_ptr(), N * H * W, cwp, ignore_index, ncls,
+                   self.wsum.data_ptr(), ws.data_ptr(), rd=[self.target], wr=[self.wsum, ws])
         self.dlogits = []
         for o in outs:
             if o.head == 'ce':
                 o.binding = dict(target=self.target, class_w=cwp, ignore_index=ignore_index, wsum=self.wsum, scale=1.0 / nex, loss=self.loss)
+                if self.ohem is not None:
+                    o.binding['ohem'] = self.ohem
                 self.dlogits.append(None)
                 continue
             d = torch.empty_like(o.y)
@@ -232,6 +257,20 @@ class TrainStep:
             torch.cuda.synchronize()
         self.graph = None
         self.use_graph = False
+
+    def ohem_stats(self):
+        """Per exit (tau, kept, valid) of the last step: the loss threshold, the pixels that counted and the valid pixels of the batch.
+        Synchronises the device; not part of the step."""
+        if self.ohem is None:
+            raise ValueError('this step was built without ohem')
+        if self.dev.type == 'cuda':
+            torch.cuda.synchronize()
+        res = []
+        for o in self.outs:
+            st = o.binding['ohem_state']
+            valid, kept = (int(v) for v in st['counts'].tolist())
+            res.append((float(st['tau'].item()), kept, valid))
+        return res
 
     def grads(self):
         return {p: self.g.pgrad.get(p) for p in self.params}

@@ -507,6 +507,56 @@ int addk_ce_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int3
 int64_t addk_ce_upsample_ws_floats(int32_t N, int32_t H, int32_t W);
 int addk_ce_upsample_fwd_bwd(const addk_ce_upsample_args* a, void* stream);
 
+/* Online hard example mining (OHEM, "bootstrapped" cross-entropy) for the fused loss head, per exit and per process (under DDP
+ * every rank mines its own batch; gradient averaging is unchanged).  Parameters: thresh = theta in (0, 1], a target-class
+ * probability, and min_kept_total = K = min_kept * N.  For every full-resolution pixel
+ *   z     = bilinear sample (align_corners=False) of the low-resolution NHWC logits, lh0*(lw0*a + lw1*b) + lh1*(lw0*c + lw1*d)
+ *   valid = target != ignore_index and 0 <= target < C
+ *   l     = max(0, logsumexp(z) - z[target])   fp32, unweighted; the clamp removes the -1e-7 rounding can leave, makes
+ *           thresh = 1 mean "keep everything" and keeps the bit pattern of l monotone in l.
+ * With n = number of valid pixels of the batch and l_(j) the j-th largest l among them,
+ *   tau   = min(-log theta, l_(min(K, n)))          (-log theta = (float)(-log((double)thresh)), taken on the host)
+ *   kept  = valid and l >= tau                      ties at tau are all kept: kept >= min(K, n); no traversal order enters.
+ * In exact arithmetic this is mmseg's OHEMPixelSampler / HRNet's OhemCrossEntropy written in the loss domain, with `>=` in
+ * place of their strict comparison one index further on.  n == 0: tau = -log theta, nothing is kept, wsum_kept = 0.
+ *
+ * addk_ohem_select writes, all on the stream (no host read; a captured hipGraph replays it; it clears its own histograms):
+ *   pix_loss[N,OH,OW] = l, or -1 where the pixel is not valid
+ *   tau[0], wsum_kept[0] = sum over kept pixels of class_w[target] (or 1), counts[0] = n, counts[1] = #kept
+ * Selection is EXACT: tau carries the bits a full sort of pix_loss gives — a three-pass radix select on the bit pattern of l
+ * (bits 31..21 binned while the map is written, then 20..10 and 9..0 over the stored map), integer histograms only.
+ * wsum_kept is a fixed-order two-stage sum: bit-reproducible.  addk_ohem_select_supported() is 0 for C != 19, non-positive
+ * sizes, a grid beyond the limits of addk_score_upsample_supported or N*OH*OW >= 2^31 (32-bit histogram counters).
+ *
+ * addk_ce_upsample_ohem_fwd_bwd is addk_ce_upsample_fwd_bwd with the per-pixel weight w = kept ? class_w[t] (or 1) : 0, where
+ * kept is READ from the stored map: pix_loss[n,Y,X] >= *tau — the kept set comes from one computation of l.  ce.wsum must
+ * point at wsum_kept (the normaliser sum_kept w).  Supported exactly where addk_ce_upsample_supported() is 1.
+ * Both entry points return ADDK_ERR_INVALID and launch nothing for a null pointer, thresh outside (0, 1],
+ * min_kept_total < 1 or ld < C (the head takes no thresh: its pix_loss and tau must be non-null). */
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
+  int32_t N, H, W, C, OH, OW;
+  const int64_t* target;             /* [N,OH,OW] */
+  const float* class_w;              /* [C] or NULL */
+  int32_t ignore_index;
+  float thresh;                      /* theta in (0, 1] */
+  int64_t min_kept_total;            /* K >= 1 */
+  float* pix_loss;                   /* [N,OH,OW] */
+  float* tau;                        /* 1 float */
+  float* wsum_kept;                  /* 1 float */
+  int64_t* counts;                   /* [2]: valid, kept */
+  void* ws;                          /* addk_ohem_select_ws_bytes() bytes */
+} addk_ohem_select_args;
+int addk_ohem_select_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+int64_t addk_ohem_select_ws_bytes(int32_t N, int32_t OH, int32_t OW);
+int addk_ohem_select(const addk_ohem_select_args* a, void* stream);
+typedef struct {
+  addk_ce_upsample_args ce;          /* ce.wsum: the wsum_kept of addk_ohem_select */
+  const float* pix_loss;             /* [N,OH,OW] from addk_ohem_select */
+  const float* tau;                  /* 1 float from addk_ohem_select */
+} addk_ce_upsample_ohem_args;
+int addk_ce_upsample_ohem_fwd_bwd(const addk_ce_upsample_ohem_args* a, void* stream);
+
 /* Scoring head of a validation pass (train.py:250-322, eval.py:165-193): what the evaluator, the criterion and the entropy
  * meter need of one exit, in ONE pass over the high-resolution pixel grid, straight from the LOW-resolution NHWC logits
  * [N,H,W,C] (bilinear, align_corners=False, the arithmetic of addk_resize_fwd bit for bit) — the [N,C,OH,OW] tensor is never
