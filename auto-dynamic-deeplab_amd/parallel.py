@@ -220,9 +220,9 @@ class GradSync:
         del self.works[:]
 
     def insert(self, g, bwd):
-        from .plan import Cmd, _overlap
+        from .sched import Cmd, _overlap, _region
         esz = self.flat_g.element_size()
-        base = self.flat_g.untyped_storage().data_ptr()
+        base = _region(self.flat_g)[0]
         spans = []                                    # (lo, hi) float offsets of every parameter's gradient, address order
         for p, v in self.views.items():
             lo = v.storage_offset()

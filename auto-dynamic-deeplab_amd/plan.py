@@ -11,6 +11,7 @@ the producing BatchNorm; consumers apply it while staging their tiles, so BatchN
 never cost a pass over HBM.
 """
 import collections
+import itertools
 import math
 import os
 import ctypes as C
@@ -18,6 +19,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .sched import WHOLE, Cmd, _overlap, _region, deps, level_order, levels, schedule      # noqa: F401  (the launch-list core)
 
 
 TRACE_BN = None        # diagnostics (tests/tools): a list that receives (BatchNorm module, raw TRef) of every Graph.bn call
@@ -47,11 +49,12 @@ def _ptr(x):
 
 
 class Buf:
-    """Flat fp32 device buffer."""
-    __slots__ = ('t', 'ptr', 'n', 'gbuf', 'ginit')
+    """Flat fp32 device buffer; `ordinal` is its place among the buffers of its plan (Graph.buf) and names it as a region."""
+    __slots__ = ('t', 'ptr', 'n', 'gbuf', 'ginit', 'region')
 
-    def __init__(self, n, device, zero=False):
+    def __init__(self, n, device, zero=False, ordinal=0):
         self.n = int(n)
+        self.region = (('buf', ordinal),) + WHOLE
         self.t = (torch.zeros if zero else torch.empty)(max(self.n, 4), dtype=torch.float32, device=device)
         self.ptr = self.t.data_ptr()
         self.gbuf = None       # gradient twin
@@ -79,6 +82,10 @@ class TRef:
         c0 = self.off % self.ld if self.ld else 0
         return c0, c0 + self.C
 
+    @property
+    def region(self):
+        return self.buf.region[:1] + self.cols
+
     def chan(self, c0, C):
         assert 0 <= c0 and c0 + C <= self.C
         return TRef(self.buf, self.off + c0, self.N, self.H, self.W, C, self.ld)
@@ -99,6 +106,10 @@ class Vec:
     def ptr(self):
         return self.buf.ptr + 4 * self.off
 
+    @property
+    def region(self):
+        return self.buf.region
+
     def view(self):
         return self.buf.t[self.off:self.off + self.n]
 
@@ -107,11 +118,13 @@ class LateVec:
     """A small device vector whose storage is assigned only after the launch list has been ordered (Graph._bind_late):
     the statistics vectors exchanged by the SyncBN all-reduces of ONE dependency level are laid out back to back in one
     arena, so a level costs a single plain `all_reduce` on a contiguous tensor.  `n` counts 4-byte slots; `f64` marks
-    fp64 pairs (forward statistics).  Until bound, dependency tracking uses the object itself as its region."""
-    __slots__ = ('n', 'f64', 'buf', 'off', 'binders')
+    fp64 pairs (forward statistics).  Dependency tracking names it by a serial number, before and after it is bound."""
+    __slots__ = ('n', 'f64', 'buf', 'off', 'binders', 'region')
+    _serial = itertools.count()
 
     def __init__(self, n, f64=False):
         self.n, self.f64, self.buf, self.off, self.binders = int(n), f64, None, 0, []
+        self.region = (('late', next(LateVec._serial)),) + WHOLE
 
     @property
     def ptr(self):
@@ -165,132 +178,6 @@ class Resample:
         self.src, self.emit, self.done = src, emit, False
 
 
-class Cmd:
-    """One kernel launch of a plan: fn(*args, stream).  `rd`/`wr` are the memory regions it reads / writes
-    (keys from `_region`), used to schedule independent launches on parallel HIP streams."""
-    __slots__ = ('name', 'fn', 'args', 'rd', 'wr', 'stream', 'waits', 'event', 'pin', 'tag', 'tags', 'payload', 'bkey', 'arena', 'members')
-
-    def __init__(self, name, fn, args, rd=(), wr=(), pin=False):
-        self.name, self.fn, self.args = name, fn, list(args)
-        self.rd, self.wr = [k for k in (_region(x) for x in rd) if k], [k for k in (_region(x) for x in wr) if k]
-        self.stream, self.waits, self.event, self.pin, self.tag = 0, (), None, pin, ''
-        self.tags = None
-        self.payload = None            # argument struct of a launch that has a table-driven batched form (level_batch)
-        self.bkey = 0                  # kernel-variant key: only launches with equal keys share a batch
-        self.arena, self.members = None, 1
-
-    def __iter__(self):                # unpacks like the (name, fn, args) triple it replaces
-        return iter((self.name, self.fn, self.args))
-
-    def __getitem__(self, i):
-        return (self.name, self.fn, self.args)[i]
-
-
-def _region(x):
-    """(buffer id, lo, hi): channel interval inside the pixel row for NHWC views, whole buffer otherwise."""
-    if x is None:
-        return None
-    if isinstance(x, TRef):
-        return (id(x.buf),) + x.cols
-    if isinstance(x, Vec):
-        return (id(x.buf), 0, 1 << 30)
-    if isinstance(x, LateVec):
-        return (id(x), 0, 1 << 30)
-    if isinstance(x, Buf):
-        return (id(x), 0, 1 << 30)
-    if isinstance(x, torch.Tensor):
-        # byte interval inside the storage: views of one flat parameter / gradient buffer (train.TrainStep) are distinct regions
-        lo = x.storage_offset() * x.element_size()
-        return (x.untyped_storage().data_ptr(), lo, lo + max(1, x.numel()) * x.element_size())
-    if isinstance(x, tuple):
-        return x
-    raise TypeError(type(x))
-
-
-def _overlap(a, b):
-    return a[0] == b[0] and a[1] < b[2] and b[1] < a[2]
-
-
-def deps(cmds):
-    """The hazard tracker: for every command, in list order, the set of earlier indices it has to follow (every RAW, WAW and WAR
-    relation on overlapping regions of the sequential list, directly or through the commands yielded)."""
-    writers, readers = {}, {}            # buffer id -> [(region, idx)]
-    for i, c in enumerate(cmds):
-        d = set()
-        for k in c.rd:
-            d.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-        for k in c.wr:
-            d.update(j for r, j in writers.get(k[0], ()) if _overlap(r, k))
-            d.update(j for r, j in readers.get(k[0], ()) if _overlap(r, k))
-        yield d
-        for k in c.wr:      # this write stands for the earlier accesses it FULLY covers, and only for those: a partly covered one stays listed
-            covered = lambda r: r[1] >= k[1] and r[2] <= k[2]      # noqa: E731
-            writers[k[0]] = [(r, j) for r, j in writers.get(k[0], ()) if not covered(r)] + [(k, i)]
-            readers[k[0]] = [(r, j) for r, j in readers.get(k[0], ()) if not covered(r)]
-        for k in c.rd:
-            readers.setdefault(k[0], []).append((k, i))
-
-
-def levels(cmds):
-    """Dependency level (longest path from the inputs) of every command of a launch list."""
-    level = []
-    for d in deps(cmds):
-        level.append(1 + max(level[j] for j in d) if d else 0)
-    return level
-
-
-def level_order(cmds, merge=None):
-    """Re-order a launch list in place by dependency level.  Commands of one level never depend on each other, so any order inside
-    a level is valid; program order of the original list is kept.  `merge(commands of one level) -> commands` may rewrite a level."""
-    buckets = collections.defaultdict(list)
-    for c, lv in zip(cmds, levels(cmds)):
-        buckets[lv].append(c)
-    cmds[:] = [c for lv in sorted(buckets) for c in (merge(buckets[lv]) if merge else buckets[lv])]
-
-
-def schedule(cmds, nstreams):
-    """Assign every command a stream and the cross-stream waits it needs.  A command follows the stream of its most
-    recent dependency when that dependency is still the tail of its stream (a chain stays on one stream, no event);
-    otherwise it opens on the least recently used stream and waits on events.  Program order inside a stream plus the
-    recorded waits preserve every RAW/WAW/WAR relation of the sequential list."""
-    tail = [-1] * nstreams               # index of the last command on each stream
-    # vector clocks: clock[i][t] = latest command of stream t known to have completed before command i starts.  A wait
-    # that a previous wait already implies TRANSITIVELY (A -> B -> C and A -> C) is dropped (fewer event edges in the graph).
-    clock = []
-    for i, (c, dep) in enumerate(zip(cmds, deps(cmds))):
-        if c.pin or nstreams == 1:
-            st = 0
-        elif dep:
-            last = max(dep)
-            ls = cmds[last].stream
-            st = ls if tail[ls] == last else min(range(nstreams), key=lambda t: tail[t])
-        else:
-            st = min(range(nstreams), key=lambda t: tail[t])
-        # hipStreamEndCapture (ROCm 7.2) crashes when two SIDE streams wait on each other (measured with
-        # scripts/capture_probe.py: 'mutual12' dumps core, 'ordered' does not).  Side stream s therefore only ever waits
-        # on side streams t > s (and on the main stream 0, which may wait on anybody); a command that would need the
-        # other direction runs on the main stream instead.
-        if st != 0:
-            vc0 = clock[tail[st]] if tail[st] >= 0 else [-1] * nstreams
-            if any(0 < cmds[j].stream < st and vc0[cmds[j].stream] < j for j in dep):
-                st = 0
-        vc = list(clock[tail[st]]) if tail[st] >= 0 else [-1] * nstreams
-        waits = []
-        for j in sorted(dep, reverse=True):
-            t = cmds[j].stream
-            if t != st and vc[t] < j:
-                waits.append(j)
-                vc = [max(a, b) for a, b in zip(vc, clock[j])]
-        vc[st] = i
-        clock.append(vc)
-        c.stream, c.waits = st, tuple(waits)
-        tail[st] = i
-    need = set(j for c in cmds for j in c.waits)
-    for j in need:
-        cmds[j].event = True
-    return cmds
-
-
 def _covered(intervals, c0, c1):
     """how much of [c0, c1) a list of disjoint intervals covers"""
     return sum(max(0, min(c1, b) - max(c0, a)) for a, b in intervals)
@@ -330,8 +217,10 @@ class _Table(collections.namedtuple('_Table', 'fn size')):
     per_level = False
 
     def build(self, g, name, cs):
-        tab = g._table(bytes((type(cs[0].payload) * len(cs))(*[c.payload for c in cs])))
-        return Cmd(name + '_batch', getattr(g.lib, self.fn), (tab.data_ptr(), len(cs), max(int(getattr(c.payload, self.size)) for c in cs)))
+        arr = (type(cs[0].payload) * len(cs))(*[c.payload for c in cs])
+        m = Cmd(name + '_batch', getattr(g.lib, self.fn), (g._table(bytes(arr)).data_ptr(), len(cs), max(int(getattr(c.payload, self.size)) for c in cs)))
+        m.table = arr
+        return m
 
 
 class _Prepared(collections.namedtuple('_Prepared', 'prepare run')):
@@ -341,7 +230,9 @@ class _Prepared(collections.namedtuple('_Prepared', 'prepare run')):
     def build(self, g, name, cs):
         arr = (type(cs[0].payload) * len(cs))(*[c.payload for c in cs])
         blob, meta = g._prepare(getattr(g.lib, self.prepare), arr, len(cs), self.prepare)
-        return Cmd(name + '_batch', getattr(g.lib, self.run), (g._table(blob).data_ptr(), meta))
+        m = Cmd(name + '_batch', getattr(g.lib, self.run), (g._table(blob).data_ptr(), meta))
+        m.table = arr
+        return m
 
 
 class _Arena(collections.namedtuple('_Arena', '')):
@@ -417,7 +308,7 @@ class Graph:
 
     # ---------------- memory ----------------
     def buf(self, n, zero=False):
-        b = Buf(n, self.device, zero)
+        b = Buf(n, self.device, zero, len(self._bufs))
         self._bufs.append(b)
         self.nbytes += 4 * b.n
         return b
@@ -459,7 +350,7 @@ class Graph:
             views = self.pgrad_views
             self.pgrad[p] = views[p] if views is not None and p in views else torch.empty_like(p)
             self._pcols[p] = []
-        acc = _first_touch(self._pcols[p], *(cols or (0, 1 << 30)), 'weight-gradient columns')      # no `cols`: the whole tensor
+        acc = _first_touch(self._pcols[p], *(cols or WHOLE), 'weight-gradient columns')      # no `cols`: the whole tensor
         self.pginit.add(p)
         return self.pgrad[p].data_ptr(), acc
 
@@ -475,8 +366,8 @@ class Graph:
         self.nstreams = max(1, int(nstreams))
         if self._evalbn:
             n = len(self._evalbn)
-            tab = self._table(bytes((L.BnEvalEntry * n)(*self._evalbn)))
-            self._evalbn_cmd.args[0], self._evalbn_cmd.args[1] = tab.data_ptr(), n
+            self._evalbn_cmd.table = (L.BnEvalEntry * n)(*self._evalbn)
+            self._evalbn_cmd.args[0], self._evalbn_cmd.args[1] = self._table(bytes(self._evalbn_cmd.table)).data_ptr(), n
         self._emit_batched_dw_reductions()
         self._emit_batched_wgrads()
         if self._packs:
@@ -608,11 +499,13 @@ class Graph:
             if not create:
                 return
             self._pack_cmd = self._add(self.fwd, 'conv_pack_batch', self.lib.addk_conv_pack_batch, None, 0)
+            self._pack_cmd.table = []
         nb = int(self.lib.addk_conv_pack_desc_bytes())
         buf = (C.c_uint8 * nb)()
         L.check(desc_fn(C.byref(args), buf), 'conv_pack_desc')
         self._packs.append(bytes(buf))
         args.wpack_ready = 1
+        self._pack_cmd.table.append(args)
         self._pack_cmd.rd.append(_region(weight))
         self._pack_cmd.wr.append(_region(wpk))
 
@@ -627,9 +520,9 @@ class Graph:
             waves[-1][1].add(it.dw)
         for items in [part for items, _ in waves for part in _chunks(items, 8)]:
             n = len(items)
-            tab = self._table(bytes((L.DwWreduceItem * n)(*[it for it, _, _ in items])))
-            self._add(self.bwd, 'dw_wreduce_batch', self.lib.addk_dw_wreduce_batch, tab.data_ptr(), n,
-                      rd=[ws for _, ws, _ in items], wr=[g for _, _, g in items])
+            arr = (L.DwWreduceItem * n)(*[it for it, _, _ in items])
+            self._add(self.bwd, 'dw_wreduce_batch', self.lib.addk_dw_wreduce_batch, self._table(bytes(arr)).data_ptr(), n,
+                      rd=[ws for _, ws, _ in items], wr=[g for _, _, g in items]).table = arr
 
     def _emit_batched_wgrads(self):
         """All weight gradients of the backward pass are deferred to its end and launched in a few batches: one launch
@@ -672,7 +565,7 @@ class Graph:
                     print('wgrad batch kind/cty/ctz=%s n=%d blocks=%d  %.1f GF  %.1f MB min traffic  %s' % (
                         key, n, meta[5], fl / 1e9, by / 1e6, dict(shapes)), flush=True)
                 self._add(self.bwd, 'conv_wgrad_batch', lib.addk_conv_wgrad_batch_run, blob.data_ptr(), meta,
-                          rd=[r for _, rd, _ in items for r in rd], wr=[g for _, _, g in items])
+                          rd=[r for _, rd, _ in items for r in rd], wr=[g for _, _, g in items]).table = arr
 
     # ---------------- command helpers ----------------
     def _add(self, lst, name, fn, *args, rd=(), wr=(), pin=False):
@@ -782,7 +675,8 @@ class Graph:
 
     def _defer_wgrad(self, dy, s, relu_in, weight, geom, ldw, cin_total, choff):
         """Record the gradient of columns [choff, choff + s.C) of `weight` (source `s`, output gradient `dy`) for the batched launches
-        at the end of the backward pass (_emit_batched_wgrads)."""
+        at the end of the backward pass (_emit_batched_wgrads).  What it writes is named by the weight's region (the parameters of a
+        train step are views of ONE flat buffer: the byte interval tells them apart) and the column interval inside the weight."""
         wa = L.ConvWgradArgs()
         wa.dy, wa.lddy, wa.Cout = dy.ptr, dy.ld, dy.C
         _set_geom(wa, geom)
@@ -791,7 +685,7 @@ class Graph:
         gp, acc = self.param_grad(weight, cols)
         wa.dw, wa.ldw, wa.cin_total, wa.w_choff, wa.accumulate = gp, ldw, cin_total, choff, acc
         wa.ws_floats = self.lib.addk_conv_wgrad_ws(dy.P, dy.C, s.C, geom[5] * geom[6])
-        self._wgrads.append((wa, [dy] + self.lz(s), self.pgrad[weight], (id(weight),) + cols))
+        self._wgrads.append((wa, [dy] + self.lz(s), self.pgrad[weight], (_region(weight),) + cols))
 
     def _defer_dw_wreduce(self, weight, rows, n):
         """Workspace of a depthwise weight gradient: its [rows][n] partials are reduced at the end of the backward pass, all convs in one

@@ -90,7 +90,7 @@ def main():
             free[s] = fin[i]
         return fin.max()
     print('list schedule without interference: 1 stream %.2f ms, 2 streams %.2f, 3 streams %.2f, 8 streams %.2f' % (makespan(1), makespan(2), makespan(3), makespan(8)))
-    # the planner's own stream assignment (plan.schedule: follow the most recent dependency's stream while it is that stream's tail, else the least
+    # the planner's own stream assignment (sched.schedule: follow the most recent dependency's stream while it is that stream's tail, else the least
     # recently used stream), forward and backward lists separately as TrainStep replays them, against an earliest-start assignment of the same order
     # and against a critical-path-first order (longest remaining chain first), all in the no-interference model
     import copy

@@ -1,7 +1,10 @@
 """Shared helpers for tests and for tests/golden/make_golden.py (no reference code here)."""
+import collections
+import contextlib
 from types import SimpleNamespace
 
 import numpy as np
+import pytest
 import torch
 
 import addk  # noqa: F401  (registers the package that lives in ./auto-dynamic-deeplab_amd/)
@@ -42,3 +45,28 @@ def rms_err(a, b):
     a = a.detach().double().cpu()
     b = b.detach().double().cpu()
     return float(((a - b) ** 2).mean().sqrt() / ((b ** 2).mean().sqrt() + 1e-300))
+
+
+@contextlib.contextmanager
+def dry_run():
+    """Stub the launches and accept CPU tensors, so that plans are built without a GPU exactly as they are built on one.  Yields the
+    counter of the launches a replay would have made, by command name."""
+    import addk.plan as P
+    calls = collections.Counter()
+
+    def fake_run(self, cmds, stream):
+        for name, fn, args in cmds:
+            calls[name] += 1
+    saved = P.Graph.run, P.require_device, P.current_stream
+    P.Graph.run, P.require_device, P.current_stream = fake_run, lambda x: None, lambda: 0
+    try:
+        yield calls
+    finally:
+        P.Graph.run, P.require_device, P.current_stream = saved
+
+
+@pytest.fixture()
+def dry():
+    """dry_run() around one test (the plan dry-run test files import this fixture)"""
+    with dry_run() as calls:
+        yield calls

@@ -198,7 +198,7 @@ def _train_step_collectives(rank, world):
     names = [c.name for c in ts.g.bwd]
     pos = [i for i, n in enumerate(names) if n == 'grad_allreduce']
     assert len(pos) == len(bk) and pos[0] < len(names) - 1, 'first bucket must be issued before the end of the backward list'
-    base = ts.flat_g.untyped_storage().data_ptr()
+    base = P._region(ts.flat_g)[0]                      # the name of the flat gradient buffer's storage; [1], [2]: byte interval
     for i in pos:
         lo, hi = ts.g.bwd[i].wr[0][1], ts.g.bwd[i].wr[0][2]
         later = [c.name for c in ts.g.bwd[i + 1:] if c.name != 'grad_allreduce' and any(r[0] == base and r[1] < hi and lo < r[2] for r in c.wr)]

@@ -11,21 +11,7 @@ import addk
 import addk.plan as P
 import addk.module as M
 import oracle
-from _util import ARCH_C2, ARCH_C3, GENOTYPE_AUTODEEPLAB, GENOTYPE_BASELINE_2, NETWORK_PATH_BASELINE, make_args
-
-
-@pytest.fixture()
-def dry(monkeypatch):
-    """Stub launches; allow CPU tensors.  Plans are built exactly as on the GPU box."""
-    calls = collections.Counter()
-
-    def fake_run(self, cmds, stream):
-        for name, fn, args in cmds:
-            calls[name] += 1
-    monkeypatch.setattr(P.Graph, 'run', fake_run)
-    monkeypatch.setattr(P, 'require_device', lambda x: None)
-    monkeypatch.setattr(P, 'current_stream', lambda: 0)
-    return calls
+from _util import ARCH_C2, ARCH_C3, GENOTYPE_AUTODEEPLAB, GENOTYPE_BASELINE_2, NETWORK_PATH_BASELINE, dry, make_args      # noqa: F401  (dry: the shared dry-run fixture)
 
 
 def _add(F=4, arch=ARCH_C2, sync=False):

@@ -1,4 +1,4 @@
-"""Host logic of the launch-list scheduler (plan.schedule) and of the level re-ordering pass (plan.level_order) on
+"""Host logic of the launch-list scheduler (sched.schedule) and of the level re-ordering pass (sched.level_order) on
 synthetic command DAGs: dependencies survive, the stream assignment respects the constraint that makes hipGraph capture
 safe on ROCm 7.2 (two side streams never wait on each other in both directions), implied waits are pruned."""
 import random
@@ -107,3 +107,29 @@ def test_tensor_regions_are_byte_intervals():
     ra, rb = P._region(a), P._region(b)
     assert ra[0] == rb[0] and not P._overlap(ra, rb)            # two views of one flat buffer do not alias
     assert P._overlap(P._region(flat), ra) and P._overlap(P._region(flat[30:50]), rb)
+
+
+def test_region_names_are_not_reissued_and_kinds_never_meet():
+    cpu = torch.device('cpu')
+    seen = []
+    for _ in range(50):                       # CPython hands the address (id) of a freed object to the next one of its size: a serial is not reused
+        v = P.LateVec(8)
+        assert v.region[0] not in seen and v.region[0][0] == 'late'
+        seen.append(v.region[0])
+        del v
+    # one number as buffer ordinal, LateVec serial and storage address: three different names
+    late = P.LateVec(4)
+    n = late.region[0][1]
+    buf = P.Buf(8, cpu, ordinal=n)
+    mem = (('mem', n), 0, 16)
+    keys = [P._region(buf), P._region(late), P._region(mem), P._region(P.Vec(P.Buf(8, cpu, ordinal=n + 1), 0, 8)), P._region(torch.zeros(4))]
+    assert [k[0][0] for k in keys] == ['buf', 'late', 'mem', 'buf', 'mem']
+    assert all(a[0] != b[0] and not P._overlap(a, b) for i, a in enumerate(keys) for b in keys[i + 1:])
+    t = P.TRef(buf, 4, 1, 1, 2, 4, 8)         # an NHWC view: its buffer's name, its channel interval
+    assert P._region(t) == (('buf', n), 4, 8) and P._overlap(P._region(t), P._region(buf))
+
+
+def test_plan_re_exports_the_launch_list_core():
+    import addk.sched as S
+    for name in ('Cmd', '_region', '_overlap', 'deps', 'levels', 'level_order', 'schedule'):
+        assert getattr(P, name) is getattr(S, name)

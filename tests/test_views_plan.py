@@ -19,26 +19,12 @@ import torch
 import addk
 import addk.plan as P
 from addk import _lib as L
-from _util import ARCH_C2, GENOTYPE_AUTODEEPLAB, make_args
+from _util import ARCH_C2, GENOTYPE_AUTODEEPLAB, dry, make_args      # noqa: F401  (dry: the shared dry-run fixture)
 import _views_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, HW = 2, (64, 128)
 X = (N, 3) + HW
-
-
-@pytest.fixture()
-def dry(monkeypatch):
-    """Stub launches; allow CPU tensors.  Plans are built exactly as on the GPU box."""
-    calls = collections.Counter()
-
-    def fake_run(self, cmds, stream):
-        for name, fn, args in cmds:
-            calls[name] += 1
-    monkeypatch.setattr(P.Graph, 'run', fake_run)
-    monkeypatch.setattr(P, 'require_device', lambda x: None)
-    monkeypatch.setattr(P, 'current_stream', lambda: 0)
-    return calls
 
 
 def _add(F=4, arch=ARCH_C2, classes=19):

@@ -4,21 +4,35 @@ not meant to change a plan must leave every fingerprint as it is.  No GPU: launc
 and tests/test_sep_dispatch.py do it.
 
 Per plan and per launch list the ordered records of every command are hashed: name, tag, tags, members, stream, waits, whether it
-records an event, batch key, payload (type and bytes), the read / write regions and every argument; argument structs, meta arrays
-and the tables the arguments point to are taken as bytes.  Memory is made address-independent by ONE rule: an 8-byte-aligned word,
-an integer argument or a region key that falls inside a known allocation becomes (ordinal of the allocation, byte offset).  Known
-allocations are the plan's buffers in creation order, then the parameters, the plan-owned gradients, the kept tensors and the
-tensors of the plan's front end (inputs, outputs, loss scalars, module buffers) in first-seen order.  Region keys that are object
-identities (plan.LateVec before it is bound) are numbered in first-seen order over the lists.  Also recorded: nbytes, the number and
-sizes of the buffers, the number of hoisted weight packs.
+records an event, batch key, payload, the read / write regions and every argument.  Memory is made address-independent by what each
+value is DECLARED to be, never by what its bytes look like:
+  - a ctypes Structure or Array (argument struct, payload, meta array) is walked by its `_fields_`: a pointer field becomes
+    Memory.word(value) = (ordinal of the known allocation it lies in, byte offset), everything else is the bytes it occupies.  A
+    non-null pointer in no known allocation is an error that names plan, list, command and field: it would tie the hash to the process;
+  - a positional integer argument goes through Memory.word too (a size never reaches the 2^40 and more of an address);
+  - a device table is recorded as ('table', byte length, typed hash of Cmd.table), the array of argument structs the planner made
+    it from.  Where the library turns that array into a blob of kernel descriptors and work lists (`*_batch_prepare`) the blob's
+    bytes are NOT hashed: they are a pure function of the array, the precision mode and the library, and that side is pinned by
+    tests/test_conv_dispatch.py, test_sep_dispatch.py, test_pw_dispatch.py and the *_bits fixtures.  The meta array of such a launch
+    (kind, tile configuration, count, offsets, block counts: no pointer) stays in the record as bytes;
+  - a region is named by the plan (sched._region): ('buf', n) is recorded as ('a', n), a LateVec as ('id', k) with k counted inside
+    the plan in first-seen order, the storage of a tensor as its allocation and offset.
+Known allocations are the plan's buffers in creation order, then the parameters, the plan-owned gradients, the kept tensors and the
+tensors of the plan's front end (inputs, outputs, loss scalars, module buffers) in first-seen order.  Also recorded: nbytes, the
+number and sizes of the buffers, the number of hoisted weight packs.
+
+Until the fixture was re-recorded for this rule the tool scanned every struct and blob for 8-byte-aligned words that fell inside a
+known allocation.  The blob of addk_conv_wgrad_batch_prepare ends in int4 work lists whose entries (i, e, flag, 0) read as the word
+e << 32 | i, e.g. 0x0000554000000002: about once in six processes the address space put an allocation over such a value, data was
+rewritten as (allocation, offset), and the `bwd` lists of the training plans compared unequal although the planner had made the
+same plan.  tests/test_plan_fingerprint.py keeps that case as a unit test of the walk.
 
     python tests/tools/plan_fingerprint.py                 # writes tests/golden/plan_fingerprint.json (run it on the commit to pin)
     python tests/tools/plan_fingerprint.py --check         # compares with the fixture, exit status 1 on a difference
     python tests/tools/plan_fingerprint.py --dump DIR      # also writes every record as text, one file per list (to diff two commits)
 
 tests/test_plan_fingerprint.py calls fingerprints() and compares with the fixture.  Every struct the planner fills is a ctypes
-object (zero-initialised) and every library-made blob is written into zeroed memory, so no byte needs masking: two runs of this tool
-in different processes give equal hashes."""
+object (zero-initialised), so no byte needs masking: two runs of this tool in different processes give equal hashes."""
 import argparse
 import bisect
 import collections
@@ -29,7 +43,6 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,19 +56,17 @@ _BYREF = type(C.byref(C.c_int()))
 
 
 class Memory:
-    """The known allocations of one plan; `word(v)` is the one rule that makes a value address-independent."""
+    """The known allocations of one plan; `word(v)` makes a value that is declared an address (or a positional integer) address-independent."""
 
     def __init__(self):
         self.starts, self.ends, self.ords = [], [], []
         self.n = 0
         self.tables = {}          # data_ptr of a kept uint8 table -> tensor
-        self.ids = {}             # id() of a Buf -> ordinal of its allocation; other identities: first seen
+        self.late = {}            # serial of a plan.LateVec -> its number among those of this plan, first seen
 
-    def add(self, base, nbytes, obj_id=None):
+    def add(self, base, nbytes):
         o = self.n
         self.n += 1
-        if obj_id is not None:
-            self.ids[obj_id] = ('a', o)
         if nbytes <= 0:
             return o
         i = bisect.bisect_right(self.starts, base)
@@ -74,45 +85,77 @@ class Memory:
             return ('@', self.ords[i], v - self.starts[i])
         return v
 
-    def ident(self, v):
-        if v not in self.ids:
-            w = self.word(v)
-            if w is not v:
-                return w
-            self.ids[v] = ('id', sum(1 for k in self.ids.values() if k[0] == 'id'))
-        return self.ids[v]
-
-    def blob(self, data):
-        """bytes -> bytes with every 8-byte-aligned word that is an address replaced by 1 << 63 | ordinal << 40 | offset"""
-        data = bytes(data)
-        data += b'\0' * (-len(data) % 8)
-        w = np.frombuffer(data, dtype=np.uint64).copy()
-        if not self.starts or not len(w):
-            return w.tobytes()
-        st, en = np.asarray(self.starts, dtype=np.uint64), np.asarray(self.ends, dtype=np.uint64)
-        i = np.searchsorted(st, w, side='right').astype(np.int64) - 1
-        ok = i >= 0
-        ic = np.where(ok, i, 0)
-        ok &= w < en[ic]
-        off = w - st[ic]
-        assert not bool((off[ok] >> np.uint64(40)).any())
-        enc = np.uint64(1 << 63) | (np.asarray(self.ords, dtype=np.uint64)[ic] << np.uint64(40)) | off
-        return np.where(ok, enc, w).tobytes()
+    def name(self, key):
+        """The name of a region (sched._region) in the record: the buffer's ordinal, the LateVec's number inside this plan, the
+        tensor's allocation and the offset of its storage in it."""
+        kind, v = key
+        if kind == 'buf':
+            return ('a', v)           # the buffers are the first allocations (_memory): ordinal in the plan = ordinal here
+        if kind == 'late':
+            return ('id', self.late.setdefault(v, len(self.late)))
+        w = self.word(v) if kind == 'mem' else v
+        if w == v:
+            raise UnknownPointer('region %r lies in no known allocation' % (key,))
+        return w
 
 
-def _arg(mem, a, P):
+class UnknownPointer(ValueError):
+    """A non-null pointer field that lies in no known allocation: its value, and so the hash, would depend on the process."""
+
+
+_POINTERS = (C.c_void_p, C.c_char_p, C.c_wchar_p, C._Pointer, C._CFuncPtr)
+_has_ptr = {}
+
+
+def _holds_pointers(ct):
+    if ct not in _has_ptr:
+        _has_ptr[ct] = (issubclass(ct, _POINTERS) or (issubclass(ct, C.Array) and _holds_pointers(ct._type_)) or
+                        (issubclass(ct, (C.Structure, C.Union)) and any(_holds_pointers(f[1]) for f in ct._fields_)))
+    return _has_ptr[ct]
+
+
+def _walk(mem, ct, raw, base, path, out):
+    """The bytes raw[base:] of an object of ctypes type `ct`, appended to `out` field by field: a pointer as Memory.word(value),
+    everything else as the bytes it occupies."""
+    if not _holds_pointers(ct):
+        out.append(raw[base:base + C.sizeof(ct)])
+    elif issubclass(ct, C.Structure):
+        for f in ct._fields_:
+            _walk(mem, f[1], raw, base + getattr(ct, f[0]).offset, '%s.%s' % (path, f[0]), out)
+    elif issubclass(ct, C.Array):
+        for i in range(ct._length_):
+            _walk(mem, ct._type_, raw, base + i * C.sizeof(ct._type_), '%s[%d]' % (path, i), out)
+    elif issubclass(ct, _POINTERS):
+        v = int.from_bytes(raw[base:base + C.sizeof(ct)], sys.byteorder)
+        w = mem.word(v)
+        if v and w == v:
+            raise UnknownPointer('%s = %#x lies in no known allocation' % (path, v))
+        out.append(w)
+    else:
+        raise TypeError('%s: %s' % (path, ct))
+
+
+def typed(mem, obj, path=''):
+    """sha256 over a ctypes Structure / Array, or a list of them, walked by its declared fields (_walk)"""
+    out = []
+    for i, o in enumerate(obj) if isinstance(obj, (list, tuple)) else ((None, obj),):
+        _walk(mem, type(o), bytes(o), 0, '%s%s' % (path or type(o).__name__, '' if i is None else '[%d]' % i), out)
+    return hashlib.sha256(repr(out).encode()).hexdigest()
+
+
+def _arg(mem, a, P, table=None):
     if a is None or isinstance(a, (float, str)):
         return a
     if isinstance(a, bool):
         return int(a)
     if isinstance(a, int):
-        if a in mem.tables:                                   # a table of argument structs / descriptors: its bytes, not its address
-            return ('table', hashlib.sha256(mem.blob(mem.tables[a].numpy().tobytes())).hexdigest())
+        if table is not None and a in mem.tables:             # the device table of this command: its typed source (Cmd.table), not its address
+            return ('table', mem.tables[a].numel(), typed(mem, table, 'table'))
         return mem.word(a)
     if isinstance(a, _BYREF):
         a = a._obj
     if isinstance(a, (C.Structure, C.Array)):
-        return (type(a).__name__, hashlib.sha256(mem.blob(bytes(a))).hexdigest())
+        return (type(a).__name__, typed(mem, a))
     if isinstance(a, torch.Tensor):
         return ('tensor', mem.word(a.data_ptr()), tuple(a.shape), str(a.dtype))
     if isinstance(a, P.LateVec):
@@ -122,21 +165,26 @@ def _arg(mem, a, P):
     return type(a).__name__
 
 
-def _records(mem, lst, P):
+def _records(mem, lst, P, where=''):
     out = []
-    for c in lst:
-        reg = lambda rs: [(mem.ident(k[0]), k[1], k[2]) for k in rs]      # noqa: E731
+    for i, c in enumerate(lst):
+        reg = lambda rs: [(mem.name(k[0]), k[1], k[2]) for k in rs]      # noqa: E731
         pay = c.payload
-        out.append((c.name, c.tag, sorted(c.tags) if c.tags is not None else None, c.members, c.stream, tuple(c.waits), c.event is not None,
-                    c.bkey, type(pay).__name__, _arg(mem, pay, P) if isinstance(pay, (C.Structure, P.LateVec)) else None,
-                    reg(c.rd), reg(c.wr), [_arg(mem, a, P) for a in c.args]))
+        try:
+            args = [_arg(mem, a, P, c.table) for a in c.args]
+            assert c.table is None or any(isinstance(a, tuple) and a[0] == 'table' for a in args), 'Cmd.table without a table argument'
+            out.append((c.name, c.tag, sorted(c.tags) if c.tags is not None else None, c.members, c.stream, tuple(c.waits), c.event is not None,
+                        c.bkey, type(pay).__name__, _arg(mem, pay, P) if isinstance(pay, (C.Structure, P.LateVec)) else None,
+                        reg(c.rd), reg(c.wr), args))
+        except UnknownPointer as e:
+            raise UnknownPointer('%s, command %d (%s): %s' % (where, i, c.name, e)) from None
     return out
 
 
 def _memory(g, extra):
     mem = Memory()
     for b in g._bufs:
-        mem.add(b.ptr, 4 * max(b.n, 4), id(b))
+        mem.add(b.ptr, 4 * max(b.n, 4))
     for p in g.params:
         mem.add_tensor(p)
     for p in g.params:
@@ -157,7 +205,7 @@ def _fingerprint(g, lists, extra, dump, label):
     res = {'nbytes': int(g.nbytes), 'bufs': len(g._bufs), 'buf_sizes': hashlib.sha256(repr([b.n for b in g._bufs]).encode()).hexdigest(),
            'packs': len(g._packs), 'lists': {}}
     for name, lst in lists:
-        recs = _records(mem, lst, P)
+        recs = _records(mem, lst, P, '%s/%s' % (label, name))
         text = '\n'.join(repr(r) for r in recs)
         res['lists'][name] = {'sha256': hashlib.sha256(text.encode()).hexdigest(), 'commands': len(recs),
                               'names': dict(sorted(collections.Counter(c.name for c in lst).items()))}
@@ -307,31 +355,12 @@ PLANS = (
 )
 
 
-class _dry:
-    """Stub the launches and accept CPU tensors, as the dry-run tests do; restores everything on exit."""
-
-    late = []
-
-    def __enter__(self):
-        import addk.plan as P
-        self.P, self.saved = P, (P.Graph.run, P.require_device, P.current_stream, P.LateVec.__init__)
-        P.Graph.run = lambda self, cmds, stream: None
-        # a LateVec's region key is its identity, and the merged all-reduce of a level outlives the vectors it replaced: they are kept
-        # alive here so that no later object is given the address (= identity) of a dead one
-        late, init = self.late, P.LateVec.__init__
-        P.LateVec.__init__ = lambda s, *a, **k: (init(s, *a, **k), late.append(s))[0]
-        P.require_device = lambda x: None
-        P.current_stream = lambda: 0
-        return self
-
-    def __exit__(self, *exc):
-        self.P.Graph.run, self.P.require_device, self.P.current_stream, self.P.LateVec.__init__ = self.saved
-
-
-def fingerprints(only=None, dump=None):
-    """{plan/environment: fingerprint} of every plan of PLANS (or of the names in `only`) under every environment of ENVS, built
-    in f16x3 arithmetic with every fast path on (config 2's defaults on the MI355X)."""
+def fingerprints(only=None, dump=None, hold=None, envs=ENVS):
+    """{plan/environment: fingerprint} of every plan of PLANS (or of the names in `only`) under every environment of `envs`, built
+    in f16x3 arithmetic with every fast path on (config 2's defaults on the MI355X).  `hold`: a list that receives every plan built,
+    with all its front end owns, so that it stays alive (a later build then sits at other addresses)."""
     import addk
+    from _util import dry_run
     from addk import _lib as L
     lib = addk.load()
     mode, fast = lib.addk_get_conv_precision(), lib.addk_get_fast_paths()
@@ -339,21 +368,23 @@ def fingerprints(only=None, dump=None):
     try:
         L.check(lib.addk_set_conv_precision(1), 'set_conv_precision')
         lib.addk_set_fast_paths(31)
-        with _dry():
+        with dry_run():
             for pname, build in PLANS:
                 if only and pname not in only:
                     continue
-                for ename, env in ENVS:
+                for ename, env in envs:
                     old = {k: os.environ.get(k) for k in env}
                     os.environ.update(env)
                     try:
-                        g, lists, extra, hold = build()
+                        g, lists, extra, front = build()
                         label = '%s/%s' % (pname, ename)
                         out[label] = _fingerprint(g, lists, extra, dump, label)
                     finally:
                         for k, v in old.items():
                             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-                    del g, lists, extra, hold, _dry.late[:]
+                    if hold is not None:
+                        hold.append((g, front))
+                    del g, lists, extra, front
                     gc.collect()
     finally:
         lib.addk_set_conv_precision(mode)
