@@ -73,6 +73,11 @@ class CeUpsampleOhemArgs(C.Structure):
     _fields_ = [('ce', CeUpsampleArgs), ('pix_loss', vp), ('tau', vp)]
 
 
+class CeUpsampleKdArgs(C.Structure):
+    _fields_ = [('ce', CeUpsampleArgs), ('pix_loss', vp), ('tau', vp), ('teacher', vp), ('ld_teacher', i32), ('alpha', f32),
+                ('temperature', f32), ('nvalid', vp), ('kd_out', vp)]
+
+
 class ScoreUpsampleArgs(C.Structure):
     _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
                 ('target', vp), ('class_w', vp), ('ignore_index', i32), ('wsum', vp), ('scale', f32), ('loss_out', vp),
@@ -278,6 +283,9 @@ _SIGS = {
     'addk_ohem_select_ws_bytes': (i64, [i32, i32, i32]),
     'addk_ohem_select': (i32, [C.POINTER(OhemSelectArgs), vp]),
     'addk_ce_upsample_ohem_fwd_bwd': (i32, [C.POINTER(CeUpsampleOhemArgs), vp]),
+    'addk_ce_upsample_kd_supported': (i32, [i32, i32, i32, i32, i32, i32]),
+    'addk_ce_upsample_kd_ws_floats': (i64, [i32, i32, i32]),
+    'addk_ce_upsample_kd_fwd_bwd': (i32, [C.POINTER(CeUpsampleKdArgs), vp]),
     'addk_score_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_score_upsample_ws_floats': (i64, [i32, i32, i32]),
     'addk_score_upsample': (i32, [C.POINTER(ScoreUpsampleArgs), vp]),

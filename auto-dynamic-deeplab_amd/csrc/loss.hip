@@ -191,11 +191,21 @@ constexpr int CEU_MAXBAND = 16;            // high-resolution rows per low-resol
 // addk_ohem_select; a pixel whose stored loss is below tau counts as not valid (weight 0), and p.wsum points at the kept weight sum.  The
 // keep decision is READ, never recomputed: invalid pixels carry -1 in the map and tau >= 0.  OHEM = false is the plain kernel, token for token.
 struct CeUpOhemK : CeUpK { const float* lmap; const float* tau; };
-template <bool OHEM> struct CeUpArg { typedef CeUpK type; };
-template <> struct CeUpArg<true> { typedef CeUpOhemK type; };
+// KD (self-distillation from the last exit, addk_ce_upsample_kd_fwd_bwd): the launch also gets the teacher's low-resolution logits on the
+// student's grid.  A thread keeps the teacher's four corner pixels beside the student's, samples z_t with the student's indices and
+// expression, and per pixel adds one softmax pair at temperature T: e_s = exp(z_s/T - max), e_t likewise (1/T is rounded once on the
+// host: z * rT), KL = (1/Σe_t) Σ e_t*(d_t - d_s) + log Σe_s - log Σe_t with d = z/T - max, and kg * (e_s/Σe_s - e_t/Σe_t) joins gz before the
+// gather, kg = scale*alpha*T / n.  The plain predicate decides (a select, not a factor): mining never filters the term and class_w does not
+// weigh it.  The KL partial leaves beside lsum (ws2, same ownership rule).  KD = false is the parent's kernel, instruction for instruction.
+// TVEC: the teacher's loader, px_vec_ok on ITS base and stride, chosen by the host as for scu_walk — a second run-time loader switch
+// would put the teacher's padding channels into scratch as the student's are (40 -> 72 bytes per lane).
+struct CeUpKdK : CeUpOhemK { const float* teacher; int ldt; float rT, kscale; const float* nvalid; float* ws2; };
+template <bool OHEM, bool KD = false> struct CeUpArg { typedef CeUpK type; };
+template <> struct CeUpArg<true, false> { typedef CeUpOhemK type; };
+template <bool OHEM> struct CeUpArg<OHEM, true> { typedef CeUpKdK type; };
 
-template <int CC, bool OHEM = false>
-__global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM>::type p) {
+template <int CC, bool OHEM = false, bool KD = false, bool TVEC = false>
+__global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM, KD>::type p) {
   constexpr int CP = cpad(CC);
   constexpr int NOUT = ((CEU_X - 1) * CC + 255) / 256;
   __shared__ float S0[CEU_R * CEU_X * CC], S1[CEU_R * CEU_X * CC];
@@ -214,6 +224,10 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM>
   const gfloat* cw = (const gfloat*)p.cw;
   float tau = 0.f;
   if constexpr (OHEM) tau = *(const gfloat*)p.tau;
+  [[maybe_unused]] float kg = 0.f, ksum = 0.f;
+  if constexpr (KD) {
+    kg = p.kscale / *(const gfloat*)p.nvalid;                  // n == 0: no pixel is valid and the select below never takes it
+  }
   float lsum = 0.f;
   float carry[NOUT];
 #pragma unroll
@@ -241,12 +255,20 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM>
         float v00[CP], v01[CP], v10[CP], v11[CP];
         load_px<CC>(r0 + (long)x * p.ld, v00, vec); load_px<CC>(r0 + (long)x1 * p.ld, v01, vec);
         load_px<CC>(r1 + (long)x * p.ld, v10, vec); load_px<CC>(r1 + (long)x1 * p.ld, v11, vec);
+        [[maybe_unused]] float u00[KD ? CP : 1], u01[KD ? CP : 1], u10[KD ? CP : 1], u11[KD ? CP : 1];      // the teacher's corners
+        if constexpr (KD) {
+          const float* q0 = p.teacher + ((long)(n * p.H + h0) * p.W) * p.ldt;
+          const float* q1 = p.teacher + ((long)(n * p.H + h1) * p.W) * p.ldt;
+          load_px<CC>(q0 + (long)x * p.ldt, u00, TVEC); load_px<CC>(q0 + (long)x1 * p.ldt, u01, TVEC);
+          load_px<CC>(q1 + (long)x * p.ldt, u10, TVEC); load_px<CC>(q1 + (long)x1 * p.ldt, u11, TVEC);
+        }
         const int64_t __attribute__((address_space(1)))* tp = tgt + ((long)n * p.OH + Y) * p.OW;
         for (int X = xlo; X < xhi; ++X) {
           int w0, w1; float lw0, lw1;
           src_index(X, sw, p.W, w0, w1, lw0, lw1);
           const long tg = tp[X];
           bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+          [[maybe_unused]] const bool pvalid = valid;            // the plain predicate: what the distillation term goes by
           if constexpr (OHEM) valid = valid && ((const gfloat*)p.lmap)[((long)n * p.OH + Y) * p.OW + X] >= tau;
           const float w = valid ? (cw ? cw[tg] : 1.f) : 0.f;
           float z[CC];
@@ -257,6 +279,30 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM>
             mx = fmaxf(mx, z[c]);
             if (c == tg) zt = z[c];
           }
+          [[maybe_unused]] float D[KD ? CC : 1];                 // the distillation term's part of gz
+          if constexpr (KD) {
+            float et[CC];
+            float mt = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+              et[c] = (lh0 * (lw0 * u00[c] + lw1 * u01[c]) + lh1 * (lw0 * u10[c] + lw1 * u11[c])) * p.rT;
+              mt = fmaxf(mt, et[c]);
+            }
+            const float ms = mx * p.rT;                           // rT > 0: the largest z * rT is (largest z) * rT
+            float ses = 0.f, set = 0.f, kl = 0.f;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+              const float ds = z[c] * p.rT - ms, dt = et[c] - mt;
+              const float es = __expf(ds), e = __expf(dt);
+              ses += es; set += e;
+              kl = fmaf(e, dt - ds, kl);
+              D[c] = es; et[c] = e;
+            }
+            if (own && xl >= 1 && pvalid) ksum += kl / set + (logf(ses) - logf(set));
+            const float ks = kg / ses, kt_ = kg / set;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) D[c] = pvalid ? D[c] * ks - et[c] * kt_ : 0.f;
+          }
           float se = 0.f;
 #pragma unroll
           for (int c = 0; c < CC; ++c) { z[c] = __expf(z[c] - mx); se += z[c]; }
@@ -265,7 +311,8 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM>
           const float a0 = lw0 + (xlast ? lw1 : 0.f), a1 = xlast ? 0.f : lw1;
 #pragma unroll
           for (int c = 0; c < CC; ++c) {
-            const float gz = z[c] * k - ((valid && c == tg) ? kt : 0.f);
+            float gz = z[c] * k - ((valid && c == tg) ? kt : 0.f);
+            if constexpr (KD) gz += D[c];
             A0[c] = fmaf(a0, gz, A0[c]); A1[c] = fmaf(a1, gz, A1[c]);
           }
         }
@@ -309,6 +356,25 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM>
   }
   lsum = block_sum(lsum, shs);
   if (t == 0) ((gfloat*)p.ws)[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = lsum;
+  if constexpr (KD) {
+    ksum = block_sum(ksum, shs);
+    if (t == 0) ((gfloat*)p.ws2)[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ksum;
+  }
+}
+
+// second stage of the distillation term: the KL partials in the order of sum_partials_kernel; kd = coef * Σ / n, exactly 0 when no pixel
+// is valid.  kd_out is written (a replayed graph leaves the last step's value), the loss accumulates it.
+__global__ void __launch_bounds__(256) kd_sum_kernel(const float* ws, int n, float coef, const float* nvalid, float* kd_out, float* loss_out) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += ws[i];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) {
+    const float nv = *nvalid;
+    const float kd = nv > 0.f ? s * coef / nv : 0.f;
+    *kd_out = kd;
+    *loss_out += kd;
+  }
 }
 
 int ceu_hb(int H) { return H >= 64 ? 4 : (H >= 16 ? 2 : 1); }
@@ -995,6 +1061,50 @@ extern "C" int addk_ce_upsample_ohem_fwd_bwd(const addk_ce_upsample_ohem_args* b
   if (rc) return rc;
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, a->ws, (int)(grid.x * grid.y * grid.z), a->scale, a->wsum, a->loss_out, 1);
   return addk_check_launch("ce_upsample_ohem_sum");
+}
+
+extern "C" int addk_ce_upsample_kd_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return ceu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_ce_upsample_kd_ws_floats(int32_t N, int32_t H, int32_t W) {
+  return 2 * addk_ce_upsample_ws_floats(N, H, W);                // the loss partials, then the KL partials
+}
+extern "C" int addk_ce_upsample_kd_fwd_bwd(const addk_ce_upsample_kd_args* b, void* stream) {
+  ADDK_REQUIRE(b, "ce_upsample_kd: null pointer");
+  const addk_ce_upsample_args* a = &b->ce;
+  ADDK_REQUIRE(a->logits && a->target && a->wsum && a->loss_out && a->g && a->ws && b->teacher && b->nvalid && b->kd_out, "ce_upsample_kd: null pointer");
+  ADDK_REQUIRE((b->pix_loss == nullptr) == (b->tau == nullptr), "ce_upsample_kd: pix_loss and tau come together (both NULL: no mining)");
+  ADDK_REQUIRE(b->teacher != a->logits, "ce_upsample_kd: the teacher must be another exit's logits");
+  ADDK_REQUIRE(a->ld >= a->C && a->ldg >= a->C && b->ld_teacher >= a->C, "ce_upsample_kd: short stride");
+  ADDK_REQUIRE(isfinite(b->alpha) && b->alpha > 0.f && isfinite(b->temperature) && b->temperature > 0.f,
+               "ce_upsample_kd: alpha and temperature must be positive and finite");
+  ADDK_REQUIRE(ceu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "ce_upsample_kd: unsupported shape (19 classes, at most %d output rows per input row)", CEU_MAXBAND);
+  CeUpKdK k;
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.target = a->target; k.cw = a->class_w; k.ignore = a->ignore_index; k.wsum = a->wsum; k.scale = a->scale;
+  k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate; k.ws = a->ws; k.HB = ceu_hb(a->H);
+  k.lmap = b->pix_loss; k.tau = b->tau;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(cdiv(a->W, CEU_X - 1), cdiv(a->H, k.HB), a->N);
+  const int nblk = (int)(grid.x * grid.y * grid.z);
+  k.teacher = b->teacher; k.ldt = b->ld_teacher; k.nvalid = b->nvalid; k.ws2 = a->ws + nblk;
+  k.rT = 1.f / b->temperature;
+  k.kscale = a->scale * b->alpha * b->temperature;              // the gradient's factor before 1/n; the loss takes one more T
+  const bool tvec = px_vec_ok<19>(b->teacher, b->ld_teacher);
+  if (b->pix_loss) {
+    if (tvec) hipLaunchKernelGGL((ce_up_kernel<19, true, true, true>), grid, dim3(256), 0, st, k);
+    else hipLaunchKernelGGL((ce_up_kernel<19, true, true, false>), grid, dim3(256), 0, st, k);
+  } else {
+    if (tvec) hipLaunchKernelGGL((ce_up_kernel<19, false, true, true>), grid, dim3(256), 0, st, k);
+    else hipLaunchKernelGGL((ce_up_kernel<19, false, true, false>), grid, dim3(256), 0, st, k);
+  }
+  int rc = addk_check_launch("ce_upsample_kd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, a->ws, nblk, a->scale, a->wsum, a->loss_out, 1);
+  rc = addk_check_launch("ce_upsample_kd_sum");
+  if (rc) return rc;
+  hipLaunchKernelGGL(kd_sum_kernel, dim3(1), dim3(256), 0, st, k.ws2, nblk, k.kscale * b->temperature, b->nvalid, b->kd_out, a->loss_out);
+  return addk_check_launch("ce_upsample_kd_kl_sum");
 }
 
 extern "C" int addk_ohem_select_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {

@@ -1277,16 +1277,38 @@ class Graph:
         fused up-sampling + cross-entropy launch (`addk_ce_upsample_fwd_bwd`) at the head of the backward list.  A binding with
         `ohem = (thresh, min_kept_total)` mines hard examples (include/addk.h, addk_ohem_select): `ohem_select` leaves this exit's own
         per-pixel loss map, tau and kept weight sum, and `ce_upsample_ohem` is the loss head that reads them; the binding gets the
-        tensors back as `ohem_state` (TrainStep.ohem_stats)."""
+        tensors back as `ohem_state` (TrainStep.ohem_stats).  A binding with `distill = (alpha, temperature, teacher OutRef)` and `nvalid`
+        (the count word) makes the exit a student of the teacher's low-resolution logits (`OutRef.src`): `ce_upsample_kd` takes the place
+        of `ce_upsample` / `ce_upsample_ohem`, and the binding gets `distill_state` (TrainStep.distill_stats)."""
         def emit_ce(ce):
             ohem = ce.get('ohem')
             a = self._up_args(L.CeUpsampleArgs, src, OH, OW)
             self._bind_loss(a, ce)
             gs, a.accumulate, _ = self._grad_into(src)
             a.g, a.ldg = gs.ptr, gs.ld
-            ws = torch.zeros(int(self.lib.addk_ce_upsample_ws_floats(src.N, src.H, src.W)), dtype=torch.float32, device=self.device)
+            kd = ce.get('distill')
+            ws_floats = self.lib.addk_ce_upsample_kd_ws_floats if kd else self.lib.addk_ce_upsample_ws_floats
+            ws = torch.zeros(int(ws_floats(src.N, src.H, src.W)), dtype=torch.float32, device=self.device)
             a.ws = ws.data_ptr()
             self.keep += [a, ws]
+            if kd:
+                # a student: the head's own normaliser and kept set as below, plus the last exit's low-resolution logits and the count word
+                alpha, temp, teacher = kd
+                tsrc = teacher.src
+                assert tsrc.bn is None and not tsrc.relu and (tsrc.N, tsrc.H, tsrc.W, tsrc.C) == (src.N, src.H, src.W, src.C)
+                kdo = torch.zeros(1, dtype=torch.float32, device=self.device)
+                k = L.CeUpsampleKdArgs()
+                k.ce = a                                   # a copy; with mining its normaliser is re-pointed below
+                t = self.src(tsrc)
+                k.teacher, k.ld_teacher, k.alpha, k.temperature = t.x, t.ld, alpha, temp
+                k.nvalid, k.kd_out = ce['nvalid'].data_ptr(), kdo.data_ptr()
+                ce['distill_state'] = dict(kd=kdo)
+                self.keep += [k, kdo]
+                kd_rd = self.lz(tsrc) + [ce['nvalid']]
+                if not ohem:
+                    self._add(self.bwd, 'ce_upsample_kd', self.lib.addk_ce_upsample_kd_fwd_bwd, C.byref(k),
+                              rd=self.lz(src) + [ce['target'], ce['wsum']] + kd_rd, wr=[gs, ce['loss'], ws, kdo])
+                    return
             if not ohem:
                 self._add(self.bwd, 'ce_upsample', self.lib.addk_ce_upsample_fwd_bwd, C.byref(a),
                           rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
@@ -1310,9 +1332,16 @@ class Graph:
             self.keep += [s, b, lmap, tau, wkept, counts, sws]
             self._add(self.bwd, 'ohem_select', self.lib.addk_ohem_select, C.byref(s),
                       rd=self.lz(src) + [ce['target']], wr=[lmap, tau, wkept, counts, sws])
+            if kd:
+                k.ce.wsum, k.pix_loss, k.tau = b.ce.wsum, b.pix_loss, b.tau
+                self._add(self.bwd, 'ce_upsample_kd', self.lib.addk_ce_upsample_kd_fwd_bwd, C.byref(k),
+                          rd=self.lz(src) + [ce['target'], lmap, tau, wkept] + kd_rd, wr=[gs, ce['loss'], ws, kdo])
+                return
             self._add(self.bwd, 'ce_upsample_ohem', self.lib.addk_ce_upsample_ohem_fwd_bwd, C.byref(b),
                       rd=self.lz(src) + [ce['target'], lmap, tau, wkept], wr=[gs, ce['loss'], ws])
-        return self._late_head('ce', src, OH, OW, self.bwd, self._bwd_emitters, emit_ce)
+        out = self._late_head('ce', src, OH, OW, self.bwd, self._bwd_emitters, emit_ce)
+        out.src = src
+        return out
 
     def _score_head(self, src, OH, OW):
         """Logits output of a validation plan (head 'score', set by validate.ValidationStep): nobody reads the full-resolution
@@ -1697,7 +1726,7 @@ class OutRef:
         self.bwd_cmd = None      # generic nhwc path
         self.shape = None        # (N, C, OH, OW) of the logits a fused head stands for (y is None)
         self.head = None         # Graph.head of the head that consumed the logits; None: y is the real logits.  'labels': y is the label map
-        self.src = None          # 'views': the lazy activation of the decoder's low-resolution logits this output stands for
+        self.src = None          # 'views', 'ce': the lazy activation of the decoder's low-resolution logits this output stands for
         # what the step binds to a 'ce' / 'score' / 'profile' head before finalize() — 'ce': target, class_w, ignore_index, wsum, scale, loss;
         # 'score': those + entropy, confusion, pred; 'profile': target, thr, nthr, entropy, share, confusion, pred; 'views': N, views
         self.binding = None

@@ -3,6 +3,7 @@ averaged over exits, backward, SGD(momentum, weight_decay, nesterov) — emitted
 parameter/gradient buffers and replayed as a single hipGraph launch (eager launch list when RCCL collectives
 sit inside the step)."""
 import ctypes as C
+import math
 import os
 
 import torch
@@ -49,14 +50,35 @@ def _check_ohem(ohem, N):
     return thresh, min_kept * N
 
 
+def _check_distill(distill):
+    """(alpha, temperature) -> two positive finite floats, or None; ValueError for what the library would refuse."""
+    if distill is None:
+        return None
+    if os.environ.get('ADDK_FUSE_CE', '1') != '1':
+        raise ValueError('distill needs the fused loss head (ADDK_FUSE_CE=1): there is no form over full-resolution logits')
+    try:
+        alpha, temp = distill
+        alpha, temp = float(alpha), float(temp)
+    except (TypeError, ValueError):
+        raise ValueError('distill must be (alpha, temperature), got %r' % (distill,))
+    a32, t32 = C.c_float(alpha).value, C.c_float(temp).value          # the words the library receives
+    if not (math.isfinite(a32) and math.isfinite(t32) and a32 > 0.0 and t32 > 0.0):
+        raise ValueError('distill: alpha and temperature must be positive and finite, got %r' % (distill,))
+    return alpha, temp
+
+
 class TrainStep:
     def __init__(self, model, batch_shape, lr=0.05, momentum=0.9, weight_decay=4e-5, nesterov=True, class_weight=None,
-                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None, ohem=None):
+                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None, ohem=None, distill=None):
         """ohem = (thresh, min_kept): online hard example mining in every exit's loss head (include/addk.h, addk_ohem_select) — per exit
         and per process, a pixel counts when its target-class probability is below `thresh`, and never fewer than `min_kept` pixels per
-        image (min_kept * N of the batch) count.  Only the fused loss head has this form: ValueError otherwise."""
+        image (min_kept * N of the batch) count.  Only the fused loss head has this form: ValueError otherwise.
+        distill = (alpha, temperature): self-distillation from the final exit (include/addk.h, addk_ce_upsample_kd_fwd_bwd) — every exit but
+        the last adds scale * alpha * T^2 * mean over valid pixels of KL(softmax(z_last / T) || softmax(z_exit / T)) to its loss; the last
+        exit's logits are read detached.  Needs the fused head on every exit, more than one exit and exits on one low-resolution grid."""
         lib = self.lib = L.load()
         self.ohem = _check_ohem(ohem, batch_shape[0])
+        self.distill = _check_distill(distill)
         dev = next(model.parameters()).device
         _plan.require_device(next(model.parameters()))
         self.model, self.dev = model, dev
@@ -88,6 +110,14 @@ class TrainStep:
         nex = len(outs)
         if self.ohem is not None and any(o.head != 'ce' for o in outs):
             raise ValueError('ohem: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
+        if self.distill is not None:
+            if nex < 2:
+                raise ValueError('distill: this model has a single exit, nobody to teach')
+            if any(o.head != 'ce' for o in outs):
+                raise ValueError('distill: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
+            if len({(o.src.N, o.src.H, o.src.W, o.src.C) for o in outs}) != 1:
+                raise ValueError('distill: the exits\' low-resolution logits differ in shape: %r'
+                                 % ([(o.src.N, o.src.H, o.src.W, o.src.C) for o in outs],))
         ncls = outs[0].shape[1] if outs[0].head == 'ce' else outs[0].y.shape[1]
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.wsum = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -99,12 +129,26 @@ class TrainStep:
         if self.ohem is None:             # a mining head normalises by its own kept weight sum
             g._add(g.fwd, 'ce_count', lib.addk_ce_count, self.target.data_ptr(), N * H * W, cwp, ignore_index, ncls,
                    self.wsum.data_ptr(), ws.data_ptr(), rd=[self.target], wr=[self.wsum, ws])
+        nvalid = None
+        if self.distill is not None:
+            # n of the distillation term: the unweighted count of valid pixels.  The plain step's wsum is that count; a step with class
+            # weights or mining counts once more, ONE launch for all exits
+            nvalid = self.wsum
+            if cw is not None or self.ohem is not None:
+                nvalid = self.nvalid = torch.zeros(1, dtype=torch.float32, device=dev)
+                nws = torch.zeros_like(ws)
+                self._keep.append(nws)
+                g._add(g.fwd, 'ce_count_valid', lib.addk_ce_count, self.target.data_ptr(), N * H * W, None, ignore_index, ncls,
+                       nvalid.data_ptr(), nws.data_ptr(), rd=[self.target], wr=[nvalid, nws])
         self.dlogits = []
         for o in outs:
             if o.head == 'ce':
                 o.binding = dict(target=self.target, class_w=cwp, ignore_index=ignore_index, wsum=self.wsum, scale=1.0 / nex, loss=self.loss)
                 if self.ohem is not None:
                     o.binding['ohem'] = self.ohem
+                if self.distill is not None and o is not outs[-1]:
+                    o.binding['distill'] = self.distill + (outs[-1],)
+                    o.binding['nvalid'] = nvalid
                 self.dlogits.append(None)
                 continue
             d = torch.empty_like(o.y)
@@ -271,6 +315,15 @@ class TrainStep:
             valid, kept = (int(v) for v in st['counts'].tolist())
             res.append((float(st['tau'].item()), kept, valid))
         return res
+
+    def distill_stats(self):
+        """Per student exit (every exit but the last, in order) the distillation term `kd` of the last step, as it entered the loss.
+        Synchronises the device; not part of the step."""
+        if self.distill is None:
+            raise ValueError('this step was built without distill')
+        if self.dev.type == 'cuda':
+            torch.cuda.synchronize()
+        return [float(o.binding['distill_state']['kd'].item()) for o in self.outs[:-1]]
 
     def grads(self):
         return {p: self.g.pgrad.get(p) for p in self.params}

@@ -557,6 +557,38 @@ typedef struct {
 } addk_ce_upsample_ohem_args;
 int addk_ce_upsample_ohem_fwd_bwd(const addk_ce_upsample_ohem_args* a, void* stream);
 
+/* Self-distillation from the final exit for the fused loss head ("Be Your Own Teacher"): a student exit's loss head gets a second term,
+ * the KL divergence of its softened prediction from the last exit's.  Parameters: alpha > 0 and temperature T > 0, both finite.
+ *   teacher   the low-resolution NHWC logits of the LAST exit, on the grid of ce.logits ([N,H,W,C], its own pixel stride ld_teacher);
+ *             read-only and detached: the term sends no gradient into the teacher.  The last exit itself keeps the plain head.
+ * For every full-resolution pixel z_s and z_t are the bilinear samples of the student's and the teacher's low-resolution logits with the
+ * same src_index values and the same expression lh0*(lw0*a + lw1*b) + lh1*(lw0*c + lw1*d);
+ *   valid = target != ignore_index and 0 <= target < C                       (the predicate of the plain head)
+ *   q_s = softmax(z_s / T), q_t = softmax(z_t / T), each with its own maximum subtracted (1/T is rounded to fp32 once, on the host)
+ *   KL  = sum_c q_t[c] * (log q_t[c] - log q_s[c])
+ * With n the number of valid pixels of the batch (the device word nvalid: addk_ce_count with class_w == NULL) and s = ce.scale:
+ *   kd           = s * alpha * T^2 * (1/n) * sum_valid KL
+ *   loss_out[0] += s * CE (definition of addk_ce_upsample_fwd_bwd, or of the OHEM head when pix_loss / tau are set)  +  kd
+ *   kd_out[0]    = kd                written, not accumulated: a replayed graph leaves the last step's value
+ *   g          (+)= the CE gradient of that head + the bilinear transpose of s * alpha * T * (q_s - q_t) / n over valid pixels
+ * The term is not weighted by class_w and mining never filters it (under DDP every rank uses its own n, as the CE term does).  A pixel that
+ * is not valid, and n == 0, contribute exactly 0 to kd and to the gradient (a select, not a factor 0); kd_out is finite whenever the
+ * logits are.  Deterministic: the KL partials of the workgroups are added in a fixed order, no float atomics.
+ * ws holds addk_ce_upsample_kd_ws_floats() floats.  Supported exactly where addk_ce_upsample_supported() is 1.  Returns ADDK_ERR_INVALID
+ * and launches nothing for a null teacher, nvalid, kd_out or any pointer the plain head refuses, teacher == ce.logits, ld_teacher < C,
+ * a non-finite or non-positive alpha or temperature, and exactly one of pix_loss / tau set. */
+typedef struct {
+  addk_ce_upsample_args ce;
+  const float* pix_loss; const float* tau;      /* both NULL: no mining; both set: the OHEM head's kept set */
+  const float* teacher; int32_t ld_teacher;     /* NHWC [N,H,W,C] on the grid of ce.logits */
+  float alpha, temperature;
+  const float* nvalid;                          /* device scalar: addk_ce_count with class_w == NULL */
+  float* kd_out;                                /* device scalar, written */
+} addk_ce_upsample_kd_args;
+int addk_ce_upsample_kd_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+int64_t addk_ce_upsample_kd_ws_floats(int32_t N, int32_t H, int32_t W);
+int addk_ce_upsample_kd_fwd_bwd(const addk_ce_upsample_kd_args* a, void* stream);
+
 /* Scoring head of a validation pass (train.py:250-322, eval.py:165-193): what the evaluator, the criterion and the entropy
  * meter need of one exit, in ONE pass over the high-resolution pixel grid, straight from the LOW-resolution NHWC logits
  * [N,H,W,C] (bilinear, align_corners=False, the arithmetic of addk_resize_fwd bit for bit) — the [N,C,OH,OW] tensor is never
