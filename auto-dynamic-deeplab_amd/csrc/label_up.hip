@@ -1,0 +1,231 @@
+// The inference heads on the decoder's low-resolution logits: the label map of one exit (label_up_kernel), of several views
+// (label_views_kernel), and the early-exit gate with and without the label map (gate_up_kernel).
+#include "up.h"
+
+namespace {
+
+// ---- fused logits up-sampling + label map (decoder.py:28 + eval.py:218-221) ------------------------------------------------------
+// What inference keeps of an exit: the arg-max of the up-sampled logits, one byte per high-resolution pixel.  The walk is scu_walk
+// (same tile, same interpolation), then the strict `>` arg-max sweep of score_up_kernel (a tie keeps the lowest channel) and one
+// byte store — the class index, or lut[class] (train id -> Cityscapes labelId).  No exp, no LDS, no workspace; a wave row stores 64
+// consecutive bytes.  label_px is also the store of the gate launch that leaves the map (gate_up_kernel<.., LABELS = true>).
+struct LabelUpK : UpSrc { const uint8_t* lut; uint8_t* labels; };
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) label_up_kernel(const LabelUpK p) {
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
+    float mx = -INFINITY; int am = 0;
+#pragma unroll
+    for (int c = 0; c < CC; ++c)
+      if (z[c] > mx) { mx = z[c]; am = c; }                      // strict: a tie keeps the lowest channel
+    label_px(p.lut, p.labels, pix, am);
+  });
+}
+
+// ---- fused multi-view label map: up-sample, softmax, weighted sum over views, arg-max (multi-scale + flip inference) -----------------
+// What a multi-scale submission keeps: the arg-max of the weighted mean of the class probabilities of up to 8 views of one image —
+// low-resolution NHWC maps of different sizes, some of them horizontally mirrored — one byte per high-resolution pixel.  A wave owns
+// 64 consecutive output columns and LVU_R rows; a thread owns one column X.  The view loop is outermost (run-time count, descriptors
+// from the argument block: wave-uniform).  Within a view the thread samples column Xv = mirror ? OW-1-X : X with the walk of scu_walk:
+// the two W-interpolated rows t0 / t1 stay in registers and are reloaded only when the wave-uniform row pair changes, z = lh0*t0 +
+// lh1*t1 carries the bits addk_resize_fwd writes at (Y, Xv).  Then max, exp sweep, acc[r][c] += (weight / Σe) * e[c]; acc[LVU_R][CC]
+// lives in registers (the row loop is fully unrolled: nothing is indexed at run time).  After the last view: the strict `>` arg-max of
+// acc and label_px.  No LDS, no atomics, no workspace; the maps (a few MB) stay in L2, HBM sees the one byte per pixel.
+constexpr int LVU_W = 64, LVU_WAVES = 4, LVU_R = 4;      // tile: 64 columns x (4 waves x 4 rows)
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) label_views_kernel(const addk_label_views_args p) {
+  const int lane = threadIdx.x & (LVU_W - 1), wv = threadIdx.x / LVU_W;
+  const int X = blockIdx.x * LVU_W + lane, n = blockIdx.z;
+  if (X >= p.OW) return;
+  const int ybeg = (blockIdx.y * LVU_WAVES + wv) * LVU_R;
+  float acc[LVU_R][CC];
+#pragma unroll
+  for (int r = 0; r < LVU_R; ++r)
+#pragma unroll
+    for (int c = 0; c < CC; ++c) acc[r][c] = 0.f;
+  for (int v = 0; v < p.nview; ++v) {
+    const float* x = p.view[v].logits;
+    const int ld = p.view[v].ld, H = p.view[v].H, W = p.view[v].W;
+    const long img = (long)(p.view[v].n0 + n) * H;
+    const float wt = p.view[v].weight;
+    const float sh = (float)H / (float)p.OH, sw = (float)W / (float)p.OW;
+    int w0, w1; float lw0, lw1;
+    src_index(p.view[v].mirror ? p.OW - 1 - X : X, sw, W, w0, w1, lw0, lw1);
+    float t0[CC], t1[CC];
+    int ph0 = -1, ph1 = -1;
+#pragma unroll
+    for (int r = 0; r < LVU_R; ++r) {
+      const int Y = ybeg + r;
+      if (Y < p.OH) {                                              // wave-uniform
+        int h0, h1; float lh0, lh1;
+        src_index(Y, sh, H, h0, h1, lh0, lh1);
+        if (h0 != ph0 || h1 != ph1) {                              // wave-uniform
+          const float* r0 = x + ((img + h0) * W) * ld;
+          const float* r1 = x + ((img + h1) * W) * ld;
+          float a[cpad(CC)], b[cpad(CC)];
+          load_px<CC>(r0 + (long)w0 * ld, a, VEC); load_px<CC>(r0 + (long)w1 * ld, b, VEC);
+#pragma unroll
+          for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
+          load_px<CC>(r1 + (long)w0 * ld, a, VEC); load_px<CC>(r1 + (long)w1 * ld, b, VEC);
+#pragma unroll
+          for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
+          ph0 = h0; ph1 = h1;
+        }
+        float e[CC];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < CC; ++c) { e[c] = lh0 * t0[c] + lh1 * t1[c]; mx = fmaxf(mx, e[c]); }
+        float se = 0.f;
+#pragma unroll
+        for (int c = 0; c < CC; ++c) { e[c] = __expf(e[c] - mx); se += e[c]; }
+        const float s = wt / se;
+#pragma unroll
+        for (int c = 0; c < CC; ++c) acc[r][c] += s * e[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < LVU_R; ++r) {
+    const int Y = ybeg + r;
+    if (Y < p.OH) {
+      float mx = -INFINITY; int am = 0;
+#pragma unroll
+      for (int c = 0; c < CC; ++c)
+        if (acc[r][c] > mx) { mx = acc[r][c]; am = c; }            // strict: a tie keeps the lowest channel
+      label_px(p.lut256, p.labels, ((long)n * p.OH + Y) * p.OW + X, am);
+    }
+  }
+}
+
+dim3 lvu_grid(int N, int OH, int OW) { return dim3(cdiv(OW, LVU_W), cdiv(OH, LVU_WAVES * LVU_R), N); }
+bool lvu_ok(int nview, int N, int OH, int OW, int C) {
+  if (nview < 1 || nview > ADDK_MAX_VIEWS || C != 19 || N <= 0 || OH <= 0 || OW <= 0) return false;
+  const dim3 g = lvu_grid(N, OH, OW);
+  return N <= 65535 && g.y <= 65535 && (long)(int)g.z * (int)g.y * (int)g.x < (1L << 30);
+}
+
+// ---- fused logits up-sampling + early-exit gate (decoder.py:28 + operations.py:161-180) -----------------------------------
+// The two gates of dynamic inference that need no trained EDM: the normalised Shannon entropy of the up-sampled prediction and the
+// share of pixels whose top softmax probability passes a threshold.  The walk is scu_walk (same tile, same interpolation
+// z = lh0*t0 + lh1*t1), then one max sweep and the exp sweep; no target, histogram, loss or map.  Per pixel: se = Σe, sx = Σe·d with
+// d = z - max, entropy term log se - sx/se, top probability pmax = 1/se (the largest e is exp(0) = 1), counted when pmax > *max_thr.
+// A workgroup leaves one fp32 entropy partial and one count, write-through; the workgroup that arrives LAST (csrc/bnfin.h ticket, as
+// csrc/edm.hip) adds each image's partials in a FIXED order (fp64; the counts are integers), writes (entropy, share) to `out` and to
+// the pinned host words the gate reads, and puts the ticket back to zero: one launch, bit-reproducible, graph-replayable, nothing spins.
+struct GateUpK : UpSrc {
+  const float* thr;
+  float* out; float* out_host;
+  unsigned* counter; float* part; unsigned* cnt;          // ws: [ticket, 16 bytes][nblk floats][nblk counts], image-major
+  int nblk_img;
+  double npix, ent_div;                                    // OH*OW and log(C) * OH*OW
+};
+
+// LABELS: the launch also leaves the label map of label_up_kernel, speculatively, for every image (one byte per pixel): the max sweep
+// becomes the strict `>` arg-max sweep, which leaves the max that fmaxf leaves, so `out` / `out_host` carry the bits of the plain gate
+struct GateLabelUpK : GateUpK { const uint8_t* lut; uint8_t* labels; };
+template <bool LABELS> struct GateUpArg { typedef GateUpK type; };
+template <> struct GateUpArg<true> { typedef GateLabelUpK type; };
+
+template <int CC, bool VEC, bool LABELS = false>
+__global__ void __launch_bounds__(256) gate_up_kernel(const typename GateUpArg<LABELS>::type p) {
+  const float thr = *(const gfloat*)p.thr;
+  float esum = 0.f; unsigned hit[1] = {0u};
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
+    float mx = -INFINITY;
+    if constexpr (LABELS) {
+      int am = 0;
+#pragma unroll
+      for (int c = 0; c < CC; ++c)
+        if (z[c] > mx) { mx = z[c]; am = c; }                    // strict: a tie keeps the lowest channel
+      label_px(p.lut, p.labels, pix, am);
+    } else {
+#pragma unroll
+      for (int c = 0; c < CC; ++c) mx = fmaxf(mx, z[c]);
+    }
+    float se, sx;
+    exp_sweep<CC>(z, mx, se, sx);
+    esum += logf(se) - sx / se;
+    hit[0] += (1.f / se > thr) ? 1u : 0u;
+  });
+  up_finish<1>(esum, hit, 1, p.counter, p.part, p.cnt, p.N, p.nblk_img, p.out_host != nullptr, [&](int img, double es, auto&& count) {
+    const float ent = (float)(es / p.ent_div), share = (float)((double)count(0) / p.npix);
+    ((gfloat*)p.out)[2 * img] = ent; ((gfloat*)p.out)[2 * img + 1] = share;
+    if (p.out_host) { p.out_host[2 * img] = ent; p.out_host[2 * img + 1] = share; }
+  });
+}
+
+// the gate launch's arguments behind the UpSrc prefix (both of its forms): outputs, workspace layout, normalisation
+void gate_up_fill(GateUpK& k, const addk_gate_upsample_args* a) {
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.thr = a->max_thr; k.out = a->out; k.out_host = a->out_host;
+  up_tail_fill(k, a->ws, a->N, a->OH, a->OW);
+}
+
+}  // namespace
+
+extern "C" int addk_gate_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return scu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_gate_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW) {
+  if (N <= 0 || OH <= 0 || OW <= 0) return 0;
+  return up_ws_bytes(N, OH, OW, 1);
+}
+extern "C" int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->max_thr && a->out && a->ws, "gate_upsample: null pointer");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(a->ld >= a->C, "gate_upsample: short stride");
+  GateUpK k;
+  gate_up_fill(k, a);
+  hipStream_t st = (hipStream_t)stream;
+  launch_vec(px_vec_ok<19>(a->logits, a->ld), gate_up_kernel<19, true>, gate_up_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  return addk_check_launch("gate_upsample");
+}
+extern "C" int addk_gate_label_upsample(const addk_gate_label_upsample_args* b, void* stream) {
+  ADDK_REQUIRE(b, "gate_label_upsample: null pointer");
+  const addk_gate_upsample_args* a = &b->gate;
+  ADDK_REQUIRE(a->logits && a->max_thr && a->out && a->ws && b->labels, "gate_label_upsample: null pointer");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_label_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(a->ld >= a->C, "gate_label_upsample: short stride");
+  GateLabelUpK k;
+  gate_up_fill(k, a);
+  k.lut = b->lut256; k.labels = b->labels;
+  hipStream_t st = (hipStream_t)stream;
+  launch_vec(px_vec_ok<19>(a->logits, a->ld), gate_up_kernel<19, true, true>, gate_up_kernel<19, false, true>, scu_grid(a->N, a->OH, a->OW), st, k);
+  return addk_check_launch("gate_label_upsample");
+}
+
+extern "C" int addk_label_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return scu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int addk_label_upsample(const addk_label_upsample_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->labels, "label_upsample: null pointer");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "label_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(a->ld >= a->C, "label_upsample: short stride");
+  LabelUpK k;
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.lut = a->lut256; k.labels = a->labels;
+  hipStream_t st = (hipStream_t)stream;
+  launch_vec(px_vec_ok<19>(a->logits, a->ld), label_up_kernel<19, true>, label_up_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  return addk_check_launch("label_upsample");
+}
+
+extern "C" int addk_label_views_upsample_supported(int32_t nview, int32_t N, int32_t OH, int32_t OW, int32_t C) {
+  return lvu_ok(nview, N, OH, OW, C) ? 1 : 0;
+}
+extern "C" int addk_label_views_upsample(const addk_label_views_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->labels, "label_views_upsample: null pointer");
+  ADDK_REQUIRE(lvu_ok(a->nview, a->N, a->OH, a->OW, a->C), "label_views_upsample: unsupported shape (1..%d views, 19 classes)", ADDK_MAX_VIEWS);
+  bool vec = true;
+  for (int v = 0; v < a->nview; ++v) {
+    const addk_view& w = a->view[v];
+    ADDK_REQUIRE(w.logits, "label_views_upsample: null pointer (view %d)", v);
+    ADDK_REQUIRE(w.H > 0 && w.W > 0 && w.n0 >= 0 && w.ld >= a->C, "label_views_upsample: bad size, image offset or stride (view %d)", v);
+    ADDK_REQUIRE(w.weight > 0.f && isfinite(w.weight), "label_views_upsample: a weight must be positive and finite (view %d)", v);
+    vec = vec && px_vec_ok<19>(w.logits, w.ld);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // 16-byte pixel loads only where every view allows them
+  launch_vec(vec, label_views_kernel<19, true>, label_views_kernel<19, false>, lvu_grid(a->N, a->OH, a->OW), st, *a);
+  return addk_check_launch("label_views_upsample");
+}

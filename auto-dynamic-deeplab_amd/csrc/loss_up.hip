@@ -1,0 +1,529 @@
+// The training head on the decoder's low-resolution logits: fused up-sampling + cross-entropy, forward and backward (ce_up_kernel, with
+// its mining and distillation forms), and the hard example mining that feeds it (ohem_*_kernel, addk_ohem_select).
+#include <string>
+#include "up.h"
+
+namespace {
+
+// ---- fused logits up-sampling + cross-entropy, forward and backward (decoder.py:28 + train.py:70,231) -------------------
+// The training step never needs the full-resolution logits: loss and gradient are computed straight from the low-resolution
+// NHWC logits.  F.interpolate(mode='bilinear', align_corners=False) index arithmetic as in resize.hip (ATen's
+// area_pixel_compute_source_index in fp32).  A high-resolution pixel (Y, X) reads the low-resolution rows h0(Y), h0+1 and
+// columns w0(X), w0+1; it is OWNED by (h0, w0): thread (r, xl) of a block walks the pixels of row Y = first_row(h) + r whose
+// w0 is its column, computes each pixel's softmax ONCE and accumulates the pixel's gradient into A0 (column w0) and A1
+// (column w0 + 1).  A1 moves to the right neighbour lane, the 16 rows of the band are reduced through LDS in a fixed order
+// with the row weights, and the part that belongs to row h + 1 is carried in registers to the next band: a gather with no
+// atomics and no second pass over the 1.3 GB/exit of full-resolution logits and gradients the three-kernel form wrote and re-read.
+// A block owns 31 output columns x HB output rows; it re-walks one band above (for the carry) and one column to the left
+// (for A1): (HB+1)/HB * 32/31 redundant softmax work, counted once in the loss (own bands, xl >= 1).
+//
+struct CeUpK : UpSrc {
+  const int64_t* target; const float* cw; int ignore;
+  const float* wsum; float scale;
+  float* g; int ldg; int accumulate;
+  float* ws; int HB;
+};
+
+__host__ __device__ __forceinline__ int ce_idx0(int dst, float scale, int in) {
+  float s = scale * ((float)dst + 0.5f) - 0.5f;
+  if (s < 0.f) s = 0.f;
+  int i0 = (int)s;
+  return i0 > in - 1 ? in - 1 : i0;
+}
+// smallest output index whose i0 is >= i (i0 is monotone in the output index)
+__host__ __device__ __forceinline__ int ce_first_out(int i, float scale, int in, int out) {
+  if (i <= 0) return 0;
+  int g = (int)(((float)i + 0.5f) / scale - 0.5f);
+  if (g < 0) g = 0;
+  if (g > out) g = out;
+  while (g > 0 && ce_idx0(g - 1, scale, in) >= i) --g;
+  while (g < out && ce_idx0(g, scale, in) < i) ++g;
+  return g;
+}
+
+constexpr int CEU_R = 8, CEU_X = 32;       // rows per pass / lanes per row (31 output columns + the left neighbour)
+constexpr int CEU_MAXBAND = 16;            // high-resolution rows per low-resolution row the kernel takes (host check)
+
+// OHEM (online hard example mining, addk_ce_upsample_ohem_fwd_bwd): the launch also gets the per-pixel loss map and the device word tau of
+// addk_ohem_select; a pixel whose stored loss is below tau counts as not valid (weight 0), and p.wsum points at the kept weight sum.  The
+// keep decision is READ, never recomputed: invalid pixels carry -1 in the map and tau >= 0.  OHEM = false is the plain kernel, token for token.
+struct CeUpOhemK : CeUpK { const float* lmap; const float* tau; };
+// KD (self-distillation from the last exit, addk_ce_upsample_kd_fwd_bwd): the launch also gets the teacher's low-resolution logits on the
+// student's grid.  A thread keeps the teacher's four corner pixels beside the student's, samples z_t with the student's indices and
+// expression, and per pixel adds one softmax pair at temperature T: e_s = exp(z_s/T - max), e_t likewise (1/T is rounded once on the
+// host: z * rT), KL = (1/Σe_t) Σ e_t*(d_t - d_s) + log Σe_s - log Σe_t with d = z/T - max, and kg * (e_s/Σe_s - e_t/Σe_t) joins gz before the
+// gather, kg = scale*alpha*T / n.  The plain predicate decides (a select, not a factor): mining never filters the term and class_w does not
+// weigh it.  The KL partial leaves beside lsum (ws2, same ownership rule).  KD = false is the parent's kernel, instruction for instruction.
+// TVEC: the teacher's loader, px_vec_ok on ITS base and stride, chosen by the host as for scu_walk — a second run-time loader switch
+// would put the teacher's padding channels into scratch as the student's are (40 -> 72 bytes per lane).
+struct CeUpKdK : CeUpOhemK { const float* teacher; int ldt; float rT, kscale; const float* nvalid; float* ws2; };
+template <bool OHEM, bool KD = false> struct CeUpArg { typedef CeUpK type; };
+template <> struct CeUpArg<true, false> { typedef CeUpOhemK type; };
+template <bool OHEM> struct CeUpArg<OHEM, true> { typedef CeUpKdK type; };
+
+template <int CC, bool OHEM = false, bool KD = false, bool TVEC = false>
+__global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM, KD>::type p) {
+  constexpr int CP = cpad(CC);
+  constexpr int NOUT = ((CEU_X - 1) * CC + 255) / 256;
+  __shared__ float S0[CEU_R * CEU_X * CC], S1[CEU_R * CEU_X * CC];
+  __shared__ float shs[4];
+  const int t = threadIdx.x, xl = t & (CEU_X - 1), r = t / CEU_X;
+  const int tx0 = blockIdx.x * (CEU_X - 1), hb = blockIdx.y * p.HB, n = blockIdx.z;
+  const int x = tx0 - 1 + xl;                                   // the low-resolution column this thread owns as w0
+  const float sh = (float)p.H / (float)p.OH, sw = (float)p.W / (float)p.OW;
+  const float inv = p.scale / *(const gfloat*)p.wsum;
+  int xlo = 0, xhi = 0;
+  if (x >= 0 && x < p.W) { xlo = ce_first_out(x, sw, p.W, p.OW); xhi = (x + 1 < p.W) ? ce_first_out(x + 1, sw, p.W, p.OW) : p.OW; }
+  const bool xlast = x == p.W - 1;
+  const int x1 = x + (x < p.W - 1 ? 1 : 0);
+  const bool vec = (p.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0) && p.ld >= CP;      // px_vec_ok
+  const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
+  const gfloat* cw = (const gfloat*)p.cw;
+  float tau = 0.f;
+  if constexpr (OHEM) tau = *(const gfloat*)p.tau;
+  [[maybe_unused]] float kg = 0.f, ksum = 0.f;
+  if constexpr (KD) {
+    kg = p.kscale / *(const gfloat*)p.nvalid;                  // n == 0: no pixel is valid and the select below never takes it
+  }
+  float lsum = 0.f;
+  float carry[NOUT];
+#pragma unroll
+  for (int k = 0; k < NOUT; ++k) carry[k] = 0.f;
+  const int hstart = hb > 0 ? hb - 1 : 0;
+  const int hend = hb + p.HB < p.H ? hb + p.HB : p.H;
+  for (int h = hstart; h < hend; ++h) {
+    const int ylo = ce_first_out(h, sh, p.H, p.OH);
+    const int yhi = (h + 1 < p.H) ? ce_first_out(h + 1, sh, p.H, p.OH) : p.OH;
+    const bool own = h >= hb;
+    float b0[NOUT], b1[NOUT];
+#pragma unroll
+    for (int k = 0; k < NOUT; ++k) { b0[k] = 0.f; b1[k] = 0.f; }
+    for (int yb = ylo; yb < yhi; yb += CEU_R) {                 // the band in passes of CEU_R rows (one pass at the x8 of config 2)
+      const int Y = yb + r;
+      float A0[CC], A1[CC];
+#pragma unroll
+      for (int c = 0; c < CC; ++c) { A0[c] = 0.f; A1[c] = 0.f; }
+      float lh0 = 0.f, lh1 = 0.f;
+      if (Y < yhi && xhi > xlo) {
+        int h0, h1;
+        src_index(Y, sh, p.H, h0, h1, lh0, lh1);
+        const float* r0 = p.x + ((long)(n * p.H + h0) * p.W) * p.ld;
+        const float* r1 = p.x + ((long)(n * p.H + h1) * p.W) * p.ld;
+        float v00[CP], v01[CP], v10[CP], v11[CP];
+        load_px<CC>(r0 + (long)x * p.ld, v00, vec); load_px<CC>(r0 + (long)x1 * p.ld, v01, vec);
+        load_px<CC>(r1 + (long)x * p.ld, v10, vec); load_px<CC>(r1 + (long)x1 * p.ld, v11, vec);
+        [[maybe_unused]] float u00[KD ? CP : 1], u01[KD ? CP : 1], u10[KD ? CP : 1], u11[KD ? CP : 1];      // the teacher's corners
+        if constexpr (KD) {
+          const float* q0 = p.teacher + ((long)(n * p.H + h0) * p.W) * p.ldt;
+          const float* q1 = p.teacher + ((long)(n * p.H + h1) * p.W) * p.ldt;
+          load_px<CC>(q0 + (long)x * p.ldt, u00, TVEC); load_px<CC>(q0 + (long)x1 * p.ldt, u01, TVEC);
+          load_px<CC>(q1 + (long)x * p.ldt, u10, TVEC); load_px<CC>(q1 + (long)x1 * p.ldt, u11, TVEC);
+        }
+        const int64_t __attribute__((address_space(1)))* tp = tgt + ((long)n * p.OH + Y) * p.OW;
+        for (int X = xlo; X < xhi; ++X) {
+          int w0, w1; float lw0, lw1;
+          src_index(X, sw, p.W, w0, w1, lw0, lw1);
+          const long tg = tp[X];
+          bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+          [[maybe_unused]] const bool pvalid = valid;            // the plain predicate: what the distillation term goes by
+          if constexpr (OHEM) valid = valid && ((const gfloat*)p.lmap)[((long)n * p.OH + Y) * p.OW + X] >= tau;
+          const float w = valid ? (cw ? cw[tg] : 1.f) : 0.f;
+          float z[CC];
+          float mx = -INFINITY, zt = 0.f;
+#pragma unroll
+          for (int c = 0; c < CC; ++c) {
+            z[c] = lh0 * (lw0 * v00[c] + lw1 * v01[c]) + lh1 * (lw0 * v10[c] + lw1 * v11[c]);
+            mx = fmaxf(mx, z[c]);
+            if (c == tg) zt = z[c];
+          }
+          [[maybe_unused]] float D[KD ? CC : 1];                 // the distillation term's part of gz
+          if constexpr (KD) {
+            float et[CC];
+            float mt = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+              et[c] = (lh0 * (lw0 * u00[c] + lw1 * u01[c]) + lh1 * (lw0 * u10[c] + lw1 * u11[c])) * p.rT;
+              mt = fmaxf(mt, et[c]);
+            }
+            const float ms = mx * p.rT;                           // rT > 0: the largest z * rT is (largest z) * rT
+            float ses = 0.f, set = 0.f, kl = 0.f;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) {
+              const float ds = z[c] * p.rT - ms, dt = et[c] - mt;
+              const float es = __expf(ds), e = __expf(dt);
+              ses += es; set += e;
+              kl = fmaf(e, dt - ds, kl);
+              D[c] = es; et[c] = e;
+            }
+            if (own && xl >= 1 && pvalid) ksum += kl / set + (logf(ses) - logf(set));
+            const float ks = kg / ses, kt_ = kg / set;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) D[c] = pvalid ? D[c] * ks - et[c] * kt_ : 0.f;
+          }
+          float se = 0.f;
+#pragma unroll
+          for (int c = 0; c < CC; ++c) { z[c] = __expf(z[c] - mx); se += z[c]; }
+          if (own && xl >= 1 && valid) lsum += w * (logf(se) + mx - zt);
+          const float k = w * inv / se, kt = w * inv;
+          const float a0 = lw0 + (xlast ? lw1 : 0.f), a1 = xlast ? 0.f : lw1;
+#pragma unroll
+          for (int c = 0; c < CC; ++c) {
+            float gz = z[c] * k - ((valid && c == tg) ? kt : 0.f);
+            if constexpr (KD) gz += D[c];
+            A0[c] = fmaf(a0, gz, A0[c]); A1[c] = fmaf(a1, gz, A1[c]);
+          }
+        }
+      }
+      // column w0 + 1 belongs to the right neighbour lane; then the rows of the pass go through LDS
+#pragma unroll
+      for (int c = 0; c < CC; ++c) {
+        float fromleft = __shfl_up(A1[c], 1, CEU_X);
+        if (xl == 0) fromleft = 0.f;
+        const float R = A0[c] + fromleft;
+        S0[(r * CEU_X + xl) * CC + c] = lh0 * R;
+        S1[(r * CEU_X + xl) * CC + c] = lh1 * R;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < NOUT; ++k) {
+        const int j = t + 256 * k;
+        if (j < (CEU_X - 1) * CC) {
+          const int off = CC + j;                               // (ox = 1 + j / CC, c = j % CC) -> ox * CC + c
+#pragma unroll
+          for (int rr = 0; rr < CEU_R; ++rr) { b0[k] += S0[rr * CEU_X * CC + off]; b1[k] += S1[rr * CEU_X * CC + off]; }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < NOUT; ++k) {
+      const int j = t + 256 * k;
+      if (j < (CEU_X - 1) * CC) {
+        const int ox = 1 + j / CC, c = j - (ox - 1) * CC;
+        if (h == p.H - 1) { b0[k] += b1[k]; b1[k] = 0.f; }
+        const float o = carry[k] + b0[k];
+        carry[k] = b1[k];
+        const int col = tx0 - 1 + ox;
+        if (own && col < p.W) {
+          gfloat* gp = (gfloat*)p.g + ((long)(n * p.H + h) * p.W + col) * p.ldg + c;
+          *gp = p.accumulate ? *gp + o : o;
+        }
+      }
+    }
+  }
+  lsum = block_sum(lsum, shs);
+  if (t == 0) ((gfloat*)p.ws)[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = lsum;
+  if constexpr (KD) {
+    ksum = block_sum(ksum, shs);
+    if (t == 0) ((gfloat*)p.ws2)[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ksum;
+  }
+}
+
+// second stage of the distillation term: the KL partials in the order of sum_partials_kernel; kd = coef * Σ / n, exactly 0 when no pixel
+// is valid.  kd_out is written (a replayed graph leaves the last step's value), the loss accumulates it.
+__global__ void __launch_bounds__(256) kd_sum_kernel(const float* ws, int n, float coef, const float* nvalid, float* kd_out, float* loss_out) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += ws[i];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) {
+    const float nv = *nvalid;
+    const float kd = nv > 0.f ? s * coef / nv : 0.f;
+    *kd_out = kd;
+    *loss_out += kd;
+  }
+}
+
+int ceu_hb(int H) { return H >= 64 ? 4 : (H >= 16 ? 2 : 1); }
+bool ceu_ok(int N, int H, int W, int OH, int OW, int C) {
+  if (C != 19 || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return false;
+  const float sh = (float)H / (float)OH;
+  for (int h = 0; h < H; ++h) {
+    const int lo = ce_first_out(h, sh, H, OH), hi = h + 1 < H ? ce_first_out(h + 1, sh, H, OH) : OH;
+    if (hi - lo > CEU_MAXBAND) return false;
+  }
+  return true;
+}
+
+// ---- online hard example mining for the fused loss head (addk_ohem_select) -------------------------------------------------------------
+// Per exit: the per-pixel loss l = max(0, logsumexp(z) - z[target]) of every valid full-resolution pixel, the EXACT order statistic
+// l_(min(K, n)) of the batch and tau = min(-log theta, l_(k)), all on the stream.  l >= 0, so its fp32 bit pattern orders like l: a
+// three-pass most-significant-first radix select on the bits (11 + 11 + 10) finds the pattern of the k-th largest value.
+//   ohem_loss_kernel     the walk of scu_walk (same tile, same interpolation); writes l (or -1: not valid) to the [N,OH,OW] map and bins
+//                        bits 31..21 into a 2048-bin LDS histogram (a thread merges the run of equal bins of its column first), flushed
+//                        with 32-bit integer atomics: order-independent, exact.
+//   ohem_scan_kernel     ONE workgroup between the passes: walks a histogram from the top bin down to the bin that holds rank k, appends
+//                        its index to the selected prefix and leaves the rank within that bin.  A launch of its own, not a scan at the
+//                        top of every workgroup of the next pass: the refinement kernels stay pure streaming loops (no 8 KB histogram
+//                        re-read and no block scan in ~1000 workgroups), at the price of three 1-workgroup launches per exit.
+//   ohem_refine_kernel   streams the STORED map: pixels whose leading bits equal the prefix are binned on the next 11 / 10 bits.
+//   ohem_keep_kernel     streams the stored map against tau: per workgroup the count of kept pixels and the sum of their weights;
+//   ohem_keep_sum_kernel one workgroup adds the partials in a fixed order (the float sum as sum_partials_kernel does).
+// Workspace (32-bit words): [0..2047] hist of pass 0, [2048..4095] pass 1, [4096..5119] pass 2, [5120] prefix, [5121] rank, then
+// OHEM_KEEP_BLOCKS float weight partials and as many kept counts.  The first 5122 words are cleared by the launch sequence itself.
+constexpr int OHEM_B0 = 2048, OHEM_B2 = 1024;
+constexpr int OHEM_SEL = 2 * OHEM_B0 + OHEM_B2, OHEM_PART = OHEM_SEL + 2;
+constexpr int OHEM_KEEP_BLOCKS = 1024;
+constexpr unsigned OHEM_NONE = 0xffffffffu;                       // prefix of an empty selection (n == 0): no bit pattern matches it
+
+__global__ void __launch_bounds__(256) ohem_clear_kernel(unsigned* ws) {
+  for (int i = threadIdx.x; i < OHEM_PART; i += 256) ((gu32*)ws)[i] = 0u;
+}
+
+struct OhemLossK : UpSrc { const int64_t* target; int ignore; float* lmap; unsigned* hist; };
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) ohem_loss_kernel(const OhemLossK p) {
+  __shared__ unsigned hist[OHEM_B0];
+  const int t = threadIdx.x;
+  for (int i = t; i < OHEM_B0; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)p.target;
+  int key = -1; unsigned run = 0;                                // pending run of equal bins of this column
+  scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
+    const long tg = tgt[pix];
+    const bool valid = tg != p.ignore && tg >= 0 && tg < CC;
+    float mx = -INFINITY, zt = 0.f;
+#pragma unroll
+    for (int c = 0; c < CC; ++c) {
+      mx = fmaxf(mx, z[c]);
+      if (c == tg) zt = z[c];
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < CC; ++c) se += __expf(z[c] - mx);
+    const float l = valid ? fmaxf(0.f, logf(se) + mx - zt) : -1.f;
+    ((gfloat*)p.lmap)[pix] = l;
+    const int k = valid ? (int)(__float_as_uint(l) >> 21) : -1;
+    run_count(hist, key, run, k);
+  });
+  run_flush(hist, key, run);
+  __syncthreads();
+  for (int i = t; i < OHEM_B0; i += 256) {
+    const unsigned v = hist[i];
+    if (v) atomicAdd(&p.hist[i], v);
+  }
+}
+
+// One workgroup.  hist: NBIN = 256 * per counters of the pass; sel = {prefix, rank}.  pass 0 takes rank = min(K, n) with n the histogram's
+// total (also written to counts[0]); the last pass turns the completed 32-bit pattern into tau = min(tau_theta, l_(k)).
+__global__ void __launch_bounds__(256) ohem_scan_kernel(const unsigned* hist, int per, int bits, int pass, unsigned* sel, unsigned long long kmin,
+                                                        float tau_theta, float* tau, long long* counts) {
+  __shared__ unsigned sc[256];
+  const int t = threadIdx.x, nbin = 256 * per;
+  const gu32* h = (const gu32*)hist;
+  // thread t owns the bins nbin-1 - t*per ... nbin - (t+1)*per, largest first
+  unsigned c = 0;
+  for (int j = 0; j < per; ++j) c += h[nbin - 1 - (t * per + j)];
+  sc[t] = c;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {                            // inclusive scan over the threads
+    const unsigned add = t >= d ? sc[t - d] : 0u;
+    __syncthreads();
+    sc[t] += add;
+    __syncthreads();
+  }
+  const unsigned total = sc[255], above = sc[t] - c;
+  unsigned prefix = 0u, k;
+  if (pass == 0) {
+    k = kmin < (unsigned long long)total ? (unsigned)kmin : total;
+    if (t == 0) ((__attribute__((address_space(1))) long long*)counts)[0] = (long long)total;
+  } else {
+    prefix = ((const gu32*)sel)[0]; k = ((const gu32*)sel)[1];
+  }
+  __syncthreads();                                               // every thread has read sel before one rewrites it
+  if (k == 0u || prefix == OHEM_NONE) {                          // nothing to select: n == 0
+    if (t == 0) {
+      ((gu32*)sel)[0] = OHEM_NONE; ((gu32*)sel)[1] = 0u;
+      if (tau) *(gfloat*)tau = tau_theta;
+    }
+    return;
+  }
+  if (above < k && k <= above + c) {                             // exactly one thread: 1 <= k <= total
+    unsigned a = above; int b = nbin - 1 - t * per;
+    for (int j = 0; j < per; ++j, --b) {
+      const unsigned v = h[b];
+      if (k <= a + v) break;
+      a += v;
+    }
+    const unsigned np = (prefix << bits) | (unsigned)b;
+    ((gu32*)sel)[0] = np; ((gu32*)sel)[1] = k - a;
+    if (tau) *(gfloat*)tau = fminf(tau_theta, __uint_as_float(np));
+  }
+}
+
+// pixels of the stored map whose bits >> PS equal the selected prefix are binned on (bits >> BS) & (NBIN - 1)
+template <int PS, int BS, int NBIN>
+__global__ void __launch_bounds__(256) ohem_refine_kernel(const float* lmap, long n, const unsigned* sel, unsigned* hist) {
+  __shared__ unsigned sh[NBIN];
+  const int t = threadIdx.x;
+  for (int i = t; i < NBIN; i += 256) sh[i] = 0u;
+  __syncthreads();
+  const unsigned prefix = ((const gu32*)sel)[0];
+  if (prefix == OHEM_NONE) return;                               // uniform over the grid
+  const gu32* m = (const gu32*)lmap;
+  for (long i = (long)blockIdx.x * 256 + t; i < n; i += (long)gridDim.x * 256) {
+    const unsigned b = m[i];
+    if ((b >> PS) == prefix) atomicAdd(&sh[(b >> BS) & (NBIN - 1)], 1u);
+  }
+  __syncthreads();
+  for (int i = t; i < NBIN; i += 256) {
+    const unsigned v = sh[i];
+    if (v) atomicAdd(&hist[i], v);
+  }
+}
+
+__global__ void __launch_bounds__(256) ohem_keep_kernel(const float* lmap, const int64_t* target, const float* cw, long n, const float* tau,
+                                                        float* wpart, unsigned* kpart) {
+  __shared__ float shs[4];
+  __shared__ unsigned shk[4];
+  const int t = threadIdx.x;
+  const float ta = *(const gfloat*)tau;
+  const gfloat* m = (const gfloat*)lmap;
+  const int64_t __attribute__((address_space(1)))* tgt = (const int64_t __attribute__((address_space(1)))*)target;
+  float s = 0.f; unsigned k = 0u;
+  for (long i = (long)blockIdx.x * 256 + t; i < n; i += (long)gridDim.x * 256) {
+    if (m[i] >= ta) {                                            // not valid: -1 < 0 <= tau
+      ++k;
+      s += cw ? ((const gfloat*)cw)[tgt[i]] : 1.f;
+    }
+  }
+  s = block_sum(s, shs);
+  for (int mk = 32; mk > 0; mk >>= 1) k += __shfl_xor(k, mk);
+  if ((t & 63) == 0) shk[t >> 6] = k;
+  __syncthreads();
+  if (t == 0) { ((gfloat*)wpart)[blockIdx.x] = s; ((gu32*)kpart)[blockIdx.x] = shk[0] + shk[1] + shk[2] + shk[3]; }
+}
+
+__global__ void __launch_bounds__(256) ohem_keep_sum_kernel(const float* wpart, const unsigned* kpart, int n, float* wsum, long long* counts) {
+  __shared__ float shs[4];
+  __shared__ unsigned long long shk[4];
+  const int t = threadIdx.x;
+  float s = 0.f; unsigned long long k = 0ull;
+  for (int i = t; i < n; i += 256) { s += ((const gfloat*)wpart)[i]; k += ((const gu32*)kpart)[i]; }
+  s = block_sum(s, shs);
+  for (int mk = 32; mk > 0; mk >>= 1) k += __shfl_xor(k, mk);
+  if ((t & 63) == 0) shk[t >> 6] = k;
+  __syncthreads();
+  if (t == 0) {
+    *(gfloat*)wsum = s;
+    ((__attribute__((address_space(1))) long long*)counts)[1] = (long long)(shk[0] + shk[1] + shk[2] + shk[3]);
+  }
+}
+
+bool ohem_ok(int N, int H, int W, int OH, int OW, int C) {
+  return scu_ok(N, H, W, OH, OW, C) && (long)N * OH * OW < (1L << 31);
+}
+int ohem_stream_blocks(long n) { long b = cdiv(n, 256 * 16); if (b < 1) b = 1; if (b > OHEM_KEEP_BLOCKS) b = OHEM_KEEP_BLOCKS; return (int)b; }
+
+// The training head's launches, all three entry points (`name`: the entry point's prefix in error texts and launch names): the stride and
+// shape checks, one fill of the argument struct (CeUpKdK extends CeUpOhemK extends CeUpK: a plainer form takes its base), the
+// instantiation by (mining: lmap / tau given, distillation: kd given, the teacher's loader), the loss partials' sum and, for a student,
+// the KL partials' sum.
+int ceu_launch(const char* name, const addk_ce_upsample_args* a, const float* lmap, const float* tau, const addk_ce_upsample_kd_args* kd,
+               hipStream_t st) {
+  ADDK_REQUIRE(a->ld >= a->C && a->ldg >= a->C && (!kd || kd->ld_teacher >= a->C), "%s: short stride", name);
+  ADDK_REQUIRE(ceu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "%s: unsupported shape (19 classes, at most %d output rows per input row)", name, CEU_MAXBAND);
+  CeUpKdK k{};
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.target = a->target; k.cw = a->class_w; k.ignore = a->ignore_index; k.wsum = a->wsum; k.scale = a->scale;
+  k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate; k.ws = a->ws; k.HB = ceu_hb(a->H);
+  k.lmap = lmap; k.tau = tau;
+  const dim3 grid(cdiv(a->W, CEU_X - 1), cdiv(a->H, k.HB), a->N);
+  const int nblk = (int)(grid.x * grid.y * grid.z);
+  if (kd) {
+    k.teacher = kd->teacher; k.ldt = kd->ld_teacher; k.nvalid = kd->nvalid; k.ws2 = a->ws + nblk;
+    k.rT = 1.f / kd->temperature;
+    k.kscale = a->scale * kd->alpha * kd->temperature;           // the gradient's factor before 1/n; the loss takes one more T
+    const bool tvec = px_vec_ok<19>(kd->teacher, kd->ld_teacher);
+    if (lmap) launch_vec(tvec, ce_up_kernel<19, true, true, true>, ce_up_kernel<19, true, true, false>, grid, st, k);
+    else launch_vec(tvec, ce_up_kernel<19, false, true, true>, ce_up_kernel<19, false, true, false>, grid, st, k);
+  } else if (lmap) {
+    hipLaunchKernelGGL((ce_up_kernel<19, true>), grid, dim3(256), 0, st, static_cast<const CeUpOhemK&>(k));
+  } else {
+    hipLaunchKernelGGL(ce_up_kernel<19>, grid, dim3(256), 0, st, static_cast<const CeUpK&>(k));
+  }
+  const std::string n(name);
+  int rc = addk_check_launch(name);
+  if (rc) return rc;
+  hipLaunchKernelGGL(sum_partials_kernel<>, dim3(1), dim3(256), 0, st, a->ws, nblk, a->scale, a->wsum, a->loss_out, 1);
+  rc = addk_check_launch((n + "_sum").c_str());
+  if (rc || !kd) return rc;
+  hipLaunchKernelGGL(kd_sum_kernel, dim3(1), dim3(256), 0, st, k.ws2, nblk, k.kscale * kd->temperature, kd->nvalid, kd->kd_out, a->loss_out);
+  return addk_check_launch((n + "_kl_sum").c_str());
+}
+
+}  // namespace
+
+extern "C" int addk_ce_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return ceu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_ce_upsample_ws_floats(int32_t N, int32_t H, int32_t W) {
+  return (int64_t)N * cdiv(H, ceu_hb(H)) * cdiv(W, CEU_X - 1);
+}
+extern "C" int addk_ce_upsample_fwd_bwd(const addk_ce_upsample_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->target && a->wsum && a->loss_out && a->g && a->ws, "ce_upsample: null pointer");
+  return ceu_launch("ce_upsample", a, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int addk_ce_upsample_ohem_fwd_bwd(const addk_ce_upsample_ohem_args* b, void* stream) {
+  ADDK_REQUIRE(b, "ce_upsample_ohem: null pointer");
+  const addk_ce_upsample_args* a = &b->ce;
+  ADDK_REQUIRE(a->logits && a->target && a->wsum && a->loss_out && a->g && a->ws && b->pix_loss && b->tau, "ce_upsample_ohem: null pointer");
+  return ceu_launch("ce_upsample_ohem", a, b->pix_loss, b->tau, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int addk_ce_upsample_kd_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return ceu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_ce_upsample_kd_ws_floats(int32_t N, int32_t H, int32_t W) {
+  return 2 * addk_ce_upsample_ws_floats(N, H, W);                // the loss partials, then the KL partials
+}
+extern "C" int addk_ce_upsample_kd_fwd_bwd(const addk_ce_upsample_kd_args* b, void* stream) {
+  ADDK_REQUIRE(b, "ce_upsample_kd: null pointer");
+  const addk_ce_upsample_args* a = &b->ce;
+  ADDK_REQUIRE(a->logits && a->target && a->wsum && a->loss_out && a->g && a->ws && b->teacher && b->nvalid && b->kd_out, "ce_upsample_kd: null pointer");
+  ADDK_REQUIRE((b->pix_loss == nullptr) == (b->tau == nullptr), "ce_upsample_kd: pix_loss and tau come together (both NULL: no mining)");
+  ADDK_REQUIRE(b->teacher != a->logits, "ce_upsample_kd: the teacher must be another exit's logits");
+  ADDK_REQUIRE(isfinite(b->alpha) && b->alpha > 0.f && isfinite(b->temperature) && b->temperature > 0.f,
+               "ce_upsample_kd: alpha and temperature must be positive and finite");
+  return ceu_launch("ce_upsample_kd", a, b->pix_loss, b->tau, b, (hipStream_t)stream);
+}
+
+extern "C" int addk_ohem_select_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
+  return ohem_ok(N, H, W, OH, OW, C) ? 1 : 0;
+}
+extern "C" int64_t addk_ohem_select_ws_bytes(int32_t N, int32_t OH, int32_t OW) {
+  if (N <= 0 || OH <= 0 || OW <= 0) return 0;
+  return 4 * (int64_t)(OHEM_PART + 2 * OHEM_KEEP_BLOCKS);
+}
+extern "C" int addk_ohem_select(const addk_ohem_select_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->target && a->pix_loss && a->tau && a->wsum_kept && a->counts && a->ws, "ohem_select: null pointer");
+  ADDK_REQUIRE(a->thresh > 0.f && a->thresh <= 1.f, "ohem_select: thresh must lie in (0, 1]");
+  ADDK_REQUIRE(a->min_kept_total >= 1, "ohem_select: min_kept_total must be at least 1");
+  ADDK_REQUIRE(a->ld >= a->C, "ohem_select: short stride");
+  ADDK_REQUIRE(ohem_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "ohem_select: unsupported shape (19 classes, fewer than 2^31 pixels)");
+  unsigned* w = (unsigned*)a->ws;
+  unsigned* sel = w + OHEM_SEL;
+  float* wpart = (float*)(w + OHEM_PART);
+  unsigned* kpart = w + OHEM_PART + OHEM_KEEP_BLOCKS;
+  const float tau_theta = a->thresh >= 1.f ? 0.f : (float)(-log((double)a->thresh));
+  const long npix = (long)a->N * a->OH * a->OW;
+  const int nb = ohem_stream_blocks(npix);
+  long long* counts = (long long*)a->counts;
+  OhemLossK k;
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.target = a->target; k.ignore = a->ignore_index; k.lmap = a->pix_loss; k.hist = w;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 one(1), blk(256);
+  hipLaunchKernelGGL(ohem_clear_kernel, one, blk, 0, st, w);
+  launch_vec(px_vec_ok<19>(a->logits, a->ld), ohem_loss_kernel<19, true>, ohem_loss_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w, OHEM_B0 / 256, 11, 0, sel, (unsigned long long)a->min_kept_total, tau_theta, (float*)nullptr, counts);
+  hipLaunchKernelGGL((ohem_refine_kernel<21, 10, OHEM_B0>), dim3(nb), blk, 0, st, a->pix_loss, npix, sel, w + OHEM_B0);
+  hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w + OHEM_B0, OHEM_B0 / 256, 11, 1, sel, 0ull, tau_theta, (float*)nullptr, counts);
+  hipLaunchKernelGGL((ohem_refine_kernel<10, 0, OHEM_B2>), dim3(nb), blk, 0, st, a->pix_loss, npix, sel, w + 2 * OHEM_B0);
+  hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w + 2 * OHEM_B0, OHEM_B2 / 256, 10, 2, sel, 0ull, tau_theta, a->tau, counts);
+  hipLaunchKernelGGL(ohem_keep_kernel, dim3(nb), blk, 0, st, a->pix_loss, a->target, a->class_w, npix, a->tau, wpart, kpart);
+  hipLaunchKernelGGL(ohem_keep_sum_kernel, one, blk, 0, st, wpart, kpart, nb, a->wsum_kept, counts);
+  return addk_check_launch("ohem_select");
+}

@@ -9,7 +9,7 @@ DynamicPlan ('edm', ADD.py:379-438): [stems+cells up to gate k + EDM] and, per g
 GatePlan ('entropy' / 'max', operations.py:161-180; the reference's own branch ADD.py:440-488 is broken, SURVEY Q6, so the
 semantics are this project's): the gate judges exit k's PREDICTION, so head k runs before the decision —
 [trunk up to exit k] [head k down to the decoder's low-resolution logits + the gate launch] [resize of head k to NCHW] ...
-[remaining cells + final head + its resize].  The gate launch (csrc/loss.hip gate_up_kernel) takes the entropy / top-probability
+[remaining cells + final head + its resize].  The gate launch (csrc/label_up.hip gate_up_kernel) takes the entropy / top-probability
 share of the x8 up-sampled prediction straight from the low-resolution logits and writes them to pinned host words; the full-size
 logits are written only for the image that leaves.  Exit k's logits are forward()'s (`model(x)[k]`): aspp_size from 2^-(last+2)
 and conv_aspp[k] when the level differs; no EDM runs, so its in-place ReLU (Q3) does not happen.  The 2^-last size (Q5) is a

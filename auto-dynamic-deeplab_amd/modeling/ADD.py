@@ -320,7 +320,7 @@ class ADD(AddkModule):
         `model(x)[k]` (aspp_size from 2^-(last+2), conv_aspp[k] when the level differs; no EDM, so no in-place ReLU) — the heads
         training optimises are the ones an entropy gate must judge; Q5's size stays a quirk of the 'edm' path only.  For every early
         exit in order: trunk up to it, head k down to the decoder's low-resolution logits, the gate value of the full-resolution
-        prediction softmax(interpolate(logits_k, size, bilinear, align_corners=False)) in one launch (csrc/loss.hip), decision on
+        prediction softmax(interpolate(logits_k, size, bilinear, align_corners=False)) in one launch (csrc/label_up.hip), decision on
         the host.  'entropy': value = mean over pixels of -sum p log p / log 19, the image leaves when value < threshold.  'max':
         value = share of pixels with max_c p > threshold, the image leaves when value > threshold (one number in both roles,
         ADD.py:476,481).  On exit y = exit k's [1,19,H,W] logits and earlier_exit = 1; after the last gate fails the final head's

@@ -1281,64 +1281,56 @@ class Graph:
         (the count word) makes the exit a student of the teacher's low-resolution logits (`OutRef.src`): `ce_upsample_kd` takes the place
         of `ce_upsample` / `ce_upsample_ohem`, and the binding gets `distill_state` (TrainStep.distill_stats)."""
         def emit_ce(ce):
-            ohem = ce.get('ohem')
+            lib, ohem, kd = self.lib, ce.get('ohem'), ce.get('distill')
+            f32 = dict(dtype=torch.float32, device=self.device)
             a = self._up_args(L.CeUpsampleArgs, src, OH, OW)
             self._bind_loss(a, ce)
             gs, a.accumulate, _ = self._grad_into(src)
             a.g, a.ldg = gs.ptr, gs.ld
-            kd = ce.get('distill')
-            ws_floats = self.lib.addk_ce_upsample_kd_ws_floats if kd else self.lib.addk_ce_upsample_ws_floats
-            ws = torch.zeros(int(ws_floats(src.N, src.H, src.W)), dtype=torch.float32, device=self.device)
+            ws_floats = lib.addk_ce_upsample_kd_ws_floats if kd else lib.addk_ce_upsample_ws_floats
+            ws = torch.zeros(int(ws_floats(src.N, src.H, src.W)), **f32)
             a.ws = ws.data_ptr()
             self.keep += [a, ws]
+            if kd:                                         # the KL term's word: kept here, before the mining tensors (the plan's kept order)
+                kdo = torch.zeros(1, **f32)
+                self.keep.append(kdo)
+            # the launch: the plain head, unless a block below changes it; the KD struct is a superset of the mining struct
+            args = L.CeUpsampleKdArgs() if kd else L.CeUpsampleOhemArgs() if ohem else a
+            name, fn, norm = 'ce_upsample', lib.addk_ce_upsample_fwd_bwd, [ce['wsum']]
+            rd_more, wr = [], [gs, ce['loss'], ws]
+            if ohem:
+                # mining: this exit's loss map, tau and kept weight sum; the head reads them, the kept weight sum is its normaliser
+                if lib.addk_ohem_select_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
+                    raise L.AddkError('hard example mining takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
+                                      % (src.C, src.N, src.H, src.W, OH, OW))
+                lmap, tau, wkept = torch.zeros((src.N, OH, OW), **f32), torch.zeros(1, **f32), torch.zeros(1, **f32)
+                counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+                sws = torch.zeros(int(lib.addk_ohem_select_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=self.device)
+                self.nbytes += lmap.numel() * 4
+                s = self._up_args(L.OhemSelectArgs, src, OH, OW)
+                s.target, s.class_w, s.ignore_index = a.target, a.class_w, a.ignore_index
+                s.thresh, s.min_kept_total = ohem
+                s.pix_loss, s.tau, s.wsum_kept, s.counts, s.ws = lmap.data_ptr(), tau.data_ptr(), wkept.data_ptr(), counts.data_ptr(), sws.data_ptr()
+                ce['ohem_state'] = dict(pix_loss=lmap, tau=tau, wsum_kept=wkept, counts=counts)
+                self.keep += [s, lmap, tau, wkept, counts, sws]
+                self._add(self.bwd, 'ohem_select', lib.addk_ohem_select, C.byref(s), rd=self.lz(src) + [ce['target']], wr=[lmap, tau, wkept, counts, sws])
+                a.wsum, args.pix_loss, args.tau = wkept.data_ptr(), lmap.data_ptr(), tau.data_ptr()
+                name, fn, norm = 'ce_upsample_ohem', lib.addk_ce_upsample_ohem_fwd_bwd, [lmap, tau, wkept]
             if kd:
-                # a student: the head's own normaliser and kept set as below, plus the last exit's low-resolution logits and the count word
+                # a student: the head's own normaliser and kept set as above, plus the last exit's low-resolution logits and the count word
                 alpha, temp, teacher = kd
                 tsrc = teacher.src
                 assert tsrc.bn is None and not tsrc.relu and (tsrc.N, tsrc.H, tsrc.W, tsrc.C) == (src.N, src.H, src.W, src.C)
-                kdo = torch.zeros(1, dtype=torch.float32, device=self.device)
-                k = L.CeUpsampleKdArgs()
-                k.ce = a                                   # a copy; with mining its normaliser is re-pointed below
                 t = self.src(tsrc)
-                k.teacher, k.ld_teacher, k.alpha, k.temperature = t.x, t.ld, alpha, temp
-                k.nvalid, k.kd_out = ce['nvalid'].data_ptr(), kdo.data_ptr()
+                args.teacher, args.ld_teacher, args.alpha, args.temperature = t.x, t.ld, alpha, temp
+                args.nvalid, args.kd_out = ce['nvalid'].data_ptr(), kdo.data_ptr()
                 ce['distill_state'] = dict(kd=kdo)
-                self.keep += [k, kdo]
-                kd_rd = self.lz(tsrc) + [ce['nvalid']]
-                if not ohem:
-                    self._add(self.bwd, 'ce_upsample_kd', self.lib.addk_ce_upsample_kd_fwd_bwd, C.byref(k),
-                              rd=self.lz(src) + [ce['target'], ce['wsum']] + kd_rd, wr=[gs, ce['loss'], ws, kdo])
-                    return
-            if not ohem:
-                self._add(self.bwd, 'ce_upsample', self.lib.addk_ce_upsample_fwd_bwd, C.byref(a),
-                          rd=self.lz(src) + [ce['target'], ce['wsum']], wr=[gs, ce['loss'], ws])
-                return
-            if self.lib.addk_ohem_select_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
-                raise L.AddkError('hard example mining takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
-                                  % (src.C, src.N, src.H, src.W, OH, OW))
-            f32 = dict(dtype=torch.float32, device=self.device)
-            lmap, tau, wkept = torch.zeros((src.N, OH, OW), **f32), torch.zeros(1, **f32), torch.zeros(1, **f32)
-            counts = torch.zeros(2, dtype=torch.int64, device=self.device)
-            sws = torch.zeros(int(self.lib.addk_ohem_select_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=self.device)
-            self.nbytes += lmap.numel() * 4
-            s = self._up_args(L.OhemSelectArgs, src, OH, OW)
-            s.target, s.class_w, s.ignore_index = a.target, a.class_w, a.ignore_index
-            s.thresh, s.min_kept_total = ohem
-            s.pix_loss, s.tau, s.wsum_kept, s.counts, s.ws = lmap.data_ptr(), tau.data_ptr(), wkept.data_ptr(), counts.data_ptr(), sws.data_ptr()
-            b = L.CeUpsampleOhemArgs()
-            b.ce = a                                   # a copy: the head's arguments with the kept weight sum as the normaliser
-            b.ce.wsum, b.pix_loss, b.tau = wkept.data_ptr(), lmap.data_ptr(), tau.data_ptr()
-            ce['ohem_state'] = dict(pix_loss=lmap, tau=tau, wsum_kept=wkept, counts=counts)
-            self.keep += [s, b, lmap, tau, wkept, counts, sws]
-            self._add(self.bwd, 'ohem_select', self.lib.addk_ohem_select, C.byref(s),
-                      rd=self.lz(src) + [ce['target']], wr=[lmap, tau, wkept, counts, sws])
-            if kd:
-                k.ce.wsum, k.pix_loss, k.tau = b.ce.wsum, b.pix_loss, b.tau
-                self._add(self.bwd, 'ce_upsample_kd', self.lib.addk_ce_upsample_kd_fwd_bwd, C.byref(k),
-                          rd=self.lz(src) + [ce['target'], lmap, tau, wkept] + kd_rd, wr=[gs, ce['loss'], ws, kdo])
-                return
-            self._add(self.bwd, 'ce_upsample_ohem', self.lib.addk_ce_upsample_ohem_fwd_bwd, C.byref(b),
-                      rd=self.lz(src) + [ce['target'], lmap, tau, wkept], wr=[gs, ce['loss'], ws])
+                name, fn = 'ce_upsample_kd', lib.addk_ce_upsample_kd_fwd_bwd
+                rd_more, wr = self.lz(tsrc) + [ce['nvalid']], wr + [kdo]
+            if args is not a:
+                args.ce = a                                # a copy of the base arguments, with the final normaliser
+                self.keep.append(args)
+            self._add(self.bwd, name, fn, C.byref(args), rd=self.lz(src) + [ce['target']] + norm + rd_more, wr=wr)
         out = self._late_head('ce', src, OH, OW, self.bwd, self._bwd_emitters, emit_ce)
         out.src = src
         return out
@@ -1487,6 +1479,14 @@ class Graph:
         self._add(self.fwd, 'argmax_nchw', self.lib.addk_argmax_nchw, y.data_ptr(), N, Cc, OH * OW, am.data_ptr(), rd=[y], wr=[am])
         self._add(self.fwd, 'label_cast_torch', _label_cast_torch, am, lut, lab, rd=[am, lut], wr=[lab], pin=True)
 
+    def _gate_args(self, src, OH, OW, thr, gout, host_out):
+        """(GateUpsampleArgs, workspace) of the fused gate launch, with and without the label map: a zeroed ticket workspace of its own"""
+        a = self._up_args(L.GateUpsampleArgs, src, OH, OW)
+        ws = self.buf((int(self.lib.addk_gate_upsample_ws_bytes(src.N, OH, OW)) + 3) // 4, zero=True)
+        a.max_thr, a.out, a.ws = thr.data_ptr(), gout.data_ptr(), ws.ptr
+        a.out_host = host_out.data_ptr() if host_out is not None else None
+        return a, ws
+
     def gate_head(self, src, OH, OW, host_out, thr, kind='entropy'):
         """Logits output of a gated early exit (`self.gate`, set by dynamic.GatePlan): the exit's gate value (modeling/operations.py:161-180)
         and, separately, the resize that writes the [N,C,OH,OW] logits.  Fused form: ONE `gate_upsample` launch (`addk_gate_upsample`)
@@ -1513,10 +1513,7 @@ class Graph:
         if labels and fused:
             out.gate_out, out.gate_fused = gout, True
             a = L.GateLabelUpsampleArgs()
-            a.gate = self._up_args(L.GateUpsampleArgs, src, OH, OW)
-            ws = self.buf((int(lib.addk_gate_upsample_ws_bytes(N, OH, OW)) + 3) // 4, zero=True)
-            a.gate.max_thr, a.gate.out, a.gate.ws = thr.data_ptr(), gout.data_ptr(), ws.ptr
-            a.gate.out_host = host_out.data_ptr() if host_out is not None else None
+            a.gate, ws = self._gate_args(src, OH, OW, thr, gout, host_out)
             a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
             self.keep += [a, lut]
             self._add(self.fwd, 'gate_label_upsample', lib.addk_gate_label_upsample, C.byref(a), rd=self.lz(src) + [thr, lut],
@@ -1528,10 +1525,7 @@ class Graph:
         out.gate_out = gout
         out.gate_fused = fused
         if out.gate_fused:
-            a = self._up_args(L.GateUpsampleArgs, src, OH, OW)
-            ws = self.buf((int(lib.addk_gate_upsample_ws_bytes(N, OH, OW)) + 3) // 4, zero=True)
-            a.max_thr, a.out, a.ws = thr.data_ptr(), gout.data_ptr(), ws.ptr
-            a.out_host = host_out.data_ptr() if host_out is not None else None
+            a, ws = self._gate_args(src, OH, OW, thr, gout, host_out)
             self.keep.append(a)
             self._add(self.fwd, 'gate_upsample', lib.addk_gate_upsample, C.byref(a), rd=self.lz(src) + [thr], wr=[gout, ws])
             out.gate_cut = len(self.fwd)

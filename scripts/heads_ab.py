@@ -1,4 +1,4 @@
-"""Two builds of libaddk.so on the gather heads of csrc/loss.hip, alternating in ONE process: addk_score_upsample (N = 2) and
+"""Two builds of libaddk.so on the gather heads of csrc/score_up.hip and csrc/label_up.hip, alternating in ONE process: addk_score_upsample (N = 2) and
 addk_gate_upsample (N = 1) at config 2's head shape, (128, 256) -> (1024, 2048), pixel stride 24.
 
     python scripts/heads_ab.py --a /path/to/parent/libaddk.so [--b auto-dynamic-deeplab_amd/libaddk.so] [--iters 3000] [--repeats 5]

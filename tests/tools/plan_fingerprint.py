@@ -237,8 +237,8 @@ def _tensors(*objs):
     return out
 
 
-def _train_step(F, shape, sync=False):
-    """the fused train step as bench.py builds it (flat gradient views, fused up-sampling + loss)"""
+def _train_step(F, shape, sync=False, **kw):
+    """the fused train step as bench.py builds it (flat gradient views, fused up-sampling + loss); `kw`: ohem=, distill="""
     import addk.train as T
     comm = None
     if sync:                       # the forced exchange at world 1 without a process group: arena binding, packed all-reduces, gradient buckets
@@ -246,7 +246,7 @@ def _train_step(F, shape, sync=False):
         comm = object.__new__(parallel.SyncBNComm)
         comm.group, comm.force, comm.size, comm.rank, comm.calls, comm.log, comm.small, comm._small_tried = None, True, 1, 0, 0, None, None, True
     m = _model(F, sync)
-    ts = T.TrainStep(m, shape, sync_comm=comm, use_graph=False, nstreams=2)
+    ts = T.TrainStep(m, shape, sync_comm=comm, use_graph=False, nstreams=2, **kw)
     g = ts.g
     extra = _tensors(ts, ts.inref, *ts.outs) + list(m.buffers())
     return g, [('fwd', g.fwd), ('bwd', g.bwd)], extra, (ts, m)
@@ -311,6 +311,16 @@ def _segmenter(F, shape, exit, lut=None):
     return g, [('fwd', g.fwd)], extra, (seg, m)
 
 
+def _multi_view(F, shape):
+    """multi-scale + flip label-map inference: the trunk once per scale and one label_views_upsample"""
+    from addk.segment import MultiViewSegmenter
+    m = _model(F)
+    seg = MultiViewSegmenter(m, shape, use_graph=False, nstreams=2)
+    g = seg.g
+    extra = _tensors(seg, seg.inref) + [g.view_labels] + list(m.buffers())
+    return g, [('fwd', g.fwd)], extra, (seg, m)
+
+
 def _gate(F, shape, kind, env=None, mode=()):
     """dynamic inference gated by entropy / top-probability share, and the segments it replays (trunk + head + gate, resize, remainder);
     `mode` as in _dynamic"""
@@ -352,6 +362,10 @@ PLANS = (
     ('dynamic_labels', lambda: _dynamic(20, (1, 3, 65, 129), 'labels', None)),
     ('gate_entropy_labels', lambda: _gate(20, (1, 3, 65, 129), 'entropy', mode=('labels', None))),     # gate_label_upsample, nothing behind the cut
     ('gate_max_labels_unfused', lambda: _gate(20, (1, 3, 65, 129), 'max', {'ADDK_FUSE_GATE': '0'}, ('labels', None))),   # _labels_cold behind the cut
+    ('train_step_ohem', lambda: _train_step(4, (2, 3, 65, 129), ohem=(0.7, 1000))),                     # ohem_select + ce_upsample_ohem per exit
+    ('train_step_distill', lambda: _train_step(4, (2, 3, 65, 129), distill=(0.5, 2.0))),                # ce_upsample_kd for the students
+    ('train_step_distill_ohem', lambda: _train_step(4, (2, 3, 65, 129), ohem=(0.7, 1000), distill=(0.5, 2.0))),
+    ('multi_view_segmenter', lambda: _multi_view(4, (2, 3, 65, 129))),                                  # default scales and flip: label_views_upsample
 )
 
 
