@@ -263,6 +263,7 @@ _SIGS = {
     'addk_bn_bwd_apply': (i32, [vp, i32, vp, i32, vp, vp, vp, i64, i32, vp, i32, vp]),
     'addk_resize_fwd': (i32, [C.POINTER(ResizeArgs), vp]),
     'addk_resize_bwd': (i32, [C.POINTER(ResizeBwdArgs), vp]),
+    'addk_resize_bwd_config': (i32, [C.POINTER(ResizeBwdArgs), C.POINTER(i32)]),
     'addk_resize_bwd_batch_key': (i32, [C.POINTER(ResizeBwdArgs)]),
     'addk_resize_bwd_batch_prepare': (i64, [vp, i32, vp, i64, vp]),
     'addk_resize_bwd_batch_run': (i32, [vp, vp, vp]),

@@ -26,6 +26,26 @@ __device__ __forceinline__ float tap_weight(int o, int i, float scale, int in) {
   return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
 }
 
+// Block sums of the (dA, dB) pairs the NHWC backward kernels keep per thread (as affine_sum_bwd_kernel's): the pixel lanes write an
+// [npl][C4][2] fp64 panel, one barrier, then thread k < 2C adds the npl rows of column (channel k / 2, A|B) in fixed order into row `row` of the slab
+__device__ __forceinline__ void panel_sum(double* panel, const double (&sA)[4], const double (&sB)[4], bool active, int pl, int c, int C, int C4, int npl, double* slab, long row) {
+  if (active) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { panel[((pl * C4) + c + e) * 2] = sA[e]; panel[((pl * C4) + c + e) * 2 + 1] = sB[e]; }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < C * 2; k += 256) {
+    const int ch = k >> 1, ab = k & 1;
+    double acc = 0.0;
+    for (int r = 0; r < npl; ++r) acc += panel[((r * C4) + ch) * 2 + ab];
+    slab[row * C * 2 + k] = acc;
+  }
+}
+
+__device__ __forceinline__ float4 fma4(float k, const float4 d, const float4 dz) {
+  return make_float4(fmaf(k, d.x, dz.x), fmaf(k, d.y, dz.y), fmaf(k, d.z, dz.z), fmaf(k, d.w, dz.w));
+}
+
 struct RsK {
   addk_src src; int N, H, W, OH, OW;
   float* y; int ldy; int nchw;
@@ -216,7 +236,7 @@ __global__ void __launch_bounds__(256) resize_bwd_kernel(const RsK p) {
         while (whi > wlo && tap_weight(whi, iw, sw, p.W) == 0.f) --whi;
         const int nh = hhi - hlo + 1, nw = whi - wlo + 1;
         if (nh <= 5 && nw <= 5 && p.vec && nrem >= 4) {
-          // up to x2 up-sampling: <= 5x5 taps, every load of a row unconditional (clamped column, zero weight) and independent
+          // up to x2 up-sampling: <= 5x5 taps
           float ww5[5]; int wo5[5];
 #pragma unroll
           for (int k = 0; k < 5; ++k) {
@@ -230,10 +250,7 @@ __global__ void __launch_bounds__(256) resize_bwd_kernel(const RsK p) {
 #pragma unroll
             for (int b = 0; b < 5; ++b) d5[b] = ld4(rowp + wo5[b]);
 #pragma unroll
-            for (int b = 0; b < 5; ++b) {
-              const float k = wh * ww5[b];
-              dz.x = fmaf(k, d5[b].x, dz.x); dz.y = fmaf(k, d5[b].y, dz.y); dz.z = fmaf(k, d5[b].z, dz.z); dz.w = fmaf(k, d5[b].w, dz.w);
-            }
+            for (int b = 0; b < 5; ++b) dz = fma4(wh * ww5[b], d5[b], dz);
           }
         } else if (nh <= 8 && nw <= 8) {
           // per-axis weights in registers (static indexing), then at most 8x8 taps
@@ -250,8 +267,7 @@ __global__ void __launch_bounds__(256) resize_bwd_kernel(const RsK p) {
               for (int b = 0; b < 8; ++b) {
                 if (ww8[b] != 0.f) {
                   float4 d = ld4g(p.dy + ((long)(n * p.OH + hlo + a) * p.OW + wlo + b) * p.lddy + c, nrem, p.vec);
-                  float k = wh8[a] * ww8[b];
-                  dz.x = fmaf(k, d.x, dz.x); dz.y = fmaf(k, d.y, dz.y); dz.z = fmaf(k, d.z, dz.z); dz.w = fmaf(k, d.w, dz.w);
+                  dz = fma4(wh8[a] * ww8[b], d, dz);
                 }
               }
             }
@@ -264,8 +280,7 @@ __global__ void __launch_bounds__(256) resize_bwd_kernel(const RsK p) {
               float ww = tap_weight(ow, iw, sw, p.W);
               if (ww == 0.f) continue;
               float4 d = ld4g(p.dy + ((long)(n * p.OH + oh) * p.OW + ow) * p.lddy + c, nrem, p.vec);
-              float k = wh * ww;
-              dz.x = fmaf(k, d.x, dz.x); dz.y = fmaf(k, d.y, dz.y); dz.z = fmaf(k, d.z, dz.z); dz.w = fmaf(k, d.w, dz.w);
+              dz = fma4(wh * ww, d, dz);
             }
           }
         }
@@ -288,21 +303,8 @@ __global__ void __launch_bounds__(256) resize_bwd_kernel(const RsK p) {
       }
     }
   }
-  if (!NCHW && p.dab) {
-    // [npl][C4][2] panel, one barrier, fixed-order column sums (see affine_sum_bwd_kernel)
-    const int C4 = p.nq * 4;
-    if (active) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { redt[((pl * C4) + c + e) * 2] = sA[e]; redt[((pl * C4) + c + e) * 2 + 1] = sB[e]; }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < C * 2; k += 256) {
-      const int ch = k >> 1, ab = k & 1;
-      double acc = 0.0;
-      for (int r = 0; r < p.npl; ++r) acc += redt[((r * C4) + ch) * 2 + ab];
-      p.dab[(long)blockIdx.x * C * 2 + k] = acc;
-    }
-  }
+  const int C4 = p.nq * 4;
+  if (!NCHW && p.dab) panel_sum(redt, sA, sB, active, pl, c, C, C4, p.npl, p.dab, blockIdx.x);
 }
 
 // Table-driven backward for resizes of at most x2 up-sampling (every in-network resize of the path: /4, /2, x2 and the
@@ -374,10 +376,7 @@ __device__ __forceinline__ void resize_bwd_tab_body(const RsK& p, int tiles_per_
 #pragma unroll
         for (int b = 0; b < MT; ++b) d5[b] = ld4(rowp + wo5[b]);
 #pragma unroll
-        for (int b = 0; b < MT; ++b) {
-          const float k = wh * ww5[b];
-          dz.x = fmaf(k, d5[b].x, dz.x); dz.y = fmaf(k, d5[b].y, dz.y); dz.z = fmaf(k, d5[b].z, dz.z); dz.w = fmaf(k, d5[b].w, dz.w);
-        }
+        for (int b = 0; b < MT; ++b) dz = fma4(wh * ww5[b], d5[b], dz);
       }
       dz.x *= gs; dz.y *= gs; dz.z *= gs; dz.w *= gs;
       if (p.src.relu || p.dab) {
@@ -400,17 +399,7 @@ __device__ __forceinline__ void resize_bwd_tab_body(const RsK& p, int tiles_per_
   if (p.dab) {
     const int C4 = p.nq * 4;
     __syncthreads();
-    if (active) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { redt[((pl * C4) + c + e) * 2] = sA[e]; redt[((pl * C4) + c + e) * 2 + 1] = sB[e]; }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < C * 2; k += 256) {
-      const int ch = k >> 1, ab = k & 1;
-      double acc = 0.0;
-      for (int r = 0; r < p.npl; ++r) acc += redt[((r * C4) + ch) * 2 + ab];
-      p.dab[(long)bx * C * 2 + k] = acc;
-    }
+    panel_sum(redt, sA, sB, active, pl, c, C, C4, p.npl, p.dab, bx);
   }
 }
 
@@ -428,78 +417,44 @@ __global__ void __launch_bounds__(256) resize_bwd_tab_batch_kernel(const RsTabIt
   resize_bwd_tab_body<MT>(e.p, e.tpr, e.ntiles, e.tw, blockIdx.x, e.rows);
 }
 
-// table-driven backward: 0 = not covered, else the taps-per-axis variant (5 / 9 / 17); fills the launch geometry
-int rs_tab_config(const addk_resize_bwd_args* a, RsK& k, RsTabItem& it, size_t& sh) {
-  if (!a || a->nchw_in || !a->dy || !a->g || a->src.C <= 0 || a->src.C > 1024 || a->ldg < a->src.C || a->lddy < a->src.C) return 0;
-  if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->OH <= 0 || a->OW <= 0) return 0;
-  if ((a->src.relu || a->dab) && !(a->src.x && a->src.ld >= a->src.C)) return 0;
-  if ((a->src.a == nullptr) != (a->src.b == nullptr)) return 0;
-  k = RsK{};
-  k.src = a->src; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
-  k.dy = a->dy; k.lddy = a->lddy; k.dy_scale = a->dy_scale; k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate; k.dab = (double*)a->dab;
-  k.P = (long)a->N * a->H * a->W;
-  EwMap m = ew_map(a->src.C); k.nq = m.nq; k.npl = m.npl;
-  k.vec = aligned16(a->dy) && a->lddy % 4 == 0 && aligned16(a->g) && a->ldg % 4 == 0 && a->src.C % 4 == 0 && (!a->src.x || src_vec_ok(a->src));
-  const bool up2 = a->OH <= 2 * a->H + 1 && a->OW <= 2 * a->W + 1, up4 = a->OH <= 4 * a->H + 1 && a->OW <= 4 * a->W + 1,
-             up8 = a->OH <= 8 * a->H + 1 && a->OW <= 8 * a->W + 1;
-  if (!(k.vec && a->src.C == m.nq * 4 && m.npl >= 2 && (up2 || up4 || up8) && (addk_get_fast_paths() & ADDK_FAST_DWTILE) && k.P < (1L << 30))) return 0;
-  int tw = m.npl >= 4 ? m.npl * 4 : m.npl * 8; if (tw > RT_MAXW) tw = RT_MAXW; if (tw > a->W) tw = a->W;      // (2-3 pixel lanes: 260-512 channels)
-  it.tpr = cdiv(a->W, tw); it.ntiles = a->N * a->H * it.tpr; it.tw = tw; it.rows = ew_rows(k.P, a->src.C);
-  it.p = k;
-  sh = (size_t)m.npl * m.nq * 4 * 2 * sizeof(double);
-  return up2 ? 5 : up4 ? 9 : 17;
+// ---- host -------------------------------------------------------------------------------------------------------------------------------------
+// what the forward and the backward kernel argument share
+RsK rs_fill(const addk_src& src, int N, int H, int W, int OH, int OW) {
+  RsK k{};
+  k.src = src; k.N = N; k.H = H; k.W = W; k.OH = OH; k.OW = OW;
+  return k;
 }
 
-}  // namespace
-
-// batched form: key >= 0 (the kernel variant) when the launch runs on the table-driven kernel and may share a batch
-extern "C" int addk_resize_bwd_batch_key(const addk_resize_bwd_args* a) {
-  RsK k; RsTabItem it; size_t sh;
-  return rs_tab_config(a, k, it, sh) > 0 ? rs_tab_config(a, k, it, sh) : -1;
+// Wide NHWC tensors (the concat buffers at F=40, level 3: 1600 channels) run as launches of at most 1024 channels (a workgroup holds 256 channel
+// quads): rs_for_slices hands f the launch itself or, one after the other, its slices.  A launch that cannot be sliced goes to f whole and fails its checks.
+constexpr int RS_SLICE = 1024;
+template <class T> T* rs_at(T* p, int c0) { return p ? p + c0 : p; }
+addk_src rs_slice_src(addk_src s, int c0) {
+  s.C = s.C - c0 < RS_SLICE ? s.C - c0 : RS_SLICE;
+  s.x = rs_at(s.x, c0); s.a = rs_at(s.a, c0); s.b = rs_at(s.b, c0);
+  return s;
 }
-// host_blob = NULL: returns the blob size in bytes.  meta[0..3] = variant, n, grid x, dynamic LDS bytes
-extern "C" int64_t addk_resize_bwd_batch_prepare(const addk_resize_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
-  size_t lds = 0;
-  const int64_t total = batch_prepare<RsTabItem>("resize_bwd_batch_prepare", a, n, host_blob, blob_bytes, meta, [](const addk_resize_bwd_args* x, RsTabItem& it, BatchItem& b) {
-    RsK k; size_t sh;
-    const int key = rs_tab_config(x, k, it, sh);
-    b = BatchItem{key, it.rows, 1, sh};
-    return key > 0;
-  }, &lds);
-  if (total > 0) meta[3] = (int64_t)lds;
-  return total;
-}
-extern "C" int addk_resize_bwd_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
-  ADDK_REQUIRE(dev_blob && meta && meta[1] > 0 && meta[2] > 0, "resize_bwd_batch_run: bad args");
-  const RsTabItem* tab = reinterpret_cast<const RsTabItem*>(dev_blob);
-  const dim3 grid((unsigned)meta[2], 1, (unsigned)meta[1]);
-  hipStream_t st = (hipStream_t)stream;
-  if (meta[0] == 5) hipLaunchKernelGGL(resize_bwd_tab_batch_kernel<5>, grid, dim3(256), (size_t)meta[3], st, tab);
-  else if (meta[0] == 9) hipLaunchKernelGGL(resize_bwd_tab_batch_kernel<9>, grid, dim3(256), (size_t)meta[3], st, tab);
-  else if (meta[0] == 17) hipLaunchKernelGGL(resize_bwd_tab_batch_kernel<17>, grid, dim3(256), (size_t)meta[3], st, tab);
-  else { addk_set_error("resize_bwd_batch_run: unknown variant %d", (int)meta[0]); return ADDK_ERR_INVALID; }
-  return addk_check_launch("resize_bwd_batch");
-}
-
-extern "C" int addk_resize_fwd(const addk_resize_args* a, void* stream) {
-  if (a && a->src.C > 1024 && !a->nchw_out) {      // wide concat buffers (F=40, level 3: 1600 channels): 1024-channel slices
-    for (int c0 = 0; c0 < a->src.C; c0 += 1024) {
-      addk_resize_args b = *a;
-      b.src.x = a->src.x + c0; b.src.C = a->src.C - c0 < 1024 ? a->src.C - c0 : 1024;
-      if (a->src.a) { b.src.a = a->src.a + c0; b.src.b = a->src.b + c0; }
-      b.y = a->y + c0;
-      int rc = addk_resize_fwd(&b, stream);
-      if (rc) return rc;
-    }
-    return ADDK_OK;
+bool rs_sliced(const addk_resize_args* a) { return a && a->src.C > RS_SLICE && !a->nchw_out; }
+bool rs_sliced(const addk_resize_bwd_args* a) { return a && a->src.C > RS_SLICE && !a->nchw_in && !a->dab; }
+addk_resize_args rs_slice(addk_resize_args a, int c0) { a.src = rs_slice_src(a.src, c0); a.y = rs_at(a.y, c0); return a; }
+addk_resize_bwd_args rs_slice(addk_resize_bwd_args a, int c0) { a.src = rs_slice_src(a.src, c0); a.dy = rs_at(a.dy, c0); a.g = rs_at(a.g, c0); return a; }
+template <typename Args, typename F>
+int rs_for_slices(const Args* a, F f) {
+  if (!rs_sliced(a)) return f(a);
+  for (int c0 = 0; c0 < a->src.C; c0 += RS_SLICE) {
+    const Args b = rs_slice(*a, c0);
+    if (const int rc = f(&b)) return rc;
   }
+  return ADDK_OK;
+}
+
+int rs_fwd(const addk_resize_args* a, hipStream_t st) {
   ADDK_REQUIRE(a && a->src.x && a->y && a->src.C > 0 && a->src.C <= 1024 && a->src.ld >= a->src.C, "resize_fwd: bad args");
   ADDK_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0, "resize_fwd: empty shape");
   ADDK_REQUIRE((a->src.a == nullptr) == (a->src.b == nullptr), "resize_fwd: a/b must come together");
-  RsK k{};
-  k.src = a->src; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW; k.y = a->y; k.ldy = a->ldy; k.nchw = a->nchw_out;
+  RsK k = rs_fill(a->src, a->N, a->H, a->W, a->OH, a->OW);
+  k.y = a->y; k.ldy = a->ldy; k.nchw = a->nchw_out;
   k.P = (long)a->N * a->OH * a->OW;
-  hipStream_t st = (hipStream_t)stream;
   if (a->nchw_out) {
     long b = cdiv(k.P, 256); if (b > 8192) b = 8192;
     hipLaunchKernelGGL(resize_fwd_nchw_kernel, dim3((unsigned)b), dim3(256), 0, st, k);
@@ -513,63 +468,126 @@ extern "C" int addk_resize_fwd(const addk_resize_args* a, void* stream) {
   return addk_check_launch("resize_fwd");
 }
 
-extern "C" int addk_resize_bwd(const addk_resize_bwd_args* a, void* stream) {
-  if (a && a->src.C > 1024 && !a->nchw_in && !a->dab) {
-    for (int c0 = 0; c0 < a->src.C; c0 += 1024) {
-      addk_resize_bwd_args b = *a;
-      b.src.C = a->src.C - c0 < 1024 ? a->src.C - c0 : 1024;
-      if (a->src.x) b.src.x = a->src.x + c0;
-      if (a->src.a) { b.src.a = a->src.a + c0; b.src.b = a->src.b + c0; }
-      b.dy = a->dy + c0; b.g = a->g + c0;
-      int rc = addk_resize_bwd(&b, stream);
-      if (rc) return rc;
-    }
-    return ADDK_OK;
-  }
+// The kernel of one resize backward launch of at most 1024 channels.  rs_choose_bwd checks the arguments and decides; the launch, the batch
+// key and prepare and addk_resize_bwd_config read the choice.
+enum { RS_NHWC = 0, RS_NHWC_TAB = 1, RS_NCHW = 2, RS_NCHW_TILE = 3 };
+struct RsChoice {
+  int kind, taps;           // taps: taps per axis of the table-driven kernel (its template parameter: 5 / 9 / 17), else 0
+  RsTabItem it;             // it.p: the kernel argument of every kind; tpr, ntiles, tw, rows: the table-driven kernel's geometry and batch descriptor
+  int tiles_x, tiles_y;     // RS_NCHW_TILE
+  int gx, gy; size_t lds;   // grid and dynamic LDS bytes
+  int key;                  // batch key (= taps): a table-driven launch, shares a batch with equal keys; -1: none
+};
+
+// The fast-path mask (ADDK_FAST_DWTILE) is tested here and nowhere else: it gates the launch as well as the key.
+int rs_choose_bwd(const addk_resize_bwd_args* a, RsChoice& c) {
   ADDK_REQUIRE(a && a->dy && a->g && a->src.C > 0 && a->src.C <= 1024 && a->ldg >= a->src.C, "resize_bwd: bad args");
   ADDK_REQUIRE(a->N > 0 && a->H > 0 && a->W > 0 && a->OH > 0 && a->OW > 0, "resize_bwd: empty shape");
   ADDK_REQUIRE(!(a->src.relu || a->dab) || (a->src.x && a->src.ld >= a->src.C), "resize_bwd: prologue needs the forward input");
   ADDK_REQUIRE((a->src.a == nullptr) == (a->src.b == nullptr), "resize_bwd: a/b must come together");
-  RsK k{};
-  k.src = a->src; k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
+  ADDK_REQUIRE(!a->nchw_in || (!a->src.relu && !a->dab), "resize_bwd: NCHW gradient input has no prologue support");
+  ADDK_REQUIRE(a->nchw_in || a->lddy >= a->src.C, "resize_bwd: short lddy");
+  c = RsChoice{};
+  RsK& k = c.it.p = rs_fill(a->src, a->N, a->H, a->W, a->OH, a->OW);
   k.dy = a->dy; k.lddy = a->lddy; k.dy_scale = a->dy_scale; k.g = a->g; k.ldg = a->ldg; k.accumulate = a->accumulate; k.dab = (double*)a->dab;
   k.P = (long)a->N * a->H * a->W;
-  hipStream_t st = (hipStream_t)stream;
+  c.gy = 1; c.key = -1;
+  const bool fast = (addk_get_fast_paths() & ADDK_FAST_DWTILE) != 0;
   if (a->nchw_in) {
-    ADDK_REQUIRE(!a->src.relu && !a->dab, "resize_bwd: NCHW gradient input has no prologue support");
     k.nq = 1; k.npl = 256;
     // receptive block of an 8x8 tile: (8 + 2) / scale + 4 output rows / columns (out_range's margins), at most RB_PM
     const float invh = (float)a->OH / (float)a->H, invw = (float)a->OW / (float)a->W;
     const bool fits = (RB_T + 2) * invh + 5.f <= (float)RB_PM && (RB_T + 2) * invw + 5.f <= (float)RB_PM &&
                       2.f * invh + 5.f <= (float)RB_MAXT && 2.f * invw + 5.f <= (float)RB_MAXT && invh >= 1.f && invw >= 1.f;
-    if (fits && (addk_get_fast_paths() & ADDK_FAST_DWTILE)) {
-      const int txs = cdiv(a->W, RB_T), tys = cdiv(a->H, RB_T);
-      dim3 grid((unsigned)(a->N * tys * txs), (unsigned)a->src.C);
-      hipLaunchKernelGGL(resize_bwd_nchw_tile_kernel, grid, dim3(256), 0, st, k, txs, tys);
-      return addk_check_launch("resize_bwd_nchw_tile");
-    }
-    long b = cdiv(k.P, 256); if (b > 8192) b = 8192;
-    hipLaunchKernelGGL(resize_bwd_kernel<true>, dim3((unsigned)b), dim3(256), 0, st, k);
-  } else {
-    ADDK_REQUIRE(a->lddy >= a->src.C, "resize_bwd: short lddy");
-    EwMap m = ew_map(a->src.C); k.nq = m.nq; k.npl = m.npl;
-    k.vec = aligned16(a->dy) && a->lddy % 4 == 0 && aligned16(a->g) && a->ldg % 4 == 0 && a->src.C % 4 == 0 &&
-            (!a->src.x || src_vec_ok(a->src));
-    int rows = ew_rows(k.P, a->src.C);
-    size_t sh = (size_t)m.npl * m.nq * 4 * 2 * sizeof(double);
-    // at most x2 up-sampling (<= 5 taps per axis), vector-aligned, a few pixel lanes per workgroup: the table-driven kernel
-    const bool up2 = a->OH <= 2 * a->H + 1 && a->OW <= 2 * a->W + 1, up4 = a->OH <= 4 * a->H + 1 && a->OW <= 4 * a->W + 1,
-               up8 = a->OH <= 8 * a->H + 1 && a->OW <= 8 * a->W + 1;
-    if (k.vec && a->src.C == m.nq * 4 && m.npl >= 2 && (up2 || up4 || up8) && (addk_get_fast_paths() & ADDK_FAST_DWTILE) &&
-        (long)a->N * a->H * a->W < (1L << 30)) {
-      int tw = m.npl >= 4 ? m.npl * 4 : m.npl * 8; if (tw > RT_MAXW) tw = RT_MAXW; if (tw > a->W) tw = a->W;      // (2-3 pixel lanes: 260-512 channels)
-      const int tpr = cdiv(a->W, tw), ntiles = a->N * a->H * tpr;
-      if (up2) hipLaunchKernelGGL(resize_bwd_tab_kernel<5>, dim3(rows), dim3(256), sh, st, k, tpr, ntiles, tw);
-      else if (up4) hipLaunchKernelGGL(resize_bwd_tab_kernel<9>, dim3(rows), dim3(256), sh, st, k, tpr, ntiles, tw);
-      else hipLaunchKernelGGL(resize_bwd_tab_kernel<17>, dim3(rows), dim3(256), sh, st, k, tpr, ntiles, tw);
-      return addk_check_launch("resize_bwd_tab");
-    }
-    hipLaunchKernelGGL(resize_bwd_kernel<false>, dim3(rows), dim3(256), sh, st, k);
+    c.kind = fits && fast ? RS_NCHW_TILE : RS_NCHW;
+    c.tiles_x = cdiv(a->W, RB_T); c.tiles_y = cdiv(a->H, RB_T);
+    if (c.kind == RS_NCHW_TILE) { c.gx = a->N * c.tiles_y * c.tiles_x; c.gy = a->src.C; }
+    else c.gx = cdiv(k.P, 256) > 8192 ? 8192 : cdiv(k.P, 256);
+    return ADDK_OK;
   }
+  EwMap m = ew_map(a->src.C); k.nq = m.nq; k.npl = m.npl;
+  k.vec = aligned16(a->dy) && a->lddy % 4 == 0 && aligned16(a->g) && a->ldg % 4 == 0 && a->src.C % 4 == 0 && (!a->src.x || src_vec_ok(a->src));
+  c.kind = RS_NHWC;
+  c.gx = c.it.rows = ew_rows(k.P, a->src.C);
+  c.lds = (size_t)m.npl * m.nq * 4 * 2 * sizeof(double);
+  // the table-driven kernel: at most x2 / x4 / x8 up-sampling (<= 5 / 9 / 17 taps per axis), vector-aligned, a few pixel lanes per workgroup
+  const bool up2 = a->OH <= 2 * a->H + 1 && a->OW <= 2 * a->W + 1, up4 = a->OH <= 4 * a->H + 1 && a->OW <= 4 * a->W + 1,
+             up8 = a->OH <= 8 * a->H + 1 && a->OW <= 8 * a->W + 1;
+  if (!(k.vec && a->src.C == m.nq * 4 && m.npl >= 2 && (up2 || up4 || up8) && fast && k.P < (1L << 30))) return ADDK_OK;
+  int tw = m.npl >= 4 ? m.npl * 4 : m.npl * 8; if (tw > RT_MAXW) tw = RT_MAXW; if (tw > a->W) tw = a->W;      // (2-3 pixel lanes: 260-512 channels)
+  c.kind = RS_NHWC_TAB; c.taps = c.key = up2 ? 5 : up4 ? 9 : 17;
+  c.it.tpr = cdiv(a->W, tw); c.it.ntiles = a->N * a->H * c.it.tpr; c.it.tw = tw;
+  return ADDK_OK;
+}
+
+int rs_launch_bwd(const RsChoice& c, hipStream_t st) {
+  const RsTabItem& t = c.it;
+  const dim3 grid((unsigned)c.gx, (unsigned)c.gy);
+  if (c.kind == RS_NHWC_TAB) {
+    if (c.taps == 5) hipLaunchKernelGGL(resize_bwd_tab_kernel<5>, grid, dim3(256), c.lds, st, t.p, t.tpr, t.ntiles, t.tw);
+    else if (c.taps == 9) hipLaunchKernelGGL(resize_bwd_tab_kernel<9>, grid, dim3(256), c.lds, st, t.p, t.tpr, t.ntiles, t.tw);
+    else hipLaunchKernelGGL(resize_bwd_tab_kernel<17>, grid, dim3(256), c.lds, st, t.p, t.tpr, t.ntiles, t.tw);
+    return addk_check_launch("resize_bwd_tab");
+  }
+  if (c.kind == RS_NCHW_TILE) {
+    hipLaunchKernelGGL(resize_bwd_nchw_tile_kernel, grid, dim3(256), 0, st, t.p, c.tiles_x, c.tiles_y);
+    return addk_check_launch("resize_bwd_nchw_tile");
+  }
+  if (c.kind == RS_NCHW) hipLaunchKernelGGL(resize_bwd_kernel<true>, grid, dim3(256), 0, st, t.p);
+  else hipLaunchKernelGGL(resize_bwd_kernel<false>, grid, dim3(256), c.lds, st, t.p);
   return addk_check_launch("resize_bwd");
+}
+
+}  // namespace
+
+extern "C" int addk_resize_fwd(const addk_resize_args* a, void* stream) {
+  return rs_for_slices(a, [stream](const addk_resize_args* s) { return rs_fwd(s, (hipStream_t)stream); });
+}
+
+extern "C" int addk_resize_bwd(const addk_resize_bwd_args* a, void* stream) {
+  return rs_for_slices(a, [stream](const addk_resize_bwd_args* s) {
+    RsChoice c;
+    const int rc = rs_choose_bwd(s, c);
+    return rc ? rc : rs_launch_bwd(c, (hipStream_t)stream);
+  });
+}
+
+// cfg[8]: include/addk.h.  A launch of more than 1024 channels reports its first slice and the number of slices (its key is -1: it is no single launch).
+extern "C" int addk_resize_bwd_config(const addk_resize_bwd_args* a, int32_t* cfg) {
+  ADDK_REQUIRE(cfg, "resize_bwd_config: null cfg");
+  const bool sliced = rs_sliced(a);
+  const addk_resize_bwd_args first = sliced ? rs_slice(*a, 0) : addk_resize_bwd_args{};
+  RsChoice c;
+  if (const int rc = rs_choose_bwd(sliced ? &first : a, c)) return rc;
+  cfg[0] = c.kind; cfg[1] = c.taps; cfg[2] = c.gx; cfg[3] = c.gy; cfg[4] = (int32_t)c.lds; cfg[5] = c.kind == RS_NHWC_TAB ? c.it.tw : 0;
+  cfg[6] = sliced ? cdiv(a->src.C, RS_SLICE) : 1; cfg[7] = sliced ? -1 : c.key;
+  return ADDK_OK;
+}
+
+// batched form: key >= 0 (the kernel variant) when the launch runs on the table-driven kernel and may share a batch
+// Kept on purpose: an argument struct that addk_resize_bwd rejects with an error has key -1 (no error: the plan asks for the key of every
+// launch it records), and a rejected item makes prepare fail like any other item that does not run on the table-driven kernel.
+extern "C" int addk_resize_bwd_batch_key(const addk_resize_bwd_args* a) { RsChoice c; return rs_choose_bwd(a, c) == ADDK_OK ? c.key : -1; }
+// host_blob = NULL: returns the blob size in bytes.  meta[0..3] = variant, n, grid x, dynamic LDS bytes
+extern "C" int64_t addk_resize_bwd_batch_prepare(const addk_resize_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta) {
+  size_t lds = 0;
+  const int64_t total = batch_prepare<RsTabItem>("resize_bwd_batch_prepare", a, n, host_blob, blob_bytes, meta, [](const addk_resize_bwd_args* x, RsTabItem& it, BatchItem& b) {
+    RsChoice c;
+    if (rs_choose_bwd(x, c) != ADDK_OK || c.key < 0) return false;
+    it = c.it; b = BatchItem{c.key, c.gx, c.gy, c.lds};
+    return true;
+  }, &lds);
+  if (total > 0) meta[3] = (int64_t)lds;
+  return total;
+}
+extern "C" int addk_resize_bwd_batch_run(const void* dev_blob, const int64_t* meta, void* stream) {
+  ADDK_REQUIRE(dev_blob && meta && meta[1] > 0 && meta[2] > 0, "resize_bwd_batch_run: bad args");
+  const RsTabItem* tab = reinterpret_cast<const RsTabItem*>(dev_blob);
+  const dim3 grid((unsigned)meta[2], 1, (unsigned)meta[1]);
+  hipStream_t st = (hipStream_t)stream;
+  if (meta[0] == 5) hipLaunchKernelGGL(resize_bwd_tab_batch_kernel<5>, grid, dim3(256), (size_t)meta[3], st, tab);      // the batch kernels' own ladder (as dw_batch_run)
+  else if (meta[0] == 9) hipLaunchKernelGGL(resize_bwd_tab_batch_kernel<9>, grid, dim3(256), (size_t)meta[3], st, tab);
+  else if (meta[0] == 17) hipLaunchKernelGGL(resize_bwd_tab_batch_kernel<17>, grid, dim3(256), (size_t)meta[3], st, tab);
+  else { addk_set_error("resize_bwd_batch_run: unknown variant %d", (int)meta[0]); return ADDK_ERR_INVALID; }
+  return addk_check_launch("resize_bwd_batch");
 }

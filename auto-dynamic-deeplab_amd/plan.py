@@ -1150,6 +1150,13 @@ class Graph:
         a = Act(act.raw, act.bn, act.relu or relu_in, act.needs_grad, rs=act.rs)
         return self.affine_sum([a])
 
+    def _rs_args(self, cls, src, OH, OW, relu_in=False):
+        """A ResizeArgs / ResizeBwdArgs with the prefix the two share filled in: the source and the two grids."""
+        a = cls()
+        a.src = self.src(src, relu_in)
+        a.N, a.H, a.W, a.OH, a.OW = src.N, src.H, src.W, OH, OW
+        return a
+
     def resize(self, src, OH, OW, relu_in=False):
         """Bilinear resize.  A lazy BN without pending ReLU passes through (affine commutes with
         interpolation); a pending ReLU forces materialisation."""
@@ -1157,10 +1164,8 @@ class Graph:
         relu = bool(src.relu or relu_in)
         N, H, W, Cc = src.N, src.H, src.W, src.C
         out = self.tensor(N, OH, OW, Cc)
-        ar = L.ResizeArgs()
         carrier = src if relu else Act(src.raw, None, False, src.needs_grad, rs=src.rs)
-        ar.src = self.src(carrier, relu_in)
-        ar.N, ar.H, ar.W, ar.OH, ar.OW = N, H, W, OH, OW
+        ar = self._rs_args(L.ResizeArgs, carrier, OH, OW, relu_in)
         ar.y, ar.ldy, ar.nchw_out = out.ptr, out.ld, 0
         self.keep.append(ar)
         tag = self.tag
@@ -1178,10 +1183,8 @@ class Graph:
         res = Act(out, None if relu else src.bn, False, src.needs_grad, rs=rs)
         if self.want_grad and src.needs_grad:
             def emit_bwd(dy):
-                ba = L.ResizeBwdArgs()
+                ba = self._rs_args(L.ResizeBwdArgs, carrier, OH, OW, relu_in)
                 ba.dy, ba.lddy, ba.nchw_in = dy.ptr, dy.ld, 0
-                ba.src = self.src(carrier, relu_in)
-                ba.N, ba.H, ba.W, ba.OH, ba.OW = N, H, W, OH, OW
                 # without a pending ReLU the BatchNorm passed through the interpolation: its (dA,dB) come from the consumers of `res`
                 gs, ba.accumulate, slab = self._grad_into(src, lib.addk_ew_rows(N * H * W, Cc) if relu else None)
                 ba.g, ba.ldg, ba.dab = gs.ptr, gs.ld, _ptr(slab)
@@ -1219,10 +1222,8 @@ class Graph:
             def emit_bwd():
                 if out.dy_ptr is None and not out.dynamic:
                     return
-                ba = L.ResizeBwdArgs()
+                ba = self._rs_args(L.ResizeBwdArgs, src, OH, OW)
                 ba.dy, ba.lddy, ba.nchw_in, ba.dy_scale = out.dy_ptr, 0, 1, out.dy_scale
-                ba.src = self.src(src)
-                ba.N, ba.H, ba.W, ba.OH, ba.OW = src.N, src.H, src.W, OH, OW
                 gs, ba.accumulate, _ = self._grad_into(src)
                 ba.g, ba.ldg = gs.ptr, gs.ld
                 self.keep.append(ba)
@@ -1235,9 +1236,7 @@ class Graph:
         """The full-resolution logits: (y [N,C,OH,OW], emit); emit() appends the `resize_nchw` launch that writes y, now or later."""
         y = torch.empty((src.N, src.C, OH, OW), dtype=torch.float32, device=self.device)
         self.nbytes += y.numel() * 4
-        ar = L.ResizeArgs()
-        ar.src = self.src(src)
-        ar.N, ar.H, ar.W, ar.OH, ar.OW = src.N, src.H, src.W, OH, OW
+        ar = self._rs_args(L.ResizeArgs, src, OH, OW)
         ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
         self.keep.append(ar)
         return y, lambda: self._add(self.fwd, 'resize_nchw', self.lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])

@@ -444,6 +444,13 @@ int addk_resize_bwd(const addk_resize_bwd_args* a, void* stream);
 int addk_resize_bwd_batch_key(const addk_resize_bwd_args* a);
 int64_t addk_resize_bwd_batch_prepare(const addk_resize_bwd_args* a, int32_t n, void* host_blob, int64_t blob_bytes, int64_t* meta);
 int addk_resize_bwd_batch_run(const void* dev_blob, const int64_t* meta, void* stream);
+/* The kernel a resize backward launch takes (what the launch, the batch key and prepare read): cfg[8] = kind (0 NHWC per-thread gather,
+ * 1 NHWC table-driven: 16-byte aligned, C % 4 == 0, at least 2 pixel lanes (C <= 512), OH <= 8 H + 1 and OW <= 8 W + 1, < 2^30 pixels,
+ * ADDK_FAST_DWTILE set; 2 NCHW per-thread; 3 NCHW LDS-tiled: up-sampling by x1 to x8.3 per axis, ADDK_FAST_DWTILE set), taps per axis of the
+ * table-driven kernel (5 / 9 / 17; else 0), grid x, grid y, dynamic LDS bytes, input pixels per row segment of the table-driven kernel
+ * (else 0), number of 1024-channel slices the launch runs as (more than 1: the other entries describe the first slice and the key is -1),
+ * batch key or -1.  Arguments addk_resize_bwd rejects are rejected here with the same error; addk_resize_bwd_batch_key gives -1 for them. */
+int addk_resize_bwd_config(const addk_resize_bwd_args* a, int32_t* cfg);
 
 /* ---------------------------------------------------------------------------------------
  * Global average pool with lazy prologue (AdaptiveAvgPool2d(1), aspp_train.py:13,50; ADD.py:506).
