@@ -78,6 +78,16 @@ class CeUpsampleKdArgs(C.Structure):
                 ('temperature', f32), ('nvalid', vp), ('kd_out', vp)]
 
 
+class DiceStatsArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
+                ('target', vp), ('ignore_index', i32), ('weight', f32), ('smooth', f32), ('scale', f32), ('coef', vp), ('dice_out', vp),
+                ('loss_out', vp), ('ws', vp)]
+
+
+class CeUpsampleDiceArgs(C.Structure):
+    _fields_ = [('kd', CeUpsampleKdArgs), ('coef', vp)]
+
+
 class ScoreUpsampleArgs(C.Structure):
     _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
                 ('target', vp), ('class_w', vp), ('ignore_index', i32), ('wsum', vp), ('scale', f32), ('loss_out', vp),
@@ -287,6 +297,10 @@ _SIGS = {
     'addk_ce_upsample_kd_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_ce_upsample_kd_ws_floats': (i64, [i32, i32, i32]),
     'addk_ce_upsample_kd_fwd_bwd': (i32, [C.POINTER(CeUpsampleKdArgs), vp]),
+    'addk_dice_stats_supported': (i32, [i32, i32, i32, i32, i32, i32]),
+    'addk_dice_stats_ws_bytes': (i64, [i32, i32, i32]),
+    'addk_dice_stats': (i32, [C.POINTER(DiceStatsArgs), vp]),
+    'addk_ce_upsample_dice_fwd_bwd': (i32, [C.POINTER(CeUpsampleDiceArgs), vp]),
     'addk_score_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_score_upsample_ws_floats': (i64, [i32, i32, i32]),
     'addk_score_upsample': (i32, [C.POINTER(ScoreUpsampleArgs), vp]),

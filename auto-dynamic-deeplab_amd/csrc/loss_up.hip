@@ -1,5 +1,5 @@
 // The training head on the decoder's low-resolution logits: fused up-sampling + cross-entropy, forward and backward (ce_up_kernel, with
-// its mining and distillation forms), and the hard example mining that feeds it (ohem_*_kernel, addk_ohem_select).
+// its mining, distillation and soft-Dice forms), and the hard example mining that feeds it (ohem_*_kernel, addk_ohem_select).
 #include <string>
 #include "up.h"
 
@@ -57,12 +57,25 @@ struct CeUpOhemK : CeUpK { const float* lmap; const float* tau; };
 // TVEC: the teacher's loader, px_vec_ok on ITS base and stride, chosen by the host as for scu_walk — a second run-time loader switch
 // would put the teacher's padding channels into scratch as the student's are (40 -> 72 bytes per lane).
 struct CeUpKdK : CeUpOhemK { const float* teacher; int ldt; float rT, kscale; const float* nvalid; float* ws2; };
-template <bool OHEM, bool KD = false> struct CeUpArg { typedef CeUpK type; };
-template <> struct CeUpArg<true, false> { typedef CeUpOhemK type; };
-template <bool OHEM> struct CeUpArg<OHEM, true> { typedef CeUpKdK type; };
+// DICE (the soft-Dice region term, addk_ce_upsample_dice_fwd_bwd): the launch also gets the coefficient table of addk_dice_stats (dice_up.hip),
+// A_c then B_c, staged in LDS once per workgroup.  Per pixel, after the CE sweep has left e_c in z and Σe: rs = 1/Σe, one more sweep for
+// dot = Σ_c p_c*G_c = rs*Σ_c e_c*B_c - p_t*A_t with p_c = e_c*rs and G_c = B_c - A_c*[t = c], B_c read from LDS (no G[] array), then the gather
+// loop's gz gets p_j*(G_j - dot) under the plain predicate: mining never filters the term and class_w does not weigh it.  Every DICE form takes the widest struct; DICE = false is the
+// parent's kernel, instruction for instruction.
+struct CeUpDiceK : CeUpKdK { const float* coef; };
+template <bool OHEM, bool KD = false, bool DICE = false> struct CeUpArg { typedef CeUpK type; };
+template <> struct CeUpArg<true, false, false> { typedef CeUpOhemK type; };
+template <bool OHEM> struct CeUpArg<OHEM, true, false> { typedef CeUpKdK type; };
+template <bool OHEM, bool KD> struct CeUpArg<OHEM, KD, true> { typedef CeUpDiceK type; };
+template <int CC> __device__ __forceinline__ float* dice_coef_lds() { __shared__ float s[2 * CC]; return s; }
+// An index offset of 0 the compiler cannot see through: a sweep that adds it to its table index READS the table where it uses it.  Plain
+// reads are loop-invariant and the compiler keeps all 19 B_c in registers across the pixel loop (the G[] array in another place): the plain
+// form then needs 257 registers and drops to one wave per SIMD.  (No `valid ? f(B_c) : 0` per class either: the compiler turns a select
+// whose operand hangs on a load into a branch around that load, 19 branches and 19 exposed LDS latencies per pixel.)
+__device__ __forceinline__ int opaque_zero() { int o = 0; asm volatile("" : "+v"(o)); return o; }
 
-template <int CC, bool OHEM = false, bool KD = false, bool TVEC = false>
-__global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM, KD>::type p) {
+template <int CC, bool OHEM = false, bool KD = false, bool TVEC = false, bool DICE = false>
+__global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM, KD, DICE>::type p) {
   constexpr int CP = cpad(CC);
   constexpr int NOUT = ((CEU_X - 1) * CC + 255) / 256;
   __shared__ float S0[CEU_R * CEU_X * CC], S1[CEU_R * CEU_X * CC];
@@ -84,6 +97,13 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM,
   [[maybe_unused]] float kg = 0.f, ksum = 0.f;
   if constexpr (KD) {
     kg = p.kscale / *(const gfloat*)p.nvalid;                  // n == 0: no pixel is valid and the select below never takes it
+  }
+  [[maybe_unused]] const float* sco = nullptr;              // A_c at [c], B_c at [CC + c]
+  if constexpr (DICE) {
+    float* stage = dice_coef_lds<CC>();
+    if (t < 2 * CC) stage[t] = ((const gfloat*)p.coef)[t];
+    sco = stage;
+    __syncthreads();
   }
   float lsum = 0.f;
   float carry[NOUT];
@@ -166,9 +186,25 @@ __global__ void __launch_bounds__(256) ce_up_kernel(const typename CeUpArg<OHEM,
           if (own && xl >= 1 && valid) lsum += w * (logf(se) + mx - zt);
           const float k = w * inv / se, kt = w * inv;
           const float a0 = lw0 + (xlast ? lw1 : 0.f), a1 = xlast ? 0.f : lw1;
+          // G_c = B_c - A_c*[t = c]: the sweeps take B_c from LDS, and the target's own p_t*A_t (e_t once more: the bits of z[t]) apart.
+          // valid ? ... : 0 is a select on two per-pixel values, rsd and p_t*A_t; the gather loop then has the parent's select, on c == t
+          [[maybe_unused]] float rsd = 0.f, ktp = 0.f, dot = 0.f;
+          if constexpr (DICE) {
+            const float rs = 1.f / se;
+            const float* B = sco + CC + opaque_zero();
+#pragma unroll
+            for (int c = 0; c < CC; ++c) dot = fmaf(z[c], B[c], dot);
+            const float ptA = pvalid ? (__expf(zt - mx) * rs) * sco[pvalid ? (int)tg : 0] : 0.f;
+            dot = dot * rs - ptA;                               // Σ_c p_c*G_c
+            rsd = pvalid ? rs : 0.f;
+            ktp = (valid ? kt : 0.f) + ptA;
+          }
+          [[maybe_unused]] const float* B = DICE ? sco + CC + opaque_zero() : nullptr;
 #pragma unroll
           for (int c = 0; c < CC; ++c) {
-            float gz = z[c] * k - ((valid && c == tg) ? kt : 0.f);
+            float gz;
+            if constexpr (DICE) gz = z[c] * fmaf(B[c] - dot, rsd, k) - (c == tg ? ktp : 0.f);     // e_c*(k + (B_c - dot)/Σe) - [t = c]*(kt + p_t*A_t)
+            else gz = z[c] * k - ((valid && c == tg) ? kt : 0.f);
             if constexpr (KD) gz += D[c];
             A0[c] = fmaf(a0, gz, A0[c]); A1[c] = fmaf(a1, gz, A1[c]);
           }
@@ -419,9 +455,9 @@ int ohem_stream_blocks(long n) { long b = cdiv(n, 256 * 16); if (b < 1) b = 1; i
 // The training head's launches, all three entry points (`name`: the entry point's prefix in error texts and launch names): the stride and
 // shape checks, one fill of the argument struct (CeUpKdK extends CeUpOhemK extends CeUpK: a plainer form takes its base), the
 // instantiation by (mining: lmap / tau given, distillation: kd given, the teacher's loader), the loss partials' sum and, for a student,
-// the KL partials' sum.
+// the KL partials' sum.  coef: the soft-Dice forms of the same instantiations.
 int ceu_launch(const char* name, const addk_ce_upsample_args* a, const float* lmap, const float* tau, const addk_ce_upsample_kd_args* kd,
-               hipStream_t st) {
+               hipStream_t st, const float* coef = nullptr) {
   ADDK_REQUIRE(a->ld >= a->C && a->ldg >= a->C && (!kd || kd->ld_teacher >= a->C), "%s: short stride", name);
   ADDK_REQUIRE(ceu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "%s: unsupported shape (19 classes, at most %d output rows per input row)", name, CEU_MAXBAND);
   CeUpKdK k{};
@@ -435,7 +471,17 @@ int ceu_launch(const char* name, const addk_ce_upsample_args* a, const float* lm
     k.teacher = kd->teacher; k.ldt = kd->ld_teacher; k.nvalid = kd->nvalid; k.ws2 = a->ws + nblk;
     k.rT = 1.f / kd->temperature;
     k.kscale = a->scale * kd->alpha * kd->temperature;           // the gradient's factor before 1/n; the loss takes one more T
-    const bool tvec = px_vec_ok<19>(kd->teacher, kd->ld_teacher);
+  }
+  const bool tvec = kd && px_vec_ok<19>(kd->teacher, kd->ld_teacher);
+  if (coef) {
+    CeUpDiceK d{};
+    static_cast<CeUpKdK&>(d) = k;
+    d.coef = coef;
+    if (kd && lmap) launch_vec(tvec, ce_up_kernel<19, true, true, true, true>, ce_up_kernel<19, true, true, false, true>, grid, st, d);
+    else if (kd) launch_vec(tvec, ce_up_kernel<19, false, true, true, true>, ce_up_kernel<19, false, true, false, true>, grid, st, d);
+    else if (lmap) hipLaunchKernelGGL((ce_up_kernel<19, true, false, false, true>), grid, dim3(256), 0, st, d);
+    else hipLaunchKernelGGL((ce_up_kernel<19, false, false, false, true>), grid, dim3(256), 0, st, d);
+  } else if (kd) {
     if (lmap) launch_vec(tvec, ce_up_kernel<19, true, true, true>, ce_up_kernel<19, true, true, false>, grid, st, k);
     else launch_vec(tvec, ce_up_kernel<19, false, true, true>, ce_up_kernel<19, false, true, false>, grid, st, k);
   } else if (lmap) {
@@ -488,6 +534,21 @@ extern "C" int addk_ce_upsample_kd_fwd_bwd(const addk_ce_upsample_kd_args* b, vo
   ADDK_REQUIRE(isfinite(b->alpha) && b->alpha > 0.f && isfinite(b->temperature) && b->temperature > 0.f,
                "ce_upsample_kd: alpha and temperature must be positive and finite");
   return ceu_launch("ce_upsample_kd", a, b->pix_loss, b->tau, b, (hipStream_t)stream);
+}
+
+extern "C" int addk_ce_upsample_dice_fwd_bwd(const addk_ce_upsample_dice_args* d, void* stream) {
+  ADDK_REQUIRE(d, "ce_upsample_dice: null pointer");
+  const addk_ce_upsample_kd_args* b = &d->kd;
+  const addk_ce_upsample_args* a = &b->ce;
+  ADDK_REQUIRE(a->logits && a->target && a->wsum && a->loss_out && a->g && a->ws && d->coef, "ce_upsample_dice: null pointer");
+  ADDK_REQUIRE((b->pix_loss == nullptr) == (b->tau == nullptr), "ce_upsample_dice: pix_loss and tau come together (both NULL: no mining)");
+  if (b->teacher) {
+    ADDK_REQUIRE(b->nvalid && b->kd_out, "ce_upsample_dice: null pointer");
+    ADDK_REQUIRE(b->teacher != a->logits, "ce_upsample_dice: the teacher must be another exit's logits");
+    ADDK_REQUIRE(isfinite(b->alpha) && b->alpha > 0.f && isfinite(b->temperature) && b->temperature > 0.f,
+                 "ce_upsample_dice: alpha and temperature must be positive and finite");
+  }
+  return ceu_launch("ce_upsample_dice", a, b->pix_loss, b->tau, b->teacher ? b : nullptr, (hipStream_t)stream, d->coef);
 }
 
 extern "C" int addk_ohem_select_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {

@@ -1278,9 +1278,12 @@ class Graph:
         per-pixel loss map, tau and kept weight sum, and `ce_upsample_ohem` is the loss head that reads them; the binding gets the
         tensors back as `ohem_state` (TrainStep.ohem_stats).  A binding with `distill = (alpha, temperature, teacher OutRef)` and `nvalid`
         (the count word) makes the exit a student of the teacher's low-resolution logits (`OutRef.src`): `ce_upsample_kd` takes the place
-        of `ce_upsample` / `ce_upsample_ohem`, and the binding gets `distill_state` (TrainStep.distill_stats)."""
+        of `ce_upsample` / `ce_upsample_ohem`, and the binding gets `distill_state` (TrainStep.distill_stats).  A binding with
+        `dice = (weight, smooth)` adds the soft-Dice region term (include/addk.h, addk_dice_stats): `dice_stats`, directly in front of the
+        head, leaves the coefficient table and the term; the head is `ce_upsample_dice`, whatever else it is, and reads the table; the
+        binding gets `dice_state` (TrainStep.dice_stats)."""
         def emit_ce(ce):
-            lib, ohem, kd = self.lib, ce.get('ohem'), ce.get('distill')
+            lib, ohem, kd, dice = self.lib, ce.get('ohem'), ce.get('distill'), ce.get('dice')
             f32 = dict(dtype=torch.float32, device=self.device)
             a = self._up_args(L.CeUpsampleArgs, src, OH, OW)
             self._bind_loss(a, ce)
@@ -1294,7 +1297,7 @@ class Graph:
                 kdo = torch.zeros(1, **f32)
                 self.keep.append(kdo)
             # the launch: the plain head, unless a block below changes it; the KD struct is a superset of the mining struct
-            args = L.CeUpsampleKdArgs() if kd else L.CeUpsampleOhemArgs() if ohem else a
+            args = L.CeUpsampleKdArgs() if kd or dice else L.CeUpsampleOhemArgs() if ohem else a
             name, fn, norm = 'ce_upsample', lib.addk_ce_upsample_fwd_bwd, [ce['wsum']]
             rd_more, wr = [], [gs, ce['loss'], ws]
             if ohem:
@@ -1329,6 +1332,23 @@ class Graph:
             if args is not a:
                 args.ce = a                                # a copy of the base arguments, with the final normaliser
                 self.keep.append(args)
+            if dice:
+                # the region term: the batch's per-class sums first (they add the term to the loss), then the head with their table
+                if lib.addk_dice_stats_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
+                    raise L.AddkError('the soft-Dice term takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
+                                      % (src.C, src.N, src.H, src.W, OH, OW))
+                coef, dout = torch.zeros(2 * src.C, **f32), torch.zeros(1 + src.C, **f32)
+                dws = torch.zeros(int(lib.addk_dice_stats_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=self.device)
+                d = self._up_args(L.DiceStatsArgs, src, OH, OW)
+                d.target, d.ignore_index, d.scale, d.loss_out = a.target, a.ignore_index, a.scale, a.loss_out
+                d.weight, d.smooth = dice
+                d.coef, d.dice_out, d.ws = coef.data_ptr(), dout.data_ptr(), dws.data_ptr()
+                ce['dice_state'] = dict(dice=dout, coef=coef)
+                self._add(self.bwd, 'dice_stats', lib.addk_dice_stats, C.byref(d), rd=self.lz(src) + [ce['target']], wr=[coef, dout, ce['loss'], dws])
+                head = L.CeUpsampleDiceArgs()
+                head.kd, head.coef = args, coef.data_ptr()       # a copy of the head's arguments, complete by now
+                self.keep += [d, coef, dout, dws, head]
+                args, name, fn, rd_more = head, 'ce_upsample_dice', lib.addk_ce_upsample_dice_fwd_bwd, rd_more + [coef]
             self._add(self.bwd, name, fn, C.byref(args), rd=self.lz(src) + [ce['target']] + norm + rd_more, wr=wr)
         out = self._late_head('ce', src, OH, OW, self.bwd, self._bwd_emitters, emit_ce)
         out.src = src

@@ -67,18 +67,39 @@ def _check_distill(distill):
     return alpha, temp
 
 
+def _check_dice(dice):
+    """(weight, smooth) -> a positive and a non-negative finite float, or None; ValueError for what the library would refuse."""
+    if dice is None:
+        return None
+    if os.environ.get('ADDK_FUSE_CE', '1') != '1':
+        raise ValueError('dice needs the fused loss head (ADDK_FUSE_CE=1): there is no form over full-resolution logits')
+    try:
+        weight, smooth = dice
+        weight, smooth = float(weight), float(smooth)
+    except (TypeError, ValueError):
+        raise ValueError('dice must be (weight, smooth), got %r' % (dice,))
+    w32, s32 = C.c_float(weight).value, C.c_float(smooth).value       # the words the library receives
+    if not (math.isfinite(w32) and math.isfinite(s32) and w32 > 0.0 and s32 >= 0.0):
+        raise ValueError('dice: weight must be positive, smooth non-negative, both finite, got %r' % (dice,))
+    return weight, smooth
+
+
 class TrainStep:
     def __init__(self, model, batch_shape, lr=0.05, momentum=0.9, weight_decay=4e-5, nesterov=True, class_weight=None,
-                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None, ohem=None, distill=None):
+                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None, ohem=None, distill=None, dice=None):
         """ohem = (thresh, min_kept): online hard example mining in every exit's loss head (include/addk.h, addk_ohem_select) — per exit
         and per process, a pixel counts when its target-class probability is below `thresh`, and never fewer than `min_kept` pixels per
         image (min_kept * N of the batch) count.  Only the fused loss head has this form: ValueError otherwise.
         distill = (alpha, temperature): self-distillation from the final exit (include/addk.h, addk_ce_upsample_kd_fwd_bwd) — every exit but
         the last adds scale * alpha * T^2 * mean over valid pixels of KL(softmax(z_last / T) || softmax(z_exit / T)) to its loss; the last
-        exit's logits are read detached.  Needs the fused head on every exit, more than one exit and exits on one low-resolution grid."""
+        exit's logits are read detached.  Needs the fused head on every exit, more than one exit and exits on one low-resolution grid.
+        dice = (weight, smooth): a soft-Dice region term in every exit's loss head (include/addk.h, addk_dice_stats) — per exit and per
+        process, scale * weight * (1 - mean over the classes present in the batch of (2 I_c + smooth) / (P_c + Y_c + smooth)) over the valid
+        pixels; class_weight does not weigh it and ohem does not filter it.  Only the fused loss head has this form: ValueError otherwise."""
         lib = self.lib = L.load()
         self.ohem = _check_ohem(ohem, batch_shape[0])
         self.distill = _check_distill(distill)
+        self.dice = _check_dice(dice)
         dev = next(model.parameters()).device
         _plan.require_device(next(model.parameters()))
         self.model, self.dev = model, dev
@@ -110,6 +131,8 @@ class TrainStep:
         nex = len(outs)
         if self.ohem is not None and any(o.head != 'ce' for o in outs):
             raise ValueError('ohem: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
+        if self.dice is not None and any(o.head != 'ce' for o in outs):
+            raise ValueError('dice: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
         if self.distill is not None:
             if nex < 2:
                 raise ValueError('distill: this model has a single exit, nobody to teach')
@@ -149,6 +172,8 @@ class TrainStep:
                 if self.distill is not None and o is not outs[-1]:
                     o.binding['distill'] = self.distill + (outs[-1],)
                     o.binding['nvalid'] = nvalid
+                if self.dice is not None:
+                    o.binding['dice'] = self.dice
                 self.dlogits.append(None)
                 continue
             d = torch.empty_like(o.y)
@@ -324,6 +349,19 @@ class TrainStep:
         if self.dev.type == 'cuda':
             torch.cuda.synchronize()
         return [float(o.binding['distill_state']['kd'].item()) for o in self.outs[:-1]]
+
+    def dice_stats(self):
+        """Per exit (dice, [D_c, or None for a class absent from the batch]) of the last step: the term as it entered the loss and the
+        per-class soft-Dice scores.  Synchronises the device; not part of the step."""
+        if self.dice is None:
+            raise ValueError('this step was built without dice')
+        if self.dev.type == 'cuda':
+            torch.cuda.synchronize()
+        res = []
+        for o in self.outs:
+            v = o.binding['dice_state']['dice'].tolist()
+            res.append((v[0], [None if d < 0 else d for d in v[1:]]))
+        return res
 
     def grads(self):
         return {p: self.g.pgrad.get(p) for p in self.params}

@@ -596,6 +596,58 @@ int addk_ce_upsample_kd_supported(int32_t N, int32_t H, int32_t W, int32_t OH, i
 int64_t addk_ce_upsample_kd_ws_floats(int32_t N, int32_t H, int32_t W);
 int addk_ce_upsample_kd_fwd_bwd(const addk_ce_upsample_kd_args* a, void* stream);
 
+/* Soft-Dice region term for the fused loss head: a per-class overlap measure beside the per-pixel cross-entropy, per exit and per process
+ * (under DDP every rank uses its own sums, as mining and distillation do; gradient averaging is unchanged).  Parameters: weight > 0 and
+ * smooth >= 0, both finite.  For every full-resolution pixel x
+ *   z     = bilinear sample (align_corners=False) of the low-resolution NHWC logits, lh0*(lw0*a + lw1*b) + lh1*(lw0*c + lw1*d)
+ *   p     = softmax(z)  (e = exp(z - max z), p = e * (1 / sum e))
+ *   valid = target != ignore_index and 0 <= target < C                       (the predicate of the plain head)
+ * Over the valid pixels of the batch, per class c:
+ *   I_c = sum p_c(x) [t(x) = c]      P_c = sum p_c(x)      Y_c = #{x : t(x) = c}
+ *   D_c = (2 I_c + smooth) / (P_c + Y_c + smooth)          present = {c : Y_c > 0}, m = |present|, s = scale
+ *   dice = s * weight * (1 - (1/m) sum_{c in present} D_c),   exactly 0 when m == 0
+ * and with k = s * weight / m the gradient with respect to z is
+ *   A_c = k * 2 / (P_c + Y_c + smooth),  B_c = k * (2 I_c + smooth) / (P_c + Y_c + smooth)^2     (both 0 for an absent class)
+ *   G_j(x) = B_j - A_j [t(x) = j],       dz_j(x) = valid ? p_j * (G_j - sum_c p_c G_c) : 0       (a select, not a factor)
+ * The select is taken once per pixel, on 1 / sum e and on p_t * A_t: a pixel that is not valid adds exactly 0 whenever its logits are finite.
+ * The term is not weighted by class_w and mining never filters it: a kept set filters the cross-entropy term only.
+ *
+ * addk_dice_stats is the reduction, all on the stream (no host read, no host memset: a captured hipGraph replays it; it clears its own
+ * count table).  It writes
+ *   coef[0..C)   = A_c,  coef[C..2C) = B_c         what the head reads; all zero when m == 0
+ *   dice_out[0]  = dice,  dice_out[1 + c] = D_c, or -1 for an absent class        written, not accumulated
+ *   loss_out[0] += dice
+ * and leaves in ws, as 32-bit words, [0..C) the counts Y_c (uint32), [32..32+C) I_c and [64..64+C) P_c (float) of this call; the rest is
+ * scratch.  Y_c is exact (integer atomics); I_c and P_c are per-workgroup fp32 partials added in a fixed order in fp64; D_c, A_c, B_c and
+ * the term are formed in fp64 and rounded once.  No float atomics: two calls give equal bits.  addk_dice_stats_supported() is 0 for
+ * C != 19, non-positive sizes, a grid beyond the limits of addk_score_upsample_supported or N*OH*OW >= 2^31 (32-bit counters).
+ * Returns ADDK_ERR_INVALID and launches nothing for a null pointer, ld < C, a non-finite weight or smooth, weight <= 0 or smooth < 0. */
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
+  int32_t N, H, W, C, OH, OW;
+  const int64_t* target;             /* [N,OH,OW] */
+  int32_t ignore_index;
+  float weight, smooth, scale;
+  float* coef;                       /* [2*C], written */
+  float* dice_out;                   /* [1 + C], written */
+  float* loss_out;                   /* device scalar, accumulated */
+  void* ws;                          /* addk_dice_stats_ws_bytes() bytes */
+} addk_dice_stats_args;
+int addk_dice_stats_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+int64_t addk_dice_stats_ws_bytes(int32_t N, int32_t OH, int32_t OW);
+int addk_dice_stats(const addk_dice_stats_args* a, void* stream);
+/* The loss head with the term's gradient: addk_ce_upsample_kd_fwd_bwd (kd.teacher == NULL: no distillation, and alpha, temperature, nvalid
+ * and kd_out are not read; kd.pix_loss == kd.tau == NULL: no mining) whose g additionally gets the bilinear transpose of dz above, with
+ * A_c and B_c READ from coef (addk_dice_stats of the same logits and target, earlier on the stream).  The loss partials are the head's
+ * own: the term entered loss_out in addk_dice_stats.  With an all-zero coef the gradient is the other entry points'.  ws as for the head
+ * it extends: addk_ce_upsample_kd_ws_floats() floats with a teacher, addk_ce_upsample_ws_floats() without.  Supported exactly where
+ * addk_ce_upsample_supported() is 1; refuses a null coef and what the head it extends refuses. */
+typedef struct {
+  addk_ce_upsample_kd_args kd;
+  const float* coef;                 /* [2*C] from addk_dice_stats */
+} addk_ce_upsample_dice_args;
+int addk_ce_upsample_dice_fwd_bwd(const addk_ce_upsample_dice_args* a, void* stream);
+
 /* Scoring head of a validation pass (train.py:250-322, eval.py:165-193): what the evaluator, the criterion and the entropy
  * meter need of one exit, in ONE pass over the high-resolution pixel grid, straight from the LOW-resolution NHWC logits
  * [N,H,W,C] (bilinear, align_corners=False, the arithmetic of addk_resize_fwd bit for bit) — the [N,C,OH,OW] tensor is never
