@@ -122,6 +122,14 @@ class ProfileUpsampleArgs(C.Structure):
                 ('target', vp), ('thr', vp), ('nthr', i32), ('ent_out', vp), ('share_out', vp), ('cm', vp), ('pred_out', vp), ('ws', vp)]
 
 
+class RowsItem(C.Structure):
+    _fields_ = [('src', vp), ('dst', vp), ('row_bytes', i64)]
+
+
+class GatherRowsArgs(C.Structure):
+    _fields_ = [('items', vp), ('nitems', i32), ('src_row', vp), ('dst_row', vp), ('nrows', i32)]
+
+
 class DwArgs(C.Structure):
     _fields_ = [('src', Src), ('N', i32), ('H', i32), ('W', i32), ('OH', i32), ('OW', i32), ('KH', i32), ('KW', i32),
                 ('stride', i32), ('pad', i32), ('dil', i32), ('w', vp), ('y', vp), ('ldy', i32)]
@@ -320,6 +328,7 @@ _SIGS = {
     'addk_entropy_sum': (i32, [vp, i32, i32, i64, vp, vp, vp]),
     'addk_argmax_nchw': (i32, [vp, i32, i32, i64, vp, vp]),
     'addk_confusion': (i32, [vp, vp, i64, i32, vp, vp]),
+    'addk_gather_rows': (i32, [C.POINTER(GatherRowsArgs), vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -19,12 +19,16 @@ output='labels' (both plans): every exit ends in a label head instead (plan.Grap
 arg-max map of its logits; no [N,C,H,W] buffer exists.  'edm': [early head k] and the final head end in one `label_upsample` launch.
 'entropy' / 'max': the gate launch leaves the map as well (`gate_label_upsample`), so nothing is left to replay for the image that
 leaves — [trunk up to exit k] [head k + the gate-and-labels launch] ... [remaining cells + final head + its `label_upsample`]."""
+import collections
+import ctypes as C
 import os
 
 import torch
 
+from . import _lib as L
+from . import plan as _plan
 from .module import ensure_layout
-from .plan import Act, Graph, OutRef, env_graph_infer, env_streams, label_lut as _label_lut
+from .plan import Act, Cmd, Graph, OutRef, env_graph_infer, env_streams, label_lut as _label_lut
 
 OUTPUTS = ('logits', 'labels')
 
@@ -71,16 +75,17 @@ class DynamicPlan:
                     self.final = model._head(g, y, low, size, aspp_size, it, model.network_arch[i], resize=False, adapt=False)
         self._finish(x)
 
-    def _begin(self, modules, x, output, label_lut, words):
+    def _begin(self, modules, x, output, label_lut, words, batched=False):
         """What both plans start with: the checks, the inference Graph with its label mode, `words` pinned host words the gate value
-        travels through and the event the host waits on, and the input -> its activation."""
+        travels through and the event the host waits on, and the input -> its activation.  `batched`: a sub-plan of BatchedGate, the
+        one caller that decides per image; `words` then covers every image of the batch."""
         if output not in OUTPUTS:
             raise ValueError('output must be one of %s (got %r)' % (OUTPUTS, output))
         lut = _label_lut(label_lut, x.device)
         for m in modules:
             for p in m.parameters():
                 ensure_layout(p)
-        if x.shape[0] != 1:
+        if x.shape[0] != 1 and not batched:
             # ADD.py:421 `if confidence_value > threshold` on a [bs, 1] tensor raises for bs > 1 ("Boolean value of Tensor with more
             # than one value is ambiguous"): the gate is a per-image decision (eval.py:195-230 runs bs = 1); same error class here
             raise RuntimeError('dynamic_inference gates one image at a time (got batch size %d): the reference\'s '
@@ -94,6 +99,7 @@ class DynamicPlan:
             self._conf_host = self._conf_host.pin_memory()
             self._conf_evt = torch.cuda.Event()
         a, self.inref = g.input_nchw(x)
+        self.in_name = a.raw.buf.region[0]             # the input staging buffer: what depends on the image is reachable from it
         return a
 
     def _finish(self, x):
@@ -166,14 +172,15 @@ KINDS = ('entropy', 'max')
 class GatePlan(DynamicPlan):
     """Dynamic inference gated by the entropy ('entropy') or the top-probability share ('max') of each early exit's prediction."""
 
-    def __init__(self, model, x, kind, output='logits', label_lut=None):
+    def __init__(self, model, x, kind, output='logits', label_lut=None, batched=False):
         from .modeling.ADD import _aspp_size
         if kind not in KINDS:
             raise ValueError('confidence must be one of %s (got %r)' % (('edm',) + KINDS, kind))
         self.kind = kind
         # (entropy, share) of the gated exit travel through pinned host memory: the gate launch writes them there itself; on the
         # stand-alone path an asynchronous 8-byte copy does.  Either way the host waits on ONE event, not on the whole device
-        a = self._begin((model,), x, output, label_lut, 2)
+        # (`batched`, a sub-plan of BatchedGate: the pair of every image of the batch)
+        a = self._begin((model,), x, output, label_lut, 2 * x.shape[0] if batched else 2, batched)
         g = self.g
         self._thr = torch.zeros(1, dtype=torch.float32, device=x.device)      # the word the 'max' gate compares against
         size = (a.H, a.W)
@@ -220,3 +227,284 @@ class GatePlan(DynamicPlan):
                 pos = hend
             self._seg(pos, -1)
         return self.final.y, 0, value
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# batched gating: per-image exits with batch compaction
+# ------------------------------------------------------------------------------------------------------------------------
+def _names(regions, kind=None):
+    return {r[0] for r in regions if kind is None or r[0][0] == kind}
+
+
+class _SubPlan(GatePlan):
+    """The gate plan (label heads) at one live batch size of a BatchedGate, and what it hands over at a cut.  Nothing here is a
+    hand-kept list of activations: everything is read off the launch list's named regions (sched.Cmd.rd / wr)."""
+
+    def __init__(self, model, x, kind, label_lut):
+        super().__init__(model, x, kind, 'labels', label_lut, batched=True)
+        self.batch = int(x.shape[0])
+        self._live = {}
+        # which launches depend on the image: those that (transitively, in list order) read something written from the staging buffer
+        tainted, self.image_dep = set(), []
+        for c in self.g.fwd:
+            dep = self.in_name in _names(c.wr) or bool(_names(c.rd) & tainted)
+            if dep:
+                tainted |= _names(c.wr)
+            self.image_dep.append(dep)
+
+    def live(self, pos):
+        """The state a run that continues at launch `pos` needs from fwd[:pos] -> (per-image plan buffers in order of first write,
+        the input-independent launches of fwd[:pos] to replay, in list order).  Live = plan buffers written by fwd[:pos] and read by
+        fwd[pos:].  Per-image = written by a launch that depends on the image; the rest (the eval-BN affine table, the hoisted weight
+        packs, anything computed from parameters only) is recomputed by replaying its producers, never copied.  On that side a buffer
+        that fwd[pos:] names as WRITTEN counts as read as well: a conv lists its hoisted weight pack under `wr` (without the hoist it
+        packs the weights itself) and reads what `conv_pack_batch` left there."""
+        got = self._live.get(pos)
+        if got is not None:
+            return got
+        fwd = self.g.fwd
+        later, touched = set(), set()
+        for c in fwd[pos:]:
+            later |= _names(c.rd)
+            touched |= _names(c.wr)
+        first, per_image = {}, set()
+        for i, c in enumerate(fwd[:pos]):
+            for j, r in enumerate(c.wr):
+                if r[0][0] == 'buf':
+                    first.setdefault(r[0], (i, j))
+                    if self.image_dep[i]:
+                        per_image.add(r[0])
+        bufs = [self.g._bufs[n[1]] for n in sorted(first, key=first.get) if n in later and n in per_image]
+        needed, replay = (later | touched) - per_image, []
+        for i in range(pos - 1, -1, -1):
+            c = fwd[i]
+            if not self.image_dep[i] and _names(c.wr) & needed:
+                replay.append(c)
+                needed |= _names(c.rd)
+        replay.reverse()
+        self._live[pos] = bufs, replay
+        return bufs, replay
+
+
+def pair_live(pm, pn, k):
+    """The per-image live buffers of sub-plans `pm` and `pn` behind gate k, paired in order of first write -> [(Buf of pm, Buf of pn,
+    words per image)].  Refuses what it cannot move row by row: a buffer that is not one whole NHWC tensor of its plan's batch, another
+    count, another per-image geometry (H, W, ld)."""
+    a, b = pm.live(pm.head_rng[k][1])[0], pn.live(pn.head_rng[k][1])[0]
+    if len(a) != len(b):
+        raise L.AddkError('gate %d: the plans of batch %d and %d keep %d and %d per-image buffers alive' % (k, pm.batch, pn.batch, len(a), len(b)))
+    pairs = []
+    for x, y in zip(a, b):
+        for p, buf in ((pm, x), (pn, y)):
+            if buf.geom is None or buf.geom[0] != p.batch or buf.n != p.batch * buf.geom[1] * buf.geom[2] * buf.geom[3]:
+                raise L.AddkError('gate %d: live buffer %r of the batch-%d plan is not one whole NHWC tensor of its batch' % (k, buf.region[0], p.batch))
+        if x.geom[1:] != y.geom[1:]:
+            raise L.AddkError('gate %d: live buffers %r / %r differ per image: (H, W, ld) %r and %r' % (k, x.region[0], y.region[0], x.geom[1:], y.geom[1:]))
+        pairs.append((x, y, x.geom[1] * x.geom[2] * x.geom[3]))
+    return pairs
+
+
+class BatchedGate:
+    """Gated dynamic inference of a batch: every image takes GatePlan's decision on its own, and the images that left stop costing
+    anything.
+
+        bg = BatchedGate(model, (N, 3, H, W), confidence='entropy' | 'max', label_lut=None)
+        labels, exits, values = bg.run(images, threshold)
+
+    One sub-plan per live batch size n in 1..N — a gate plan with label heads emitted at batch n, built on first use and kept — replayed
+    segment by segment through DynamicPlan._seg.  Plan N runs up to the first gate; the host reads the 2n pinned words, one
+    `addk_gather_rows` launch scatters the leavers' rows of that exit's label map to their original indices, and when 0 < n' < n images
+    stay, ONE more moves the per-image live state (_SubPlan.live, pair_live) into plan n', which continues behind the same gate; its
+    input-independent tables are recomputed there by replaying their launches.  With n' = n the same plan goes on and nothing is copied.
+
+    `threshold`: a number, or one number per gate.  -> labels: uint8 [N,H,W], owned by this object and overwritten by the next call
+    (the class index, or label_lut[class]); exits: int64 [N] on the host, the index into forward()'s outputs each image left at;
+    values: float32 [N, gates] on the host, NaN where a gate was not evaluated for that image.  Surviving images keep their order."""
+
+    def __init__(self, model, batch_shape, confidence='entropy', label_lut=None):
+        if confidence == 'edm':
+            raise ValueError("BatchedGate gates by 'entropy' or 'max': the 'edm' gate stays with the single-image path")
+        if confidence not in KINDS:
+            raise ValueError('confidence must be one of %s (got %r)' % (KINDS, confidence))
+        shape = tuple(int(v) for v in batch_shape)
+        if len(shape) != 4 or shape[0] < 1:
+            raise ValueError('batch_shape must be (N >= 1, 3, H, W) (got %r)' % (batch_shape,))
+        self.model, self.kind, self.shape, self.N = model, confidence, shape, shape[0]
+        self.device = next(model.parameters()).device
+        self.lut = _label_lut(label_lut, self.device)
+        self.gates = model.num_exits() - 1
+        self.subs = {}                 # live batch size -> _SubPlan
+        self.tables = {}               # ('state', m, n, k) / ('labels', n, k) -> (device item table, items, pairs)
+        cuda = self.device.type == 'cuda'
+        self.labels = torch.zeros((self.N,) + shape[2:], dtype=torch.uint8, device=self.device)
+        # index words: per gate (and once more for the final head) three rows — the leavers' rows in the plan, their original indices, the
+        # stayers' rows in the plan.  Written on the host, copied to the device words the launches read; one event per slot guards the reuse
+        self._idx_host = torch.zeros((self.gates + 1, 3, self.N), dtype=torch.int32)
+        self._idx_dev = torch.zeros((self.gates + 1, 3, self.N), dtype=torch.int32, device=self.device)
+        self._idx_evt = [None] * (self.gates + 1)
+        if cuda:
+            self._idx_host = self._idx_host.pin_memory()
+        self.counts = collections.Counter()    # 'state' / 'labels' gather_rows launches, ('seg', n) segments run per sub-plan; all calls
+        self.trace = []                # last call: (live batch, begin, end) of every segment run
+        self.moves = []                # last call: (batch before, batch after, gate, rows that stayed)
+        self.calls = 0
+
+    # ---- sub-plans -------------------------------------------------------------------------------------------------------
+    def sub(self, n):
+        p = self.subs.get(n)
+        if p is None:
+            x = torch.empty((n,) + self.shape[1:], dtype=torch.float32, device=self.device)
+            p = self.subs[n] = _SubPlan(self.model, x, self.kind, self.lut)
+            assert len(p.trunk_end) == self.gates
+        return p
+
+    def check_params(self):
+        return all(p.check_params() for p in self.subs.values())
+
+    @property
+    def nbytes(self):
+        """device bytes: {live batch size: its sub-plan's} and 'total' (the sub-plans built so far, the output map, the index words)"""
+        per = {n: int(p.g.nbytes) for n, p in sorted(self.subs.items())}
+        per['total'] = sum(per.values()) + self.labels.numel() + 4 * self._idx_dev.numel()
+        return per
+
+    def close(self):
+        """Wait for the device, then drop every captured graph and every sub-plan."""
+        if self.device.type == 'cuda':
+            torch.cuda.synchronize()
+        for p in self.subs.values():
+            p.graphs.clear()
+            p.segs.clear()
+        self.subs.clear()
+        self.tables.clear()
+
+    # ---- launches --------------------------------------------------------------------------------------------------------
+    def _seg(self, plan, i0, i1):
+        self.trace.append((plan.batch, i0, len(plan.g.fwd) if i1 < 0 else i1))
+        self.counts[('seg', plan.batch)] += 1
+        plan._seg(i0, i1)
+
+    def _items(self, key, triples):
+        tab = self.tables.get(key)
+        if tab is None:
+            arr = (L.RowsItem * len(triples))()
+            for it, (src, dst, nbytes) in zip(arr, triples):
+                it.src, it.dst, it.row_bytes = src, dst, nbytes
+            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+            tab = self.tables[key] = (host.to(self.device) if self.device.type == 'cuda' else host.clone(), len(triples))
+        return tab
+
+    def _gather(self, what, plan, table, src_row, dst_row, nrows):
+        """one addk_gather_rows launch on the current stream, through the plan's launch loop"""
+        a = L.GatherRowsArgs()
+        a.items, a.nitems, a.nrows = table[0].data_ptr(), table[1], nrows
+        a.src_row = None if src_row is None else src_row.data_ptr()
+        a.dst_row = None if dst_row is None else dst_row.data_ptr()
+        self.counts[what] += 1
+        plan.g.run([Cmd('gather_rows', plan.g.lib.addk_gather_rows, (C.byref(a),))], _plan.current_stream())
+
+    def _set_idx(self, slot, *rows):
+        if self._idx_evt[slot] is not None:
+            self._idx_evt[slot].synchronize()          # the previous copy out of these pinned words has been made
+        for r, vals in enumerate(rows):
+            if vals:
+                self._idx_host[slot, r, :len(vals)] = torch.tensor(vals, dtype=torch.int32)
+        self._idx_dev[slot].copy_(self._idx_host[slot], non_blocking=True)
+        if self.device.type == 'cuda':
+            if self._idx_evt[slot] is None:
+                self._idx_evt[slot] = torch.cuda.Event()
+            self._idx_evt[slot].record()
+        return self._idx_dev[slot]
+
+    def _scatter(self, plan, k, y, src_row, dst_row, nrows):
+        """rows of exit k's label map of `plan` -> the output map, at the images' original indices"""
+        H, W = self.shape[2:]
+        table = self._items(('labels', plan.batch, k), [(y.data_ptr(), self.labels.data_ptr(), H * W)])
+        self._gather('labels', plan, table, src_row, dst_row, nrows)
+
+    def _move(self, pm, pn, k, stay, src_row):
+        """the live state behind gate k: rows `stay` of plan pm -> rows 0.. of plan pn"""
+        key = ('state', pm.batch, pn.batch, k)
+        if key not in self.tables:
+            pairs = pair_live(pm, pn, k)
+            self._items(key, [(x.ptr, y.ptr, 4 * words) for x, y, words in pairs])
+            self.tables[key] += (pairs,)
+        replay = pn.live(pn.head_rng[k][1])[1]
+        if replay:
+            pn.g.run(replay, _plan.current_stream())
+        self._gather('state', pn, self.tables[key], src_row, None, len(stay))
+        self.moves.append((pm.batch, pn.batch, k, list(stay)))
+
+    def transition_pairs(self):
+        """For tests: per live buffer of every transition of the last call, (the rows taken from the larger plan, the rows of the
+        smaller plan) as [n', words] views of the plan buffers."""
+        out = []
+        for m, n, k, stay in self.moves:
+            for x, y, words in self.tables[('state', m, n, k)][2]:
+                out.append((x.t[:m * words].view(m, words)[stay], y.t[:n * words].view(n, words)))
+        return out
+
+    # ---- one call --------------------------------------------------------------------------------------------------------
+    def _thresholds(self, threshold):
+        try:
+            return [float(threshold)] * self.gates
+        except TypeError:
+            pass
+        thr = [float(v) for v in threshold]
+        if len(thr) != self.gates:
+            raise ValueError('one threshold per gate: %d gates, %d thresholds' % (self.gates, len(thr)))
+        return thr
+
+    def run(self, images, threshold):
+        thr = self._thresholds(threshold)
+        if tuple(images.shape) != self.shape:
+            raise ValueError('this BatchedGate was built for %r (got %r)' % (self.shape, tuple(images.shape)))
+        N, G = self.N, self.gates
+        exits = torch.full((N,), G, dtype=torch.int64)
+        values = torch.full((N, G), float('nan'), dtype=torch.float32)
+        self.calls += 1
+        self.trace, self.moves = [], []
+        entropy = self.kind == 'entropy'
+        col = 0 if entropy else 1
+        plan = self.sub(N)
+        plan.calls += 1
+        plan.x_static.copy_(images)
+        idx, pos = list(range(N)), 0            # original index of every live row; where the live plan continues
+        with torch.no_grad():
+            for k in range(G):
+                h = plan.heads[k]
+                cut, hend = plan.head_rng[k]
+                # a finite word for the kernel: every top probability lies in (0, 1], so clamping an infinite threshold changes no comparison
+                plan._thr.fill_(min(max(thr[k], -1.0), 2.0))
+                self._seg(plan, pos, cut)
+                n = len(idx)
+                if not h.gate_fused:
+                    plan._conf_host.copy_(h.gate_out.reshape(-1)[:2 * n], non_blocking=True)
+                if plan._conf_evt is not None:
+                    plan._conf_evt.record()
+                    plan._conf_evt.synchronize()                  # the host waits for these 2n words only
+                words = plan._conf_host.tolist()
+                vals = [words[2 * i + col] * (h.gate_scale if col == 0 else 1.0) for i in range(n)]
+                leave = [i for i in range(n) if ((vals[i] < thr[k]) if entropy else (vals[i] > thr[k]))]
+                stay = [i for i in range(n) if i not in leave]
+                for i in range(n):
+                    values[idx[i], k] = vals[i]
+                if leave:
+                    if hend > cut:
+                        self._seg(plan, cut, hend)
+                    d = self._set_idx(k, leave, [idx[i] for i in leave], stay)
+                    self._scatter(plan, k, h.y, d[0], d[1], len(leave))
+                    for i in leave:
+                        exits[idx[i]] = k
+                    if not stay:
+                        return self.labels, exits, values
+                    nxt = self.sub(len(stay))
+                    nxt.calls += 1
+                    self._move(plan, nxt, k, stay, d[2])
+                    plan = nxt
+                    idx = [idx[i] for i in stay]
+                pos = plan.head_rng[k][1]
+            self._seg(plan, pos, -1)
+            d = self._set_idx(G, [], idx, [])
+            self._scatter(plan, G, plan.final.y, None, d[1], len(idx))
+        return self.labels, exits, values

@@ -351,6 +351,37 @@ class ADD(AddkModule):
             torch.cuda.synchronize()
         return y, earlier_exit, time.perf_counter() - tic, conf
 
+    def dynamic_inference_batch(self, x, threshold, confidence='entropy', label_lut=None):
+        """dynamic_inference for a batch, label maps only -> (labels, exits, seconds, values).
+
+        Every image takes the decision dynamic_inference(confidence='entropy' | 'max', output='labels') takes for it alone — exit k's
+        head is forward()'s, the gate value is that image's, 'entropy' leaves when value < threshold and 'max' when
+        share(threshold) > threshold — and the images that left stop costing anything: the survivors' state is compacted into the
+        plan of the smaller batch (dynamic.BatchedGate).  `threshold`: a number, or one number per gate (num_exits() - 1 of them).
+        labels: uint8 [N,H,W], owned by the cached plan and overwritten by the next call of the same shape and mode — the class index,
+        or label_lut[class]; exits: int64 [N] on the host, the index into forward()'s outputs each image left at (num_exits() - 1:
+        the final head); values: float32 [N, num_exits() - 1] on the host, NaN where a gate was not evaluated for that image.
+
+        'edm', any other `confidence`, a `label_lut` that is not 256 uint8 entries, an empty batch or a threshold sequence of the
+        wrong length raise ValueError."""
+        from ..dynamic import BatchedGate
+        from ..plan import label_lut as _label_lut
+        lut = _label_lut(label_lut, 'cpu')
+        key = ('dynb', confidence, tuple(x.shape), int(L.load().addk_get_conv_precision()), None if lut is None else bytes(lut.numpy().tobytes()))
+        if x.is_cuda:
+            torch.cuda.synchronize()
+        tic = time.perf_counter()
+        plans = self._plans()
+        bg = plans.get(key)
+        if bg is None or not bg.check_params():
+            if bg is not None:
+                bg.close()
+            bg = plans[key] = BatchedGate(self, tuple(x.shape), confidence, lut)
+        labels, exits, values = bg.run(x, threshold)
+        if x.is_cuda:
+            torch.cuda.synchronize()
+        return labels, exits, time.perf_counter() - tic, values
+
     @staticmethod
     def _lut_from_key(lut):
         return None if lut is None else torch.frombuffer(bytearray(lut), dtype=torch.uint8)

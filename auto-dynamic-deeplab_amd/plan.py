@@ -50,10 +50,11 @@ def _ptr(x):
 
 class Buf:
     """Flat fp32 device buffer; `ordinal` is its place among the buffers of its plan (Graph.buf) and names it as a region."""
-    __slots__ = ('t', 'ptr', 'n', 'gbuf', 'ginit', 'region')
+    __slots__ = ('t', 'ptr', 'n', 'gbuf', 'ginit', 'region', 'geom')
 
     def __init__(self, n, device, zero=False, ordinal=0):
         self.n = int(n)
+        self.geom = None       # (N, H, W, ld) where the whole buffer is one NHWC tensor (Graph.tensor)
         self.region = (('buf', ordinal),) + WHOLE
         self.t = (torch.zeros if zero else torch.empty)(max(self.n, 4), dtype=torch.float32, device=device)
         self.ptr = self.t.data_ptr()
@@ -315,7 +316,9 @@ class Graph:
 
     def tensor(self, N, H, W, Cc, ld=None):
         ld = ld or (Cc + 3) // 4 * 4
-        return TRef(self.buf(N * H * W * ld, zero=(ld != Cc)), 0, N, H, W, Cc, ld)
+        b = self.buf(N * H * W * ld, zero=(ld != Cc))
+        b.geom = (N, H, W, ld)
+        return TRef(b, 0, N, H, W, Cc, ld)
 
     def vec(self, n, zero=False):
         return Vec(self.buf(n, zero), 0, n)

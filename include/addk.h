@@ -824,6 +824,34 @@ int addk_argmax_nchw(const float* logits, int32_t N, int32_t C, int64_t HW, int6
 int addk_confusion(const int64_t* gt, const int64_t* pred, int64_t n, int32_t num_class, int64_t* cm, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Row gather / scatter over several buffers in ONE launch (csrc/rows.hip): batch compaction of batched dynamic inference
+ * (dynamic.BatchedGate).  Every item is a buffer of equal-sized rows (one row per image); for every item i and every r < nrows the launch
+ * copies row_bytes bytes from  src + src_row[r] * row_bytes  to  dst + dst_row[r] * row_bytes.  A NULL index array stands for 0..nrows-1.
+ * The same entry point compacts the survivors' activations into the buffers of a smaller plan (dst_row NULL) and scatters label rows
+ * to their original indices (src_row = rows of the exit's map, dst_row = original indices, row_bytes = H*W).
+ *   - items, src_row, dst_row are DEVICE memory.  The indices are read when the launch RUNS, so a table built once serves every call
+ *     and only the index words change between calls.
+ *   - Sources and destinations NEVER overlap (they belong to different plans); rows that overlap give undefined bytes.  Two rows of
+ *     dst_row must differ.
+ *   - Any row_bytes >= 1 and any alignment: 16-byte accesses where a row's source and destination share their offset inside a 16-byte
+ *     line (4-byte accesses where they share it inside a word, bytes otherwise), single bytes at the two ends of a row; nothing outside
+ *     the destination rows is written.  No atomics, no workspace: deterministic.
+ *   - The work is cut into units of 16 KiB of one row; workgroups walk the units of all items in one sequence (a running prefix over the
+ *     items), so items that differ in size by orders of magnitude load the grid evenly.
+ * The launch function reads the item table back (a stream-ordered copy of nitems entries and a wait on `stream`) to check it and to
+ * count the units; it therefore cannot be captured into a hipGraph (ADDK_ERR_INVALID while `stream` is capturing).
+ * Returns ADDK_ERR_INVALID and launches nothing for a null argument struct, table or item pointer, nitems < 1 or > 65536, nrows < 1,
+ * row_bytes < 1, or more than 2^31 - 1 units.
+ * ------------------------------------------------------------------------------------- */
+typedef struct { const void* src; void* dst; int64_t row_bytes; } addk_rows_item;
+typedef struct {
+  const addk_rows_item* items; int32_t nitems;   /* device table */
+  const int32_t* src_row; const int32_t* dst_row;/* device [nrows]; NULL = 0..nrows-1 */
+  int32_t nrows;
+} addk_gather_rows_args;
+int addk_gather_rows(const addk_gather_rows_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * GPU input pipeline: Cityscapes sample preparation from DECODED 8-bit planes (reference
  * dataloaders/datasets/cityscapes.py:64-91 encode_segmap; dataloaders/custom_transforms.py:238-286 train_preprocess,
  * :322-347 full_image_eval_preprocess).  Bit-exact with the reference's PIL calls: the resampling tables are built on the
