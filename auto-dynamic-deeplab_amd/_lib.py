@@ -122,6 +122,22 @@ class ProfileUpsampleArgs(C.Structure):
                 ('target', vp), ('thr', vp), ('nthr', i32), ('ent_out', vp), ('share_out', vp), ('cm', vp), ('pred_out', vp), ('ws', vp)]
 
 
+class GateUpsampleTArgs(C.Structure):
+    _fields_ = [('gate', GateUpsampleArgs), ('inv_temp', vp), ('lut256', vp), ('labels', vp)]
+
+
+class ProfileUpsampleTArgs(C.Structure):
+    _fields_ = [('profile', ProfileUpsampleArgs), ('inv_temp', vp)]
+
+
+CALIB_MAX_T, CALIB_BINS = 8, 16
+
+
+class CalibUpsampleArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
+                ('target', vp), ('inv_temp', vp), ('nt', i32), ('bins', vp), ('nll', vp), ('ws', vp)]
+
+
 class RowsItem(C.Structure):
     _fields_ = [('src', vp), ('dst', vp), ('row_bytes', i64)]
 
@@ -323,6 +339,11 @@ _SIGS = {
     'addk_profile_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
     'addk_profile_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_profile_upsample': (i32, [C.POINTER(ProfileUpsampleArgs), vp]),
+    'addk_gate_upsample_t': (i32, [C.POINTER(GateUpsampleTArgs), vp]),
+    'addk_profile_upsample_t': (i32, [C.POINTER(ProfileUpsampleTArgs), vp]),
+    'addk_calib_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
+    'addk_calib_upsample_ws_bytes': (i64, [i32, i32, i32]),
+    'addk_calib_upsample': (i32, [C.POINTER(CalibUpsampleArgs), vp]),
     'addk_sgd_step': (i32, [vp, vp, vp, i64, vp, f32, f32, i32, i32, f32, vp]),
     'addk_fill': (i32, [vp, i64, f32, vp]),
     'addk_entropy_sum': (i32, [vp, i32, i32, i64, vp, vp, vp]),

@@ -1,5 +1,5 @@
 // The inference heads on the decoder's low-resolution logits: the label map of one exit (label_up_kernel), of several views
-// (label_views_kernel), and the early-exit gate with and without the label map (gate_up_kernel).
+// (label_views_kernel), and the early-exit gate with and without the label map, plain and tempered (gate_up_kernel).
 #include "up.h"
 
 namespace {
@@ -124,12 +124,19 @@ struct GateUpK : UpSrc {
 // LABELS: the launch also leaves the label map of label_up_kernel, speculatively, for every image (one byte per pixel): the max sweep
 // becomes the strict `>` arg-max sweep, which leaves the max that fmaxf leaves, so `out` / `out_host` carry the bits of the plain gate
 struct GateLabelUpK : GateUpK { const uint8_t* lut; uint8_t* labels; };
-template <bool LABELS> struct GateUpArg { typedef GateUpK type; };
-template <> struct GateUpArg<true> { typedef GateLabelUpK type; };
+// TEMP: the tempered launch (addk_gate_upsample_t) judges softmax(z * *inv_temp); the word rides behind the untempered arguments, whose
+// layout and kernels stay as they are
+template <class K> struct Tempered : K { const float* inv_temp; };
+template <bool LABELS, bool TEMP = false> struct GateUpArg { typedef GateUpK type; };
+template <> struct GateUpArg<true, false> { typedef GateLabelUpK type; };
+template <> struct GateUpArg<false, true> { typedef Tempered<GateUpK> type; };
+template <> struct GateUpArg<true, true> { typedef Tempered<GateLabelUpK> type; };
 
-template <int CC, bool VEC, bool LABELS = false>
-__global__ void __launch_bounds__(256) gate_up_kernel(const typename GateUpArg<LABELS>::type p) {
+template <int CC, bool VEC, bool LABELS = false, bool TEMP = false>
+__global__ void __launch_bounds__(256) gate_up_kernel(const typename GateUpArg<LABELS, TEMP>::type p) {
   const float thr = *(const gfloat*)p.thr;
+  float it = 1.f;
+  if constexpr (TEMP) it = *(const gfloat*)p.inv_temp;
   float esum = 0.f; unsigned hit[1] = {0u};
   scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
     float mx = -INFINITY;
@@ -144,7 +151,8 @@ __global__ void __launch_bounds__(256) gate_up_kernel(const typename GateUpArg<L
       for (int c = 0; c < CC; ++c) mx = fmaxf(mx, z[c]);
     }
     float se, sx;
-    exp_sweep<CC>(z, mx, se, sx);
+    if constexpr (TEMP) exp_sweep_t<CC>(z, mx, it, se, sx);
+    else exp_sweep<CC>(z, mx, se, sx);
     esum += logf(se) - sx / se;
     hit[0] += (1.f / se > thr) ? 1u : 0u;
   });
@@ -193,6 +201,29 @@ extern "C" int addk_gate_label_upsample(const addk_gate_label_upsample_args* b, 
   hipStream_t st = (hipStream_t)stream;
   launch_vec(px_vec_ok<19>(a->logits, a->ld), gate_up_kernel<19, true, true>, gate_up_kernel<19, false, true>, scu_grid(a->N, a->OH, a->OW), st, k);
   return addk_check_launch("gate_label_upsample");
+}
+
+extern "C" int addk_gate_upsample_t(const addk_gate_upsample_t_args* b, void* stream) {
+  ADDK_REQUIRE(b, "gate_upsample_t: null pointer");
+  const addk_gate_upsample_args* a = &b->gate;
+  ADDK_REQUIRE(a->logits && a->max_thr && a->out && a->ws && b->inv_temp, "gate_upsample_t: null pointer");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample_t: unsupported shape (19 classes)");
+  ADDK_REQUIRE(a->ld >= a->C, "gate_upsample_t: short stride");
+  const bool vec = px_vec_ok<19>(a->logits, a->ld);
+  const dim3 grid = scu_grid(a->N, a->OH, a->OW);
+  hipStream_t st = (hipStream_t)stream;
+  if (b->labels) {
+    Tempered<GateLabelUpK> k;
+    gate_up_fill(k, a);
+    k.lut = b->lut256; k.labels = b->labels; k.inv_temp = b->inv_temp;
+    launch_vec(vec, gate_up_kernel<19, true, true, true>, gate_up_kernel<19, false, true, true>, grid, st, k);
+  } else {
+    Tempered<GateUpK> k;
+    gate_up_fill(k, a);
+    k.inv_temp = b->inv_temp;
+    launch_vec(vec, gate_up_kernel<19, true, false, true>, gate_up_kernel<19, false, false, true>, grid, st, k);
+  }
+  return addk_check_launch("gate_upsample_t");
 }
 
 extern "C" int addk_label_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {

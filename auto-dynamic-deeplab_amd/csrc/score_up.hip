@@ -1,5 +1,5 @@
 // The validation heads on the decoder's low-resolution logits: the scoring head (confusion matrix, loss, entropy: score_up_kernel) and
-// the per-image exit profile (profile_up_kernel).
+// the per-image exit profile, plain and tempered (profile_up_kernel).
 #include "up.h"
 
 namespace {
@@ -89,8 +89,14 @@ struct ProfileUpK : UpSrc {
   double npix, ent_div;
 };
 
-template <int CC, bool VEC>
-__global__ void __launch_bounds__(256) profile_up_kernel(const ProfileUpK p) {
+// TEMP: the tempered launch (addk_profile_upsample_t) takes entropy and shares from softmax(z * *inv_temp); the word rides behind the
+// untempered arguments, whose layout and kernels stay as they are
+struct ProfileUpTK : ProfileUpK { const float* inv_temp; };
+template <bool TEMP> struct ProfileUpArg { typedef ProfileUpK type; };
+template <> struct ProfileUpArg<true> { typedef ProfileUpTK type; };
+
+template <int CC, bool VEC, bool TEMP = false>
+__global__ void __launch_bounds__(256) profile_up_kernel(const typename ProfileUpArg<TEMP>::type p) {
   __shared__ unsigned hist[CC * CC];
   const int t = threadIdx.x;
   for (int i = t; i < CC * CC; i += 256) hist[i] = 0u;
@@ -102,6 +108,8 @@ __global__ void __launch_bounds__(256) profile_up_kernel(const ProfileUpK p) {
   float esum = 0.f; unsigned hit[PRU_NT];
 #pragma unroll
   for (int j = 0; j < PRU_NT; ++j) hit[j] = 0u;
+  float it = 1.f;
+  if constexpr (TEMP) it = *(const gfloat*)p.inv_temp;
   int key = -1; unsigned run = 0;                                // pending (gt, pred) run of this column
   scu_walk<CC, VEC>(p, [&](long pix, const float (&z)[CC]) {
     const long tg = tgt[pix];
@@ -110,7 +118,8 @@ __global__ void __launch_bounds__(256) profile_up_kernel(const ProfileUpK p) {
     for (int c = 0; c < CC; ++c)
       if (z[c] > mx) { mx = z[c]; am = c; }                      // strict: a tie keeps the lowest channel
     float se, sx;
-    exp_sweep<CC>(z, mx, se, sx);
+    if constexpr (TEMP) exp_sweep_t<CC>(z, mx, it, se, sx);
+    else exp_sweep<CC>(z, mx, se, sx);
     esum += logf(se) - sx / se;
     const float pmax = 1.f / se;
 #pragma unroll
@@ -165,6 +174,13 @@ extern "C" int64_t addk_profile_upsample_ws_bytes(int32_t N, int32_t OH, int32_t
   if (N <= 0 || OH <= 0 || OW <= 0) return 0;
   return up_ws_bytes(N, OH, OW, PRU_NT);
 }
+// the profile launch's arguments behind the UpSrc prefix (both of its forms)
+static void profile_up_fill(ProfileUpK& k, const addk_profile_upsample_args* a) {
+  static_cast<UpSrc&>(k) = up_src(a);
+  k.target = a->target; k.thr = a->thr; k.nthr = a->nthr;
+  k.ent = a->ent_out; k.share = a->share_out; k.cm = reinterpret_cast<unsigned long long*>(a->cm); k.pred = a->pred_out;
+  up_tail_fill(k, a->ws, a->N, a->OH, a->OW);
+}
 extern "C" int addk_profile_upsample(const addk_profile_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->target && a->ent_out && a->cm && a->ws, "profile_upsample: null pointer");
   ADDK_REQUIRE(addk_profile_upsample_supported(a->N, a->H, a->W, a->OH, a->OW, a->C, a->nthr) == 1,
@@ -172,11 +188,23 @@ extern "C" int addk_profile_upsample(const addk_profile_upsample_args* a, void* 
   ADDK_REQUIRE(a->nthr == 0 || (a->thr && a->share_out), "profile_upsample: null pointer");
   ADDK_REQUIRE(a->ld >= a->C, "profile_upsample: short stride");
   ProfileUpK k;
-  static_cast<UpSrc&>(k) = up_src(a);
-  k.target = a->target; k.thr = a->thr; k.nthr = a->nthr;
-  k.ent = a->ent_out; k.share = a->share_out; k.cm = reinterpret_cast<unsigned long long*>(a->cm); k.pred = a->pred_out;
-  up_tail_fill(k, a->ws, a->N, a->OH, a->OW);
+  profile_up_fill(k, a);
   hipStream_t st = (hipStream_t)stream;
   launch_vec(px_vec_ok<19>(a->logits, a->ld), profile_up_kernel<19, true>, profile_up_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
   return addk_check_launch("profile_upsample");
+}
+extern "C" int addk_profile_upsample_t(const addk_profile_upsample_t_args* b, void* stream) {
+  ADDK_REQUIRE(b, "profile_upsample_t: null pointer");
+  const addk_profile_upsample_args* a = &b->profile;
+  ADDK_REQUIRE(a->logits && a->target && a->ent_out && a->cm && a->ws && b->inv_temp, "profile_upsample_t: null pointer");
+  ADDK_REQUIRE(addk_profile_upsample_supported(a->N, a->H, a->W, a->OH, a->OW, a->C, a->nthr) == 1,
+               "profile_upsample_t: unsupported shape (19 classes, at most %d thresholds)", PRU_NT);
+  ADDK_REQUIRE(a->nthr == 0 || (a->thr && a->share_out), "profile_upsample_t: null pointer");
+  ADDK_REQUIRE(a->ld >= a->C, "profile_upsample_t: short stride");
+  ProfileUpTK k;
+  profile_up_fill(k, a);
+  k.inv_temp = b->inv_temp;
+  hipStream_t st = (hipStream_t)stream;
+  launch_vec(px_vec_ok<19>(a->logits, a->ld), profile_up_kernel<19, true, true>, profile_up_kernel<19, false, true>, scu_grid(a->N, a->OH, a->OW), st, k);
+  return addk_check_launch("profile_upsample_t");
 }

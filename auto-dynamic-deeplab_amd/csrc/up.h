@@ -1,6 +1,6 @@
 // Device and host code that more than one family of logits heads uses (loss_up.hip: the training head and hard example mining;
-// dice_up.hip: the soft-Dice term's reduction; score_up.hip: the validation scoring head and the exit profile; label_up.hip: the label-map heads and the exit gate; loss.hip: the
-// drop-in criterion): the block sum and the second-stage sum of partials, the argument prefix and pixel loader of the decoder's
+// dice_up.hip: the soft-Dice term's reduction; score_up.hip: the validation scoring head and the exit profile; label_up.hip: the
+// label-map heads and the exit gate; calib_up.hip: the calibration head; loss.hip: the drop-in criterion): the block sum and the second-stage sum of partials, the argument prefix and pixel loader of the decoder's
 // low-resolution NHWC logits, the up-sampling walk of the gather heads with its grid, the label store, and the last-arriver tail of
 // the gate-style heads.  Everything sits in the unit's anonymous namespace.
 #pragma once
@@ -113,6 +113,13 @@ __device__ __forceinline__ void exp_sweep(const float (&z)[CC], float mx, float&
   se = 0.f; sx = 0.f;
 #pragma unroll
   for (int c = 0; c < CC; ++c) { const float d = z[c] - mx; const float e = __expf(d); se += e; sx += e * d; }
+}
+// the sweep of the tempered heads, softmax(z·it): d = (z - mx)·it, the rest as above, so it = 1.0f leaves exp_sweep's bits
+template <int CC>
+__device__ __forceinline__ void exp_sweep_t(const float (&z)[CC], float mx, float it, float& se, float& sx) {
+  se = 0.f; sx = 0.f;
+#pragma unroll
+  for (int c = 0; c < CC; ++c) { const float d = (z[c] - mx) * it; const float e = __expf(d); se += e; sx += e * d; }
 }
 
 // the launch grid of the two gather heads (one workgroup per tile and image) and its workgroup count, which sizes their workspaces

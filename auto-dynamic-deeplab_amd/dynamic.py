@@ -169,10 +169,34 @@ class DynamicPlan:
 KINDS = ('entropy', 'max')
 
 
-class GatePlan(DynamicPlan):
-    """Dynamic inference gated by the entropy ('entropy') or the top-probability share ('max') of each early exit's prediction."""
+def check_temperature(temperature, nex):
+    """`temperature` of a tempered gate or profile -> None, or one positive finite float per exit of forward() (`nex` of them: what
+    calibrate.ExitCalibration.fit() returns).  A scalar serves every exit; anything else is a ValueError."""
+    if temperature is None:
+        return None
+    try:
+        ts = [float(temperature)] * nex
+    except TypeError:
+        ts = [float(t) for t in temperature]
+        if len(ts) != nex:
+            raise ValueError('temperature takes a scalar or one number per exit: %d exits, %d temperatures' % (nex, len(ts)))
+    if any(not (0.0 < t < float('inf')) for t in ts):
+        raise ValueError('a temperature must be positive and finite (got %r)' % (ts,))
+    return tuple(ts)
 
-    def __init__(self, model, x, kind, output='logits', label_lut=None, batched=False):
+
+def inverse_words(ts):
+    """the fp32 words 1 / T the tempered launches read"""
+    return torch.tensor([1.0 / t for t in ts], dtype=torch.float32)
+
+
+class GatePlan(DynamicPlan):
+    """Dynamic inference gated by the entropy ('entropy') or the top-probability share ('max') of each early exit's prediction.
+    `temperature` (None, a scalar or one per exit of forward(): check_temperature): the gates judge softmax(z_k / T_k) — the tempered
+    plan, whose gate launches read 1 / T_k from device words (set_temperature: no rebuild, no recapture); exit k's logits and label
+    map are what they are without it."""
+
+    def __init__(self, model, x, kind, output='logits', label_lut=None, batched=False, temperature=None):
         from .modeling.ADD import _aspp_size
         if kind not in KINDS:
             raise ValueError('confidence must be one of %s (got %r)' % (('edm',) + KINDS, kind))
@@ -183,6 +207,11 @@ class GatePlan(DynamicPlan):
         a = self._begin((model,), x, output, label_lut, 2 * x.shape[0] if batched else 2, batched)
         g = self.g
         self._thr = torch.zeros(1, dtype=torch.float32, device=x.device)      # the word the 'max' gate compares against
+        self.nex = model.num_exits()
+        self.temperature, self._temp = None, None
+        if temperature is not None:
+            check_temperature(temperature, self.nex)
+            self._temp = torch.ones(max(self.nex - 1, 1), dtype=torch.float32, device=x.device)      # 1 / T of every gate
         size = (a.H, a.W)
         aspp_size = _aspp_size(size, model.network_arch[-1] + 2)       # forward()'s (ADD.emit)
         self.trunk_end, self.head_rng, self.heads, self.final = [], [], [], None
@@ -192,11 +221,26 @@ class GatePlan(DynamicPlan):
             else:
                 self.trunk_end.append(len(g.fwd))
                 g.gate = {'kind': kind, 'host': self._conf_host if x.is_cuda else None, 'thr': self._thr}
+                if self._temp is not None:
+                    g.gate['temp'] = self._temp[len(self.heads):len(self.heads) + 1]
                 h = model._head(g, y, low, size, aspp_size, it, lvl)
                 g.gate = None
                 self.heads.append(h)
                 self.head_rng.append((h.gate_cut, len(g.fwd)))          # [trunk_end, gate_cut): head + gate; [gate_cut, end): resize (labels: empty)
         self._finish(x)
+        if temperature is not None:
+            self.set_temperature(temperature)
+
+    def set_temperature(self, temperature):
+        """Other temperatures for the calls that follow (a tempered plan only).  The gates use the first num_exits() - 1 values; the words
+        are written only when the values change."""
+        if self._temp is None or temperature is None:
+            raise ValueError('this plan was built %s a temperature: the other kind is another plan' % ('without' if self._temp is None else 'with'))
+        ts = check_temperature(temperature, self.nex)
+        if ts != self.temperature:
+            if self.nex > 1:
+                self._temp.copy_(inverse_words(ts[:self.nex - 1]))
+            self.temperature = ts
 
     def run(self, x, threshold):
         """-> (logits or label map, earlier_exit, gate value).  The image leaves at the first exit whose entropy is BELOW the threshold
@@ -240,8 +284,8 @@ class _SubPlan(GatePlan):
     """The gate plan (label heads) at one live batch size of a BatchedGate, and what it hands over at a cut.  Nothing here is a
     hand-kept list of activations: everything is read off the launch list's named regions (sched.Cmd.rd / wr)."""
 
-    def __init__(self, model, x, kind, label_lut):
-        super().__init__(model, x, kind, 'labels', label_lut, batched=True)
+    def __init__(self, model, x, kind, label_lut, temperature=None):
+        super().__init__(model, x, kind, 'labels', label_lut, batched=True, temperature=temperature)
         self.batch = int(x.shape[0])
         self._live = {}
         # which launches depend on the image: those that (transitively, in list order) read something written from the staging buffer
@@ -319,9 +363,10 @@ class BatchedGate:
 
     `threshold`: a number, or one number per gate.  -> labels: uint8 [N,H,W], owned by this object and overwritten by the next call
     (the class index, or label_lut[class]); exits: int64 [N] on the host, the index into forward()'s outputs each image left at;
-    values: float32 [N, gates] on the host, NaN where a gate was not evaluated for that image.  Surviving images keep their order."""
+    values: float32 [N, gates] on the host, NaN where a gate was not evaluated for that image.  Surviving images keep their order.
+    `temperature`: GatePlan's, for every sub-plan; set_temperature changes the values of a tempered BatchedGate."""
 
-    def __init__(self, model, batch_shape, confidence='entropy', label_lut=None):
+    def __init__(self, model, batch_shape, confidence='entropy', label_lut=None, temperature=None):
         if confidence == 'edm':
             raise ValueError("BatchedGate gates by 'entropy' or 'max': the 'edm' gate stays with the single-image path")
         if confidence not in KINDS:
@@ -333,6 +378,7 @@ class BatchedGate:
         self.device = next(model.parameters()).device
         self.lut = _label_lut(label_lut, self.device)
         self.gates = model.num_exits() - 1
+        self.temperature = check_temperature(temperature, self.gates + 1)
         self.subs = {}                 # live batch size -> _SubPlan
         self.tables = {}               # ('state', m, n, k) / ('labels', n, k) -> (device item table, items, pairs)
         cuda = self.device.type == 'cuda'
@@ -354,9 +400,17 @@ class BatchedGate:
         p = self.subs.get(n)
         if p is None:
             x = torch.empty((n,) + self.shape[1:], dtype=torch.float32, device=self.device)
-            p = self.subs[n] = _SubPlan(self.model, x, self.kind, self.lut)
+            p = self.subs[n] = _SubPlan(self.model, x, self.kind, self.lut, self.temperature)
             assert len(p.trunk_end) == self.gates
         return p
+
+    def set_temperature(self, temperature):
+        if self.temperature is None or temperature is None:
+            raise ValueError('this BatchedGate was built %s a temperature: the other kind is another plan' % ('without' if self.temperature is None else 'with'))
+        ts = check_temperature(temperature, self.gates + 1)
+        self.temperature = ts
+        for p in self.subs.values():
+            p.set_temperature(ts)
 
     def check_params(self):
         return all(p.check_params() for p in self.subs.values())

@@ -15,11 +15,14 @@ confusion matrix.  Every point of the curve follows on the host (exit_curve) by 
     pts = prof.curve('entropy', thresholds=[0.1, 0.2, 0.3])
     pts = prof.curve('max')                  # at max_thresholds
 
-The 'edm' gate is out of reach of this pass: its early head is not forward()'s."""
+The 'edm' gate is out of reach of this pass: its early head is not forward()'s.
+
+`temperature` (None, a scalar or one per exit, e.g. calibrate.ExitCalibration.fit()): entropy and shares are those of
+softmax(z_k / T_k), what dynamic_inference(..., temperature=) judges — the curve of the tempered gates.  Matrices and maps do not move."""
 import torch
 
 from . import _lib as L
-from .dynamic import KINDS
+from .dynamic import KINDS, check_temperature, inverse_words
 from .metrics import mean_iou
 from .resident import InferenceStep
 
@@ -97,9 +100,12 @@ class ExitProfile(InferenceStep):
     head = 'profile'
 
     def __init__(self, model, batch_shape, max_thresholds=(0.5, 0.9, 0.99), ignore_index=255, keep_predictions=False,
-                 use_graph=None, nstreams=None):
+                 use_graph=None, nstreams=None, temperature=None):
         self.max_thresholds = _check_thresholds(max_thresholds)
+        self.temperature = check_temperature(temperature, model.num_exits())
         super().__init__(model, batch_shape, use_graph, nstreams)
+        # 1 / T of every exit: the words the tempered launches read (None: the untempered plan)
+        self.temp = None if self.temperature is None else inverse_words(self.temperature).to(self.dev)
         # the evaluator counts every label in [0, classes) (utils/metrics.py:34-43); ignore_index is what the loader paints elsewhere
         self.ignore_index = int(ignore_index)
         self.keep_predictions = bool(keep_predictions)
@@ -123,6 +129,17 @@ class ExitProfile(InferenceStep):
         self._write_thresholds()
         self.reset()
 
+    def set_temperature(self, temperature):
+        """Other temperatures for the steps that follow (a tempered profile only): device words, so nothing is rebuilt or captured again.
+        The logs are emptied when the values change: their entropies and shares belong to the old ones."""
+        if self.temperature is None or temperature is None:
+            raise ValueError('this ExitProfile was built %s a temperature: the other kind is another plan' % ('without' if self.temperature is None else 'with'))
+        ts = check_temperature(temperature, len(self.temperature))
+        if ts != self.temperature:
+            self.temperature = ts
+            self.temp.copy_(inverse_words(ts))
+            self.reset()
+
     # ---------------- plan ----------------
     def _emit(self, g, a):
         dev = self.dev
@@ -142,6 +159,8 @@ class ExitProfile(InferenceStep):
         for i, o in enumerate(outs):
             o.binding = dict(target=self.target, thr=self.thr, nthr=NT, entropy=self.ent[i], share=self.share[i], confusion=self.cm[i],
                              pred=self.pred[i] if self.pred is not None else None)
+            if self.temp is not None:
+                o.binding['temp'] = self.temp[i:i + 1]
         self.outs = outs
 
     # ---------------- replay ----------------

@@ -307,7 +307,7 @@ class ADD(AddkModule):
         """length of forward()'s output list"""
         return len(set(self.C_index) | {self.num_net - 1})
 
-    def dynamic_inference(self, x, threshold=1.0, confidence='edm', edm=False, output='logits', label_lut=None):
+    def dynamic_inference(self, x, threshold=1.0, confidence='edm', edm=False, output='logits', label_lut=None, *, temperature=None):
         """reference ADD.py:379-488 -> (y, earlier_exit, seconds, confidence_value).
 
         confidence='edm' (ADD.py:379-438, the reference's working gate): three plan segments share one buffer set — trunk up to the
@@ -332,11 +332,19 @@ class ADD(AddkModule):
         launch leaves the map itself.  earlier_exit, seconds and confidence_value are those of output='logits'.  Like the logits, the
         map belongs to the cached plan and is overwritten by the next call of the same shape and mode.
 
-        A batch of more than one image raises RuntimeError on every path; any other `confidence` or `output`, or a `label_lut` that
-        is not 256 uint8 entries, raises ValueError."""
-        from ..dynamic import KINDS, OUTPUTS
+        temperature ('entropy' / 'max' only): None, a scalar, or one positive finite number per exit of forward() (num_exits() of them,
+        what calibrate.ExitCalibration.fit() returns; the gates use the first num_exits() - 1).  The gate then judges
+        softmax(z_k / T_k): only the gate value and the decision change, y is the exit's raw logits (or their arg-max map) as without
+        it.  The values live in device words of a tempered plan cached under a key of its own: changing them needs no rebuild.
+
+        A batch of more than one image raises RuntimeError on every path; any other `confidence` or `output`, a `label_lut` that
+        is not 256 uint8 entries, a temperature with 'edm', of the wrong length, non-positive or non-finite raises ValueError."""
+        from ..dynamic import KINDS, OUTPUTS, check_temperature
         if confidence != 'edm' and confidence not in KINDS:
             raise ValueError("confidence must be 'edm', 'entropy' or 'max' (got %r)" % (confidence,))
+        if temperature is not None and confidence == 'edm':
+            raise ValueError("temperature belongs to the 'entropy' and 'max' gates: the 'edm' gate judges no softmax")
+        temperature = check_temperature(temperature, self.num_exits())
         if output not in OUTPUTS:
             raise ValueError("output must be 'logits' or 'labels' (got %r)" % (output,))
         from ..plan import label_lut as _label_lut
@@ -345,13 +353,13 @@ class ADD(AddkModule):
         if x.is_cuda:
             torch.cuda.synchronize()
         tic = time.perf_counter()
-        plan = self._dynamic_plan(x, edm, *mode) if confidence == 'edm' else self._gate_plan(x, confidence, *mode)
+        plan = self._dynamic_plan(x, edm, *mode) if confidence == 'edm' else self._gate_plan(x, confidence, *mode, temperature=temperature)
         y, earlier_exit, conf = plan.run(x, threshold)
         if x.is_cuda:
             torch.cuda.synchronize()
         return y, earlier_exit, time.perf_counter() - tic, conf
 
-    def dynamic_inference_batch(self, x, threshold, confidence='entropy', label_lut=None):
+    def dynamic_inference_batch(self, x, threshold, confidence='entropy', label_lut=None, *, temperature=None):
         """dynamic_inference for a batch, label maps only -> (labels, exits, seconds, values).
 
         Every image takes the decision dynamic_inference(confidence='entropy' | 'max', output='labels') takes for it alone — exit k's
@@ -362,12 +370,19 @@ class ADD(AddkModule):
         or label_lut[class]; exits: int64 [N] on the host, the index into forward()'s outputs each image left at (num_exits() - 1:
         the final head); values: float32 [N, num_exits() - 1] on the host, NaN where a gate was not evaluated for that image.
 
-        'edm', any other `confidence`, a `label_lut` that is not 256 uint8 entries, an empty batch or a threshold sequence of the
-        wrong length raise ValueError."""
-        from ..dynamic import BatchedGate
+        `temperature`: as in dynamic_inference — every image's gates judge softmax(z_k / T_k).
+
+        'edm', any other `confidence`, a `label_lut` that is not 256 uint8 entries, an empty batch, a threshold sequence of the
+        wrong length or a bad temperature raise ValueError."""
+        from ..dynamic import BatchedGate, check_temperature
         from ..plan import label_lut as _label_lut
         lut = _label_lut(label_lut, 'cpu')
+        if temperature is not None and confidence == 'edm':
+            raise ValueError("temperature belongs to the 'entropy' and 'max' gates: the 'edm' gate judges no softmax")
+        temperature = check_temperature(temperature, self.num_exits())
         key = ('dynb', confidence, tuple(x.shape), int(L.load().addk_get_conv_precision()), None if lut is None else bytes(lut.numpy().tobytes()))
+        if temperature is not None:
+            key += ('tempered',)
         if x.is_cuda:
             torch.cuda.synchronize()
         tic = time.perf_counter()
@@ -376,7 +391,9 @@ class ADD(AddkModule):
         if bg is None or not bg.check_params():
             if bg is not None:
                 bg.close()
-            bg = plans[key] = BatchedGate(self, tuple(x.shape), confidence, lut)
+            bg = plans[key] = BatchedGate(self, tuple(x.shape), confidence, lut, temperature)
+        if temperature is not None:
+            bg.set_temperature(temperature)
         labels, exits, values = bg.run(x, threshold)
         if x.is_cuda:
             torch.cuda.synchronize()
@@ -398,15 +415,21 @@ class ADD(AddkModule):
             p = plans[key] = DynamicPlan(self, edm, x, output, self._lut_from_key(lut))
         return p
 
-    def _gate_plan(self, x, kind, output='logits', lut=None):
+    def _gate_plan(self, x, kind, output='logits', lut=None, temperature=None):
+        """`temperature`: None selects the plan and the key of the untempered gate; anything else the tempered plan, under a key that
+        records only that it is tempered — the values are device words (GatePlan.set_temperature)."""
         from ..dynamic import GatePlan
         key = ('dyn', kind, tuple(x.shape), int(L.load().addk_get_conv_precision()))
         if output != 'logits':
             key += (output, lut)
+        if temperature is not None:
+            key += ('tempered',)
         plans = self._plans()
         p = plans.get(key)
         if p is None or not p.check_params():
-            p = plans[key] = GatePlan(self, x, kind, output, self._lut_from_key(lut))
+            p = plans[key] = GatePlan(self, x, kind, output, self._lut_from_key(lut), temperature=temperature)
+        elif temperature is not None:
+            p.set_temperature(temperature)
         return p
 
 

@@ -261,7 +261,7 @@ BATCHED = {'bn_finalize': _Table('addk_bn_finalize_batch', 'C'), 'bn_bwd': _Tabl
            'allreduce': _Arena()}
 
 
-HEADS = (None, 'ce', 'score', 'profile', 'labels', 'views')     # Graph.head / OutRef.head
+HEADS = (None, 'ce', 'score', 'profile', 'labels', 'views', 'calib')     # Graph.head / OutRef.head
 
 
 class Graph:
@@ -280,13 +280,15 @@ class Graph:
         # who consumes the decoder's low-resolution logits (resize_to_nchw): None = nobody, the resize writes [N,C,OH,OW]; 'ce' = the fused
         # up-sampling + cross-entropy launch (train.TrainStep); 'score' = the scoring launch (validate.ValidationStep); 'profile' = the
         # per-image exit-profile launch (exit_profile.ExitProfile); 'labels' = the label head (dynamic plans, segment.Segmenter); 'views' =
-        # the multi-view label head: every logits output of the plan is one or more views of ONE label map (segment.MultiViewSegmenter)
+        # the multi-view label head: every logits output of the plan is one or more views of ONE label map (segment.MultiViewSegmenter);
+        # 'calib' = the calibration launch (calibrate.ExitCalibration)
         self.head = None
         self.lut = None               # 'labels' / 'views': the uint8 [256] device table the class indices go through, or None
         self.view_outs = []           # 'views': the OutRefs of the plan's logits outputs, in emission order (= kernel order of their views)
         self.view_labels = None       # 'views': the plan-owned uint8 [N,OH,OW] map, allocated by finalize()
         self._views_tag = ''          # 'views': segment tag of the last output, stamped on the one launch
         self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}; with head None or 'labels'
+        #                               optional 'temp': the device word 1 / temperature of a tempered gate (gate_head)
         self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted ('score', 'profile')
         self.pginit = set()
         self._pcols = {}
@@ -1212,8 +1214,10 @@ class Graph:
             return self._score_head(src, OH, OW)
         elif self.head == 'profile':
             return self._profile_head(src, OH, OW)
+        elif self.head == 'calib':
+            return self._calib_head(src, OH, OW)
         elif self.gate is not None:
-            return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'])
+            return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'], self.gate.get('temp'))
         elif self.head == 'labels':
             return self._label_head(src, OH, OW)
         elif self.head == 'views':
@@ -1417,10 +1421,40 @@ class Graph:
             a.pred_out = pred.data_ptr() if pred is not None else None
             ws = torch.zeros(int(lib.addk_profile_upsample_ws_bytes(N, OH, OW)), dtype=torch.uint8, device=self.device)
             a.ws = ws.data_ptr()
+            temp = pr.get('temp')
+            if temp is not None:                     # the tempered launch: entropy and shares of softmax(z * *temp)
+                b = L.ProfileUpsampleTArgs()
+                b.profile, b.inv_temp = a, temp.data_ptr()
+                self.keep += [b, ws]
+                self._add(self.fwd, 'profile_upsample_t', lib.addk_profile_upsample_t, C.byref(b),
+                          rd=self.lz(src) + [tgt, thr, temp], wr=[ent, share, cm, pred, ws])
+                return
             self.keep += [a, ws]
             self._add(self.fwd, 'profile_upsample', lib.addk_profile_upsample, C.byref(a),
                       rd=self.lz(src) + [tgt, thr], wr=[ent, share, cm, pred, ws])
         return self._late_head('profile', src, OH, OW, self.fwd, self._fwd_late, emit_profile)
+
+    def _calib_head(self, src, OH, OW):
+        """Logits output of a calibration plan (head 'calib', set by calibrate.ExitCalibration): as in _profile_head no resize is emitted and
+        no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step sets (target, the device array of inverse
+        temperatures and its length, and this exit's bins [nt,16,3] int64 and nll [nt] fp64, both added to); finalize() then appends ONE
+        `calib_upsample` launch per exit (`addk_calib_upsample`).  There is no stand-alone form: a shape the library does not take is an
+        error."""
+        lib = self.lib
+        N, H, W, Cc = src.N, src.H, src.W, src.C
+
+        def emit_calib(cb):
+            tgt, it, nt, bins, nll = cb['target'], cb['inv_temp'], cb['nt'], cb['bins'], cb['nll']
+            if lib.addk_calib_upsample_supported(N, H, W, OH, OW, Cc, nt) != 1:
+                raise L.AddkError('the calibration head takes 19 classes and 1..%d temperatures (got %d classes, %d temperatures, '
+                                  '[%d,%d,%d] -> %dx%d)' % (L.CALIB_MAX_T, Cc, nt, N, H, W, OH, OW))
+            a = self._up_args(L.CalibUpsampleArgs, src, OH, OW)
+            a.target, a.inv_temp, a.nt, a.bins, a.nll = tgt.data_ptr(), it.data_ptr(), nt, bins.data_ptr(), nll.data_ptr()
+            ws = torch.zeros(int(lib.addk_calib_upsample_ws_bytes(N, OH, OW)), dtype=torch.uint8, device=self.device)
+            a.ws = ws.data_ptr()
+            self.keep += [a, ws]
+            self._add(self.fwd, 'calib_upsample', lib.addk_calib_upsample, C.byref(a), rd=self.lz(src) + [tgt, it], wr=[bins, nll, ws])
+        return self._late_head('calib', src, OH, OW, self.fwd, self._fwd_late, emit_calib)
 
     def _label_map(self, src, OH, OW):
         """The plan-owned uint8 [N,OH,OW] label map of a label head and its OutRef (`shape`: the logits it stands for)."""
@@ -1509,7 +1543,7 @@ class Graph:
         a.out_host = host_out.data_ptr() if host_out is not None else None
         return a, ws
 
-    def gate_head(self, src, OH, OW, host_out, thr, kind='entropy'):
+    def gate_head(self, src, OH, OW, host_out, thr, kind='entropy', temp=None):
         """Logits output of a gated early exit (`self.gate`, set by dynamic.GatePlan): the exit's gate value (modeling/operations.py:161-180)
         and, separately, the resize that writes the [N,C,OH,OW] logits.  Fused form: ONE `gate_upsample` launch (`addk_gate_upsample`)
         reads the low-resolution NHWC logits and writes (entropy, share) to the OutRef's `gate_out` [N,2] and to the pinned words `host_out`;
@@ -1521,17 +1555,39 @@ class Graph:
         is left behind the cut and the host copies `gate_out` itself (`gate_fused` False).
         In a label-map plan (head 'labels') the OutRef's `y` is the uint8 [N,OH,OW] map of _label_head.  Fused form: ONE
         `gate_label_upsample` launch (`addk_gate_label_upsample`) leaves the gate value AND the map, for every image; nothing follows the
-        cut and no [N,C,OH,OW] buffer exists.  Stand-alone form: the stand-alone gate above, then, behind the cut, _labels_cold."""
+        cut and no [N,C,OH,OW] buffer exists.  Stand-alone form: the stand-alone gate above, then, behind the cut, _labels_cold.
+        `temp`: the device word 1 / temperature of a tempered gate, which judges softmax(z * *temp): ONE `gate_upsample_t` launch
+        (`addk_gate_upsample_t`) stands where `gate_upsample` / `gate_label_upsample` stand, everything else is the same.  There is no
+        stand-alone tempered form: a shape the library does not take, or ADDK_FUSE_GATE=0, is an error."""
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
         fused = _on('ADDK_FUSE_GATE') and lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
         labels, lut = self.head == 'labels', self.lut
+        if temp is not None and not fused:
+            raise L.AddkError('a tempered gate needs the fused gate launch: 19 classes and ADDK_FUSE_GATE=1 (got %d classes, [%d,%d,%d] -> %dx%d)'
+                              % (Cc, N, H, W, OH, OW))
         if not labels or not fused:
             y, emit_resize = self._logits_resize(src, OH, OW)
         gout = torch.zeros((N, 2), dtype=torch.float32, device=self.device)
         self.keep += [gout, thr, host_out]
         if labels:
             lab, out = self._label_map(src, OH, OW)
+        if temp is not None:
+            if not labels:
+                out = OutRef(y)
+            out.gate_out, out.gate_fused = gout, True
+            a = L.GateUpsampleTArgs()
+            a.gate, ws = self._gate_args(src, OH, OW, thr, gout, host_out)
+            a.inv_temp = temp.data_ptr()
+            if labels:
+                a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
+            self.keep += [a, lut, temp]
+            self._add(self.fwd, 'gate_upsample_t', lib.addk_gate_upsample_t, C.byref(a), rd=self.lz(src) + [thr, temp] + ([lut] if labels else []),
+                      wr=[gout, ws] + ([lab] if labels else []))
+            out.gate_cut = len(self.fwd)
+            if not labels:
+                emit_resize()
+            return out
         if labels and fused:
             out.gate_out, out.gate_fused = gout, True
             a = L.GateLabelUpsampleArgs()
@@ -1744,7 +1800,8 @@ class OutRef:
         self.head = None         # Graph.head of the head that consumed the logits; None: y is the real logits.  'labels': y is the label map
         self.src = None          # 'views', 'ce': the lazy activation of the decoder's low-resolution logits this output stands for
         # what the step binds to a 'ce' / 'score' / 'profile' head before finalize() — 'ce': target, class_w, ignore_index, wsum, scale, loss;
-        # 'score': those + entropy, confusion, pred; 'profile': target, thr, nthr, entropy, share, confusion, pred; 'views': N, views
+        # 'score': those + entropy, confusion, pred; 'profile': target, thr, nthr, entropy, share, confusion, pred and optionally temp (the
+        # device word 1 / temperature: the tempered launch); 'views': N, views; 'calib': target, inv_temp, nt, bins, nll
         self.binding = None
         self.gate_out = None     # [N,2] device tensor of a gated exit: (entropy, share of pixels above the threshold)
         self.gate_scale = 1.0    # factor the host applies to gate_out[:, 0] (the stand-alone entropy kernel leaves a sum)

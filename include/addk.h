@@ -785,6 +785,58 @@ int addk_profile_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH,
 int64_t addk_profile_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW);
 int addk_profile_upsample(const addk_profile_upsample_args* a, void* stream);
 
+/* Tempered gate and profile: the launches above with every per-pixel probability taken from softmax(z * *inv_temp) instead of
+ * softmax(z) — d = (z - max z) * *inv_temp, then the same sweep (sum e, sum e*d), entropy term, top probability 1 / sum e and
+ * comparison.  inv_temp: one device-readable word, the inverse of a temperature (positive, finite), read when the launch runs, so
+ * a captured graph serves every temperature.  With *inv_temp == 1.0f the outputs carry the bits of the untempered launch on the
+ * same input (a multiply by 1.0f is exact; nothing else differs).  The arg-max does not depend on the temperature: labels,
+ * pred_out and cm are the bytes of the untempered launches at any temperature.
+ * addk_gate_upsample_t: labels == NULL is addk_gate_upsample (lut256 is ignored), otherwise addk_gate_label_upsample.
+ * Workspaces, support predicates and refusals are those of the launch each one tempers; a null inv_temp is refused as well. */
+typedef struct {
+  addk_gate_upsample_args gate;
+  const float* inv_temp;             /* device-readable word: 1 / temperature */
+  const uint8_t* lut256;             /* NULL: the class index; else lut256[class] */
+  uint8_t* labels;                   /* [N,OH,OW], or NULL: the gate alone */
+} addk_gate_upsample_t_args;
+int addk_gate_upsample_t(const addk_gate_upsample_t_args* a, void* stream);
+typedef struct {
+  addk_profile_upsample_args profile;
+  const float* inv_temp;             /* device-readable word: 1 / temperature */
+} addk_profile_upsample_t_args;
+int addk_profile_upsample_t(const addk_profile_upsample_t_args* a, void* stream);
+
+/* Calibration head (temperature scaling, Guo et al. 2017): what the reliability diagram, the expected calibration error and the
+ * fit of one temperature need of one exit, for up to ADDK_CALIB_MAX_T temperatures at once, in ONE launch over the LOW-resolution
+ * NHWC logits [N,H,W,C] (the walk and the bilinear arithmetic of the heads above: z carries the bits addk_resize_fwd writes; no
+ * [N,C,OH,OW] tensor exists).  Per pixel whose target t lies in [0, C) (the evaluator's mask, as addk_profile_upsample), with
+ * mx = max z and am = arg-max z (strict >: a tie keeps the lowest channel), and per temperature j:
+ *   se_j   = sum_c exp((z_c - mx) * inv_temp[j])        every exponent <= 0: nothing overflows for any temperature
+ *   nll_j  = log(se_j) - (z_t - mx) * inv_temp[j]
+ *   conf_j = 1 / se_j,   b = min(ADDK_CALIB_BINS - 1, (int)(conf_j * ADDK_CALIB_BINS))
+ *   bins[j][b] += (1, am == t, llrintf(conf_j * 2^24));   nll[j] += nll_j
+ * Both outputs are ADDED to: the caller zeroes them.  Deterministic: the bins take integer atomics (into replicas inside ws, which
+ * the last-arriving workgroup sums into bins and leaves at zero); the NLL leaves every workgroup as one fp32 partial per temperature,
+ * and the last-arriving workgroup adds them in a fixed order in fp64 and adds the launch's sum to nll[j] once.  No floating-point
+ * atomics.  ws: addk_calib_upsample_ws_bytes() bytes, ZERO-initialised once (the ticket word is
+ * left at zero: replayable from a hipGraph).  addk_calib_upsample_supported() is 0 where addk_score_upsample_supported() is, and for
+ * nt outside [1, ADDK_CALIB_MAX_T]; addk_calib_upsample then returns ADDK_ERR_INVALID without launching, as it does for a null
+ * pointer or ld < C. */
+#define ADDK_CALIB_MAX_T 8
+#define ADDK_CALIB_BINS 16
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
+  int32_t N, H, W, C, OH, OW;
+  const int64_t* target;             /* [N,OH,OW] */
+  const float* inv_temp; int32_t nt; /* device [nt]: 1 / temperature, read when the launch runs */
+  int64_t* bins;                     /* device [nt][ADDK_CALIB_BINS][3]: count, hits, confidence sum in units of 2^-24; accumulated */
+  double* nll;                       /* device [nt]: sum of the NLL over the counted pixels; accumulated */
+  void* ws;                          /* addk_calib_upsample_ws_bytes() zero-initialised bytes */
+} addk_calib_upsample_args;
+int addk_calib_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C, int32_t nt);
+int64_t addk_calib_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW);
+int addk_calib_upsample(const addk_calib_upsample_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Fused SGD (torch.optim.SGD(momentum, weight_decay, nesterov), train.py:126) on a flat buffer.
  *   d = g*gscale + wd*p;  buf = first ? d : mom*buf + d;  p -= lr*(nesterov ? d + mom*buf : buf)
