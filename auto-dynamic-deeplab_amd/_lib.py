@@ -138,6 +138,18 @@ class CalibUpsampleArgs(C.Structure):
                 ('target', vp), ('inv_temp', vp), ('nt', i32), ('bins', vp), ('nll', vp), ('ws', vp)]
 
 
+TRIMAP_MAX_RADIUS, TRIMAP_MAX_WIDTHS, TRIMAP_FAR = 64, 8, 255
+
+
+class BoundaryDistArgs(C.Structure):
+    _fields_ = [('target', vp), ('N', i32), ('OH', i32), ('OW', i32), ('C', i32), ('radius', i32), ('dist', vp), ('ws', vp)]
+
+
+class ConfusionBandedArgs(C.Structure):
+    _fields_ = [('target', vp), ('pred', vp), ('dist', vp), ('N', i32), ('OH', i32), ('OW', i32), ('C', i32), ('nw', i32),
+                ('width', i32 * TRIMAP_MAX_WIDTHS), ('cm', vp), ('image_stride', i64)]
+
+
 class RowsItem(C.Structure):
     _fields_ = [('src', vp), ('dst', vp), ('row_bytes', i64)]
 
@@ -349,6 +361,11 @@ _SIGS = {
     'addk_entropy_sum': (i32, [vp, i32, i32, i64, vp, vp, vp]),
     'addk_argmax_nchw': (i32, [vp, i32, i32, i64, vp, vp]),
     'addk_confusion': (i32, [vp, vp, i64, i32, vp, vp]),
+    'addk_boundary_dist_supported': (i32, [i32, i32, i32, i32, i32]),
+    'addk_boundary_dist_ws_bytes': (i64, [i32, i32, i32]),
+    'addk_boundary_dist': (i32, [C.POINTER(BoundaryDistArgs), vp]),
+    'addk_confusion_banded_supported': (i32, [i32, i32, i32, i32, i32]),
+    'addk_confusion_banded': (i32, [C.POINTER(ConfusionBandedArgs), vp]),
     'addk_gather_rows': (i32, [C.POINTER(GatherRowsArgs), vp]),
 }
 

@@ -22,6 +22,7 @@ softmax(z_k / T_k), what dynamic_inference(..., temperature=) judges — the cur
 import torch
 
 from . import _lib as L
+from . import trimap as _trimap
 from .dynamic import KINDS, check_temperature, inverse_words
 from .metrics import mean_iou
 from .resident import InferenceStep
@@ -38,7 +39,7 @@ def _check_thresholds(ts):
     return tuple(ts)
 
 
-def exit_curve(entropy, share, confusion, kind, thresholds, max_thresholds=None, exit_ms=None):
+def exit_curve(entropy, share, confusion, kind, thresholds, max_thresholds=None, exit_ms=None, band_confusion=None, widths=None):
     """Operating points of the early-exit network from per-image records, on CPU tensors:
     entropy [nex, M] fp32, share [nex, M, NT] fp32 (NT = len(max_thresholds)), confusion [nex, M, C, C] int64.
 
@@ -51,12 +52,19 @@ def exit_curve(entropy, share, confusion, kind, thresholds, max_thresholds=None,
     `exit_of_image` (int64 [M]; nex-1 is the final exit), `exit_counts` (images per exit), `num_earlier_exit` (percent of M),
     `avg_confidence` (mean over the M images; `confidence_of_image` holds the M values, fp64).  With `exit_ms` (one latency per exit,
     measured by the caller) also `expected_ms` = sum_k exit_counts[k] * exit_ms[k] / M and `fps` = 1000 / expected_ms: a PROJECTION from the supplied latencies
-    (`projected_from_exit_ms` is True), nothing here is timed."""
+    (`projected_from_exit_ms` is True), nothing here is timed.
+
+    With `band_confusion` [nex, M, nw, C, C] int64 (per image, cumulative over `widths`: ExitProfile.records()) every point also has
+    `trimap`: one dict per width with `width`, `confusion` (the chosen exits' band matrices summed), `mIoU` and `pixels`."""
     if kind not in KINDS:
         raise ValueError('kind must be one of %s (got %r)' % (KINDS, kind))
     nex, M = int(entropy.shape[0]), int(entropy.shape[1])
     if tuple(confusion.shape[:2]) != (nex, M):
         raise ValueError('confusion is %s for entropy %s' % (tuple(confusion.shape), tuple(entropy.shape)))
+    if band_confusion is not None:
+        widths = tuple(int(w) for w in (widths if widths is not None else ()))
+        if band_confusion.dim() != 5 or tuple(band_confusion.shape[:3]) != (nex, M, len(widths)):
+            raise ValueError('band_confusion is %s for %d exits, %d images and %d widths' % (tuple(band_confusion.shape), nex, M, len(widths)))
     if exit_ms is not None:
         exit_ms = [float(v) for v in exit_ms]
         if len(exit_ms) != nex:
@@ -92,6 +100,10 @@ def exit_curve(entropy, share, confusion, kind, thresholds, max_thresholds=None,
             pt['expected_ms'] = sum(c * ms for c, ms in zip(counts, exit_ms)) / M
             pt['fps'] = 1000.0 / pt['expected_ms']
             pt['projected_from_exit_ms'] = True
+        if band_confusion is not None:
+            bands = band_confusion[exit_of, torch.arange(M)].sum(0) if M else band_confusion.new_zeros(band_confusion.shape[2:])
+            fig = _trimap.band_figures(bands).reshape(2, len(widths))
+            pt['trimap'] = _trimap.band_entries(widths, bands, (fig[0], fig[1]))
         points.append(pt)
     return points
 
@@ -100,8 +112,10 @@ class ExitProfile(InferenceStep):
     head = 'profile'
 
     def __init__(self, model, batch_shape, max_thresholds=(0.5, 0.9, 0.99), ignore_index=255, keep_predictions=False,
-                 use_graph=None, nstreams=None, temperature=None):
+                 use_graph=None, nstreams=None, temperature=None, trimap=None):
         self.max_thresholds = _check_thresholds(max_thresholds)
+        # boundary-band mIoU (trimap.py): None, or the ladder of widths in pixels
+        self.trimap = _trimap.check_widths(trimap) if trimap is not None else None
         self.temperature = check_temperature(temperature, model.num_exits())
         super().__init__(model, batch_shape, use_graph, nstreams)
         # 1 / T of every exit: the words the tempered launches read (None: the untempered plan)
@@ -153,12 +167,23 @@ class ExitProfile(InferenceStep):
             self.ent = torch.zeros((nex, N), dtype=torch.float32, device=dev)             # this batch, per exit and image
             self.share = torch.zeros((nex, N, NT), dtype=torch.float32, device=dev)
             self.cm = torch.zeros((nex, N, ncls, ncls), dtype=torch.int64, device=dev)
-            self.pred = torch.zeros((nex, N, H, W), dtype=torch.uint8, device=dev) if self.keep_predictions else None
+            # the band launches read the uint8 maps: with a trimap they exist whether or not predictions() hands them out
+            want_pred = self.keep_predictions or self.trimap is not None
+            self.pred = torch.zeros((nex, N, H, W), dtype=torch.uint8, device=dev) if want_pred else None
+            if self.trimap is not None:
+                self.rings = torch.zeros((nex, N, len(self.trimap), ncls, ncls), dtype=torch.int64, device=dev)   # this batch, per image
+                self.dist = torch.zeros((N, H, W), dtype=torch.uint8, device=dev)
         # the launch adds into the matrices: zero bits of int64 written as twice as many fp32 zeros
         g._add(g.fwd, 'profile_zero', self.lib.addk_fill, self.cm.data_ptr(), 2 * self.cm.numel(), 0.0, wr=[self.cm])
+        if self.trimap is not None:
+            g._add(g.fwd, 'trimap_zero', self.lib.addk_fill, self.rings.data_ptr(), 2 * self.rings.numel(), 0.0, wr=[self.rings])
+            _trimap.emit_boundary_dist(g, self.target, self.dist, ncls, self.trimap)          # one distance map for every exit
         for i, o in enumerate(outs):
             o.binding = dict(target=self.target, thr=self.thr, nthr=NT, entropy=self.ent[i], share=self.share[i], confusion=self.cm[i],
                              pred=self.pred[i] if self.pred is not None else None)
+            if self.trimap is not None:
+                o.binding['trimap'] = dict(rings=self.rings[i], widths=self.trimap, dist=self.dist,
+                                           image_stride=len(self.trimap) * ncls * ncls)
             if self.temp is not None:
                 o.binding['temp'] = self.temp[i:i + 1]
         self.outs = outs
@@ -176,7 +201,8 @@ class ExitProfile(InferenceStep):
             self.load_batch(images, targets)
         self._replay()
         # outside the captured region, ordered behind it on the same stream: copies of the batch's rows
-        self._log.append((self.ent[:, :count].clone(), self.share[:, :count].clone(), self.cm[:, :count].clone()))
+        row = (self.ent[:, :count].clone(), self.share[:, :count].clone(), self.cm[:, :count].clone())
+        self._log.append(row + (self.rings[:, :count].clone(),) if self.trimap is not None else row)
         self.batches += 1
 
     # ---------------- results ----------------
@@ -186,19 +212,30 @@ class ExitProfile(InferenceStep):
     def records(self):
         """The single synchronisation of a pass: `entropy` [nex, M] fp32, `share` [nex, M, NT] fp32 and `confusion` [nex, M, C, C] int64
         of the M images logged since reset(), on the CPU, and `static`: per exit the summed `confusion` and its `mIoU` by
-        metrics.mean_iou — the figures ValidationStep.result() reports for the same images."""
+        metrics.mean_iou — the figures ValidationStep.result() reports for the same images.  Built with `trimap=widths`: also
+        `trimap_widths`, `band_confusion` [nex, M, nw, C, C] int64 (per image, cumulative over the widths: the pixels within widths[j] of a
+        ground-truth class boundary, include/addk.h) and, in every `static[i]`, `trimap` as in ValidationStep.result()."""
         if self._rec is not None and self._rec[0] == len(self._log):
             return self._rec[1]
         nex, NT, C_ = self.nex, len(self.max_thresholds), self.ncls
         if self._log:
-            ent, share, cm = (torch.cat(ts, dim=1) for ts in zip(*self._log))
+            ent, share, cm, *rings = (torch.cat(ts, dim=1) for ts in zip(*self._log))
         else:
             ent, share = self.ent.new_zeros((nex, 0)), self.share.new_zeros((nex, 0, NT))
             cm = self.cm.new_zeros((nex, 0, C_, C_))
+            rings = [self.rings.new_zeros((nex, 0) + tuple(self.rings.shape[2:]))] if self.trimap is not None else []
         total = cm.sum(1)
         miou = torch.stack([mean_iou(total[i]) for i in range(nex)]).cpu()
         rec = dict(entropy=ent.cpu(), share=share.cpu(), confusion=cm.cpu(), max_thresholds=self.max_thresholds,
                    static=[dict(confusion=c, mIoU=float(m)) for c, m in zip(total.cpu(), miou)])
+        if self.trimap is not None:
+            bands = rings[0].cumsum(2)             # the rings are disjoint: "within w[j]" is their prefix sum
+            cum = bands.sum(1)
+            fig = _trimap.band_figures(cum).cpu().reshape(2, nex, len(self.trimap))
+            cum = cum.cpu()
+            for i, s in enumerate(rec['static']):
+                s['trimap'] = _trimap.band_entries(self.trimap, cum[i], (fig[0, i], fig[1, i]))
+            rec['band_confusion'], rec['trimap_widths'] = bands.cpu(), self.trimap
         self._rec = (len(self._log), rec)
         return rec
 
@@ -209,7 +246,8 @@ class ExitProfile(InferenceStep):
                 raise ValueError("curve(%r) needs thresholds; only 'max' has recorded ones" % (kind,))
             thresholds = self.max_thresholds
         r = self.records()
-        return exit_curve(r['entropy'], r['share'], r['confusion'], kind, thresholds, self.max_thresholds, exit_ms)
+        return exit_curve(r['entropy'], r['share'], r['confusion'], kind, thresholds, self.max_thresholds, exit_ms,
+                          band_confusion=r.get('band_confusion'), widths=r.get('trimap_widths'))
 
     def predictions(self):
         """uint8 [N,H,W] arg-max maps of the last batch, one per exit (keep_predictions=True)."""

@@ -1367,7 +1367,8 @@ class Graph:
         sets (target, class weights, wsum and the per-exit loss / entropy / confusion / prediction tensors); finalize() then appends
         ONE `score_upsample` launch per exit to the forward list (`addk_score_upsample`).  Where the library does not take the shape
         (`addk_score_upsample_supported` == 0, e.g. C != 19) the same quantities come from the stand-alone kernels inside this plan:
-        resize + ce_fwd_bwd without a gradient + argmax_nchw + confusion + entropy_sum."""
+        resize + ce_fwd_bwd without a gradient + argmax_nchw + confusion + entropy_sum.  A binding with `trimap` (_confusion_banded) adds
+        ONE `confusion_banded` launch behind the exit's `score_upsample`; the stand-alone path refuses it (ValueError)."""
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
 
@@ -1382,7 +1383,12 @@ class Graph:
                 self.keep += [a, ws]
                 self._add(self.fwd, 'score_upsample', lib.addk_score_upsample, C.byref(a),
                           rd=self.lz(src) + [tgt, wsum], wr=[loss, ent, cm, pred, ws])
+                if sc.get('trimap') is not None:
+                    self._confusion_banded(sc['trimap'], tgt, pred, N, OH, OW, Cc)
             else:
+                if sc.get('trimap') is not None:
+                    raise ValueError('the trimap metric reads the uint8 map of the fused scoring head, which does not take this exit '
+                                     '(%d classes, [%d,%d,%d] -> %dx%d): the stand-alone path keeps an int64 map' % (Cc, N, H, W, OH, OW))
                 y, emit_resize = self._logits_resize(src, OH, OW)
                 am = torch.empty((N, OH, OW), dtype=torch.int64, device=self.device)
                 ws = torch.zeros(int(lib.addk_ce_ws_floats(N, OH * OW)), dtype=torch.float32, device=self.device)
@@ -1406,7 +1412,8 @@ class Graph:
         and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step sets (target, the device array of
         top-probability thresholds and its length, and this exit's per-image entropy [N], share [N,nthr], confusion [N,C,C] and optional
         prediction tensors); finalize() then appends ONE `profile_upsample` launch per exit (`addk_profile_upsample`).  There is no
-        stand-alone form: a shape the library does not take is an error."""
+        stand-alone form: a shape the library does not take is an error.  A binding with `trimap` (_confusion_banded) adds ONE
+        `confusion_banded` launch behind the exit's profile launch."""
         lib = self.lib
         N, H, W, Cc = src.N, src.H, src.W, src.C
 
@@ -1428,11 +1435,31 @@ class Graph:
                 self.keep += [b, ws]
                 self._add(self.fwd, 'profile_upsample_t', lib.addk_profile_upsample_t, C.byref(b),
                           rd=self.lz(src) + [tgt, thr, temp], wr=[ent, share, cm, pred, ws])
-                return
-            self.keep += [a, ws]
-            self._add(self.fwd, 'profile_upsample', lib.addk_profile_upsample, C.byref(a),
-                      rd=self.lz(src) + [tgt, thr], wr=[ent, share, cm, pred, ws])
+            else:
+                self.keep += [a, ws]
+                self._add(self.fwd, 'profile_upsample', lib.addk_profile_upsample, C.byref(a),
+                          rd=self.lz(src) + [tgt, thr], wr=[ent, share, cm, pred, ws])
+            if pr.get('trimap') is not None:
+                self._confusion_banded(pr['trimap'], tgt, pred, N, OH, OW, Cc)
         return self._late_head('profile', src, OH, OW, self.fwd, self._fwd_late, emit_profile)
+
+    def _confusion_banded(self, tm, tgt, pred, N, OH, OW, Cc):
+        """ONE `confusion_banded` launch (`addk_confusion_banded`) behind the head launch of an exit whose binding carries `trimap`: a dict
+        with `rings` (int64 [nw,C,C], or [N,nw,C,C] with `image_stride` = nw*C*C; added to), `widths` and `dist` (the uint8 map the step's one
+        `boundary_dist` launch writes).  It reads the head's uint8 prediction map."""
+        lib, widths = self.lib, tm['widths']
+        assert pred is not None, 'a trimap binding needs the exit\'s uint8 prediction map'
+        if lib.addk_confusion_banded_supported(N, OH, OW, Cc, len(widths)) != 1:
+            raise ValueError('the trimap metric takes 1 to 32 classes, 1 to %d widths and fewer than 2^31 pixels (got %d classes, %d widths, '
+                             '[%d,%d,%d])' % (L.TRIMAP_MAX_WIDTHS, Cc, len(widths), N, OH, OW))
+        a = L.ConfusionBandedArgs()
+        a.target, a.pred, a.dist = tgt.data_ptr(), pred.data_ptr(), tm['dist'].data_ptr()
+        a.N, a.OH, a.OW, a.C, a.nw = N, OH, OW, Cc, len(widths)
+        for j, w in enumerate(widths):
+            a.width[j] = w
+        a.cm, a.image_stride = tm['rings'].data_ptr(), tm.get('image_stride', 0)
+        self.keep.append(a)
+        self._add(self.fwd, 'confusion_banded', lib.addk_confusion_banded, C.byref(a), rd=[tgt, pred, tm['dist']], wr=[tm['rings']])
 
     def _calib_head(self, src, OH, OW):
         """Logits output of a calibration plan (head 'calib', set by calibrate.ExitCalibration): as in _profile_head no resize is emitted and

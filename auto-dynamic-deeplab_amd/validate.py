@@ -13,6 +13,7 @@ import math
 import torch
 
 from . import _lib as L
+from . import trimap as _trimap
 from .metrics import mean_iou
 from .resident import InferenceStep
 
@@ -21,8 +22,10 @@ class ValidationStep(InferenceStep):
     head = 'score'
 
     def __init__(self, model, batch_shape, class_weight=None, ignore_index=255, keep_predictions=False, use_graph=None,
-                 nstreams=None):
+                 nstreams=None, trimap=None):
         super().__init__(model, batch_shape, use_graph, nstreams)
+        # boundary-band mIoU (trimap.py): None, or the ladder of widths in pixels
+        self.trimap = _trimap.check_widths(trimap) if trimap is not None else None
         self.ignore_index = int(ignore_index)
         self.keep_predictions = bool(keep_predictions)
         self.cw = class_weight.to(self.dev).float().contiguous() if class_weight is not None else None
@@ -42,17 +45,26 @@ class ValidationStep(InferenceStep):
             self.scal = torch.zeros(2 * nex, dtype=torch.float32, device=dev)     # this batch: [loss per exit | entropy sum per exit]
             self.acc = torch.zeros(2 * nex, dtype=torch.float64, device=dev)      # running sums of `scal` over the batches
             self.cm = torch.zeros((nex, ncls, ncls), dtype=torch.int64, device=dev)
-            self.pred = torch.zeros((nex, N, H, W), dtype=torch.uint8, device=dev) if self.keep_predictions else None
-        ws = torch.zeros(int(lib.addk_ce_ws_floats(N, H * W)), dtype=torch.float32, device=dev)
+            # the band launches read the uint8 maps: with a trimap they exist whether or not predictions() hands them out
+            want_pred = self.keep_predictions or self.trimap is not None
+            self.pred = torch.zeros((nex, N, H, W), dtype=torch.uint8, device=dev) if want_pred else None
+            if self.trimap is not None:
+                self.rings = torch.zeros((nex, len(self.trimap), ncls, ncls), dtype=torch.int64, device=dev)   # accumulate like `cm`
+                self.dist = torch.zeros((N, H, W), dtype=torch.uint8, device=dev)
+        ws =torch.zeros(int(lib.addk_ce_ws_floats(N, H * W)), dtype=torch.float32, device=dev)
         self._keep = [ws]
         cwp = self.cw.data_ptr() if self.cw is not None else None
         g._add(g.fwd, 'score_zero', lib.addk_fill, self.scal.data_ptr(), 2 * nex, 0.0, wr=[self.scal])
         g._add(g.fwd, 'ce_count', lib.addk_ce_count, self.target.data_ptr(), N * H * W, cwp, self.ignore_index, ncls,
                self.wsum.data_ptr(), ws.data_ptr(), rd=[self.target], wr=[self.wsum, ws])      # one count for every exit
+        if self.trimap is not None:
+            _trimap.emit_boundary_dist(g, self.target, self.dist, ncls, self.trimap)          # one distance map for every exit
         for i, o in enumerate(outs):
             o.binding = dict(target=self.target, class_w=cwp, ignore_index=self.ignore_index, wsum=self.wsum, scale=1.0,
                              loss=self.scal[i:i + 1], entropy=self.scal[nex + i:nex + i + 1], confusion=self.cm[i],
                              pred=self.pred[i] if self.pred is not None else None)
+            if self.trimap is not None:
+                o.binding['trimap'] = dict(rings=self.rings[i], widths=self.trimap, dist=self.dist)
         self.outs = outs
 
     # ---------------- replay ----------------
@@ -72,24 +84,38 @@ class ValidationStep(InferenceStep):
     def reset(self):
         self.acc.zero_()
         self.cm.zero_()
+        if self.trimap is not None:
+            self.rings.zero_()
         self.batches = 0
 
     def result(self):
         """The single synchronisation of a pass.  Per exit: `confusion` (int64 device tensor), `mIoU` (Evaluator's formula),
         `confidence` (mean over batches of the normalised Shannon entropy, the reference's AverageMeter) and `loss` (mean over
-        batches); `test_loss` = sum over batches of the mean over exits (train.py:272-273), `new_pred` = mean mIoU (train.py:313)."""
+        batches); `test_loss` = sum over batches of the mean over exits (train.py:272-273), `new_pred` = mean mIoU (train.py:313).
+        Built with `trimap=widths`: also `trimap_widths` and, per exit, `trimap`: one dict per width with `width`, `confusion` (int64 [C,C]
+        over the pixels within `width` of a ground-truth class boundary, include/addk.h), its `mIoU` and `pixels`."""
         nex = self.nex
         _, _, H, W = self.batch_shape
         miou = torch.stack([mean_iou(self.cm[i]) for i in range(nex)]).double()
-        host = torch.cat([self.acc, miou]).cpu()
+        parts = [self.acc, miou]
+        if self.trimap is not None:
+            cum = self.rings.cumsum(1)             # the rings are disjoint: "within w[j]" is their prefix sum
+            parts.append(_trimap.band_figures(cum))
+        host = torch.cat(parts).cpu()
         nb = max(self.batches, 1)
         norm = math.log(self.ncls) * H * W     # operations.py:161-170: per pixel and per log C, not per image
         exits = []
         for i in range(nex):
             exits.append(dict(confusion=self.cm[i].clone(), mIoU=float(host[2 * nex + i]),
                               confidence=float(host[nex + i]) / norm / nb, loss=float(host[i]) / nb))
-        return dict(exits=exits, test_loss=float(host[:nex].sum()) / nex, new_pred=sum(e['mIoU'] for e in exits) / nex,
-                    batches=self.batches)
+        r = dict(exits=exits, test_loss=float(host[:nex].sum()) / nex, new_pred=sum(e['mIoU'] for e in exits) / nex,
+                 batches=self.batches)
+        if self.trimap is not None:
+            fig = host[3 * nex:].reshape(2, nex, len(self.trimap))
+            for i, e in enumerate(exits):
+                e['trimap'] = _trimap.band_entries(self.trimap, cum[i], (fig[0, i], fig[1, i]))
+            r['trimap_widths'] = self.trimap
+        return r
 
     def predictions(self):
         """uint8 [N,H,W] arg-max maps of the last batch, one per exit (keep_predictions=True)."""

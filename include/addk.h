@@ -876,6 +876,62 @@ int addk_argmax_nchw(const float* logits, int32_t N, int32_t C, int64_t HW, int6
 int addk_confusion(const int64_t* gt, const int64_t* pred, int64_t n, int32_t num_class, int64_t* cm, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Boundary-band ("trimap") confusion (csrc/trimap.hip): the confusion matrix restricted to the pixels within d pixels of a ground-truth
+ * class boundary, for a ladder of d (the trimap plot of the DeepLab papers).  Integer-only; the semantics are this project's own.
+ *
+ * For one image with target t (int64 [OH,OW]) and C classes:
+ *   valid(p)  : 0 <= t(p) < C, compared as 64-bit values.
+ *   E(p)      : p is an EDGE pixel when valid(p) and some 4-neighbour q INSIDE THE SAME IMAGE has valid(q) and t(q) != t(p).  The image
+ *               border makes no edge; a neighbour that is ignore or out of range makes no edge; two different invalid values make none.
+ *   D2(p)     : min over the edge pixels e of the same image of (py-ey)^2 + (px-ex)^2 (squared Euclidean distance; 0 on an edge pixel).
+ *   dist[p]   : the smallest integer k >= 0 with k*k >= D2(p) when k <= radius; otherwise, and when the image has no edge pixel,
+ *               ADDK_TRIMAP_FAR.  1 <= radius <= ADDK_TRIMAP_MAX_RADIUS.  For an integer d <= radius, "p lies within d of a
+ *               boundary" is exactly dist[p] <= d.  dist is defined for every pixel, valid or not.
+ * The definition is separable and the kernels use that form: h(y,x) = min |x-x'| over E(y,x'), and
+ * D2(y,x) = min over |dy| <= radius of dy^2 + h(y+dy,x)^2 with h <= radius (a nearest edge pixel within the radius has both offsets
+ * within it, so the windowed search is exact).  It is Euclidean, not Chebyshev or Manhattan: one foreign pixel in a uniform field
+ * gives discs.
+ *
+ * addk_boundary_dist: two launches on `stream` — edge flags (64-bit ballot words) and the row distance h as bytes into ws, then the
+ * column pass over an LDS tile of h with a halo of `radius` rows that never crosses an image.  ws needs no initialisation.
+ *
+ * Banded confusion, for strictly ascending integer widths w[0..nw) with 0 <= w[j] <= 254 and nw <= ADDK_TRIMAP_MAX_WIDTHS:
+ *   ring j holds the pixels with w[j-1] < dist <= w[j] (w[-1] = -1).  A pixel is counted when valid(p), pred[p] < C and
+ *   dist[p] <= w[nw-1]; it adds 1 to cm[ring][t*C + pred].  The rings are disjoint (one atomic per pixel); the matrix "within w[j]"
+ *   is the prefix sum over the rings, taken by the caller.  A pred byte >= C is skipped, never used as an index.
+ * addk_confusion_banded: one launch; per-workgroup LDS histograms flushed with 64-bit integer atomics.
+ *
+ * *_supported is 0 for non-positive sizes, C outside [1, 32], radius outside [1, ADDK_TRIMAP_MAX_RADIUS], nw outside
+ * [1, ADDK_TRIMAP_MAX_WIDTHS] and N*OH*OW >= 2^31.  The launchers return ADDK_ERR_INVALID WITHOUT launching where *_supported is 0,
+ * for a null pointer, for widths that are not strictly ascending or outside [0, 254], and for 0 < image_stride < nw*C*C.  Both work on
+ * the stream only (no host reads, no memsets, no state left behind: a captured hipGraph replays them), and their only atomics are
+ * integer atomics: two calls give equal bits.
+ * ------------------------------------------------------------------------------------- */
+#define ADDK_TRIMAP_MAX_RADIUS 64
+#define ADDK_TRIMAP_MAX_WIDTHS 8
+#define ADDK_TRIMAP_FAR 255
+typedef struct {
+  const int64_t* target;            /* [N,OH,OW] */
+  int32_t N, OH, OW, C, radius;
+  uint8_t* dist;                    /* [N,OH,OW], written (every byte) */
+  void* ws;                         /* addk_boundary_dist_ws_bytes() bytes, needs no initialisation */
+} addk_boundary_dist_args;
+int     addk_boundary_dist_supported(int32_t N, int32_t OH, int32_t OW, int32_t C, int32_t radius);
+int64_t addk_boundary_dist_ws_bytes(int32_t N, int32_t OH, int32_t OW);
+int     addk_boundary_dist(const addk_boundary_dist_args* a, void* stream);
+
+typedef struct {
+  const int64_t* target; const uint8_t* pred; const uint8_t* dist;   /* [N,OH,OW] each */
+  int32_t N, OH, OW, C, nw;
+  int32_t width[ADDK_TRIMAP_MAX_WIDTHS];
+  int64_t* cm;                      /* ring matrices, ADDED to: the caller zeroes them */
+  int64_t image_stride;             /* 0: one set [nw][C][C] for the batch; else int64 words between the sets of
+                                       consecutive images (>= nw*C*C): per-image matrices */
+} addk_confusion_banded_args;
+int addk_confusion_banded_supported(int32_t N, int32_t OH, int32_t OW, int32_t C, int32_t nw);
+int addk_confusion_banded(const addk_confusion_banded_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Row gather / scatter over several buffers in ONE launch (csrc/rows.hip): batch compaction of batched dynamic inference
  * (dynamic.BatchedGate).  Every item is a buffer of equal-sized rows (one row per image); for every item i and every r < nrows the launch
  * copies row_bytes bytes from  src + src_row[r] * row_bytes  to  dst + dst_row[r] * row_bytes.  A NULL index array stands for 0..nrows-1.
