@@ -6,7 +6,7 @@ one threshold for all exits.  Temperature scaling fits one scalar T per exit by 
 set; the arg-max does not move, so label maps and mIoU are untouched, and the gates then judge softmax(z_k / T_k).
 
 ExitCalibration runs the static, batched inference plan of resident.InferenceStep and ends every exit in one `addk_calib_upsample`
-launch (plan.Graph.head 'calib', csrc/calib_up.hip) that adds, for up to 8 temperatures at once, the reliability bins (16 equal-width
+launch (plan.Graph.head 'calib': heads._calib_head, csrc/calib_up.hip) that adds, for up to 8 temperatures at once, the reliability bins (16 equal-width
 bins of the top probability: count, hits, confidence sum) and the NLL sum of the exit's up-sampled prediction to device accumulators.
 
     cal = ExitCalibration(model, (N, 3, H, W))

@@ -15,7 +15,7 @@ logits are written only for the image that leaves.  Exit k's logits are forward(
 and conv_aspp[k] when the level differs; no EDM runs, so its in-place ReLU (Q3) does not happen.  The 2^-last size (Q5) is a
 quirk of the working 'edm' path and stays only there: the heads training optimises are forward()'s.
 
-output='labels' (both plans): every exit ends in a label head instead (plan.Graph.head 'labels') and returns the plan-owned uint8 [1,H,W]
+output='labels' (both plans): every exit ends in a label head instead (plan.Graph.head 'labels', heads.py) and returns the plan-owned uint8 [1,H,W]
 arg-max map of its logits; no [N,C,H,W] buffer exists.  'edm': [early head k] and the final head end in one `label_upsample` launch.
 'entropy' / 'max': the gate launch leaves the map as well (`gate_label_upsample`), so nothing is left to replay for the image that
 leaves — [trunk up to exit k] [head k + the gate-and-labels launch] ... [remaining cells + final head + its `label_upsample`]."""
@@ -28,7 +28,8 @@ import torch
 from . import _lib as L
 from . import plan as _plan
 from .module import ensure_layout
-from .plan import Act, Cmd, Graph, OutRef, env_graph_infer, env_streams, label_lut as _label_lut
+from .heads import label_lut as _label_lut
+from .plan import Act, Cmd, Graph, OutRef, env_graph_infer, env_streams
 
 OUTPUTS = ('logits', 'labels')
 

@@ -5,7 +5,7 @@ the average confidence; a sweep repeats the whole set per threshold.  For the 'e
 what the gate reads depends on the threshold of the DECISION: exit k's prediction is forward()'s `model(x)[k]`, its entropy is one
 number per image, and its top-probability share is one number per image and per top-probability threshold.  ExitProfile therefore runs
 the static, batched inference plan of resident.InferenceStep and ends every exit in one `addk_profile_upsample` launch
-(plan.Graph.head 'profile', csrc/score_up.hip profile_up_kernel) that leaves, PER IMAGE, the entropy, the share at each of `max_thresholds` and the
+(plan.Graph.head 'profile', heads.py; csrc/score_up.hip profile_up_kernel) that leaves, PER IMAGE, the entropy, the share at each of `max_thresholds` and the
 confusion matrix.  Every point of the curve follows on the host (exit_curve) by GatePlan.run's own decision rule.
 
     prof = ExitProfile(model, (N, 3, H, W), max_thresholds=(0.5, 0.9, 0.99))

@@ -347,7 +347,7 @@ class ADD(AddkModule):
         temperature = check_temperature(temperature, self.num_exits())
         if output not in OUTPUTS:
             raise ValueError("output must be 'logits' or 'labels' (got %r)" % (output,))
-        from ..plan import label_lut as _label_lut
+        from ..heads import label_lut as _label_lut
         lut = _label_lut(label_lut, 'cpu')
         mode = (output, None if lut is None else bytes(lut.numpy().tobytes())) if output == 'labels' else ()
         if x.is_cuda:
@@ -375,7 +375,7 @@ class ADD(AddkModule):
         'edm', any other `confidence`, a `label_lut` that is not 256 uint8 entries, an empty batch, a threshold sequence of the
         wrong length or a bad temperature raise ValueError."""
         from ..dynamic import BatchedGate, check_temperature
-        from ..plan import label_lut as _label_lut
+        from ..heads import label_lut as _label_lut
         lut = _label_lut(label_lut, 'cpu')
         if temperature is not None and confidence == 'edm':
             raise ValueError("temperature belongs to the 'entropy' and 'max' gates: the 'edm' gate judges no softmax")

@@ -12,7 +12,6 @@ never cost a pass over HBM.
 """
 import collections
 import itertools
-import math
 import os
 import ctypes as C
 
@@ -261,9 +260,6 @@ BATCHED = {'bn_finalize': _Table('addk_bn_finalize_batch', 'C'), 'bn_bwd': _Tabl
            'allreduce': _Arena()}
 
 
-HEADS = (None, 'ce', 'score', 'profile', 'labels', 'views', 'calib')     # Graph.head / OutRef.head
-
-
 class Graph:
     def __init__(self, device, training, want_grad, world=None):
         self.lib = L.load()
@@ -277,19 +273,17 @@ class Graph:
         self.pgrad = {}               # param -> grad tensor
         self.pgrad_views = None       # param -> view of a flat gradient buffer to use as its gradient (train.TrainStep)
         self.reorder = False          # level-order and batch the lists although this is not a training plan (set before finalize)
-        # who consumes the decoder's low-resolution logits (resize_to_nchw): None = nobody, the resize writes [N,C,OH,OW]; 'ce' = the fused
-        # up-sampling + cross-entropy launch (train.TrainStep); 'score' = the scoring launch (validate.ValidationStep); 'profile' = the
-        # per-image exit-profile launch (exit_profile.ExitProfile); 'labels' = the label head (dynamic plans, segment.Segmenter); 'views' =
-        # the multi-view label head: every logits output of the plan is one or more views of ONE label map (segment.MultiViewSegmenter);
-        # 'calib' = the calibration launch (calibrate.ExitCalibration)
+        # who consumes the decoder's low-resolution logits (resize_to_nchw; a key of heads.HEADS): None = nobody, the resize writes
+        # [N,C,OH,OW]; 'ce' = the fused up-sampling + cross-entropy launch (train.TrainStep); 'score' = the scoring launch
+        # (validate.ValidationStep); 'profile' = the per-image exit-profile launch (exit_profile.ExitProfile); 'labels' = the label head
+        # (dynamic plans, segment.Segmenter); 'views' = the multi-view label head: every logits output of the plan is one or more views of
+        # ONE label map (segment.MultiViewSegmenter); 'calib' = the calibration launch (calibrate.ExitCalibration)
         self.head = None
         self.lut = None               # 'labels' / 'views': the uint8 [256] device table the class indices go through, or None
-        self.view_outs = []           # 'views': the OutRefs of the plan's logits outputs, in emission order (= kernel order of their views)
-        self.view_labels = None       # 'views': the plan-owned uint8 [N,OH,OW] map, allocated by finalize()
-        self._views_tag = ''          # 'views': segment tag of the last output, stamped on the one launch
+        self.view_labels = None       # 'views': the plan-owned uint8 [N,OH,OW] map, allocated by finalize() (heads._emit_views)
         self.gate = None              # logits outputs of an inference plan are gated exits (dynamic.GatePlan): {'kind', 'host', 'thr'}; with head None or 'labels'
-        #                               optional 'temp': the device word 1 / temperature of a tempered gate (gate_head)
-        self._fwd_late = []           # closures emitting forward commands whose bindings arrive after the module tree was emitted ('score', 'profile')
+        #                               optional 'temp': the device word 1 / temperature of a tempered gate (heads.gate_head)
+        self._fwd_late = []           # callables emitting forward commands whose bindings arrive after the module tree was emitted (heads.py)
         self.pginit = set()
         self._pcols = {}
         self.params = []              # ordered unique params touched
@@ -1201,28 +1195,15 @@ class Graph:
         return res
 
     def resize_to_nchw(self, src, OH, OW):
-        """Final logits resize (decoder.py:28).  Returns an OutRef.  The plan chooses who consumes the low-resolution logits: the loss head
-        of a fused training step (_ce_head), the scoring head of a validation plan (_score_head), the per-image profile of an exit-profile
-        plan (_profile_head), the gate of an early exit (gate_head), the label head of a label-map plan (_label_head), the multi-view label head that all outputs
-        of a multi-view plan share (_views_head), or nobody: the resize into a contiguous [N,C,OH,OW] tensor, and its backward."""
-        assert src.bn is None and not src.relu and self.head in HEADS
-        if self.want_grad:
-            if (self.head == 'ce' and src.needs_grad
-                    and self.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1):
-                return self._ce_head(src, OH, OW)
-        elif self.head == 'score':
-            return self._score_head(src, OH, OW)
-        elif self.head == 'profile':
-            return self._profile_head(src, OH, OW)
-        elif self.head == 'calib':
-            return self._calib_head(src, OH, OW)
-        elif self.gate is not None:
-            return self.gate_head(src, OH, OW, self.gate['host'], self.gate['thr'], self.gate['kind'], self.gate.get('temp'))
-        elif self.head == 'labels':
-            return self._label_head(src, OH, OW)
-        elif self.head == 'views':
-            return self._views_head(src, OH, OW)
-        y, emit_resize = self._logits_resize(src, OH, OW)
+        """Final logits resize (decoder.py:28).  Returns an OutRef.  The plan chooses who consumes the low-resolution logits (heads.py:
+        HEADS names the heads, heads.logits_head says which one takes this output, the gate of an early exit among them), or nobody: the
+        resize into a contiguous [N,C,OH,OW] tensor, and its backward."""
+        from . import heads                      # here, not at the top: heads.py imports from this module
+        assert src.bn is None and not src.relu and (self.head is None or self.head in heads.HEADS)
+        out = heads.logits_head(self, src, OH, OW)
+        if out is not None:
+            return out
+        y, emit_resize = heads._logits_resize(self, src, OH, OW)
         emit_resize()
         out = OutRef(y)
         if self.want_grad and src.needs_grad:
@@ -1237,417 +1218,6 @@ class Graph:
                 out.bwd_args = ba
                 self._add(self.bwd, 'resize_nchw_bwd', self.lib.addk_resize_bwd, C.byref(ba), rd=self.lz(src), wr=[gs])
             self._bwd_emitters.append(emit_bwd)
-        return out
-
-    def _logits_resize(self, src, OH, OW):
-        """The full-resolution logits: (y [N,C,OH,OW], emit); emit() appends the `resize_nchw` launch that writes y, now or later."""
-        y = torch.empty((src.N, src.C, OH, OW), dtype=torch.float32, device=self.device)
-        self.nbytes += y.numel() * 4
-        ar = self._rs_args(L.ResizeArgs, src, OH, OW)
-        ar.y, ar.ldy, ar.nchw_out = y.data_ptr(), 0, 1
-        self.keep.append(ar)
-        return y, lambda: self._add(self.fwd, 'resize_nchw', self.lib.addk_resize_fwd, C.byref(ar), rd=self.lz(src), wr=[y])
-
-    def _up_args(self, cls, src, OH, OW):
-        """A *UpsampleArgs struct with the prefix the three share filled in: the low-resolution NHWC logits and the two grids."""
-        a, s = cls(), self.src(src)
-        a.logits, a.ld, a.N, a.H, a.W, a.C, a.OH, a.OW = s.x, s.ld, src.N, src.H, src.W, src.C, OH, OW
-        return a
-
-    def _late_head(self, head, src, OH, OW, lst, emitters, emit):
-        """The OutRef of a head whose step binds its tensors only after the module tree was emitted: no resize, no [N,C,OH,OW] buffer, `y`
-        is None and `shape` says what the logits would be.  finalize() runs `emitters`; by then `binding` must be there, and
-        `emit(binding)` appends the head's launches to `lst` under the tag of the exit."""
-        out = OutRef(None)
-        out.head, out.shape = head, (src.N, src.C, OH, OW)
-        tag = self.tag
-
-        def late():
-            assert out.binding is not None, 'fused logits output without a %s binding' % head
-            first = len(lst)
-            emit(out.binding)
-            for c in lst[first:]:
-                c.tag = tag
-        emitters.append(late)
-        return out
-
-    @staticmethod
-    def _bind_loss(a, b):
-        """The loss binding a step attached to an OutRef ('ce' / 'score') into the loss head's or the scoring head's arguments."""
-        a.target, a.class_w, a.ignore_index = b['target'].data_ptr(), b['class_w'], b['ignore_index']
-        a.wsum, a.scale, a.loss_out = b['wsum'].data_ptr(), b['scale'], b['loss'].data_ptr()
-
-    def _ce_head(self, src, OH, OW):
-        """Logits output of a fused training step (head 'ce', set by train.TrainStep): nobody reads the full-resolution logits, so
-        the resize is not emitted at all and the OutRef carries `shape` and the `binding` TrainStep sets; finalize() then places ONE
-        fused up-sampling + cross-entropy launch (`addk_ce_upsample_fwd_bwd`) at the head of the backward list.  A binding with
-        `ohem = (thresh, min_kept_total)` mines hard examples (include/addk.h, addk_ohem_select): `ohem_select` leaves this exit's own
-        per-pixel loss map, tau and kept weight sum, and `ce_upsample_ohem` is the loss head that reads them; the binding gets the
-        tensors back as `ohem_state` (TrainStep.ohem_stats).  A binding with `distill = (alpha, temperature, teacher OutRef)` and `nvalid`
-        (the count word) makes the exit a student of the teacher's low-resolution logits (`OutRef.src`): `ce_upsample_kd` takes the place
-        of `ce_upsample` / `ce_upsample_ohem`, and the binding gets `distill_state` (TrainStep.distill_stats).  A binding with
-        `dice = (weight, smooth)` adds the soft-Dice region term (include/addk.h, addk_dice_stats): `dice_stats`, directly in front of the
-        head, leaves the coefficient table and the term; the head is `ce_upsample_dice`, whatever else it is, and reads the table; the
-        binding gets `dice_state` (TrainStep.dice_stats)."""
-        def emit_ce(ce):
-            lib, ohem, kd, dice = self.lib, ce.get('ohem'), ce.get('distill'), ce.get('dice')
-            f32 = dict(dtype=torch.float32, device=self.device)
-            a = self._up_args(L.CeUpsampleArgs, src, OH, OW)
-            self._bind_loss(a, ce)
-            gs, a.accumulate, _ = self._grad_into(src)
-            a.g, a.ldg = gs.ptr, gs.ld
-            ws_floats = lib.addk_ce_upsample_kd_ws_floats if kd else lib.addk_ce_upsample_ws_floats
-            ws = torch.zeros(int(ws_floats(src.N, src.H, src.W)), **f32)
-            a.ws = ws.data_ptr()
-            self.keep += [a, ws]
-            if kd:                                         # the KL term's word: kept here, before the mining tensors (the plan's kept order)
-                kdo = torch.zeros(1, **f32)
-                self.keep.append(kdo)
-            # the launch: the plain head, unless a block below changes it; the KD struct is a superset of the mining struct
-            args = L.CeUpsampleKdArgs() if kd or dice else L.CeUpsampleOhemArgs() if ohem else a
-            name, fn, norm = 'ce_upsample', lib.addk_ce_upsample_fwd_bwd, [ce['wsum']]
-            rd_more, wr = [], [gs, ce['loss'], ws]
-            if ohem:
-                # mining: this exit's loss map, tau and kept weight sum; the head reads them, the kept weight sum is its normaliser
-                if lib.addk_ohem_select_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
-                    raise L.AddkError('hard example mining takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
-                                      % (src.C, src.N, src.H, src.W, OH, OW))
-                lmap, tau, wkept = torch.zeros((src.N, OH, OW), **f32), torch.zeros(1, **f32), torch.zeros(1, **f32)
-                counts = torch.zeros(2, dtype=torch.int64, device=self.device)
-                sws = torch.zeros(int(lib.addk_ohem_select_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=self.device)
-                self.nbytes += lmap.numel() * 4
-                s = self._up_args(L.OhemSelectArgs, src, OH, OW)
-                s.target, s.class_w, s.ignore_index = a.target, a.class_w, a.ignore_index
-                s.thresh, s.min_kept_total = ohem
-                s.pix_loss, s.tau, s.wsum_kept, s.counts, s.ws = lmap.data_ptr(), tau.data_ptr(), wkept.data_ptr(), counts.data_ptr(), sws.data_ptr()
-                ce['ohem_state'] = dict(pix_loss=lmap, tau=tau, wsum_kept=wkept, counts=counts)
-                self.keep += [s, lmap, tau, wkept, counts, sws]
-                self._add(self.bwd, 'ohem_select', lib.addk_ohem_select, C.byref(s), rd=self.lz(src) + [ce['target']], wr=[lmap, tau, wkept, counts, sws])
-                a.wsum, args.pix_loss, args.tau = wkept.data_ptr(), lmap.data_ptr(), tau.data_ptr()
-                name, fn, norm = 'ce_upsample_ohem', lib.addk_ce_upsample_ohem_fwd_bwd, [lmap, tau, wkept]
-            if kd:
-                # a student: the head's own normaliser and kept set as above, plus the last exit's low-resolution logits and the count word
-                alpha, temp, teacher = kd
-                tsrc = teacher.src
-                assert tsrc.bn is None and not tsrc.relu and (tsrc.N, tsrc.H, tsrc.W, tsrc.C) == (src.N, src.H, src.W, src.C)
-                t = self.src(tsrc)
-                args.teacher, args.ld_teacher, args.alpha, args.temperature = t.x, t.ld, alpha, temp
-                args.nvalid, args.kd_out = ce['nvalid'].data_ptr(), kdo.data_ptr()
-                ce['distill_state'] = dict(kd=kdo)
-                name, fn = 'ce_upsample_kd', lib.addk_ce_upsample_kd_fwd_bwd
-                rd_more, wr = self.lz(tsrc) + [ce['nvalid']], wr + [kdo]
-            if args is not a:
-                args.ce = a                                # a copy of the base arguments, with the final normaliser
-                self.keep.append(args)
-            if dice:
-                # the region term: the batch's per-class sums first (they add the term to the loss), then the head with their table
-                if lib.addk_dice_stats_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
-                    raise L.AddkError('the soft-Dice term takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
-                                      % (src.C, src.N, src.H, src.W, OH, OW))
-                coef, dout = torch.zeros(2 * src.C, **f32), torch.zeros(1 + src.C, **f32)
-                dws = torch.zeros(int(lib.addk_dice_stats_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=self.device)
-                d = self._up_args(L.DiceStatsArgs, src, OH, OW)
-                d.target, d.ignore_index, d.scale, d.loss_out = a.target, a.ignore_index, a.scale, a.loss_out
-                d.weight, d.smooth = dice
-                d.coef, d.dice_out, d.ws = coef.data_ptr(), dout.data_ptr(), dws.data_ptr()
-                ce['dice_state'] = dict(dice=dout, coef=coef)
-                self._add(self.bwd, 'dice_stats', lib.addk_dice_stats, C.byref(d), rd=self.lz(src) + [ce['target']], wr=[coef, dout, ce['loss'], dws])
-                head = L.CeUpsampleDiceArgs()
-                head.kd, head.coef = args, coef.data_ptr()       # a copy of the head's arguments, complete by now
-                self.keep += [d, coef, dout, dws, head]
-                args, name, fn, rd_more = head, 'ce_upsample_dice', lib.addk_ce_upsample_dice_fwd_bwd, rd_more + [coef]
-            self._add(self.bwd, name, fn, C.byref(args), rd=self.lz(src) + [ce['target']] + norm + rd_more, wr=wr)
-        out = self._late_head('ce', src, OH, OW, self.bwd, self._bwd_emitters, emit_ce)
-        out.src = src
-        return out
-
-    def _score_head(self, src, OH, OW):
-        """Logits output of a validation plan (head 'score', set by validate.ValidationStep): nobody reads the full-resolution
-        logits, so no resize is emitted and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step
-        sets (target, class weights, wsum and the per-exit loss / entropy / confusion / prediction tensors); finalize() then appends
-        ONE `score_upsample` launch per exit to the forward list (`addk_score_upsample`).  Where the library does not take the shape
-        (`addk_score_upsample_supported` == 0, e.g. C != 19) the same quantities come from the stand-alone kernels inside this plan:
-        resize + ce_fwd_bwd without a gradient + argmax_nchw + confusion + entropy_sum.  A binding with `trimap` (_confusion_banded) adds
-        ONE `confusion_banded` launch behind the exit's `score_upsample`; the stand-alone path refuses it (ValueError)."""
-        lib = self.lib
-        N, H, W, Cc = src.N, src.H, src.W, src.C
-
-        def emit_score(sc):
-            tgt, wsum, loss, ent, cm, pred = sc['target'], sc['wsum'], sc['loss'], sc['entropy'], sc['confusion'], sc.get('pred')
-            if lib.addk_score_upsample_supported(N, H, W, OH, OW, Cc) == 1:
-                a = self._up_args(L.ScoreUpsampleArgs, src, OH, OW)
-                self._bind_loss(a, sc)
-                a.ent_out, a.cm, a.pred_out = ent.data_ptr(), cm.data_ptr(), pred.data_ptr() if pred is not None else None
-                ws = torch.zeros(int(lib.addk_score_upsample_ws_floats(N, OH, OW)), dtype=torch.float32, device=self.device)
-                a.ws = ws.data_ptr()
-                self.keep += [a, ws]
-                self._add(self.fwd, 'score_upsample', lib.addk_score_upsample, C.byref(a),
-                          rd=self.lz(src) + [tgt, wsum], wr=[loss, ent, cm, pred, ws])
-                if sc.get('trimap') is not None:
-                    self._confusion_banded(sc['trimap'], tgt, pred, N, OH, OW, Cc)
-            else:
-                if sc.get('trimap') is not None:
-                    raise ValueError('the trimap metric reads the uint8 map of the fused scoring head, which does not take this exit '
-                                     '(%d classes, [%d,%d,%d] -> %dx%d): the stand-alone path keeps an int64 map' % (Cc, N, H, W, OH, OW))
-                y, emit_resize = self._logits_resize(src, OH, OW)
-                am = torch.empty((N, OH, OW), dtype=torch.int64, device=self.device)
-                ws = torch.zeros(int(lib.addk_ce_ws_floats(N, OH * OW)), dtype=torch.float32, device=self.device)
-                self.nbytes += am.numel() * 8
-                self.keep += [y, am, ws]
-                emit_resize()
-                self._add(self.fwd, 'ce_fwd_bwd', lib.addk_ce_fwd_bwd, y.data_ptr(), tgt.data_ptr(), N, Cc, OH * OW, sc['class_w'],
-                          sc['ignore_index'], wsum.data_ptr(), sc['scale'], loss.data_ptr(), None, ws.data_ptr(),
-                          rd=[y, tgt, wsum], wr=[loss, ws])
-                self._add(self.fwd, 'argmax_nchw', lib.addk_argmax_nchw, y.data_ptr(), N, Cc, OH * OW, am.data_ptr(), rd=[y], wr=[am])
-                self._add(self.fwd, 'confusion', lib.addk_confusion, tgt.data_ptr(), am.data_ptr(), N * OH * OW, Cc, cm.data_ptr(),
-                          rd=[tgt, am], wr=[cm])
-                # addk_entropy_sum overwrites its output: the step zeroes `ent` before every pass, which makes that the same thing
-                self._add(self.fwd, 'entropy_sum', lib.addk_entropy_sum, y.data_ptr(), N, Cc, OH * OW, ent.data_ptr(), ws.data_ptr(),
-                          rd=[y], wr=[ent, ws])
-                sc['pred_i64'] = am                    # the map of this path is int64: ValidationStep.predictions() narrows it
-        return self._late_head('score', src, OH, OW, self.fwd, self._fwd_late, emit_score)
-
-    def _profile_head(self, src, OH, OW):
-        """Logits output of an exit-profile plan (head 'profile', set by exit_profile.ExitProfile): as in _score_head no resize is emitted
-        and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step sets (target, the device array of
-        top-probability thresholds and its length, and this exit's per-image entropy [N], share [N,nthr], confusion [N,C,C] and optional
-        prediction tensors); finalize() then appends ONE `profile_upsample` launch per exit (`addk_profile_upsample`).  There is no
-        stand-alone form: a shape the library does not take is an error.  A binding with `trimap` (_confusion_banded) adds ONE
-        `confusion_banded` launch behind the exit's profile launch."""
-        lib = self.lib
-        N, H, W, Cc = src.N, src.H, src.W, src.C
-
-        def emit_profile(pr):
-            tgt, thr, nthr, ent, share, cm, pred = pr['target'], pr['thr'], pr['nthr'], pr['entropy'], pr['share'], pr['confusion'], pr.get('pred')
-            if lib.addk_profile_upsample_supported(N, H, W, OH, OW, Cc, nthr) != 1:
-                raise L.AddkError('the exit profile takes 19 classes and at most 16 thresholds (got %d classes, %d thresholds, '
-                                  '[%d,%d,%d] -> %dx%d)' % (Cc, nthr, N, H, W, OH, OW))
-            a = self._up_args(L.ProfileUpsampleArgs, src, OH, OW)
-            a.target, a.thr, a.nthr = tgt.data_ptr(), thr.data_ptr() if nthr else None, nthr
-            a.ent_out, a.share_out, a.cm = ent.data_ptr(), share.data_ptr() if nthr else None, cm.data_ptr()
-            a.pred_out = pred.data_ptr() if pred is not None else None
-            ws = torch.zeros(int(lib.addk_profile_upsample_ws_bytes(N, OH, OW)), dtype=torch.uint8, device=self.device)
-            a.ws = ws.data_ptr()
-            temp = pr.get('temp')
-            if temp is not None:                     # the tempered launch: entropy and shares of softmax(z * *temp)
-                b = L.ProfileUpsampleTArgs()
-                b.profile, b.inv_temp = a, temp.data_ptr()
-                self.keep += [b, ws]
-                self._add(self.fwd, 'profile_upsample_t', lib.addk_profile_upsample_t, C.byref(b),
-                          rd=self.lz(src) + [tgt, thr, temp], wr=[ent, share, cm, pred, ws])
-            else:
-                self.keep += [a, ws]
-                self._add(self.fwd, 'profile_upsample', lib.addk_profile_upsample, C.byref(a),
-                          rd=self.lz(src) + [tgt, thr], wr=[ent, share, cm, pred, ws])
-            if pr.get('trimap') is not None:
-                self._confusion_banded(pr['trimap'], tgt, pred, N, OH, OW, Cc)
-        return self._late_head('profile', src, OH, OW, self.fwd, self._fwd_late, emit_profile)
-
-    def _confusion_banded(self, tm, tgt, pred, N, OH, OW, Cc):
-        """ONE `confusion_banded` launch (`addk_confusion_banded`) behind the head launch of an exit whose binding carries `trimap`: a dict
-        with `rings` (int64 [nw,C,C], or [N,nw,C,C] with `image_stride` = nw*C*C; added to), `widths` and `dist` (the uint8 map the step's one
-        `boundary_dist` launch writes).  It reads the head's uint8 prediction map."""
-        lib, widths = self.lib, tm['widths']
-        assert pred is not None, 'a trimap binding needs the exit\'s uint8 prediction map'
-        if lib.addk_confusion_banded_supported(N, OH, OW, Cc, len(widths)) != 1:
-            raise ValueError('the trimap metric takes 1 to 32 classes, 1 to %d widths and fewer than 2^31 pixels (got %d classes, %d widths, '
-                             '[%d,%d,%d])' % (L.TRIMAP_MAX_WIDTHS, Cc, len(widths), N, OH, OW))
-        a = L.ConfusionBandedArgs()
-        a.target, a.pred, a.dist = tgt.data_ptr(), pred.data_ptr(), tm['dist'].data_ptr()
-        a.N, a.OH, a.OW, a.C, a.nw = N, OH, OW, Cc, len(widths)
-        for j, w in enumerate(widths):
-            a.width[j] = w
-        a.cm, a.image_stride = tm['rings'].data_ptr(), tm.get('image_stride', 0)
-        self.keep.append(a)
-        self._add(self.fwd, 'confusion_banded', lib.addk_confusion_banded, C.byref(a), rd=[tgt, pred, tm['dist']], wr=[tm['rings']])
-
-    def _calib_head(self, src, OH, OW):
-        """Logits output of a calibration plan (head 'calib', set by calibrate.ExitCalibration): as in _profile_head no resize is emitted and
-        no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step sets (target, the device array of inverse
-        temperatures and its length, and this exit's bins [nt,16,3] int64 and nll [nt] fp64, both added to); finalize() then appends ONE
-        `calib_upsample` launch per exit (`addk_calib_upsample`).  There is no stand-alone form: a shape the library does not take is an
-        error."""
-        lib = self.lib
-        N, H, W, Cc = src.N, src.H, src.W, src.C
-
-        def emit_calib(cb):
-            tgt, it, nt, bins, nll = cb['target'], cb['inv_temp'], cb['nt'], cb['bins'], cb['nll']
-            if lib.addk_calib_upsample_supported(N, H, W, OH, OW, Cc, nt) != 1:
-                raise L.AddkError('the calibration head takes 19 classes and 1..%d temperatures (got %d classes, %d temperatures, '
-                                  '[%d,%d,%d] -> %dx%d)' % (L.CALIB_MAX_T, Cc, nt, N, H, W, OH, OW))
-            a = self._up_args(L.CalibUpsampleArgs, src, OH, OW)
-            a.target, a.inv_temp, a.nt, a.bins, a.nll = tgt.data_ptr(), it.data_ptr(), nt, bins.data_ptr(), nll.data_ptr()
-            ws = torch.zeros(int(lib.addk_calib_upsample_ws_bytes(N, OH, OW)), dtype=torch.uint8, device=self.device)
-            a.ws = ws.data_ptr()
-            self.keep += [a, ws]
-            self._add(self.fwd, 'calib_upsample', lib.addk_calib_upsample, C.byref(a), rd=self.lz(src) + [tgt, it], wr=[bins, nll, ws])
-        return self._late_head('calib', src, OH, OW, self.fwd, self._fwd_late, emit_calib)
-
-    def _label_map(self, src, OH, OW):
-        """The plan-owned uint8 [N,OH,OW] label map of a label head and its OutRef (`shape`: the logits it stands for)."""
-        lab = torch.zeros((src.N, OH, OW), dtype=torch.uint8, device=self.device)
-        self.nbytes += lab.numel()
-        out = OutRef(lab)
-        out.head, out.shape = 'labels', (src.N, src.C, OH, OW)
-        return lab, out
-
-    def _label_head(self, src, OH, OW):
-        """Logits output of a label-map plan (head 'labels', set by dynamic.DynamicPlan / GatePlan and segment.Segmenter): what inference
-        keeps of an exit is the arg-max of its up-sampled logits (eval.py:218-221), so no resize is emitted and no [N,C,OH,OW] buffer exists.
-        ONE `label_upsample` launch (`addk_label_upsample`) writes the OutRef's `y`, a plan-owned uint8 [N,OH,OW] map: the class index, or
-        lut[class] with the table `self.lut`.  Where the library does not take the shape (`addk_label_upsample_supported` == 0, e.g.
-        C != 19) the same plan uses the stand-alone kernels: resize + argmax_nchw + a cast in torch ops (_labels_cold)."""
-        lib = self.lib
-        lab, out = self._label_map(src, OH, OW)
-        lut = self.lut
-        if lib.addk_label_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1:
-            a = self._up_args(L.LabelUpsampleArgs, src, OH, OW)
-            a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
-            self.keep += [a, lut]
-            self._add(self.fwd, 'label_upsample', lib.addk_label_upsample, C.byref(a), rd=self.lz(src) + [lut], wr=[lab])
-        else:
-            y, emit_resize = self._logits_resize(src, OH, OW)
-            emit_resize()
-            self._labels_cold(y, lab, lut)
-        return out
-
-    def _views_head(self, src, OH, OW):
-        """Logits output of a multi-view plan (head 'views', set by segment.MultiViewSegmenter): the plan emits the model several times —
-        once per input scale, at batch 2N where the mirrored images ride along — and ALL its logits outputs end in one label map.  Nothing is
-        emitted here and no [N,C,OH,OW] buffer exists: the OutRef keeps the low-resolution source (`src`), `shape`, and the `binding` the step
-        sets — {'N': images per view, 'size': (OH, OW) of the map, 'views': [(n0, mirror, weight), ...]}, the views this output holds (n0:
-        its first image in the batch).  The (OH, OW) passed here, the size the model would up-sample this output to, only goes into `shape`.
-        finalize() then appends ONE `label_views_upsample` launch (`addk_label_views_upsample`) that reads every view's source and writes
-        `view_labels`, the plan-owned uint8 [N,OH,OW] map.  There is no stand-alone form: C != 19 or more than 8 views is an error."""
-        if src.C != 19:
-            raise L.AddkError('the multi-view label head takes 19 classes (got %d)' % src.C)
-        out = OutRef(None)
-        out.head, out.shape, out.src = 'views', (src.N, src.C, OH, OW), src
-        if not self.view_outs:
-            self._fwd_late.append(self._emit_views)
-        self.view_outs.append(out)
-        self._views_tag = self.tag
-        return out
-
-    def _emit_views(self):
-        lib, outs = self.lib, self.view_outs
-        assert all(o.binding is not None for o in outs), 'multi-view logits output without a views binding'
-        views = [(o, v) for o in outs for v in o.binding['views']]
-        b0, Cc = outs[0].binding, outs[0].shape[1]
-        N, (OH, OW) = b0['N'], b0['size']
-        assert all(o.binding['N'] == N and tuple(o.binding['size']) == (OH, OW) and o.shape[1] == Cc for o in outs)
-        assert all(0 <= n0 and n0 + N <= o.shape[0] for o, (n0, _, _) in views)
-        if len(views) > L.MAX_VIEWS or lib.addk_label_views_upsample_supported(len(views), N, OH, OW, Cc) != 1:
-            raise L.AddkError('the multi-view label head takes 1..%d views of 19 classes (got %d views, %d classes, %d x %dx%d)'
-                              % (L.MAX_VIEWS, len(views), Cc, N, OH, OW))
-        lab = self.view_labels = torch.zeros((N, OH, OW), dtype=torch.uint8, device=self.device)
-        self.nbytes += lab.numel()
-        a, lut, rd = L.LabelViewsArgs(), self.lut, []
-        for i, (o, (n0, mirror, weight)) in enumerate(views):
-            s, v = self.src(o.src), a.view[i]
-            v.logits, v.ld, v.n0, v.H, v.W, v.mirror, v.weight = s.x, s.ld, n0, o.src.H, o.src.W, int(bool(mirror)), weight
-            rd += self.lz(o.src)
-        a.nview, a.N, a.C, a.OH, a.OW = len(views), N, Cc, OH, OW
-        a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
-        self.keep += [a, lut]
-        self._add(self.fwd, 'label_views_upsample', lib.addk_label_views_upsample, C.byref(a), rd=rd + [lut], wr=[lab]).tag = self._views_tag
-
-    def _labels_cold(self, y, lab, lut):
-        """Cold path of the two label heads: the map from materialised logits y [N,C,OH,OW] — `argmax_nchw`, then the cast / table look-up
-        to uint8 in torch ops."""
-        N, Cc, OH, OW = y.shape
-        am = torch.empty((N, OH, OW), dtype=torch.int64, device=self.device)
-        self.nbytes += am.numel() * 8
-        self.keep += [y, am, lut]
-        self._add(self.fwd, 'argmax_nchw', self.lib.addk_argmax_nchw, y.data_ptr(), N, Cc, OH * OW, am.data_ptr(), rd=[y], wr=[am])
-        self._add(self.fwd, 'label_cast_torch', _label_cast_torch, am, lut, lab, rd=[am, lut], wr=[lab], pin=True)
-
-    def _gate_args(self, src, OH, OW, thr, gout, host_out):
-        """(GateUpsampleArgs, workspace) of the fused gate launch, with and without the label map: a zeroed ticket workspace of its own"""
-        a = self._up_args(L.GateUpsampleArgs, src, OH, OW)
-        ws = self.buf((int(self.lib.addk_gate_upsample_ws_bytes(src.N, OH, OW)) + 3) // 4, zero=True)
-        a.max_thr, a.out, a.ws = thr.data_ptr(), gout.data_ptr(), ws.ptr
-        a.out_host = host_out.data_ptr() if host_out is not None else None
-        return a, ws
-
-    def gate_head(self, src, OH, OW, host_out, thr, kind='entropy', temp=None):
-        """Logits output of a gated early exit (`self.gate`, set by dynamic.GatePlan): the exit's gate value (modeling/operations.py:161-180)
-        and, separately, the resize that writes the [N,C,OH,OW] logits.  Fused form: ONE `gate_upsample` launch (`addk_gate_upsample`)
-        reads the low-resolution NHWC logits and writes (entropy, share) to the OutRef's `gate_out` [N,2] and to the pinned words `host_out`;
-        the `resize_nchw` launch FOLLOWS it, so a plan cut at `gate_cut` replays the resize only for an image that leaves here.  `thr`: the
-        device word the 'max' gate compares against.
-        Where the library does not take the shape (`addk_gate_upsample_supported` == 0, e.g. C != 19) or with ADDK_FUSE_GATE=0, the same
-        plan uses the stand-alone kernels on the materialised logits — `resize_nchw` first, then `entropy_sum` ('entropy': gate_out[0, 0]
-        holds the un-normalised sum, `gate_scale` the factor the host applies) or a count in torch ops ('max': gate_out[0, 1]); nothing
-        is left behind the cut and the host copies `gate_out` itself (`gate_fused` False).
-        In a label-map plan (head 'labels') the OutRef's `y` is the uint8 [N,OH,OW] map of _label_head.  Fused form: ONE
-        `gate_label_upsample` launch (`addk_gate_label_upsample`) leaves the gate value AND the map, for every image; nothing follows the
-        cut and no [N,C,OH,OW] buffer exists.  Stand-alone form: the stand-alone gate above, then, behind the cut, _labels_cold.
-        `temp`: the device word 1 / temperature of a tempered gate, which judges softmax(z * *temp): ONE `gate_upsample_t` launch
-        (`addk_gate_upsample_t`) stands where `gate_upsample` / `gate_label_upsample` stand, everything else is the same.  There is no
-        stand-alone tempered form: a shape the library does not take, or ADDK_FUSE_GATE=0, is an error."""
-        lib = self.lib
-        N, H, W, Cc = src.N, src.H, src.W, src.C
-        fused = _on('ADDK_FUSE_GATE') and lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
-        labels, lut = self.head == 'labels', self.lut
-        if temp is not None and not fused:
-            raise L.AddkError('a tempered gate needs the fused gate launch: 19 classes and ADDK_FUSE_GATE=1 (got %d classes, [%d,%d,%d] -> %dx%d)'
-                              % (Cc, N, H, W, OH, OW))
-        if not labels or not fused:
-            y, emit_resize = self._logits_resize(src, OH, OW)
-        gout = torch.zeros((N, 2), dtype=torch.float32, device=self.device)
-        self.keep += [gout, thr, host_out]
-        if labels:
-            lab, out = self._label_map(src, OH, OW)
-        if temp is not None:
-            if not labels:
-                out = OutRef(y)
-            out.gate_out, out.gate_fused = gout, True
-            a = L.GateUpsampleTArgs()
-            a.gate, ws = self._gate_args(src, OH, OW, thr, gout, host_out)
-            a.inv_temp = temp.data_ptr()
-            if labels:
-                a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
-            self.keep += [a, lut, temp]
-            self._add(self.fwd, 'gate_upsample_t', lib.addk_gate_upsample_t, C.byref(a), rd=self.lz(src) + [thr, temp] + ([lut] if labels else []),
-                      wr=[gout, ws] + ([lab] if labels else []))
-            out.gate_cut = len(self.fwd)
-            if not labels:
-                emit_resize()
-            return out
-        if labels and fused:
-            out.gate_out, out.gate_fused = gout, True
-            a = L.GateLabelUpsampleArgs()
-            a.gate, ws = self._gate_args(src, OH, OW, thr, gout, host_out)
-            a.lut256, a.labels = lut.data_ptr() if lut is not None else None, lab.data_ptr()
-            self.keep += [a, lut]
-            self._add(self.fwd, 'gate_label_upsample', lib.addk_gate_label_upsample, C.byref(a), rd=self.lz(src) + [thr, lut],
-                      wr=[gout, ws, lab])
-            out.gate_cut = len(self.fwd)
-            return out
-        if not labels:
-            out = OutRef(y)
-        out.gate_out = gout
-        out.gate_fused = fused
-        if out.gate_fused:
-            a, ws = self._gate_args(src, OH, OW, thr, gout, host_out)
-            self.keep.append(a)
-            self._add(self.fwd, 'gate_upsample', lib.addk_gate_upsample, C.byref(a), rd=self.lz(src) + [thr], wr=[gout, ws])
-            out.gate_cut = len(self.fwd)
-            emit_resize()
-            return out
-        emit_resize()
-        if kind == 'entropy':
-            ws = torch.zeros(int(lib.addk_ce_ws_floats(N, OH * OW)), dtype=torch.float32, device=self.device)
-            self.keep.append(ws)
-            self._add(self.fwd, 'entropy_sum', lib.addk_entropy_sum, y.data_ptr(), N, Cc, OH * OW, gout.data_ptr(), ws.data_ptr(),
-                      rd=[y], wr=[gout, ws])
-            out.gate_scale = 1.0 / (math.log(19.0) * OH * OW)
-        else:
-            self._add(self.fwd, 'gate_count_torch', _gate_count_torch, y, thr, gout, rd=[y, thr], wr=[gout], pin=True)
-        out.gate_cut = len(self.fwd)
-        if labels:
-            self._labels_cold(y, lab, lut)           # behind the cut: only for an image that leaves here
         return out
 
     def gap(self, src, relu_in=False):
@@ -1770,32 +1340,6 @@ def require_device(x):
 
 def current_stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _gate_count_torch(y, thr, gout, stream):
-    """Cold path of Graph.gate_head ('max' gate on materialised logits): share of pixels with 1 / sum_c exp(z_c - max z) > thr, in torch
-    ops on the current stream (the command is pinned to the plan's main stream, which is the current one in eager runs and captures)."""
-    se = (y - y.amax(1, keepdim=True)).exp_().sum(1)
-    gout[:, 1] = (se.reciprocal_() > thr).flatten(1).float().mean(1)
-    return 0
-
-
-def _label_cast_torch(am, lut, lab, stream):
-    """Cold path of the label heads: the int64 arg-max map as uint8, through the table where there is one; torch ops on the current
-    stream (pinned to the plan's main stream, as _gate_count_torch)."""
-    lab.copy_(am if lut is None else lut[am])
-    return 0
-
-
-def label_lut(lut, device):
-    """`label_lut` of the public label-map calls as what the plan binds: None, or a uint8 [256] tensor on `device`.  Anything that is
-    not 256 uint8 entries is a ValueError."""
-    if lut is None:
-        return None
-    t = lut if isinstance(lut, torch.Tensor) else torch.as_tensor(lut)
-    if t.dtype != torch.uint8 or tuple(t.shape) != (256,):
-        raise ValueError('label_lut must be 256 uint8 entries (got %s %s)' % (t.dtype, tuple(t.shape)))
-    return t.detach().to(device).contiguous().clone()
 
 
 def _in_stage(lib, inref, N, Cc, HW, ptr, ld, stream):

@@ -1,6 +1,6 @@
 """The resident inference plan: the path in inference form, emitted ONCE over resident input (and target) buffers into a static
 plan.Graph and replayed as a single hipGraph launch.  validate.ValidationStep, exit_profile.ExitProfile and segment.Segmenter are
-this plan with another logits head (plan.Graph.head) and another result; each supplies `head`, `_emit` and its own `step`."""
+this plan with another logits head (plan.Graph.head, emitted by heads.py) and another result; each supplies `head`, `_emit` and its own `step`."""
 import torch
 
 from . import _lib as L
@@ -10,7 +10,7 @@ from .plan import Graph
 
 
 class InferenceStep:
-    head = None          # plan.Graph.head: who consumes the decoder's low-resolution logits
+    head = None          # plan.Graph.head, a key of heads.HEADS: who consumes the decoder's low-resolution logits
     lut = None           # plan.Graph.lut of a 'labels' head
     nex = 0              # exits, fixed together with `ncls` by the first build
 

@@ -1,6 +1,6 @@
 """Static label-map inference (reference eval.py:218-221: `pred = argmax(output, 1)`): one exit of the path in inference form,
 ending in the label head — ONE `addk_label_upsample` launch writes the uint8 [N,H,W] arg-max map straight from the decoder's
-low-resolution logits (plan.Graph.head 'labels'), so the [N,19,H,W] logits are never written and no such buffer exists.  The plan holds
+low-resolution logits (plan.Graph.head 'labels': heads._label_head), so the [N,19,H,W] logits are never written and no such buffer exists.  The plan holds
 the trunk only up to the chosen exit's cell: an early exit costs its share of the network.  Emitted once over a resident input
 buffer and replayed as a single hipGraph launch.
 
@@ -11,7 +11,7 @@ buffer and replayed as a single hipGraph launch.
 Multi-scale + flip inference (what a DeepLab-family submission is scored on): the arg-max of the weighted mean of the class
 probabilities over several input scales and each scale's horizontal mirror.  ONE plan holds every view — the staged input, resized per
 scale (Graph.resize), runs through the model once per scale at batch 2N, the mirrored images riding along — and ends in ONE
-`addk_label_views_upsample` launch (plan.Graph.head 'views') that reads every view's low-resolution logits and writes the map: each view
+`addk_label_views_upsample` launch (plan.Graph.head 'views': heads._views_head) that reads every view's low-resolution logits and writes the map: each view
 is interpolated once, from the decoder's grid straight to (H, W), and no [N,19,·,·] tensor exists for any of them.
 
     seg = MultiViewSegmenter(model, (N, 3, H, W), scales=(0.75, 1.0, 1.25), flip=True, label_lut=decode_segmap_lut())
@@ -22,7 +22,7 @@ import math
 import torch
 
 from . import _lib as L
-from . import plan as _plan
+from .heads import label_lut as _label_lut
 from .resident import InferenceStep
 
 
@@ -34,7 +34,7 @@ class Segmenter(InferenceStep):
         if not isinstance(model, ADD):
             raise TypeError('Segmenter takes an ADD model (got %s)' % type(model).__name__)
         self.exit = range(model.num_exits())[exit]             # forward()'s output list; IndexError out of range
-        self.lut = _plan.label_lut(label_lut, next(model.parameters()).device)
+        self.lut = _label_lut(label_lut, next(model.parameters()).device)
         super().__init__(model, batch_shape, use_graph, nstreams, target=False)
         self._build()
 
@@ -93,7 +93,7 @@ class MultiViewSegmenter(InferenceStep):
             raise ValueError('weights must be positive and finite (got %r)' % (weights,))
         self.scales, self.weights = scales, weights
         self.exit = range(model.num_exits())[exit]             # forward()'s output list; IndexError out of range
-        self.lut = _plan.label_lut(label_lut, next(model.parameters()).device)
+        self.lut = _label_lut(label_lut, next(model.parameters()).device)
         self.image_shape = (N, Cin, H, W)
         super().__init__(model, (per * N, Cin, H, W), use_graph, nstreams, target=False)
         self._build()

@@ -1,7 +1,7 @@
 """Validation pass of the path (reference train.py:250-322, eval.py:165-193): forward of all exits in inference form and, per
 exit, the criterion, the evaluator's confusion matrix and the entropy meter — emitted as ONE static plan over resident
 input / target buffers and replayed as a single hipGraph launch.  The full-resolution logits are never written: every exit
-ends in one `addk_score_upsample` launch that scores the decoder's low-resolution logits (plan.Graph.head 'score').
+ends in one `addk_score_upsample` launch that scores the decoder's low-resolution logits (plan.Graph.head 'score': heads._score_head).
 
     val = ValidationStep(model, (N, 3, H, W), class_weight=w)
     for images, targets in loader:

@@ -12,6 +12,7 @@ import torch
 
 import addk
 import addk._lib as L
+import addk.heads as H
 import addk.plan as P
 from _util import ARCH_C2, GENOTYPE_AUTODEEPLAB, dry, make_args      # noqa: F401  (dry: the shared dry-run fixture)
 
@@ -182,22 +183,22 @@ def test_unfused_head_single_exit_or_unsupported_exit_raises(dry, monkeypatch):
     with pytest.raises(ValueError):
         TrainStep(OneExit(), SHAPE, distill=(1.0, 4.0), use_graph=False)
     # exits whose low-resolution logits differ in shape
-    real_head = P.Graph._ce_head
+    real_head = H.HEADS['ce']
 
-    def odd_head(self, src, OH, OW):
-        out = real_head(self, src, OH, OW)
+    def odd_head(g, src, OH, OW):
+        out = real_head(g, src, OH, OW)
         if not seen:                                                 # the first exit claims a map one row shorter
             r = src.raw
             out.src = P.Act(P.TRef(r.buf, r.off, r.N, r.H - 1, r.W, r.C, r.ld), needs_grad=True)
         seen.append(1)
         return out
     seen = []
-    monkeypatch.setattr(P.Graph, '_ce_head', odd_head)
+    monkeypatch.setitem(H.HEADS, 'ce', odd_head)
     try:
         with pytest.raises(ValueError):
             TrainStep(_add(4), SHAPE, distill=(1.0, 4.0), use_graph=False)
     finally:
-        monkeypatch.setattr(P.Graph, '_ce_head', real_head)
+        monkeypatch.setitem(H.HEADS, 'ce', real_head)
     # an exit whose shape the fused head does not take (more than 16 output rows per input row): no materialised fallback
     lib = addk.load()
     monkeypatch.setattr(lib, 'addk_ce_upsample_supported', lambda *a: 0)

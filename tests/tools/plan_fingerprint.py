@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Fingerprints of the dry-built launch plans, for refactors of the planner (plan.py, parallel.py, dynamic.py): a change that is
+"""Fingerprints of the dry-built launch plans, for refactors of the planner (plan.py, heads.py, parallel.py, dynamic.py): a change that is
 not meant to change a plan must leave every fingerprint as it is.  No GPU: launches are stubbed the way tests/test_plan_dryrun.py
 and tests/test_sep_dispatch.py do it.
 
@@ -238,7 +238,7 @@ def _tensors(*objs):
 
 
 def _train_step(F, shape, sync=False, **kw):
-    """the fused train step as bench.py builds it (flat gradient views, fused up-sampling + loss); `kw`: ohem=, distill="""
+    """the fused train step as bench.py builds it (flat gradient views, fused up-sampling + loss); `kw`: ohem=, distill=, dice="""
     import addk.train as T
     comm = None
     if sync:                       # the forced exchange at world 1 without a process group: arena binding, packed all-reduces, gradient buckets
@@ -281,30 +281,43 @@ def _dynamic(F, shape, *mode):
     return g, lists, extra, (plan, m, edm)
 
 
-def _validation(F, shape, classes=19):
-    """the validation pass: one scoring head per exit (7 classes: the stand-alone kernels inside the plan), class weights and maps"""
+def _validation(F, shape, classes=19, **kw):
+    """the validation pass: one scoring head per exit (7 classes: the stand-alone kernels inside the plan), class weights and maps;
+    `kw`: trimap= in place of the kept maps"""
     from addk.validate import ValidationStep
     m = _model(F, classes=classes)
-    vs = ValidationStep(m, shape, class_weight=torch.ones(classes), keep_predictions=True, use_graph=False, nstreams=2)
+    vs = ValidationStep(m, shape, class_weight=torch.ones(classes), use_graph=False, nstreams=2, **(kw or dict(keep_predictions=True)))
     g = vs.g
     extra = _tensors(vs, vs.inref) + list(m.buffers())
     return g, [('fwd', g.fwd)], extra, (vs, m)
 
 
-def _exit_profile(F, shape):
-    """the exit profile: one profile_upsample per exit, three top-probability thresholds, prediction maps"""
+def _exit_profile(F, shape, **kw):
+    """the exit profile: one profile_upsample per exit, three top-probability thresholds, prediction maps; `kw`: temperature=, trimap=
+    in place of the kept maps"""
     from addk.exit_profile import ExitProfile
     m = _model(F)
-    prof = ExitProfile(m, shape, max_thresholds=(0.5, 0.9, 0.99), keep_predictions=True, use_graph=False, nstreams=2)
+    prof = ExitProfile(m, shape, max_thresholds=(0.5, 0.9, 0.99), use_graph=False, nstreams=2, **(kw or dict(keep_predictions=True)))
     g = prof.g
     extra = _tensors(prof, prof.inref) + list(m.buffers())
     return g, [('fwd', g.fwd)], extra, (prof, m)
 
 
-def _segmenter(F, shape, exit, lut=None):
-    """static label-map inference of one exit: the trunk up to that exit's cell and one label_upsample"""
-    from addk.segment import Segmenter
+def _calibration(F, shape):
+    """the calibration pass: one calib_upsample per exit, the default ladder of temperatures"""
+    from addk.calibrate import ExitCalibration
     m = _model(F)
+    cal = ExitCalibration(m, shape, use_graph=False, nstreams=2)
+    g = cal.g
+    extra = _tensors(cal, cal.inref) + list(m.buffers())
+    return g, [('fwd', g.fwd)], extra, (cal, m)
+
+
+def _segmenter(F, shape, exit=-1, lut=None, classes=19):
+    """static label-map inference of one exit: the trunk up to that exit's cell and one label_upsample (7 classes: the stand-alone
+    kernels and the cast in torch ops)"""
+    from addk.segment import Segmenter
+    m = _model(F, classes=classes)
     seg = Segmenter(m, shape, exit=exit, label_lut=lut, use_graph=False, nstreams=2)
     g = seg.g
     extra = _tensors(seg, seg.inref) + list(m.buffers())
@@ -321,14 +334,14 @@ def _multi_view(F, shape):
     return g, [('fwd', g.fwd)], extra, (seg, m)
 
 
-def _gate(F, shape, kind, env=None, mode=()):
+def _gate(F, shape, kind, env=None, mode=(), temperature=None):
     """dynamic inference gated by entropy / top-probability share, and the segments it replays (trunk + head + gate, resize, remainder);
-    `mode` as in _dynamic"""
+    `mode` as in _dynamic; `temperature`: the tempered plan, that value at every exit"""
     old = {k: os.environ.get(k) for k in env or {}}
     os.environ.update(env or {})
     try:
         m = _model(F, train=False)
-        plan = m._gate_plan(torch.empty(*shape), kind, *mode)
+        plan = m._gate_plan(torch.empty(*shape), kind, *mode, temperature=temperature and [temperature] * m.num_exits())
         segs = [(0, plan.head_rng[0][0]), plan.head_rng[0], (plan.head_rng[0][1], -1)]
         segs = [s for s in segs if s[0] != s[1]]              # the stand-alone form leaves nothing behind the cut
         with torch.no_grad():
@@ -341,6 +354,17 @@ def _gate(F, shape, kind, env=None, mode=()):
     lists = [('fwd', g.fwd)] + [('seg%d' % k, plan.segs[(i0, i1 if i1 >= 0 else len(g.fwd))]) for k, (i0, i1) in enumerate(segs)]
     extra = _tensors(plan, plan.inref, *plan.heads, plan.final) + list(m.buffers())
     return g, lists, extra, (plan, m)
+
+
+def _batched_gate(F, shape, kind, n):
+    """the sub-plan of a BatchedGate at live batch `n`: the gate plan with label heads, its pinned words covering every image"""
+    from addk.dynamic import BatchedGate
+    m = _model(F, train=False)
+    bg = BatchedGate(m, shape, kind)
+    plan = bg.sub(n)
+    g = plan.g
+    extra = _tensors(plan, plan.inref, *plan.heads, plan.final) + list(m.buffers())
+    return g, [('fwd', g.fwd)], extra, (bg, m)
 
 
 PLANS = (
@@ -366,6 +390,15 @@ PLANS = (
     ('train_step_distill', lambda: _train_step(4, (2, 3, 65, 129), distill=(0.5, 2.0))),                # ce_upsample_kd for the students
     ('train_step_distill_ohem', lambda: _train_step(4, (2, 3, 65, 129), ohem=(0.7, 1000), distill=(0.5, 2.0))),
     ('multi_view_segmenter', lambda: _multi_view(4, (2, 3, 65, 129))),                                  # default scales and flip: label_views_upsample
+    ('gate_entropy_tempered', lambda: _gate(20, (1, 3, 65, 129), 'entropy', temperature=1.5)),          # gate_upsample_t, then the resize behind the cut
+    ('gate_max_labels_tempered', lambda: _gate(20, (1, 3, 65, 129), 'max', mode=('labels', None), temperature=1.5)),   # gate_upsample_t writes the map
+    ('calibration', lambda: _calibration(4, (2, 3, 65, 129))),                                          # one calib_upsample per exit
+    ('validation_trimap', lambda: _validation(4, (2, 3, 65, 129), trimap=(1, 3, 8))),                   # score_upsample + confusion_banded per exit
+    ('exit_profile_tempered_trimap', lambda: _exit_profile(4, (2, 3, 65, 129), temperature=1.5, trimap=(1, 3, 8))),   # profile_upsample_t + confusion_banded
+    ('batched_gate_sub2', lambda: _batched_gate(4, (2, 3, 65, 129), 'entropy', 2)),
+    ('segmenter_7_classes', lambda: _segmenter(4, (1, 3, 33, 65), classes=7)),                          # addk_label_upsample_supported == 0: the cold path
+    ('train_step_dice', lambda: _train_step(4, (2, 3, 65, 129), dice=(0.5, 1.0))),                      # dice_stats + ce_upsample_dice per exit
+    ('train_step_dice_distill_ohem', lambda: _train_step(4, (2, 3, 65, 129), ohem=(0.7, 1000), distill=(0.5, 2.0), dice=(0.5, 1.0))),
 )
 
 
