@@ -173,8 +173,8 @@ class DwWreduceItem(C.Structure):
     _fields_ = [('ws', vp), ('dw', vp), ('rows', i32), ('n', i32), ('accumulate', i32), ('_pad', i32)]
 
 
-class BnEvalEntry(C.Structure):
-    _fields_ = [('gamma', vp), ('beta', vp), ('rm', vp), ('rv', vp), ('a', vp), ('b', vp), ('C', i32), ('eps', f32)]
+class BnEvalItem(C.Structure):
+    _fields_ = [('gamma', vp), ('beta', vp), ('running_mean', vp), ('running_var', vp), ('a', vp), ('b', vp), ('C', i32), ('eps', f32)]
 
 
 class BnBwdArgs(C.Structure):
@@ -221,6 +221,24 @@ class ResizeBwdArgs(C.Structure):
     _fields_ = [('dy', vp), ('lddy', i32), ('nchw_in', i32), ('dy_scale', vp), ('src', Src), ('N', i32), ('H', i32),
                 ('W', i32), ('OH', i32), ('OW', i32), ('g', vp), ('ldg', i32), ('accumulate', i32), ('dab', vp)]
 
+
+# header type name (include/addk.h) -> its mirror above; tests/test_abi.py compares sizes and offsets, and that no mirror is missing here
+STRUCTS = {
+    'addk_src': Src, 'addk_conv_args': ConvArgs, 'addk_conv_dgrad_args': ConvDgradArgs, 'addk_conv_wgrad_args': ConvWgradArgs,
+    'addk_bn_finalize_args': BnFinalizeArgs, 'addk_sep_args': SepArgs, 'addk_sep_bwd_args': SepBwdArgs,
+    'addk_ce_upsample_args': CeUpsampleArgs, 'addk_ohem_select_args': OhemSelectArgs, 'addk_ce_upsample_ohem_args': CeUpsampleOhemArgs,
+    'addk_ce_upsample_kd_args': CeUpsampleKdArgs, 'addk_dice_stats_args': DiceStatsArgs, 'addk_ce_upsample_dice_args': CeUpsampleDiceArgs,
+    'addk_score_upsample_args': ScoreUpsampleArgs, 'addk_gate_upsample_args': GateUpsampleArgs, 'addk_label_upsample_args': LabelUpsampleArgs,
+    'addk_gate_label_upsample_args': GateLabelUpsampleArgs, 'addk_view': View, 'addk_label_views_args': LabelViewsArgs,
+    'addk_profile_upsample_args': ProfileUpsampleArgs, 'addk_gate_upsample_t_args': GateUpsampleTArgs,
+    'addk_profile_upsample_t_args': ProfileUpsampleTArgs, 'addk_calib_upsample_args': CalibUpsampleArgs,
+    'addk_boundary_dist_args': BoundaryDistArgs, 'addk_confusion_banded_args': ConfusionBandedArgs, 'addk_rows_item': RowsItem,
+    'addk_gather_rows_args': GatherRowsArgs, 'addk_dw_args': DwArgs, 'addk_dw_bwd_args': DwBwdArgs, 'addk_dw_wreduce_item': DwWreduceItem,
+    'addk_bn_eval_item': BnEvalItem, 'addk_bn_bwd_args': BnBwdArgs, 'addk_slab_reduce_item': SlabReduceItem,
+    'addk_bn_coeffs_item': BnCoeffsItem, 'addk_bn_apply_item': BnApplyItem, 'addk_affine_sum_args': AffineSumArgs,
+    'addk_affine_sum_bwd_args': AffineSumBwdArgs, 'addk_edm_args': EdmArgs, 'addk_resize_args': ResizeArgs,
+    'addk_resize_bwd_args': ResizeBwdArgs,
+}
 
 _SIGS = {
     'addk_last_error': (C.c_char_p, []),
@@ -298,15 +316,15 @@ _SIGS = {
     'addk_bn_bwd_batch': (i32, [vp, i32, i32, vp]),
     'addk_bn_bwd_apply_batch': (i32, [vp, i32, i64, vp]),
     'addk_bn_finalize': (i32, [C.POINTER(BnFinalizeArgs), vp]),
-    'addk_slab_reduce': (i32, [vp, i32, i32, vp, vp]),
-    'addk_bn_eval_affine': (i32, [vp, vp, vp, vp, f32, i32, vp, vp, vp]),
+    'addk_slab_reduce': (i32, [C.POINTER(SlabReduceItem), vp]),
+    'addk_bn_eval_affine': (i32, [C.POINTER(BnEvalItem), vp]),
     'addk_bn_eval_affine_batch': (i32, [vp, i32, vp]),
     'addk_bn_bwd': (i32, [C.POINTER(BnBwdArgs), vp]),
-    'addk_bn_bwd_coeffs_from_dmv': (i32, [vp, i32, f64, vp, vp, vp]),
+    'addk_bn_bwd_coeffs': (i32, [C.POINTER(BnCoeffsItem), vp]),
     'addk_affine_sum_fwd': (i32, [C.POINTER(AffineSumArgs), vp]),
     'addk_affine_sum_bwd': (i32, [C.POINTER(AffineSumBwdArgs), vp]),
     'addk_ew_rows': (i32, [i64, i32]),
-    'addk_bn_bwd_apply': (i32, [vp, i32, vp, i32, vp, vp, vp, i64, i32, vp, i32, vp]),
+    'addk_bn_bwd_apply': (i32, [C.POINTER(BnApplyItem), vp]),
     'addk_resize_fwd': (i32, [C.POINTER(ResizeArgs), vp]),
     'addk_resize_bwd': (i32, [C.POINTER(ResizeBwdArgs), vp]),
     'addk_resize_bwd_config': (i32, [C.POINTER(ResizeBwdArgs), C.POINTER(i32)]),

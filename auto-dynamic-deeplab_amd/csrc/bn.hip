@@ -162,33 +162,38 @@ __global__ void __launch_bounds__(BN_T) bn_finalize_batch_kernel(const addk_bn_f
   bn_finalize_body(p, sh);
 }
 
-__global__ void __launch_bounds__(BN_T) slab_reduce_kernel(const double* slab, int rows, int C, double* out) {
-  __shared__ double2 sh[1][BN_RG][BN_CH];
+__device__ __forceinline__ void slab_reduce_body(const addk_slab_reduce_item& it, bn_panel sh) {
   const int c = bn_lead_channel();
   double s0, s1;
-  slab_sum(slab, rows, C, s0, s1, sh);
-  if (bn_lead() && c < C) { out[2 * c] = s0; out[2 * c + 1] = s1; }
+  slab_sum(it.partial, it.rows, it.C, s0, s1, sh);
+  if (bn_lead() && c < it.C) { it.out[2 * c] = s0; it.out[2 * c + 1] = s1; }
+}
+__global__ void __launch_bounds__(BN_T) slab_reduce_kernel(const addk_slab_reduce_item it) {
+  __shared__ double2 sh[1][BN_RG][BN_CH];
+  slab_reduce_body(it, sh);
+}
+__global__ void __launch_bounds__(BN_T) slab_reduce_batch_kernel(const addk_slab_reduce_item* __restrict__ tab) {
+  __shared__ double2 sh[1][BN_RG][BN_CH];
+  const addk_slab_reduce_item it = tab[blockIdx.y];
+  if (blockIdx.x * BN_CH >= it.C) return;
+  slab_reduce_body(it, sh);
 }
 
-__global__ void bn_eval_affine_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
-                                      int C, float* a, float* b) {
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) {
-    float g = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-    float s = g / sqrtf(rv[c] + eps);
-    a[c] = s; b[c] = be - rm[c] * s;
-  }
-}
-
-// eval mode, all BatchNorms of a plan in one launch: block b handles table entry b
-struct BnEvalEntry { const float* gamma; const float* beta; const float* rm; const float* rv; float* a; float* b; int C; float eps; };
-__global__ void bn_eval_affine_batch_kernel(const BnEvalEntry* __restrict__ tab) {
-  const BnEvalEntry e = tab[blockIdx.x];
-  for (int c = threadIdx.x; c < e.C; c += blockDim.x) {
+// channels c0, c0 + step, ... of one eval-mode BatchNorm
+__device__ __forceinline__ void bn_eval_body(const addk_bn_eval_item& e, int c0, int step) {
+  for (int c = c0; c < e.C; c += step) {
     float g = e.gamma ? e.gamma[c] : 1.f, be = e.beta ? e.beta[c] : 0.f;
-    float s = g / sqrtf(e.rv[c] + e.eps);
-    e.a[c] = s; e.b[c] = be - e.rm[c] * s;
+    float s = g / sqrtf(e.running_var[c] + e.eps);
+    e.a[c] = s; e.b[c] = be - e.running_mean[c] * s;
   }
+}
+__global__ void bn_eval_affine_kernel(const addk_bn_eval_item e) {
+  bn_eval_body(e, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+// all BatchNorms of a plan in one launch: block b handles table entry b
+__global__ void bn_eval_affine_batch_kernel(const addk_bn_eval_item* __restrict__ tab) {
+  const addk_bn_eval_item e = tab[blockIdx.x];
+  bn_eval_body(e, threadIdx.x, blockDim.x);
 }
 
 __device__ __forceinline__ void bn_bwd_body(const addk_bn_bwd_args& p, bn_panel sh) {
@@ -222,24 +227,14 @@ __global__ void __launch_bounds__(BN_T) bn_bwd_batch_kernel(const addk_bn_bwd_ar
   bn_bwd_body(p, sh);
 }
 
-__global__ void __launch_bounds__(BN_T) slab_reduce_batch_kernel(const addk_slab_reduce_item* __restrict__ tab) {
-  __shared__ double2 sh[1][BN_RG][BN_CH];
-  const addk_slab_reduce_item it = tab[blockIdx.y];
-  if (blockIdx.x * BN_CH >= it.C) return;
-  const int c = bn_lead_channel();
-  double s0, s1;
-  slab_sum(it.partial, it.rows, it.C, s0, s1, sh);
-  if (bn_lead() && c < it.C) { it.out[2 * c] = s0; it.out[2 * c + 1] = s1; }
-}
-__global__ void bn_coeffs_batch_kernel(const addk_bn_coeffs_item* __restrict__ tab) {
-  const addk_bn_coeffs_item it = tab[blockIdx.y];
+__device__ __forceinline__ void bn_coeffs_body(const addk_bn_coeffs_item& it) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < it.C) { it.c1[c] = (float)((double)it.dmv[2 * c] / it.count); it.c2[c] = (float)(2.0 * (double)it.dmv[2 * c + 1] / it.count); }
 }
-
-__global__ void bn_coeffs_kernel(const float* dmv, int C, double count, float* c1, float* c2) {
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) { c1[c] = (float)((double)dmv[2 * c] / count); c2[c] = (float)(2.0 * (double)dmv[2 * c + 1] / count); }
+__global__ void bn_coeffs_kernel(const addk_bn_coeffs_item it) { bn_coeffs_body(it); }
+__global__ void bn_coeffs_batch_kernel(const addk_bn_coeffs_item* __restrict__ tab) {
+  const addk_bn_coeffs_item it = tab[blockIdx.y];
+  bn_coeffs_body(it);
 }
 
 }  // namespace
@@ -251,16 +246,15 @@ extern "C" int addk_bn_finalize(const addk_bn_finalize_args* a, void* stream) {
   return addk_check_launch("bn_finalize");
 }
 
-extern "C" int addk_slab_reduce(const double* partial, int32_t rows, int32_t C, double* out, void* stream) {
-  ADDK_REQUIRE(partial && out && rows > 0 && C > 0, "slab_reduce: bad args");
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(C, BN_CH)), dim3(BN_T), 0, (hipStream_t)stream, partial, rows, C, out);
+extern "C" int addk_slab_reduce(const addk_slab_reduce_item* it, void* stream) {
+  ADDK_REQUIRE(it && it->partial && it->out && it->rows > 0 && it->C > 0, "slab_reduce: bad args");
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(it->C, BN_CH)), dim3(BN_T), 0, (hipStream_t)stream, *it);
   return addk_check_launch("slab_reduce");
 }
 
-extern "C" int addk_bn_eval_affine(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
-                                   int32_t C, float* a, float* b, void* stream) {
-  ADDK_REQUIRE(rm && rv && a && b && C > 0, "bn_eval_affine: bad args");
-  hipLaunchKernelGGL(bn_eval_affine_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta, rm, rv, eps, C, a, b);
+extern "C" int addk_bn_eval_affine(const addk_bn_eval_item* it, void* stream) {
+  ADDK_REQUIRE(it && it->running_mean && it->running_var && it->a && it->b && it->C > 0, "bn_eval_affine: bad args");
+  hipLaunchKernelGGL(bn_eval_affine_kernel, dim3(cdiv(it->C, 256)), dim3(256), 0, (hipStream_t)stream, *it);
   return addk_check_launch("bn_eval_affine");
 }
 
@@ -273,15 +267,15 @@ extern "C" int addk_bn_bwd(const addk_bn_bwd_args* a, void* stream) {
   return addk_check_launch("bn_bwd");
 }
 
-extern "C" int addk_bn_bwd_coeffs_from_dmv(const float* dmv, int32_t C, double count, float* c1, float* c2, void* stream) {
-  ADDK_REQUIRE(dmv && c1 && c2 && C > 0 && count > 0, "bn_bwd_coeffs: bad args");
-  hipLaunchKernelGGL(bn_coeffs_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, dmv, C, count, c1, c2);
+extern "C" int addk_bn_bwd_coeffs(const addk_bn_coeffs_item* it, void* stream) {
+  ADDK_REQUIRE(it && it->dmv && it->c1 && it->c2 && it->C > 0 && it->count > 0, "bn_bwd_coeffs: bad args");
+  hipLaunchKernelGGL(bn_coeffs_kernel, dim3(cdiv(it->C, 256)), dim3(256), 0, (hipStream_t)stream, *it);
   return addk_check_launch("bn_bwd_coeffs");
 }
 
-extern "C" int addk_bn_eval_affine_batch(const void* dev_table, int32_t n, void* stream) {
+extern "C" int addk_bn_eval_affine_batch(const addk_bn_eval_item* dev_table, int32_t n, void* stream) {
   ADDK_REQUIRE(dev_table && n > 0, "bn_eval_affine_batch: bad args");
-  hipLaunchKernelGGL(bn_eval_affine_batch_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const BnEvalEntry*>(dev_table));
+  hipLaunchKernelGGL(bn_eval_affine_batch_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, dev_table);
   return addk_check_launch("bn_eval_affine_batch");
 }
 

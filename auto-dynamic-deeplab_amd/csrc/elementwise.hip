@@ -293,71 +293,63 @@ __global__ void __launch_bounds__(256, (NT <= 2 && !EXTRA) ? 4 : 1) affine_sum_b
   }
 }
 
-// vector-aligned form: every load is a plain 16-byte load issued up front (coefficients and data are one round trip)
-__global__ void __launch_bounds__(256) bn_bwd_apply_vec_kernel(const float* g, int ldg, const float* x, int ldx, const float* mean,
-                                                               const float* c1, const float* c2, long P, float* out, int ldo,
-                                                               int nq, int npl) {
+// vector-aligned items (16-byte pointers, ld % 4 == 0, C = 4 nq): the blocks of gridDim.x stride over the item's pixels.  Every load is a
+// plain 16-byte load; coefficients and the first pixel are one round trip, and the next pixel is requested before the current one is
+// stored.  HAS_C: the item has c1 / c2 (and so x); the loop holds no condition on them (a load behind a run-time condition makes the
+// compiler wait, where the paths join, for every load in flight: the next pixel would be awaited before the current one is stored).
+template <bool HAS_C>
+__device__ __forceinline__ void bn_bwd_apply_vec_body(const addk_bn_apply_item& it, int nq, int npl) {
   const int q = threadIdx.x % nq, pl = threadIdx.x / nq;
   if (pl >= npl) return;
-  const int c = 4 * q;
-  const long pp0 = (long)blockIdx.x * npl + pl;
-  if (pp0 >= P) return;
-  float4 gv = ld4(g + pp0 * ldg + c);
-  float4 xv = c2 ? ld4(x + pp0 * ldx + c) : zero4();
-  const float4 mu = mean ? ld4(mean + c) : zero4();
-  const float4 k1 = c1 ? ld4(c1 + c) : zero4();
-  const float4 k2 = c2 ? ld4(c2 + c) : zero4();
-  for (long pp = pp0;;) {
-    const long nx = pp + (long)gridDim.x * npl;
-    float4 gn = zero4(), xn = zero4();
-    if (nx < P) { gn = ld4(g + nx * ldg + c); if (c2) xn = ld4(x + nx * ldx + c); }
-    st4(out + pp * ldo + c, make_float4(gv.x + fmaf(k2.x, xv.x - mu.x, k1.x), gv.y + fmaf(k2.y, xv.y - mu.y, k1.y),
-                                        gv.z + fmaf(k2.z, xv.z - mu.z, k1.z), gv.w + fmaf(k2.w, xv.w - mu.w, k1.w)));
-    if (nx >= P) break;
-    pp = nx; gv = gn; xv = xn;
-  }
-}
-
-// several independent tensors in one launch (vector-aligned items only): block (x, y) strides over the pixels of item y
-struct BnApplyItem { const float* g; const float* x; const float* c1; const float* c2; const float* mean; float* out; long P; int ldg, ldx, ldo, C; };
-__global__ void __launch_bounds__(256) bn_bwd_apply_batch_kernel(const BnApplyItem* __restrict__ tab) {
-  const BnApplyItem it = tab[blockIdx.y];
-  const int nq = it.C >> 2, npl = 256 / nq;
-  const int q = threadIdx.x % nq, pl = threadIdx.x / nq;
-  if (pl >= npl) return;
-  const int c = 4 * q;
-  long pp = (long)blockIdx.x * npl + pl;
+  const int c = 4 * q, p0 = blockIdx.x * npl + pl;          // p0 < 2^31: the launchers cap the grid, npl <= 256
+  long pp = p0;
   if (pp >= it.P) return;
-  const float4 k1 = ld4(it.c1 + c), k2 = ld4(it.c2 + c);
-  const float4 mu = it.mean ? ld4(it.mean + c) : zero4();
   const long step = (long)gridDim.x * npl;
-  float4 gv = ld4(it.g + pp * it.ldg + c), xv = ld4(it.x + pp * it.ldx + c);
-  for (;;) {
-    const long nx = pp + step;
-    float4 gn = zero4(), xn = zero4();
-    if (nx < it.P) { gn = ld4(it.g + nx * it.ldg + c); xn = ld4(it.x + nx * it.ldx + c); }
-    st4(it.out + pp * it.ldo + c, make_float4(gv.x + fmaf(k2.x, xv.x - mu.x, k1.x), gv.y + fmaf(k2.y, xv.y - mu.y, k1.y),
-                                              gv.z + fmaf(k2.z, xv.z - mu.z, k1.z), gv.w + fmaf(k2.w, xv.w - mu.w, k1.w)));
-    if (nx >= it.P) break;
-    pp = nx; gv = gn; xv = xn;
+  const float4 k1 = HAS_C ? ld4(it.c1 + c) : zero4(), k2 = HAS_C ? ld4(it.c2 + c) : zero4();
+  float4 mu = ld4((it.mean ? it.mean : it.g) + c);          // NULL: g's first row is read and not used (no load behind a condition)
+  mu = it.mean ? mu : zero4();
+  // the three pointers walk: one 32 x 32-bit multiply each for the first pixel, none per pixel after it
+  const float* gp = it.g + (long)p0 * it.ldg + c; const float* xp = HAS_C ? it.x + (long)p0 * it.ldx + c : it.g; float* op = it.out + (long)p0 * it.ldo + c;
+  const long sg = step * it.ldg, sx = step * it.ldx, so = step * it.ldo;
+  float4 gv = ld4(gp), xv = HAS_C ? ld4(xp) : zero4();
+  auto dy = [&]() {
+    return make_float4(gv.x + fmaf(k2.x, xv.x - mu.x, k1.x), gv.y + fmaf(k2.y, xv.y - mu.y, k1.y),
+                       gv.z + fmaf(k2.z, xv.z - mu.z, k1.z), gv.w + fmaf(k2.w, xv.w - mu.w, k1.w));
+  };
+  for (;;) {                                // the next pixel's loads and the store before them in ONE basic block: the store does not wait for them
+    pp += step; gp += sg; xp += sx;
+    if (pp >= it.P) { st4(op, dy()); break; }
+    const float4 gn = ld4(gp), xn = HAS_C ? ld4(xp) : zero4();
+    st4(op, dy());
+    op += so; gv = gn; xv = xn;
   }
 }
+template <bool HAS_C>
+__global__ void __launch_bounds__(256) bn_bwd_apply_vec_kernel(const addk_bn_apply_item it, int nq, int npl) {
+  bn_bwd_apply_vec_body<HAS_C>(it, nq, npl);
+}
+// several independent tensors in one launch: block (x, y) strides over the pixels of item y
+__global__ void __launch_bounds__(256) bn_bwd_apply_batch_kernel(const addk_bn_apply_item* __restrict__ tab) {
+  const addk_bn_apply_item it = tab[blockIdx.y];
+  const int nq = it.C >> 2;
+  if (it.c2) bn_bwd_apply_vec_body<true>(it, nq, 256 / nq);          // uniform
+  else bn_bwd_apply_vec_body<false>(it, nq, 256 / nq);
+}
 
-__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* g, int ldg, const float* x, int ldx, const float* mean,
-                                                           const float* c1, const float* c2, long P, int C, float* out, int ldo,
-                                                           int nq, int npl, int vec) {
+// any alignment, any C <= 1024 (the lone entry only): guarded loads and stores
+__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const addk_bn_apply_item it, int nq, int npl, int vec) {
   const int q = threadIdx.x % nq, pl = threadIdx.x / nq;
   if (pl >= npl) return;
-  const int c = 4 * q, nrem = C - c;
-  float4 mu = mean ? ld4g(mean + c, nrem, vec) : zero4();
-  float4 k1 = c1 ? ld4g(c1 + c, nrem, vec) : zero4();
-  float4 k2 = c2 ? ld4g(c2 + c, nrem, vec) : zero4();
-  for (long pp = (long)blockIdx.x * npl + pl; pp < P; pp += (long)gridDim.x * npl) {
-    float4 gv = ld4g(g + pp * ldg + c, nrem, vec);
-    float4 xv = c2 ? ld4g(x + pp * ldx + c, nrem, vec) : zero4();
+  const int c = 4 * q, nrem = it.C - c;
+  float4 mu = it.mean ? ld4g(it.mean + c, nrem, vec) : zero4();
+  float4 k1 = it.c1 ? ld4g(it.c1 + c, nrem, vec) : zero4();
+  float4 k2 = it.c2 ? ld4g(it.c2 + c, nrem, vec) : zero4();
+  for (long pp = (long)blockIdx.x * npl + pl; pp < it.P; pp += (long)gridDim.x * npl) {
+    float4 gv = ld4g(it.g + pp * it.ldg + c, nrem, vec);
+    float4 xv = it.c2 ? ld4g(it.x + pp * it.ldx + c, nrem, vec) : zero4();
     float4 o = make_float4(gv.x + fmaf(k2.x, xv.x - mu.x, k1.x), gv.y + fmaf(k2.y, xv.y - mu.y, k1.y),
                            gv.z + fmaf(k2.z, xv.z - mu.z, k1.z), gv.w + fmaf(k2.w, xv.w - mu.w, k1.w));
-    st4g(out + pp * ldo + c, o, nrem, vec);
+    st4g(it.out + pp * it.ldo + c, o, nrem, vec);
   }
 }
 
@@ -461,20 +453,18 @@ extern "C" int addk_affine_sum_bwd(const addk_affine_sum_bwd_args* a, void* stre
   return addk_check_launch("affine_sum_bwd");
 }
 
-extern "C" int addk_bn_bwd_apply(const float* g, int32_t ldg, const float* x, int32_t ldx, const float* mean, const float* c1,
-                                 const float* c2, int64_t P, int32_t C, float* out, int32_t ldo, void* stream) {
-  ADDK_REQUIRE(g && out && P > 0 && C > 0 && C <= 1024 && ldg >= C && ldo >= C && (!c2 || (x && ldx >= C)), "bn_bwd_apply: bad args");
-  ADDK_REQUIRE((c1 == nullptr) == (c2 == nullptr), "bn_bwd_apply: c1/c2 come together");
-  int vec = aligned16(g) && aligned16(out) && ldg % 4 == 0 && ldo % 4 == 0 && C % 4 == 0 && (!x || (aligned16(x) && ldx % 4 == 0)) &&
-            (!mean || aligned16(mean)) && (!c1 || (aligned16(c1) && aligned16(c2)));
-  EwMap m = ew_map(C);
-  if (vec && C == m.nq * 4) {
-    hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, dim3(ew_blocks(P, m.npl)), dim3(256), 0, (hipStream_t)stream, g, ldg, x, ldx, mean, c1, c2,
-                       (long)P, out, ldo, m.nq, m.npl);
-    return addk_check_launch("bn_bwd_apply");
-  }
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_blocks(P, m.npl)), dim3(256), 0, (hipStream_t)stream, g, ldg, x, ldx, mean, c1, c2,
-                     (long)P, C, out, ldo, m.nq, m.npl, vec);
+extern "C" int addk_bn_bwd_apply(const addk_bn_apply_item* it, void* stream) {
+  ADDK_REQUIRE(it && it->g && it->out && it->P > 0 && it->C > 0 && it->C <= 1024 && it->ldg >= it->C && it->ldo >= it->C &&
+               (!it->c2 || (it->x && it->ldx >= it->C)), "bn_bwd_apply: bad args");
+  ADDK_REQUIRE((it->c1 == nullptr) == (it->c2 == nullptr), "bn_bwd_apply: c1/c2 come together");
+  int vec = aligned16(it->g) && aligned16(it->out) && it->ldg % 4 == 0 && it->ldo % 4 == 0 && it->C % 4 == 0 &&
+            (!it->x || (aligned16(it->x) && it->ldx % 4 == 0)) && (!it->mean || aligned16(it->mean)) &&
+            (!it->c1 || (aligned16(it->c1) && aligned16(it->c2)));
+  EwMap m = ew_map(it->C);
+  const dim3 grid(ew_blocks(it->P, m.npl));
+  if (vec && it->C == m.nq * 4 && it->c2) hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *it, m.nq, m.npl);
+  else if (vec && it->C == m.nq * 4) hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *it, m.nq, m.npl);
+  else hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, (hipStream_t)stream, *it, m.nq, m.npl, vec);
   return addk_check_launch("bn_bwd_apply");
 }
 
@@ -495,13 +485,10 @@ extern "C" int addk_sgd_step(float* p, const float* g, float* buf, int64_t n, co
   return addk_check_launch("sgd_step");
 }
 
-// table entries as addk_bn_apply_item (include/addk.h); every item must be vector-aligned (16-byte pointers, ld % 4 == 0,
-// C % 4 == 0, C <= 1024) with c1, c2 given (mean optional)
+// every item must be vector-aligned (include/addk.h)
 extern "C" int addk_bn_bwd_apply_batch(const addk_bn_apply_item* dev_table, int32_t n, int64_t max_P, void* stream) {
   ADDK_REQUIRE(dev_table && n > 0 && max_P > 0, "bn_bwd_apply_batch: bad args");
-  static_assert(sizeof(addk_bn_apply_item) == sizeof(BnApplyItem), "item layout");
   long b = cdiv(max_P, 6); if (b > 2048) b = 2048; if (b < 1) b = 1;
-  hipLaunchKernelGGL(bn_bwd_apply_batch_kernel, dim3((unsigned)b, n), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const BnApplyItem*>(dev_table));
+  hipLaunchKernelGGL(bn_bwd_apply_batch_kernel, dim3((unsigned)b, n), dim3(256), 0, (hipStream_t)stream, dev_table);
   return addk_check_launch("bn_bwd_apply_batch");
 }

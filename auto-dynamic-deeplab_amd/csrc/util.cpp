@@ -29,7 +29,7 @@ int addk_check_launch(const char* what) {
 }
 
 extern "C" const char* addk_last_error(void) { return g_err; }
-extern "C" int addk_version(void) { return 1; }
+extern "C" int addk_version(void) { return 2; }
 
 // Environment switches (A/B aids; INTEGRATION.md lists them): every one is read ONCE, under a lock, through this function — the only
 // getenv of the library.  An unset variable yields `dflt`; a set one its integer value.

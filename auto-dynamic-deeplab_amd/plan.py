@@ -365,7 +365,7 @@ class Graph:
         self.nstreams = max(1, int(nstreams))
         if self._evalbn:
             n = len(self._evalbn)
-            self._evalbn_cmd.table = (L.BnEvalEntry * n)(*self._evalbn)
+            self._evalbn_cmd.table = (L.BnEvalItem * n)(*self._evalbn)
             self._evalbn_cmd.args[0], self._evalbn_cmd.args[1] = self._table(bytes(self._evalbn_cmd.table)).data_ptr(), n
         self._emit_batched_dw_reductions()
         self._emit_batched_wgrads()
@@ -853,10 +853,8 @@ class Graph:
                 red = LateVec(4 * Cc, f64=True)      # fp64 [C][2], summed over ranks
                 sri = L.SlabReduceItem()
                 sri.partial, sri.rows, sri.C = slab.ptr, rows, Cc
-                csr = self._add(self.fwd, 'slab_reduce', lib.addk_slab_reduce, slab.ptr, rows, Cc, None, rd=[slab], wr=[red])
-                csr.payload = sri
-                red.binders += [lambda p, sri=sri: setattr(sri, 'out', p), lambda p, csr=csr: csr.args.__setitem__(3, p),
-                                lambda p: setattr(fa, 'partial', p)]
+                self._add(self.fwd, 'slab_reduce', lib.addk_slab_reduce, C.byref(sri), rd=[slab], wr=[red]).payload = sri
+                red.binders += [lambda p, sri=sri: setattr(sri, 'out', p), lambda p: setattr(fa, 'partial', p)]
                 self.world.emit_allreduce(self, self.fwd, red)    # every rank has the same per-rank count
                 fa.rows = 1
                 st.count = count * self.world.size
@@ -887,8 +885,8 @@ class Graph:
                 cfin.payload = fa
         else:
             # inference: (a, b) of ALL BatchNorms come from one batched launch placed where the first one is emitted
-            e = L.BnEvalEntry()
-            e.gamma, e.beta, e.rm, e.rv = gam, bet, mod.running_mean.data_ptr(), mod.running_var.data_ptr()
+            e = L.BnEvalItem()
+            e.gamma, e.beta, e.running_mean, e.running_var = gam, bet, mod.running_mean.data_ptr(), mod.running_var.data_ptr()
             e.a, e.b, e.C, e.eps = a.ptr, b.ptr, Cc, mod.eps
             if not self._evalbn:
                 self._evalbn_cmd = self._add(self.fwd, 'bn_eval_affine_batch', lib.addk_bn_eval_affine_batch, None, 0)
@@ -932,23 +930,18 @@ class Graph:
                     self.world.emit_allreduce(self, self.bwd, dmv)
                     cit = L.BnCoeffsItem()
                     cit.c1, cit.c2, cit.count, cit.C = c1.ptr, c2.ptr, st.count, Cc
-                    cco = self._add(self.bwd, 'bn_bwd_coeffs', lib.addk_bn_bwd_coeffs_from_dmv, None, Cc, st.count, c1.ptr, c2.ptr,
-                                    rd=[dmv], wr=[c1, c2])
-                    cco.payload = cit
-                    dmv.binders += [lambda p, ba=ba: setattr(ba, 'dmv', p), lambda p, cit=cit: setattr(cit, 'dmv', p),
-                                    lambda p, cco=cco: cco.args.__setitem__(0, p)]
+                    self._add(self.bwd, 'bn_bwd_coeffs', lib.addk_bn_bwd_coeffs, C.byref(cit), rd=[dmv], wr=[c1, c2]).payload = cit
+                    dmv.binders += [lambda p, ba=ba: setattr(ba, 'dmv', p), lambda p, cit=cit: setattr(cit, 'dmv', p)]
                 else:
                     ba.c1, ba.c2 = c1.ptr, c2.ptr
                     self._add(self.bwd, 'bn_bwd', lib.addk_bn_bwd, C.byref(ba), rd=rd_bn, wr=pg + [c1, c2]).payload = ba
                 # dy_raw = G + c1 + c2*x, in place on the accumulated gradient
-                cap = self._add(self.bwd, 'bn_bwd_apply', lib.addk_bn_bwd_apply, g.ptr, g.ld, raw.ptr, raw.ld, _ptr(mu),
-                                c1.ptr, c2.ptr, raw.P, Cc, g.ptr, g.ld, rd=[g, raw, c1, c2, mu], wr=[g])
+                it = L.BnApplyItem()
+                it.g, it.x, it.c1, it.c2, it.mean, it.out, it.P = g.ptr, raw.ptr, c1.ptr, c2.ptr, _ptr(mu), g.ptr, raw.P
+                it.ldg, it.ldx, it.ldo, it.C = g.ld, raw.ld, g.ld, Cc
+                cap = self._add(self.bwd, 'bn_bwd_apply', lib.addk_bn_bwd_apply, C.byref(it), rd=[g, raw, c1, c2, mu], wr=[g])
                 if Cc % 4 == 0 and Cc <= 1024 and g.ld % 4 == 0 and raw.ld % 4 == 0 and g.ptr % 16 == 0 and raw.ptr % 16 == 0:
-                    it = L.BnApplyItem()
-                    it.g, it.x, it.c1, it.c2, it.out, it.P = g.ptr, raw.ptr, c1.ptr, c2.ptr, g.ptr, raw.P
-                    it.mean = _ptr(mu)
-                    it.ldg, it.ldx, it.ldo, it.C = g.ld, raw.ld, g.ld, Cc
-                    cap.payload = it
+                    cap.payload = it          # vector-aligned: may join a table
             self._bwd_emitters.append(emit_bwd)
         return act
 

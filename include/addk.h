@@ -38,6 +38,9 @@ extern "C" {
 #define ADDK_ERR_HIP (-3)
 
 const char* addk_last_error(void);
+/* 2: the lone entries addk_slab_reduce, addk_bn_eval_affine, addk_bn_bwd_coeffs (version 1: addk_bn_bwd_coeffs_from_dmv) and
+ * addk_bn_bwd_apply take one item struct where version 1 took positional arguments; the _batch entries and every struct layout
+ * are those of version 1. */
 int addk_version(void);
 /* Probes MFMA f32 16x16x4 fragment layout on the device: out[256] = A(16x4)·B(4x16) with
  * A[i][k] = i*4+k, B[k][j] = (k+1)*(j+2) (asymmetric).  Used by smoke tests. */
@@ -347,25 +350,28 @@ int addk_bn_finalize(const addk_bn_finalize_args* a, void* stream);
 /* n independent BatchNorms in one launch; dev_table = device array of n argument structs, max_C = largest C among them */
 int addk_bn_finalize_batch(const addk_bn_finalize_args* dev_table, int32_t n, int32_t max_C, void* stream);
 
+/* Every BatchNorm op below comes as X(const item*, stream), one launch for one item, and X_batch(dev_table, n, ..., stream), one
+ * launch for a device array of n items of the same type. */
+
 /* sum the rows of a partial slab into out[C][2] (the vector that is all-reduced over RCCL) */
-int addk_slab_reduce(const double* partial, int32_t rows, int32_t C, double* out, void* stream);
 typedef struct addk_slab_reduce_item { const double* partial; double* out; int32_t rows, C; } addk_slab_reduce_item;
+int addk_slab_reduce(const addk_slab_reduce_item* it, void* stream);
 int addk_slab_reduce_batch(const addk_slab_reduce_item* dev_table, int32_t n, int32_t max_C, void* stream);
 
-/* eval mode: a = gamma/sqrt(running_var+eps), b = beta - running_mean*a */
-int addk_bn_eval_affine(const float* gamma, const float* beta, const float* rm, const float* rv,
-                        float eps, int32_t C, float* a, float* b, void* stream);
-
-/* The same for every BatchNorm of an inference plan in ONE launch: `dev_table` is a device array of n entries
- * {gamma, beta, running_mean, running_var, a, b (pointers), int32 C, float eps} (56 bytes each). */
-int addk_bn_eval_affine_batch(const void* dev_table, int32_t n, void* stream);
+/* eval mode: a = gamma/sqrt(running_var+eps), b = beta - running_mean*a (gamma / beta NULL: 1 / 0); 56 bytes */
+typedef struct addk_bn_eval_item {
+  const float* gamma; const float* beta; const float* running_mean; const float* running_var; float* a; float* b; int32_t C; float eps;
+} addk_bn_eval_item;
+int addk_bn_eval_affine(const addk_bn_eval_item* it, void* stream);
+/* the same for every BatchNorm of an inference plan in ONE launch */
+int addk_bn_eval_affine_batch(const addk_bn_eval_item* dev_table, int32_t n, void* stream);
 
 /* Backward of the statistics + affine:  given the partial (dA,dB) slabs of every consumer,
  *   dgamma (+)= invstd*(dA - mean*dB), dbeta (+)= dB,
  *   dmean_tot = -a*dB - 2*mean*dvar,  dvar = -0.5*gamma*(dA-mean*dB)*invstd^3,
  *   c1 = dmean_tot/count, c2 = 2*dvar/count  so that  dx_raw = G + c1 + c2*x.
  * With SyncBN, `dmv` receives (dmean_tot, dvar) per channel for the cross-rank all-reduce
- * and addk_bn_bwd_coeffs_from_dmv() finishes the job. */
+ * and addk_bn_bwd_coeffs() finishes the job. */
 typedef struct addk_bn_bwd_args {
   const double* slab[ADDK_MAX_SLAB]; int32_t rows[ADDK_MAX_SLAB]; int32_t nslab;
   int32_t C; double count;
@@ -377,8 +383,9 @@ typedef struct addk_bn_bwd_args {
 } addk_bn_bwd_args;
 int addk_bn_bwd(const addk_bn_bwd_args* a, void* stream);
 int addk_bn_bwd_batch(const addk_bn_bwd_args* dev_table, int32_t n, int32_t max_C, void* stream);
-int addk_bn_bwd_coeffs_from_dmv(const float* dmv, int32_t C, double count, float* c1, float* c2, void* stream);
+/* c1 = dmv[c][0] / count, c2 = 2 * dmv[c][1] / count from the all-reduced dmv */
 typedef struct addk_bn_coeffs_item { const float* dmv; float* c1; float* c2; double count; int32_t C, _pad; } addk_bn_coeffs_item;
+int addk_bn_bwd_coeffs(const addk_bn_coeffs_item* it, void* stream);
 int addk_bn_bwd_coeffs_batch(const addk_bn_coeffs_item* dev_table, int32_t n, int32_t max_C, void* stream);
 
 /* ---------------------------------------------------------------------------------------
@@ -407,15 +414,14 @@ int addk_ew_rows(int64_t P, int32_t C);
 
 /* dy[p,c] = g[p,c] + c1[c] + c2[c]*(x[p,c] - mean[c])   (BN backward applied to the accumulated gradient;
  * mean/c1/c2 may be NULL = 0).  The centred form (addk_bn_bwd_args.centered) keeps c2*x from cancelling against a c1 that
- * carries -c2*mean: the reference subtracts the mean first (batchnorm.py:51-53 / ATen batch_norm_backward).  out may alias g. */
-int addk_bn_bwd_apply(const float* g, int32_t ldg, const float* x, int32_t ldx, const float* mean,
-                      const float* c1, const float* c2, int64_t P, int32_t C, float* out, int32_t ldo,
-                      void* stream);
-/* the same for n independent tensors in one launch (vector-aligned items only: 16-byte pointers, ld % 4 == 0, C % 4 == 0;
- * out[p,c] = g[p,c] + c1[c] + c2[c]*(x[p,c] - mean[c]), mean may be NULL */
+ * carries -c2*mean: the reference subtracts the mean first (batchnorm.py:51-53 / ATen batch_norm_backward).  out may alias g.
+ * c1 and c2 come together; x is needed only with c2; C <= 1024.  The lone entry accepts any alignment (an item that is not
+ * vector-aligned runs a generic kernel); the table form demands vector-aligned items: 16-byte pointers, ld % 4 == 0, C % 4 == 0. */
 typedef struct addk_bn_apply_item {
   const float* g; const float* x; const float* c1; const float* c2; const float* mean; float* out; int64_t P; int32_t ldg, ldx, ldo, C;
 } addk_bn_apply_item;
+int addk_bn_bwd_apply(const addk_bn_apply_item* it, void* stream);
+/* the same for n independent tensors in one launch, max_P = largest P among them */
 int addk_bn_bwd_apply_batch(const addk_bn_apply_item* dev_table, int32_t n, int64_t max_P, void* stream);
 
 /* ---------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Time the BatchNorm slab kernels (csrc/bn.hip) through the C ABI at every shape config 2's train plan runs them at (NET_FIN and
-NET_BWD of tests/test_gpu_bn_kernels.py), as single launches and as batch tables, for one or more builds of the library:
+NET_BWD of tests/test_gpu_bn_kernels.py; slab_reduce, the SyncBN form of the forward sums, at the slabs of NET_FIN), as single launches
+and as batch tables, for one or more builds of the library:
 
     python scripts/bn_time.py [--launches 200] [--rounds 3] [--batch 4] LIB [LIB ...]
 
@@ -7,7 +8,8 @@ Each LIB is a path to a libaddk.so, optionally NAME=PATH; the libraries are time
 so a parent build and a new build see the same device state.  A measurement is LAUNCHES launches captured into one graph (no host in
 the loop), warmed by one replay and timed over one more between two HIP events; the launches walk round 8 copies of the slabs, so a 9-slab
 list (3.9 MB) is not served from one XCD's L2 alone, as it is not in the step.  Printed: microseconds per launch, the median over the
-rounds; `batch` is one table of BATCH entries of the shape (microseconds per launch of the table).  Last column: first library / last."""
+rounds and, in brackets, the spread max - min of the rounds; `batch` is one table of BATCH entries of the shape (microseconds per launch
+of the table).  Last column: first library / last."""
 import argparse
 import ctypes as C
 import os
@@ -43,6 +45,13 @@ def fin_args(Cc, count, rows):
     return a
 
 
+def reduce_args(Cc, count, rows):
+    it = L.SlabReduceItem()
+    it.partial, it.out, it.rows, it.C = dev(rows, Cc, 2, dtype=f64).data_ptr(), dev(Cc, 2, dtype=f64).data_ptr(), rows, Cc
+    KEEP.append(it)
+    return it
+
+
 def bwd_args(Cc, count, rows):
     a = L.BnBwdArgs()
     for i, r in enumerate(rows):
@@ -65,8 +74,18 @@ def bind(path):
     lib = C.CDLL(path)
     for name in ('addk_bn_finalize', 'addk_bn_bwd'):
         getattr(lib, name).argtypes, getattr(lib, name).restype = [C.c_void_p, C.c_void_p], C.c_int
-    for name in ('addk_bn_finalize_batch', 'addk_bn_bwd_batch'):
+    for name in ('addk_bn_finalize_batch', 'addk_bn_bwd_batch', 'addk_slab_reduce_batch'):
         getattr(lib, name).argtypes, getattr(lib, name).restype = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], C.c_int
+    # the lone slab_reduce takes the table's item since version 2 of the library, positional arguments before
+    if lib.addk_version() >= 2:
+        lib.addk_slab_reduce.argtypes = [C.c_void_p, C.c_void_p]
+        reduce = lambda it, st: lib.addk_slab_reduce(C.addressof(it), st)                              # noqa: E731
+    else:
+        lib.addk_slab_reduce.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        reduce = lambda it, st: lib.addk_slab_reduce(it.partial, it.rows, it.C, it.out, st)            # noqa: E731
+    by_address = lambda fn: lambda a, st: fn(C.addressof(a), st)                                       # noqa: E731
+    lib.kinds = {'finalize': (by_address(lib.addk_bn_finalize), lib.addk_bn_finalize_batch), 'bwd': (by_address(lib.addk_bn_bwd), lib.addk_bn_bwd_batch),
+                 'reduce': (reduce, lib.addk_slab_reduce_batch)}
     return lib
 
 
@@ -106,23 +125,21 @@ def main():
         libs.append((name or os.path.basename(os.path.dirname(os.path.abspath(path))), bind(os.path.abspath(path))))
     torch.manual_seed(0)
     rowsets = []                                              # (label, {lib name: {form: graph}})
-    for kind, shapes in (('finalize', NET_FIN), ('bwd', NET_BWD)):
-        make = fin_args if kind == 'finalize' else bwd_args
+    for kind, shapes, make in (('finalize', NET_FIN, fin_args), ('bwd', NET_BWD, bwd_args), ('reduce', NET_FIN, reduce_args)):
         for Cc, count, rows in shapes:
             copies = [make(Cc, count, rows) for _ in range(COPIES)]
             tabs = [table([copies[(j + i) % COPIES] for i in range(o.batch)]) for j in range(COPIES)] if kind == 'bwd' else \
-                [table([make(Cc, count, rows) for _ in range(o.batch)]) for _ in range(COPIES)]     # finalize entries: outputs of their own
+                [table([make(Cc, count, rows) for _ in range(o.batch)]) for _ in range(COPIES)]     # finalize / reduce entries: outputs of their own
             graphs = {}
             for name, lib in libs:
-                one = getattr(lib, 'addk_bn_' + kind)
-                bat = getattr(lib, 'addk_bn_%s_batch' % kind)
+                one, bat = lib.kinds[kind]
                 graphs[name] = {
-                    'single': graph_of(lambda j, st: one(C.addressof(copies[j % COPIES]), st), o.launches),
+                    'single': graph_of(lambda j, st: one(copies[j % COPIES], st), o.launches),
                     'batch': graph_of(lambda j, st: bat(tabs[j % COPIES].data_ptr(), o.batch, Cc, st), o.launches)}
             rowsets.append(('%-8s C=%-3d rows=%s' % (kind, Cc, rows), graphs))
     names = [n for n, _ in libs]
-    print('# us per launch, median of %d rounds of %d graph-replayed launches; batch = one table of %d entries' % (o.rounds, o.launches, o.batch))
-    print('%-64s' % 'shape' + ''.join('%14s' % (n + ' ' + f) for f in ('single', 'batch') for n in names) + '   %s/%s single, batch' % (names[0], names[-1]))
+    print('# us per launch, median of %d rounds of %d graph-replayed launches [max - min of the rounds]; batch = one table of %d entries' % (o.rounds, o.launches, o.batch))
+    print('%-64s' % 'shape' + ''.join('%22s' % (n + ' ' + f) for f in ('single', 'batch') for n in names) + '   %s/%s single, batch' % (names[0], names[-1]))
     tot = {(n, f): 0.0 for n in names for f in ('single', 'batch')}
     for label, graphs in rowsets:
         t = {(n, f): [] for n in names for f in ('single', 'batch')}
@@ -133,9 +150,9 @@ def main():
         med = {k: statistics.median(v) for k, v in t.items()}
         for k, v in med.items():
             tot[k] += v
-        print('%-64s' % label + ''.join('%14.2f' % med[(n, f)] for f in ('single', 'batch') for n in names)
+        print('%-64s' % label + ''.join('%14.2f [%5.2f]' % (med[(n, f)], max(t[(n, f)]) - min(t[(n, f)])) for f in ('single', 'batch') for n in names)
               + '   %5.2fx %5.2fx' % (med[(names[0], 'single')] / med[(names[-1], 'single')], med[(names[0], 'batch')] / med[(names[-1], 'batch')]), flush=True)
-    print('%-64s' % 'sum over the shapes' + ''.join('%14.2f' % tot[(n, f)] for f in ('single', 'batch') for n in names))
+    print('%-64s' % 'sum over the shapes' + ''.join('%14.2f        ' % tot[(n, f)] for f in ('single', 'batch') for n in names))
 
 
 if __name__ == '__main__':

@@ -79,8 +79,14 @@ def bind(path):
     lib = C.CDLL(path)
     for name in ('addk_affine_sum_fwd', 'addk_affine_sum_bwd'):
         getattr(lib, name).argtypes, getattr(lib, name).restype = [C.c_void_p, C.c_void_p], C.c_int
-    lib.addk_bn_bwd_apply.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                      C.c_void_p, C.c_int32, C.c_void_p]
+    # the lone entry takes the table's item since version 2 of the library, positional arguments before: `lib.apply(item, stream)` either way
+    if lib.addk_version() >= 2:
+        lib.addk_bn_bwd_apply.argtypes = [C.c_void_p, C.c_void_p]
+        lib.apply = lambda it, st: lib.addk_bn_bwd_apply(C.addressof(it), st)
+    else:
+        lib.addk_bn_bwd_apply.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                          C.c_void_p, C.c_int32, C.c_void_p]
+        lib.apply = lambda it, st: lib.addk_bn_bwd_apply(it.g, it.ldg, it.x, it.ldx, it.mean, it.c1, it.c2, it.P, it.C, it.out, it.ldo, st)
     lib.addk_bn_bwd_apply_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
     lib.addk_ew_rows.argtypes, lib.addk_ew_rows.restype = [C.c_int64, C.c_int32], C.c_int
     lib.addk_bn_bwd_apply.restype = lib.addk_bn_bwd_apply_batch.restype = C.c_int
@@ -162,8 +168,7 @@ def main():
         nc = copies_for(2 * t4)
         items = [apply_item(P, Cc) for _ in range(nc)]
         run('bn_bwd_apply P=%d C=%d' % (P, Cc), 3 * t4,
-            lambda lib: graph_of(lambda j, st: (lambda it: lib.addk_bn_bwd_apply(it.g, Cc, it.x, Cc, it.mean, it.c1, it.c2, P, Cc, it.out, Cc, st))(items[j % nc]),
-                                 o.launches))
+            lambda lib: graph_of(lambda j, st: lib.apply(items[j % nc], st), o.launches))
         nc = copies_for(2 * t4 * o.batch)
         tabs = [table([apply_item(P, Cc) for _ in range(o.batch)]) for _ in range(nc)]
         run('bn_bwd_apply_batch %d x (P=%d C=%d)' % (o.batch, P, Cc), 3 * t4 * o.batch,

@@ -27,17 +27,14 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), 'libaddk.so does not export %s' % n
     assert set(names) == set(L.EXPORTED_SYMBOLS), set(names) ^ set(L.EXPORTED_SYMBOLS)
-    assert lib.addk_version() >= 1
+    assert lib.addk_version() >= 2
 
 
 def test_struct_layouts_match_header():
-    structs = {'addk_src': L.Src, 'addk_conv_args': L.ConvArgs, 'addk_conv_dgrad_args': L.ConvDgradArgs,
-               'addk_conv_wgrad_args': L.ConvWgradArgs, 'addk_dw_args': L.DwArgs, 'addk_sep_args': L.SepArgs, 'addk_sep_bwd_args': L.SepBwdArgs, 'addk_ce_upsample_args': L.CeUpsampleArgs, 'addk_dw_bwd_args': L.DwBwdArgs,
-               'addk_bn_finalize_args': L.BnFinalizeArgs, 'addk_bn_bwd_args': L.BnBwdArgs,
-               'addk_affine_sum_args': L.AffineSumArgs, 'addk_affine_sum_bwd_args': L.AffineSumBwdArgs,
-               'addk_resize_args': L.ResizeArgs, 'addk_edm_args': L.EdmArgs, 'addk_resize_bwd_args': L.ResizeBwdArgs,
-               'addk_dw_wreduce_item': L.DwWreduceItem, 'addk_bn_apply_item': L.BnApplyItem,
-               'addk_slab_reduce_item': L.SlabReduceItem, 'addk_bn_coeffs_item': L.BnCoeffsItem}
+    structs = L.STRUCTS
+    mirrors = {c for c in vars(L).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__module__ == L.__name__}
+    assert mirrors == set(structs.values()), 'not in _lib.STRUCTS: %s' % sorted(c.__name__ for c in mirrors - set(structs.values()))
+    assert len(set(structs.values())) == len(structs)
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "addk.h"', 'int main(void){']
     for cname, cls in structs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

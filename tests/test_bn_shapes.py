@@ -36,7 +36,8 @@ def network_shapes(monkeypatch):
             s['bn'].add((b.C, int(b.count)))
             s['bwd'].add((b.C, int(b.count), tuple(sorted(b.rows[i] for i in range(b.nslab)))))
         elif c.fn is lib.addk_bn_bwd_apply:
-            s['apply'].add((int(a[8]), int(a[7])))
+            it = obj(a[0])
+            s['apply'].add((it.C, int(it.P)))
         elif c.fn is lib.addk_affine_sum_fwd:
             f = obj(a[0])
             s['affine'].add((int(f.P), f.C, f.nterm, f.ldo))

@@ -273,7 +273,9 @@ def test_slab_reduce_and_the_syncbn_finalize(lib):
     reds = []
     for f in fins:
         red = _nan(f.C, 2, dtype=f64)
-        L.check(lib.addk_slab_reduce(f.slab.data_ptr(), f.rows, f.C, red.data_ptr(), _st()), 'slab_reduce')
+        it = L.SlabReduceItem()
+        it.partial, it.out, it.rows, it.C = f.slab.data_ptr(), red.data_ptr(), f.rows, f.C
+        L.check(lib.addk_slab_reduce(C.byref(it), _st()), 'slab_reduce')
         _close('slab_reduce C=%d rows=%d' % (f.C, f.rows), red, f.slab.sum(0), 1e-12 * f.slab.abs().sum(0))
         reds.append(red)
     outs = [_nan(f.C, 2, dtype=f64) for f in fins]
@@ -303,8 +305,10 @@ def test_bn_eval_affine(lib):
     for Cc, affine in ((40, True), (19, True), (256, False), (1024, True), (1600, True), (1, True)):
         e = dict(C=Cc, gamma=(1 + 0.3 * _randn(gen, Cc)) if affine else None, beta=_randn(gen, Cc) if affine else None,
                  rm=_randn(gen, Cc), rv=0.01 + 2 * _rand(gen, Cc), a=_nan(Cc), b=_nan(Cc))
-        L.check(lib.addk_bn_eval_affine(_p(e['gamma']), _p(e['beta']), _p(e['rm']), _p(e['rv']), EPS, Cc, _p(e['a']), _p(e['b']), _st()),
-                'bn_eval_affine')
+        x = L.BnEvalItem()
+        x.gamma, x.beta, x.running_mean, x.running_var, x.a, x.b = _p(e['gamma']), _p(e['beta']), _p(e['rm']), _p(e['rv']), _p(e['a']), _p(e['b'])
+        x.C, x.eps = Cc, EPS
+        L.check(lib.addk_bn_eval_affine(C.byref(x), _st()), 'bn_eval_affine')
         g = e['gamma'].double() if affine else 1.0
         be = e['beta'].double() if affine else torch.zeros(Cc, dtype=f64, device='cuda')
         rm = e['rm'].double()
@@ -315,9 +319,9 @@ def test_bn_eval_affine(lib):
         cases.append(e)
     ents = []
     for e in cases:
-        x = L.BnEvalEntry()
+        x = L.BnEvalItem()
         e['a2'], e['b2'] = _nan(e['C']), _nan(e['C'])
-        x.gamma, x.beta, x.rm, x.rv, x.a, x.b = _p(e['gamma']), _p(e['beta']), _p(e['rm']), _p(e['rv']), _p(e['a2']), _p(e['b2'])
+        x.gamma, x.beta, x.running_mean, x.running_var, x.a, x.b = _p(e['gamma']), _p(e['beta']), _p(e['rm']), _p(e['rv']), _p(e['a2']), _p(e['b2'])
         x.C, x.eps = e['C'], EPS
         ents.append(x)
     tab = _table(ents)
@@ -447,7 +451,7 @@ NINE = (501, 989, 989, 989, 989, 501, 501, 128, 512)       # the 9-slab list of 
 @pytest.mark.parametrize('accumulate', [0, 1])
 def test_bn_bwd_variants_and_the_dmv_route(lib, centered, accumulate):
     """centered 0 / 1, accumulate 0 / 1 into dgamma / dbeta, gamma NULL, and both outputs: c1 / c2 directly, or dmv followed by
-    bn_bwd_coeffs_from_dmv (and its batch form).  At world 1 the dmv route gives c1 / c2 within ONE extra rounding of the direct route:
+    bn_bwd_coeffs (and its batch form).  At world 1 the dmv route gives c1 / c2 within ONE extra rounding of the direct route:
     dmv rounds (dmean, dvar) to fp32 once more before the division by the count, so the two results are at most one fp32 ulp apart."""
     gen = _gen(6 + 2 * centered + accumulate)
     cases = [(40, 63250, NINE), (80, 16002, (256, 501, 666, 682, 989)), (19, 777, (447, 449)), (256, 2, (1,)), (1024, 4096, (64, 3))]
@@ -465,7 +469,9 @@ def test_bn_bwd_variants_and_the_dmv_route(lib, centered, accumulate):
     coeffs, items = [], []
     for b, d in zip(viadmv, direct):
         c1, c2 = _nan(b.C), _nan(b.C)
-        L.check(lib.addk_bn_bwd_coeffs_from_dmv(b.dmv.data_ptr(), b.C, float(b.count), c1.data_ptr(), c2.data_ptr(), _st()), 'bn_bwd_coeffs')
+        one = L.BnCoeffsItem()
+        one.dmv, one.c1, one.c2, one.count, one.C = b.dmv.data_ptr(), c1.data_ptr(), c2.data_ptr(), float(b.count), b.C
+        L.check(lib.addk_bn_bwd_coeffs(C.byref(one), _st()), 'bn_bwd_coeffs')
         R = b.ref()
         for name, got, dir_ in (('c1', c1, d.c1), ('c2', c2, d.c2)):
             v, S, N = R[name]
@@ -506,8 +512,10 @@ def _apply_vecs(gen, Cc):
 
 def _apply(lib, g, x, mean, c1, c2, out):
     P, Cc = g.shape
-    L.check(lib.addk_bn_bwd_apply(g.data_ptr(), g.stride(0), _p(x), x.stride(0) if x is not None else 0, _p(mean), _p(c1), _p(c2), P, Cc,
-                                  out.data_ptr(), out.stride(0), _st()), 'bn_bwd_apply')
+    it = L.BnApplyItem()
+    it.g, it.x, it.c1, it.c2, it.mean, it.out, it.P = g.data_ptr(), _p(x), _p(c1), _p(c2), _p(mean), out.data_ptr(), P
+    it.ldg, it.ldx, it.ldo, it.C = g.stride(0), x.stride(0) if x is not None else 0, out.stride(0), Cc
+    L.check(lib.addk_bn_bwd_apply(C.byref(it), _st()), 'bn_bwd_apply')
 
 
 def test_bn_bwd_apply_in_place_at_network_shapes(lib):

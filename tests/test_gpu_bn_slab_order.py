@@ -74,7 +74,9 @@ def test_slab_sums_follow_the_written_order_bit_for_bit(lib):
     outs, items = [], []
     for rows, Cc, slab, ref in cases:
         red = K._nan(Cc, 2, dtype=f64)
-        L.check(lib.addk_slab_reduce(slab.data_ptr(), rows, Cc, red.data_ptr(), K._st()), 'slab_reduce')
+        one = L.SlabReduceItem()
+        one.partial, one.out, one.rows, one.C = slab.data_ptr(), red.data_ptr(), rows, Cc
+        L.check(lib.addk_slab_reduce(C.byref(one), K._st()), 'slab_reduce')
         K._same_bits('slab_reduce rows=%d C=%d against the written order' % (rows, Cc), red, ref)
         o = K._nan(Cc, 2, dtype=f64)
         it = L.SlabReduceItem()

@@ -227,8 +227,10 @@ def _apply_single(lib, c, ld):
     P, Cc = c['P'], c['C']
     gbuf, g_d = _rows_of(c['g'], P, Cc, ld)
     xbuf, x_d = _rows_of(c['x'], P, Cc, ld)
-    L.check(lib.addk_bn_bwd_apply(g_d.data_ptr(), ld, x_d.data_ptr(), ld, c['mean'].data_ptr(), c['c1'].data_ptr(), c['c2'].data_ptr(), P, Cc,
-                                  g_d.data_ptr(), ld, _st()), 'bn_bwd_apply')
+    it = L.BnApplyItem()
+    it.g, it.x, it.c1, it.c2, it.mean, it.out, it.P = g_d.data_ptr(), x_d.data_ptr(), c['c1'].data_ptr(), c['c2'].data_ptr(), c['mean'].data_ptr(), g_d.data_ptr(), P
+    it.ldg, it.ldx, it.ldo, it.C = ld, ld, ld, Cc
+    L.check(lib.addk_bn_bwd_apply(C.byref(it), _st()), 'bn_bwd_apply')
     torch.cuda.synchronize()
     if ld > Cc:
         assert torch.isnan(gbuf[:P * ld].view(P, ld)[:, Cc:]).all(), 'bn_bwd_apply wrote past C'
