@@ -341,6 +341,8 @@ _SIGS = {
     'addk_ce_count': (i32, [vp, i64, vp, i32, i32, vp, vp, vp]),
     'addk_ce_fwd_bwd': (i32, [vp, vp, i32, i32, i64, vp, i32, vp, f32, vp, vp, vp, vp]),
     'addk_ce_ws_floats': (i64, [i32, i64]),
+    'addk_head_classes': (i32, [C.POINTER(i32), i32]),
+    'addk_gate_head_classes': (i32, [C.POINTER(i32), i32]),
     'addk_ce_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_ce_upsample_ws_floats': (i64, [i32, i32, i32]),
     'addk_ce_upsample_fwd_bwd': (i32, [C.POINTER(CeUpsampleArgs), vp]),
@@ -353,6 +355,7 @@ _SIGS = {
     'addk_ce_upsample_kd_fwd_bwd': (i32, [C.POINTER(CeUpsampleKdArgs), vp]),
     'addk_dice_stats_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_dice_stats_ws_bytes': (i64, [i32, i32, i32]),
+    'addk_dice_stats_ws_bytes_classes': (i64, [i32, i32, i32, i32]),
     'addk_dice_stats': (i32, [C.POINTER(DiceStatsArgs), vp]),
     'addk_ce_upsample_dice_fwd_bwd': (i32, [C.POINTER(CeUpsampleDiceArgs), vp]),
     'addk_score_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
@@ -413,6 +416,37 @@ def load():
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
+
+
+def _classes(query):
+    out = (i32 * query(None, 0))()
+    query(out, len(out))
+    return tuple(out)
+
+
+def _classes_text(counts):
+    first, *more = counts
+    return '%d classes' % first + (' (or %s)' % ', '.join(map(str, more)) if more else '')
+
+
+def head_classes():
+    """The class counts the training heads and the label head are compiled for (`addk_head_classes`: csrc/up.h holds the list)."""
+    return _classes(load().addk_head_classes)
+
+
+def gate_head_classes():
+    """The class counts the scoring, profile, calibration, gate and multi-view heads are compiled for (`addk_gate_head_classes`)."""
+    return _classes(load().addk_gate_head_classes)
+
+
+def head_classes_text():
+    """'19 classes (or 21)': how the error messages name head_classes()."""
+    return _classes_text(head_classes())
+
+
+def gate_head_classes_text():
+    """'19 classes': how the error messages name gate_head_classes()."""
+    return _classes_text(gate_head_classes())
 
 
 def check(rc, what=''):

@@ -7,7 +7,7 @@ namespace {
 // ---- fused logits up-sampling + calibration statistics (temperature scaling, Guo et al. 2017) --------------------------------------
 // What the reliability diagram, the ECE and the fit of one temperature per exit need, for CAL_T temperatures in one walk.  The walk is
 // scu_walk (same tile, same interpolation z = lh0*t0 + lh1*t1), then the strict `>` arg-max sweep of score_up_kernel; d = z - mx is
-// formed once and every temperature j runs its own exp sweep over d * it[j]: CAL_T x 19 exponentials per pixel, so the kernel is bound
+// formed once and every temperature j runs its own exp sweep over d * it[j]: CAL_T x CC exponentials per pixel, so the kernel is bound
 // by the transcendental rate, not by memory (the target, 8 bytes per pixel, is the only HBM stream).  it[], the NLL partials and
 // the pending runs stay in registers (the temperature loop is fully unrolled behind a wave-uniform `j < nt`).
 // Bins: on real data most pixels of a tile fall into the top bin, so nothing reaches LDS per pixel.  A thread merges the run of equal
@@ -163,7 +163,7 @@ extern "C" int64_t addk_calib_upsample_ws_bytes(int32_t N, int32_t OH, int32_t O
 extern "C" int addk_calib_upsample(const addk_calib_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->target && a->inv_temp && a->bins && a->nll && a->ws, "calib_upsample: null pointer");
   ADDK_REQUIRE(addk_calib_upsample_supported(a->N, a->H, a->W, a->OH, a->OW, a->C, a->nt) == 1,
-               "calib_upsample: unsupported shape (19 classes, 1..%d temperatures)", CAL_T);
+               "calib_upsample: unsupported shape (%s, 1..%d temperatures)", gate_classes_text().c_str(), CAL_T);
   ADDK_REQUIRE(a->ld >= a->C, "calib_upsample: short stride");
   CalibUpK k;
   static_cast<UpSrc&>(k) = up_src(a);
@@ -172,6 +172,9 @@ extern "C" int addk_calib_upsample(const addk_calib_upsample_args* a, void* stre
   k.counter = (unsigned*)a->ws; k.part = (float*)((char*)a->ws + 16);
   k.rep = (unsigned long long*)(k.part + (long)CAL_T * scu_blocks(a->N, a->OH, a->OW));      // 8-byte aligned: 16 + 32 x nblk
   hipStream_t st = (hipStream_t)stream;
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), calib_up_kernel<19, true>, calib_up_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), calib_up_kernel<CC, true>, calib_up_kernel<CC, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  });
   return addk_check_launch("calib_upsample");
 }

@@ -1,19 +1,20 @@
 // The soft-Dice region term of the training head (addk_dice_stats): the per-class sums over the whole full-resolution batch that the term
 // and its gradient need, straight from the decoder's low-resolution logits, and the coefficient table ce_up_kernel<..., DICE> (loss_up.hip)
 // reads.  Semantics: include/addk.h.
-//   dice_clear_kernel    zeroes the 19-bin count table: the launch sequence clears what it accumulates into.
+//   dice_clear_kernel    zeroes the count table (32 words: one bin per class, CC <= 32): the launch sequence clears what it accumulates into.
 //   dice_stats_kernel    the walk of scu_walk (the tile, grid and interpolation of ohem_loss_kernel): one softmax per valid pixel, I_c and
-//                        P_c in registers (38 values), reduced over the workgroup (lanes by shuffle, the four waves in order) to one row
-//                        of [blk][38] fp32 partials; Y_c through an LDS histogram (run_count / run_flush) and 32-bit integer atomics.
+//                        P_c in registers (2*CC values), reduced over the workgroup (lanes by shuffle, the four waves in order) to one row
+//                        of [blk][2*CC] fp32 partials; Y_c through an LDS histogram (run_count / run_flush) and 32-bit integer atomics.
 //   dice_finish_kernel   ONE workgroup: thread t adds the partial rows t, t + 256, ... in fp64, then lanes, then the four waves in order
 //                        (the order of up_finish); then D_c, A_c, B_c, m and the term in fp64, rounded once.
-// Workspace (32-bit words): [0..18] Y_c, [32..50] I_c, [64..82] P_c (left for inspection), from word 96 the partial rows.
+// Workspace (32-bit words): [0..CC-1] Y_c, [32..] I_c, [64..] P_c (left for inspection), from word 96 the partial rows, 2*CC words each.
+// CC is the launch's class count (up.h: head_classes); the three tables hold up to 32 classes (static_assert below).
 #include "up.h"
 
 namespace {
 
-constexpr int DICE_C = 19;
 constexpr int DICE_I = 32, DICE_P = 64, DICE_PART = 96;            // word offsets into the workspace
+static_assert(HEAD_CMAX <= DICE_I && DICE_I + HEAD_CMAX <= DICE_P && DICE_P + HEAD_CMAX <= DICE_PART, "a class table of the dice workspace holds 32 classes");
 
 __global__ void __launch_bounds__(64) dice_clear_kernel(unsigned* ws) {
   if (threadIdx.x < DICE_I) ((gu32*)ws)[threadIdx.x] = 0u;
@@ -69,9 +70,9 @@ __global__ void __launch_bounds__(256) dice_stats_kernel(const DiceStatsK p) {
   }
 }
 
+template <int CC>
 __global__ void __launch_bounds__(256) dice_finish_kernel(unsigned* ws, long nblk, float weight, float smooth, float scale,
                                                            float* coef, float* dice_out, float* loss_out) {
-  constexpr int CC = DICE_C;
   __shared__ double shd[4][2 * CC];
   __shared__ double sD[CC];
   __shared__ int spres[CC];
@@ -128,7 +129,7 @@ __global__ void __launch_bounds__(256) dice_finish_kernel(unsigned* ws, long nbl
 }
 
 bool dice_ok(int N, int H, int W, int OH, int OW, int C) {
-  return C == DICE_C && scu_ok(N, H, W, OH, OW, C) && (long)N * OH * OW < (1L << 31);
+  return scu_head_ok(N, H, W, OH, OW, C) && (long)N * OH * OW < (1L << 31);
 }
 
 }  // namespace
@@ -136,24 +137,33 @@ bool dice_ok(int N, int H, int W, int OH, int OW, int C) {
 extern "C" int addk_dice_stats_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
   return dice_ok(N, H, W, OH, OW, C) ? 1 : 0;
 }
+extern "C" int64_t addk_dice_stats_ws_bytes_classes(int32_t N, int32_t OH, int32_t OW, int32_t C) {
+  if (N <= 0 || OH <= 0 || OW <= 0 || !head_class_ok(C)) return 0;
+  return 4 * ((int64_t)DICE_PART + 2 * C * (int64_t)scu_blocks(N, OH, OW));
+}
+// The query from before the class-count list: the FIRST count's size (19 classes) and no other.  A launch with more classes needs
+// addk_dice_stats_ws_bytes_classes: its partial rows are 2 x C floats per workgroup, and addk_dice_stats cannot see how large ws is.
 extern "C" int64_t addk_dice_stats_ws_bytes(int32_t N, int32_t OH, int32_t OW) {
-  if (N <= 0 || OH <= 0 || OW <= 0) return 0;
-  return 4 * ((int64_t)DICE_PART + 2 * DICE_C * (int64_t)scu_blocks(N, OH, OW));
+  return addk_dice_stats_ws_bytes_classes(N, OH, OW, HeadClasses::v[0]);
 }
 extern "C" int addk_dice_stats(const addk_dice_stats_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->target && a->coef && a->dice_out && a->loss_out && a->ws, "dice_stats: null pointer");
   ADDK_REQUIRE(isfinite(a->weight) && a->weight > 0.f && isfinite(a->smooth) && a->smooth >= 0.f,
                "dice_stats: weight must be positive, smooth non-negative, both finite");
   ADDK_REQUIRE(a->ld >= a->C, "dice_stats: short stride");
-  ADDK_REQUIRE(dice_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "dice_stats: unsupported shape (19 classes, fewer than 2^31 pixels)");
+  ADDK_REQUIRE(dice_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "dice_stats: unsupported shape (%s, fewer than 2^31 pixels)",
+               head_classes_text().c_str());
   unsigned* w = (unsigned*)a->ws;
   DiceStatsK k;
   static_cast<UpSrc&>(k) = up_src(a);
   k.target = a->target; k.ignore = a->ignore_index; k.hist = w; k.part = (float*)(w + DICE_PART);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(dice_clear_kernel, dim3(1), dim3(64), 0, st, w);
-  launch_vec(px_vec_ok<DICE_C>(a->logits, a->ld), dice_stats_kernel<DICE_C, true>, dice_stats_kernel<DICE_C, false>, scu_grid(a->N, a->OH, a->OW), st, k);
-  hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(256), 0, st, w, scu_blocks(a->N, a->OH, a->OW), a->weight, a->smooth, a->scale,
-                     a->coef, a->dice_out, a->loss_out);
+  head_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), dice_stats_kernel<CC, true>, dice_stats_kernel<CC, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+    hipLaunchKernelGGL(dice_finish_kernel<CC>, dim3(1), dim3(256), 0, st, w, scu_blocks(a->N, a->OH, a->OW), a->weight, a->smooth, a->scale,
+                       a->coef, a->dice_out, a->loss_out);
+  });
   return addk_check_launch("dice_stats");
 }

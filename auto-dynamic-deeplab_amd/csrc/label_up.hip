@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256) label_views_kernel(const addk_label_views
 
 dim3 lvu_grid(int N, int OH, int OW) { return dim3(cdiv(OW, LVU_W), cdiv(OH, LVU_WAVES * LVU_R), N); }
 bool lvu_ok(int nview, int N, int OH, int OW, int C) {
-  if (nview < 1 || nview > ADDK_MAX_VIEWS || C != 19 || N <= 0 || OH <= 0 || OW <= 0) return false;
+  if (nview < 1 || nview > ADDK_MAX_VIEWS || !gate_class_ok(C) || N <= 0 || OH <= 0 || OW <= 0) return false;
   const dim3 g = lvu_grid(N, OH, OW);
   return N <= 65535 && g.y <= 65535 && (long)(int)g.z * (int)g.y * (int)g.x < (1L << 30);
 }
@@ -118,7 +118,7 @@ struct GateUpK : UpSrc {
   float* out; float* out_host;
   unsigned* counter; float* part; unsigned* cnt;          // ws: [ticket, 16 bytes][nblk floats][nblk counts], image-major
   int nblk_img;
-  double npix, ent_div;                                    // OH*OW and log(C) * OH*OW
+  double npix, ent_div;                                    // OH*OW and log(19) * OH*OW (up.h, up_tail_fill)
 };
 
 // LABELS: the launch also leaves the label map of label_up_kernel, speculatively, for every image (one byte per pixel): the max sweep
@@ -181,25 +181,31 @@ extern "C" int64_t addk_gate_upsample_ws_bytes(int32_t N, int32_t OH, int32_t OW
 }
 extern "C" int addk_gate_upsample(const addk_gate_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->max_thr && a->out && a->ws, "gate_upsample: null pointer");
-  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample: unsupported shape (%s)", gate_classes_text().c_str());
   ADDK_REQUIRE(a->ld >= a->C, "gate_upsample: short stride");
   GateUpK k;
   gate_up_fill(k, a);
   hipStream_t st = (hipStream_t)stream;
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), gate_up_kernel<19, true>, gate_up_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), gate_up_kernel<CC, true>, gate_up_kernel<CC, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  });
   return addk_check_launch("gate_upsample");
 }
 extern "C" int addk_gate_label_upsample(const addk_gate_label_upsample_args* b, void* stream) {
   ADDK_REQUIRE(b, "gate_label_upsample: null pointer");
   const addk_gate_upsample_args* a = &b->gate;
   ADDK_REQUIRE(a->logits && a->max_thr && a->out && a->ws && b->labels, "gate_label_upsample: null pointer");
-  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_label_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_label_upsample: unsupported shape (%s)", gate_classes_text().c_str());
   ADDK_REQUIRE(a->ld >= a->C, "gate_label_upsample: short stride");
   GateLabelUpK k;
   gate_up_fill(k, a);
   k.lut = b->lut256; k.labels = b->labels;
   hipStream_t st = (hipStream_t)stream;
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), gate_up_kernel<19, true, true>, gate_up_kernel<19, false, true>, scu_grid(a->N, a->OH, a->OW), st, k);
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), gate_up_kernel<CC, true, true>, gate_up_kernel<CC, false, true>, scu_grid(a->N, a->OH, a->OW), st, k);
+  });
   return addk_check_launch("gate_label_upsample");
 }
 
@@ -207,37 +213,43 @@ extern "C" int addk_gate_upsample_t(const addk_gate_upsample_t_args* b, void* st
   ADDK_REQUIRE(b, "gate_upsample_t: null pointer");
   const addk_gate_upsample_args* a = &b->gate;
   ADDK_REQUIRE(a->logits && a->max_thr && a->out && a->ws && b->inv_temp, "gate_upsample_t: null pointer");
-  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample_t: unsupported shape (19 classes)");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "gate_upsample_t: unsupported shape (%s)", gate_classes_text().c_str());
   ADDK_REQUIRE(a->ld >= a->C, "gate_upsample_t: short stride");
-  const bool vec = px_vec_ok<19>(a->logits, a->ld);
   const dim3 grid = scu_grid(a->N, a->OH, a->OW);
   hipStream_t st = (hipStream_t)stream;
-  if (b->labels) {
-    Tempered<GateLabelUpK> k;
-    gate_up_fill(k, a);
-    k.lut = b->lut256; k.labels = b->labels; k.inv_temp = b->inv_temp;
-    launch_vec(vec, gate_up_kernel<19, true, true, true>, gate_up_kernel<19, false, true, true>, grid, st, k);
-  } else {
-    Tempered<GateUpK> k;
-    gate_up_fill(k, a);
-    k.inv_temp = b->inv_temp;
-    launch_vec(vec, gate_up_kernel<19, true, false, true>, gate_up_kernel<19, false, false, true>, grid, st, k);
-  }
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    const bool vec = px_vec_ok<CC>(a->logits, a->ld);
+    if (b->labels) {
+      Tempered<GateLabelUpK> k;
+      gate_up_fill(k, a);
+      k.lut = b->lut256; k.labels = b->labels; k.inv_temp = b->inv_temp;
+      launch_vec(vec, gate_up_kernel<CC, true, true, true>, gate_up_kernel<CC, false, true, true>, grid, st, k);
+    } else {
+      Tempered<GateUpK> k;
+      gate_up_fill(k, a);
+      k.inv_temp = b->inv_temp;
+      launch_vec(vec, gate_up_kernel<CC, true, false, true>, gate_up_kernel<CC, false, false, true>, grid, st, k);
+    }
+  });
   return addk_check_launch("gate_upsample_t");
 }
 
 extern "C" int addk_label_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
-  return scu_ok(N, H, W, OH, OW, C) ? 1 : 0;
+  return scu_head_ok(N, H, W, OH, OW, C) ? 1 : 0;
 }
 extern "C" int addk_label_upsample(const addk_label_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->labels, "label_upsample: null pointer");
-  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "label_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(scu_head_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "label_upsample: unsupported shape (%s)", head_classes_text().c_str());
   ADDK_REQUIRE(a->ld >= a->C, "label_upsample: short stride");
   LabelUpK k;
   static_cast<UpSrc&>(k) = up_src(a);
   k.lut = a->lut256; k.labels = a->labels;
   hipStream_t st = (hipStream_t)stream;
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), label_up_kernel<19, true>, label_up_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  head_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), label_up_kernel<CC, true>, label_up_kernel<CC, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  });
   return addk_check_launch("label_upsample");
 }
 
@@ -246,17 +258,20 @@ extern "C" int addk_label_views_upsample_supported(int32_t nview, int32_t N, int
 }
 extern "C" int addk_label_views_upsample(const addk_label_views_args* a, void* stream) {
   ADDK_REQUIRE(a && a->labels, "label_views_upsample: null pointer");
-  ADDK_REQUIRE(lvu_ok(a->nview, a->N, a->OH, a->OW, a->C), "label_views_upsample: unsupported shape (1..%d views, 19 classes)", ADDK_MAX_VIEWS);
-  bool vec = true;
+  ADDK_REQUIRE(lvu_ok(a->nview, a->N, a->OH, a->OW, a->C), "label_views_upsample: unsupported shape (1..%d views, %s)", ADDK_MAX_VIEWS,
+               gate_classes_text().c_str());
   for (int v = 0; v < a->nview; ++v) {
     const addk_view& w = a->view[v];
     ADDK_REQUIRE(w.logits, "label_views_upsample: null pointer (view %d)", v);
     ADDK_REQUIRE(w.H > 0 && w.W > 0 && w.n0 >= 0 && w.ld >= a->C, "label_views_upsample: bad size, image offset or stride (view %d)", v);
     ADDK_REQUIRE(w.weight > 0.f && isfinite(w.weight), "label_views_upsample: a weight must be positive and finite (view %d)", v);
-    vec = vec && px_vec_ok<19>(w.logits, w.ld);
   }
   hipStream_t st = (hipStream_t)stream;
-  // 16-byte pixel loads only where every view allows them
-  launch_vec(vec, label_views_kernel<19, true>, label_views_kernel<19, false>, lvu_grid(a->N, a->OH, a->OW), st, *a);
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    bool vec = true;                                             // 16-byte pixel loads only where every view allows them
+    for (int v = 0; v < a->nview; ++v) vec = vec && px_vec_ok<CC>(a->view[v].logits, a->view[v].ld);
+    launch_vec(vec, label_views_kernel<CC, true>, label_views_kernel<CC, false>, lvu_grid(a->N, a->OH, a->OW), st, *a);
+  });
   return addk_check_launch("label_views_upsample");
 }

@@ -18,7 +18,7 @@ __global__ void __launch_bounds__(256) ce_count_kernel(const int64_t* target, lo
   if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 
-// CC > 0: class count known at compile time, logits of a pixel live in registers (19 = Cityscapes);
+// CC > 0: class count known at compile time, logits of a pixel live in registers (the counts of up.h's HeadClasses);
 // CC == 0: generic fallback that re-reads the (cache-resident) logits instead of indexing a register array.
 template <int CC>
 __global__ void __launch_bounds__(256) ce_kernel(const float* logits, const int64_t* target, int N, int C, long HW, const float* cw,
@@ -124,9 +124,10 @@ extern "C" int addk_ce_fwd_bwd(const float* logits, const int64_t* target, int32
   ADDK_REQUIRE(logits && target && wsum && loss_out && ws && N > 0 && C > 0 && HW > 0, "ce_fwd_bwd: bad args");
   hipStream_t st = (hipStream_t)stream;
   int b = ce_blocks((long)N * HW);
-  if (C == 19)
-    hipLaunchKernelGGL(ce_kernel<19>, dim3(b), dim3(256), 0, st, logits, target, N, C, (long)HW, class_w, ignore_index, wsum, scale, dlogits, ws);
-  else
+  const bool fast = head_classes(C, [&](auto cc) {                // the class count at compile time, where the heads have it
+    hipLaunchKernelGGL(ce_kernel<decltype(cc)::value>, dim3(b), dim3(256), 0, st, logits, target, N, C, (long)HW, class_w, ignore_index, wsum, scale, dlogits, ws);
+  });
+  if (!fast)
     hipLaunchKernelGGL(ce_kernel<0>, dim3(b), dim3(256), 0, st, logits, target, N, C, (long)HW, class_w, ignore_index, wsum, scale, dlogits, ws);
   int rc = addk_check_launch("ce");
   if (rc) return rc;

@@ -69,9 +69,9 @@ template <bool OHEM> struct CeUpArg<OHEM, true, false> { typedef CeUpKdK type; }
 template <bool OHEM, bool KD> struct CeUpArg<OHEM, KD, true> { typedef CeUpDiceK type; };
 template <int CC> __device__ __forceinline__ float* dice_coef_lds() { __shared__ float s[2 * CC]; return s; }
 // An index offset of 0 the compiler cannot see through: a sweep that adds it to its table index READS the table where it uses it.  Plain
-// reads are loop-invariant and the compiler keeps all 19 B_c in registers across the pixel loop (the G[] array in another place): the plain
+// reads are loop-invariant and the compiler keeps all CC B_c in registers across the pixel loop (the G[] array in another place): the plain
 // form then needs 257 registers and drops to one wave per SIMD.  (No `valid ? f(B_c) : 0` per class either: the compiler turns a select
-// whose operand hangs on a load into a branch around that load, 19 branches and 19 exposed LDS latencies per pixel.)
+// whose operand hangs on a load into a branch around that load, CC branches and CC exposed LDS latencies per pixel.)
 __device__ __forceinline__ int opaque_zero() { int o = 0; asm volatile("" : "+v"(o)); return o; }
 
 template <int CC, bool OHEM = false, bool KD = false, bool TVEC = false, bool DICE = false>
@@ -272,7 +272,7 @@ __global__ void __launch_bounds__(256) kd_sum_kernel(const float* ws, int n, flo
 
 int ceu_hb(int H) { return H >= 64 ? 4 : (H >= 16 ? 2 : 1); }
 bool ceu_ok(int N, int H, int W, int OH, int OW, int C) {
-  if (C != 19 || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return false;
+  if (!head_class_ok(C) || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return false;
   const float sh = (float)H / (float)OH;
   for (int h = 0; h < H; ++h) {
     const int lo = ce_first_out(h, sh, H, OH), hi = h + 1 < H ? ce_first_out(h + 1, sh, H, OH) : OH;
@@ -448,7 +448,7 @@ __global__ void __launch_bounds__(256) ohem_keep_sum_kernel(const float* wpart, 
 }
 
 bool ohem_ok(int N, int H, int W, int OH, int OW, int C) {
-  return scu_ok(N, H, W, OH, OW, C) && (long)N * OH * OW < (1L << 31);
+  return scu_head_ok(N, H, W, OH, OW, C) && (long)N * OH * OW < (1L << 31);
 }
 int ohem_stream_blocks(long n) { long b = cdiv(n, 256 * 16); if (b < 1) b = 1; if (b > OHEM_KEEP_BLOCKS) b = OHEM_KEEP_BLOCKS; return (int)b; }
 
@@ -459,7 +459,8 @@ int ohem_stream_blocks(long n) { long b = cdiv(n, 256 * 16); if (b < 1) b = 1; i
 int ceu_launch(const char* name, const addk_ce_upsample_args* a, const float* lmap, const float* tau, const addk_ce_upsample_kd_args* kd,
                hipStream_t st, const float* coef = nullptr) {
   ADDK_REQUIRE(a->ld >= a->C && a->ldg >= a->C && (!kd || kd->ld_teacher >= a->C), "%s: short stride", name);
-  ADDK_REQUIRE(ceu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "%s: unsupported shape (19 classes, at most %d output rows per input row)", name, CEU_MAXBAND);
+  ADDK_REQUIRE(ceu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "%s: unsupported shape (%s, at most %d output rows per input row)", name,
+               head_classes_text().c_str(), CEU_MAXBAND);
   CeUpKdK k{};
   static_cast<UpSrc&>(k) = up_src(a);
   k.target = a->target; k.cw = a->class_w; k.ignore = a->ignore_index; k.wsum = a->wsum; k.scale = a->scale;
@@ -472,23 +473,26 @@ int ceu_launch(const char* name, const addk_ce_upsample_args* a, const float* lm
     k.rT = 1.f / kd->temperature;
     k.kscale = a->scale * kd->alpha * kd->temperature;           // the gradient's factor before 1/n; the loss takes one more T
   }
-  const bool tvec = kd && px_vec_ok<19>(kd->teacher, kd->ld_teacher);
-  if (coef) {
-    CeUpDiceK d{};
-    static_cast<CeUpKdK&>(d) = k;
-    d.coef = coef;
-    if (kd && lmap) launch_vec(tvec, ce_up_kernel<19, true, true, true, true>, ce_up_kernel<19, true, true, false, true>, grid, st, d);
-    else if (kd) launch_vec(tvec, ce_up_kernel<19, false, true, true, true>, ce_up_kernel<19, false, true, false, true>, grid, st, d);
-    else if (lmap) hipLaunchKernelGGL((ce_up_kernel<19, true, false, false, true>), grid, dim3(256), 0, st, d);
-    else hipLaunchKernelGGL((ce_up_kernel<19, false, false, false, true>), grid, dim3(256), 0, st, d);
-  } else if (kd) {
-    if (lmap) launch_vec(tvec, ce_up_kernel<19, true, true, true>, ce_up_kernel<19, true, true, false>, grid, st, k);
-    else launch_vec(tvec, ce_up_kernel<19, false, true, true>, ce_up_kernel<19, false, true, false>, grid, st, k);
-  } else if (lmap) {
-    hipLaunchKernelGGL((ce_up_kernel<19, true>), grid, dim3(256), 0, st, static_cast<const CeUpOhemK&>(k));
-  } else {
-    hipLaunchKernelGGL(ce_up_kernel<19>, grid, dim3(256), 0, st, static_cast<const CeUpK&>(k));
-  }
+  head_classes(a->C, [&](auto cc) {                               // ceu_ok: a->C is of the list
+    constexpr int CC = decltype(cc)::value;
+    const bool tvec = kd && px_vec_ok<CC>(kd->teacher, kd->ld_teacher);
+    if (coef) {
+      CeUpDiceK d{};
+      static_cast<CeUpKdK&>(d) = k;
+      d.coef = coef;
+      if (kd && lmap) launch_vec(tvec, ce_up_kernel<CC, true, true, true, true>, ce_up_kernel<CC, true, true, false, true>, grid, st, d);
+      else if (kd) launch_vec(tvec, ce_up_kernel<CC, false, true, true, true>, ce_up_kernel<CC, false, true, false, true>, grid, st, d);
+      else if (lmap) hipLaunchKernelGGL((ce_up_kernel<CC, true, false, false, true>), grid, dim3(256), 0, st, d);
+      else hipLaunchKernelGGL((ce_up_kernel<CC, false, false, false, true>), grid, dim3(256), 0, st, d);
+    } else if (kd) {
+      if (lmap) launch_vec(tvec, ce_up_kernel<CC, true, true, true>, ce_up_kernel<CC, true, true, false>, grid, st, k);
+      else launch_vec(tvec, ce_up_kernel<CC, false, true, true>, ce_up_kernel<CC, false, true, false>, grid, st, k);
+    } else if (lmap) {
+      hipLaunchKernelGGL((ce_up_kernel<CC, true>), grid, dim3(256), 0, st, static_cast<const CeUpOhemK&>(k));
+    } else {
+      hipLaunchKernelGGL(ce_up_kernel<CC>, grid, dim3(256), 0, st, static_cast<const CeUpK&>(k));
+    }
+  });
   const std::string n(name);
   int rc = addk_check_launch(name);
   if (rc) return rc;
@@ -500,6 +504,9 @@ int ceu_launch(const char* name, const addk_ce_upsample_args* a, const float* lm
 }
 
 }  // namespace
+
+extern "C" int addk_head_classes(int32_t* out, int32_t cap) { return classes_out<HeadClasses>(out, cap); }
+extern "C" int addk_gate_head_classes(int32_t* out, int32_t cap) { return classes_out<GateClasses>(out, cap); }
 
 extern "C" int addk_ce_upsample_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C) {
   return ceu_ok(N, H, W, OH, OW, C) ? 1 : 0;
@@ -563,7 +570,8 @@ extern "C" int addk_ohem_select(const addk_ohem_select_args* a, void* stream) {
   ADDK_REQUIRE(a->thresh > 0.f && a->thresh <= 1.f, "ohem_select: thresh must lie in (0, 1]");
   ADDK_REQUIRE(a->min_kept_total >= 1, "ohem_select: min_kept_total must be at least 1");
   ADDK_REQUIRE(a->ld >= a->C, "ohem_select: short stride");
-  ADDK_REQUIRE(ohem_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "ohem_select: unsupported shape (19 classes, fewer than 2^31 pixels)");
+  ADDK_REQUIRE(ohem_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "ohem_select: unsupported shape (%s, fewer than 2^31 pixels)",
+               head_classes_text().c_str());
   unsigned* w = (unsigned*)a->ws;
   unsigned* sel = w + OHEM_SEL;
   float* wpart = (float*)(w + OHEM_PART);
@@ -578,7 +586,10 @@ extern "C" int addk_ohem_select(const addk_ohem_select_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const dim3 one(1), blk(256);
   hipLaunchKernelGGL(ohem_clear_kernel, one, blk, 0, st, w);
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), ohem_loss_kernel<19, true>, ohem_loss_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  head_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), ohem_loss_kernel<CC, true>, ohem_loss_kernel<CC, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  });
   hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w, OHEM_B0 / 256, 11, 0, sel, (unsigned long long)a->min_kept_total, tau_theta, (float*)nullptr, counts);
   hipLaunchKernelGGL((ohem_refine_kernel<21, 10, OHEM_B0>), dim3(nb), blk, 0, st, a->pix_loss, npix, sel, w + OHEM_B0);
   hipLaunchKernelGGL(ohem_scan_kernel, one, blk, 0, st, w + OHEM_B0, OHEM_B0 / 256, 11, 1, sel, 0ull, tau_theta, (float*)nullptr, counts);

@@ -8,10 +8,10 @@ namespace {
 // Confusion matrix, loss and entropy of one exit from the low-resolution NHWC logits, as a GATHER: a wave owns 64 consecutive
 // columns X of the high-resolution grid and walks SCU_R rows; a thread keeps the two W-interpolated rows t0 = lw0*v(h0,w0) +
 // lw1*v(h0,w1), t1 = (same on h1) of its column in registers and reloads them only when the (wave-uniform) pair (h0, h1)
-// changes, so at the x8 of config 2 the four neighbours are read once per 8 pixels and a pixel costs 19 x 3 flops of
+// changes, so at the x8 of config 2 the four neighbours are read once per 8 pixels and a pixel costs CC x 3 flops of
 // interpolation — z = lh0*t0 + lh1*t1 is the expression of resize_fwd_nchw_kernel / ce_up_kernel, operation for operation.
 // One max/arg-max sweep, one exp sweep (Σe, Σe·d) serves loss and entropy.  HBM traffic: the target (coalesced 512 B per wave
-// row) and the optional uint8 map; the logits (5 MB at config 2) stay in L2.  Counts go to a 361-entry LDS histogram (a thread
+// row) and the optional uint8 map; the logits (5 MB at config 2) stay in L2.  Counts go to a CC x CC LDS histogram (361 entries at 19 classes, 441 at 21) (a thread
 // merges the run of equal (gt, pred) keys of its column first), flushed once per workgroup with 64-bit integer atomics:
 // order-independent, exact.  Loss and entropy leave the workgroup as two partials reduced in a fixed order.
 struct ScoreUpK : UpSrc {
@@ -152,7 +152,7 @@ extern "C" int64_t addk_score_upsample_ws_floats(int32_t N, int32_t OH, int32_t 
 extern "C" int addk_score_upsample(const addk_score_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->target && a->wsum && a->loss_out && a->ent_out && a->cm && a->ws, "score_upsample: null pointer");
   ADDK_REQUIRE(a->ld >= a->C, "score_upsample: short stride");
-  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "score_upsample: unsupported shape (19 classes)");
+  ADDK_REQUIRE(scu_ok(a->N, a->H, a->W, a->OH, a->OW, a->C), "score_upsample: unsupported shape (%s)", gate_classes_text().c_str());
   const dim3 grid = scu_grid(a->N, a->OH, a->OW);
   ScoreUpK k;
   static_cast<UpSrc&>(k) = up_src(a);
@@ -160,7 +160,10 @@ extern "C" int addk_score_upsample(const addk_score_upsample_args* a, void* stre
   k.cm = reinterpret_cast<unsigned long long*>(a->cm); k.pred = a->pred_out;
   k.ws = a->ws; k.nblk = (int)scu_blocks(a->N, a->OH, a->OW);
   hipStream_t st = (hipStream_t)stream;
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), score_up_kernel<19, true>, score_up_kernel<19, false>, grid, st, k);
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), score_up_kernel<CC, true>, score_up_kernel<CC, false>, grid, st, k);
+  });
   int rc = addk_check_launch("score_upsample");
   if (rc) return rc;
   hipLaunchKernelGGL(score_sum_kernel, dim3(2), dim3(256), 0, st, a->ws, k.nblk, a->scale, a->wsum, a->loss_out, a->ent_out);
@@ -184,13 +187,16 @@ static void profile_up_fill(ProfileUpK& k, const addk_profile_upsample_args* a) 
 extern "C" int addk_profile_upsample(const addk_profile_upsample_args* a, void* stream) {
   ADDK_REQUIRE(a && a->logits && a->target && a->ent_out && a->cm && a->ws, "profile_upsample: null pointer");
   ADDK_REQUIRE(addk_profile_upsample_supported(a->N, a->H, a->W, a->OH, a->OW, a->C, a->nthr) == 1,
-               "profile_upsample: unsupported shape (19 classes, at most %d thresholds)", PRU_NT);
+               "profile_upsample: unsupported shape (%s, at most %d thresholds)", gate_classes_text().c_str(), PRU_NT);
   ADDK_REQUIRE(a->nthr == 0 || (a->thr && a->share_out), "profile_upsample: null pointer");
   ADDK_REQUIRE(a->ld >= a->C, "profile_upsample: short stride");
   ProfileUpK k;
   profile_up_fill(k, a);
   hipStream_t st = (hipStream_t)stream;
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), profile_up_kernel<19, true>, profile_up_kernel<19, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), profile_up_kernel<CC, true>, profile_up_kernel<CC, false>, scu_grid(a->N, a->OH, a->OW), st, k);
+  });
   return addk_check_launch("profile_upsample");
 }
 extern "C" int addk_profile_upsample_t(const addk_profile_upsample_t_args* b, void* stream) {
@@ -198,13 +204,16 @@ extern "C" int addk_profile_upsample_t(const addk_profile_upsample_t_args* b, vo
   const addk_profile_upsample_args* a = &b->profile;
   ADDK_REQUIRE(a->logits && a->target && a->ent_out && a->cm && a->ws && b->inv_temp, "profile_upsample_t: null pointer");
   ADDK_REQUIRE(addk_profile_upsample_supported(a->N, a->H, a->W, a->OH, a->OW, a->C, a->nthr) == 1,
-               "profile_upsample_t: unsupported shape (19 classes, at most %d thresholds)", PRU_NT);
+               "profile_upsample_t: unsupported shape (%s, at most %d thresholds)", gate_classes_text().c_str(), PRU_NT);
   ADDK_REQUIRE(a->nthr == 0 || (a->thr && a->share_out), "profile_upsample_t: null pointer");
   ADDK_REQUIRE(a->ld >= a->C, "profile_upsample_t: short stride");
   ProfileUpTK k;
   profile_up_fill(k, a);
   k.inv_temp = b->inv_temp;
   hipStream_t st = (hipStream_t)stream;
-  launch_vec(px_vec_ok<19>(a->logits, a->ld), profile_up_kernel<19, true, true>, profile_up_kernel<19, false, true>, scu_grid(a->N, a->OH, a->OW), st, k);
+  gate_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), profile_up_kernel<CC, true, true>, profile_up_kernel<CC, false, true>, scu_grid(a->N, a->OH, a->OW), st, k);
+  });
   return addk_check_launch("profile_upsample_t");
 }

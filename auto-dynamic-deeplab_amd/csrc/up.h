@@ -5,10 +5,50 @@
 // the gate-style heads.  Everything sits in the unit's anonymous namespace.
 #pragma once
 #include <math.h>
+#include <string>
+#include <type_traits>
 #include "common.h"
 #include "bnfin.h"
 
 namespace {
+
+// The class counts the heads are compiled for, one list per group of heads.  Every head kernel is a template on the class count CC; the
+// dispatchers below turn a run-time C into it, and a further count is one more entry of a list.
+//   HeadClasses: the training heads (ce_up_kernel in all its forms, ohem_loss_kernel, the Dice reduction), the label head and the compile-time
+//                form of ce_kernel: Cityscapes (19) and Pascal VOC (21), the reference's two datasets.
+//   GateClasses: the scoring, profile, calibration, gate and multi-view heads: 19 (DESIGN section 27 says why not yet 21).
+struct HeadClasses { static constexpr int v[] = {19, 21}; };
+struct GateClasses { static constexpr int v[] = {19}; };
+template <class L> constexpr int nclasses() { return sizeof(L::v) / sizeof(L::v[0]); }
+template <class L> constexpr int cmax(int i = 0) { return i == nclasses<L>() ? 0 : (L::v[i] > cmax<L>(i + 1) ? L::v[i] : cmax<L>(i + 1)); }
+constexpr int HEAD_CMAX = cmax<HeadClasses>();                    // what a fixed-size class table has to hold (dice_up.hip asserts it)
+// f(cc) with decltype(cc)::value == C for a C of the list L (true), or nothing (false): the one place where a launcher gets its CC
+template <class L, int I = 0, class F>
+bool classes_of(int C, F&& f) {
+  if constexpr (I < nclasses<L>()) {
+    if (C == L::v[I]) { f(std::integral_constant<int, L::v[I]>{}); return true; }
+    return classes_of<L, I + 1>(C, f);
+  } else {
+    return false;
+  }
+}
+template <class F> bool head_classes(int C, F&& f) { return classes_of<HeadClasses>(C, f); }
+template <class F> bool gate_classes(int C, F&& f) { return classes_of<GateClasses>(C, f); }
+bool head_class_ok(int C) { return head_classes(C, [](auto) {}); }
+bool gate_class_ok(int C) { return gate_classes(C, [](auto) {}); }
+// "19 classes (or 21)": a list as the error texts name it, here and in Python (_lib.head_classes_text builds the same words from the
+// exported list: addk_head_classes, addk_gate_head_classes)
+template <class L> std::string classes_text() {
+  std::string s = std::to_string(L::v[0]) + " classes";
+  for (int i = 1; i < nclasses<L>(); ++i) s += (i == 1 ? " (or " : ", ") + std::to_string(L::v[i]);
+  return nclasses<L>() > 1 ? s + ")" : s;
+}
+template <class L> int classes_out(int32_t* out, int32_t cap) {
+  for (int i = 0; out && i < nclasses<L>() && i < cap; ++i) out[i] = L::v[i];
+  return nclasses<L>();
+}
+std::string head_classes_text() { return classes_text<HeadClasses>(); }
+std::string gate_classes_text() { return classes_text<GateClasses>(); }
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
@@ -125,10 +165,13 @@ __device__ __forceinline__ void exp_sweep_t(const float (&z)[CC], float mx, floa
 // the launch grid of the two gather heads (one workgroup per tile and image) and its workgroup count, which sizes their workspaces
 dim3 scu_grid(int N, int OH, int OW) { return dim3(cdiv(OW, SCU_W), cdiv(OH, SCU_WAVES * SCU_R), N); }
 long scu_blocks(int N, int OH, int OW) { const dim3 g = scu_grid(N, OH, OW); return (long)(int)g.z * (int)g.y * (int)g.x; }
-bool scu_ok(int N, int H, int W, int OH, int OW, int C) {
-  if (C != 19 || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return false;
+// the walk's limits alone, then with the class count of a head of either list
+bool scu_geom_ok(int N, int H, int W, int OH, int OW) {
+  if (N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return false;
   return N <= 65535 && scu_grid(N, OH, OW).y <= 65535 && scu_blocks(N, OH, OW) < (1L << 30);
 }
+bool scu_ok(int N, int H, int W, int OH, int OW, int C) { return gate_class_ok(C) && scu_geom_ok(N, H, W, OH, OW); }
+bool scu_head_ok(int N, int H, int W, int OH, int OW, int C) { return head_class_ok(C) && scu_geom_ok(N, H, W, OH, OW); }
 
 typedef __attribute__((address_space(1))) uint8_t gu8;
 __device__ __forceinline__ void label_px(const uint8_t* lut, uint8_t* labels, long pix, int am) {
@@ -136,7 +179,9 @@ __device__ __forceinline__ void label_px(const uint8_t* lut, uint8_t* labels, lo
 }
 
 // The workspace of a gate-style head with nk counts per workgroup, [ticket, 16 bytes][nblk floats][nblk x nk counts], image-major, and
-// what both heads' argument structs say about it and about the normalisation (log 19: the heads take 19 classes)
+// what both heads' argument structs say about it and about the normalisation.  The divisor is log 19 at EVERY class count, not log C:
+// the reference calls normalized_shannon_entropy without num_class (modeling/ADD.py:474), so its gate divides by log 19 whatever the
+// dataset, and so does the stand-alone path (heads._gate_alone)
 int64_t up_ws_bytes(int N, int OH, int OW, int nk) { return 16 + (4 + 4 * (int64_t)nk) * scu_blocks(N, OH, OW); }
 template <class K> void up_tail_fill(K& k, void* ws, int N, int OH, int OW) {
   const dim3 grid = scu_grid(N, OH, OW);

@@ -85,8 +85,8 @@ def _ce_head(g, src, OH, OW):
         if ohem:
             # mining: this exit's loss map, tau and kept weight sum; the head reads them, the kept weight sum is its normaliser
             if lib.addk_ohem_select_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
-                raise L.AddkError('hard example mining takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
-                                  % (src.C, src.N, src.H, src.W, OH, OW))
+                raise L.AddkError('hard example mining takes %s and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
+                                  % (L.head_classes_text(), src.C, src.N, src.H, src.W, OH, OW))
             lmap, tau, wkept = torch.zeros((src.N, OH, OW), **f32), torch.zeros(1, **f32), torch.zeros(1, **f32)
             counts = torch.zeros(2, dtype=torch.int64, device=g.device)
             sws = torch.zeros(int(lib.addk_ohem_select_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=g.device)
@@ -117,10 +117,10 @@ def _ce_head(g, src, OH, OW):
         if dice:
             # the region term: the batch's per-class sums first (they add the term to the loss), then the head with their table
             if lib.addk_dice_stats_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
-                raise L.AddkError('the soft-Dice term takes 19 classes and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
-                                  % (src.C, src.N, src.H, src.W, OH, OW))
+                raise L.AddkError('the soft-Dice term takes %s and fewer than 2^31 pixels (got %d classes, [%d,%d,%d] -> %dx%d)'
+                                  % (L.head_classes_text(), src.C, src.N, src.H, src.W, OH, OW))
             coef, dout = torch.zeros(2 * src.C, **f32), torch.zeros(1 + src.C, **f32)
-            dws = torch.zeros(int(lib.addk_dice_stats_ws_bytes(src.N, OH, OW)), dtype=torch.uint8, device=g.device)
+            dws = torch.zeros(int(lib.addk_dice_stats_ws_bytes_classes(src.N, OH, OW, src.C)), dtype=torch.uint8, device=g.device)
             d = _up_args(g, L.DiceStatsArgs, src, OH, OW)
             d.target, d.ignore_index, d.scale, d.loss_out = a.target, a.ignore_index, a.scale, a.loss_out
             d.weight, d.smooth = dice
@@ -142,7 +142,7 @@ def _score_head(g, src, OH, OW):
     logits, so no resize is emitted and no [N,C,OH,OW] buffer exists.  The OutRef carries `shape` and the `binding` the step
     sets (target, class weights, wsum and the per-exit loss / entropy / confusion / prediction tensors); finalize() then appends
     ONE `score_upsample` launch per exit to the forward list (`addk_score_upsample`).  Where the library does not take the shape
-    (`addk_score_upsample_supported` == 0, e.g. C != 19) the same quantities come from the stand-alone kernels inside this plan:
+    (`addk_score_upsample_supported` == 0, e.g. a class count outside `_lib.gate_head_classes()`) the same quantities come from the stand-alone kernels inside this plan:
     resize + ce_fwd_bwd without a gradient + argmax_nchw + confusion + entropy_sum.  A binding with `trimap` (_confusion_banded) adds
     ONE `confusion_banded` launch behind the exit's `score_upsample`; the stand-alone path refuses it (ValueError)."""
     lib = g.lib
@@ -197,8 +197,8 @@ def _profile_head(g, src, OH, OW):
     def emit_profile(pr):
         tgt, thr, nthr, ent, share, cm, pred = pr['target'], pr['thr'], pr['nthr'], pr['entropy'], pr['share'], pr['confusion'], pr.get('pred')
         if lib.addk_profile_upsample_supported(N, H, W, OH, OW, Cc, nthr) != 1:
-            raise L.AddkError('the exit profile takes 19 classes and at most 16 thresholds (got %d classes, %d thresholds, '
-                              '[%d,%d,%d] -> %dx%d)' % (Cc, nthr, N, H, W, OH, OW))
+            raise L.AddkError('the exit profile takes %s and at most 16 thresholds (got %d classes, %d thresholds, '
+                              '[%d,%d,%d] -> %dx%d)' % (L.gate_head_classes_text(), Cc, nthr, N, H, W, OH, OW))
         a = _up_args(g, L.ProfileUpsampleArgs, src, OH, OW)
         a.target, a.thr, a.nthr = tgt.data_ptr(), thr.data_ptr() if nthr else None, nthr
         a.ent_out, a.share_out, a.cm = ent.data_ptr(), share.data_ptr() if nthr else None, cm.data_ptr()
@@ -252,8 +252,8 @@ def _calib_head(g, src, OH, OW):
     def emit_calib(cb):
         tgt, it, nt, bins, nll = cb['target'], cb['inv_temp'], cb['nt'], cb['bins'], cb['nll']
         if lib.addk_calib_upsample_supported(N, H, W, OH, OW, Cc, nt) != 1:
-            raise L.AddkError('the calibration head takes 19 classes and 1..%d temperatures (got %d classes, %d temperatures, '
-                              '[%d,%d,%d] -> %dx%d)' % (L.CALIB_MAX_T, Cc, nt, N, H, W, OH, OW))
+            raise L.AddkError('the calibration head takes %s and 1..%d temperatures (got %d classes, %d temperatures, '
+                              '[%d,%d,%d] -> %dx%d)' % (L.gate_head_classes_text(), L.CALIB_MAX_T, Cc, nt, N, H, W, OH, OW))
         a = _up_args(g, L.CalibUpsampleArgs, src, OH, OW)
         a.target, a.inv_temp, a.nt, a.bins, a.nll = tgt.data_ptr(), it.data_ptr(), nt, bins.data_ptr(), nll.data_ptr()
         ws = torch.zeros(int(lib.addk_calib_upsample_ws_bytes(N, OH, OW)), dtype=torch.uint8, device=g.device)
@@ -277,7 +277,7 @@ def _label_head(g, src, OH, OW):
     keeps of an exit is the arg-max of its up-sampled logits (eval.py:218-221), so no resize is emitted and no [N,C,OH,OW] buffer exists.
     ONE `label_upsample` launch (`addk_label_upsample`) writes the OutRef's `y`, a plan-owned uint8 [N,OH,OW] map: the class index, or
     lut[class] with the table `g.lut`.  Where the library does not take the shape (`addk_label_upsample_supported` == 0, e.g.
-    C != 19) the same plan uses the stand-alone kernels: resize + argmax_nchw + a cast in torch ops (_labels_cold)."""
+    a class count outside `_lib.head_classes()`) the same plan uses the stand-alone kernels: resize + argmax_nchw + a cast in torch ops (_labels_cold)."""
     lib = g.lib
     lab, out = _label_map(g, src, OH, OW)
     lut = g.lut
@@ -312,9 +312,9 @@ def _views_head(g, src, OH, OW):
     sets — {'N': images per view, 'size': (OH, OW) of the map, 'views': [(n0, mirror, weight), ...]}, the views this output holds (n0:
     its first image in the batch).  The (OH, OW) passed here, the size the model would up-sample this output to, only goes into `shape`.
     finalize() then appends ONE `label_views_upsample` launch (`addk_label_views_upsample`) that reads every view's source and writes
-    `Graph.view_labels`, the plan-owned uint8 [N,OH,OW] map.  There is no stand-alone form: C != 19 or more than 8 views is an error."""
-    if src.C != 19:
-        raise L.AddkError('the multi-view label head takes 19 classes (got %d)' % src.C)
+    `Graph.view_labels`, the plan-owned uint8 [N,OH,OW] map.  There is no stand-alone form: a class count outside `_lib.gate_head_classes()` or more than 8 views is an error."""
+    if src.C not in L.gate_head_classes():
+        raise L.AddkError('the multi-view label head takes %s (got %d)' % (L.gate_head_classes_text(), src.C))
     out = OutRef(None)
     out.head, out.shape, out.src = 'views', (src.N, src.C, OH, OW), src
     views = next((em for em in g._fwd_late if isinstance(em, _Views)), None)
@@ -335,8 +335,8 @@ def _emit_views(g, outs, tag):
     assert all(o.binding['N'] == N and tuple(o.binding['size']) == (OH, OW) and o.shape[1] == Cc for o in outs)
     assert all(0 <= n0 and n0 + N <= o.shape[0] for o, (n0, _, _) in views)
     if len(views) > L.MAX_VIEWS or lib.addk_label_views_upsample_supported(len(views), N, OH, OW, Cc) != 1:
-        raise L.AddkError('the multi-view label head takes 1..%d views of 19 classes (got %d views, %d classes, %d x %dx%d)'
-                          % (L.MAX_VIEWS, len(views), Cc, N, OH, OW))
+        raise L.AddkError('the multi-view label head takes 1..%d views of %s (got %d views, %d classes, %d x %dx%d)'
+                          % (L.MAX_VIEWS, L.gate_head_classes_text(), len(views), Cc, N, OH, OW))
     lab = g.view_labels = torch.zeros((N, OH, OW), dtype=torch.uint8, device=g.device)
     g.nbytes += lab.numel()
     a, lut, rd = L.LabelViewsArgs(), g.lut, []
@@ -376,7 +376,7 @@ def gate_head(g, src, OH, OW, host_out, thr, kind='entropy', temp=None):
     (`addk_gate_upsample`) reads the low-resolution NHWC logits and writes (entropy, share) to the OutRef's `gate_out` [N,2] and to the
     pinned words `host_out`; the `resize_nchw` launch FOLLOWS it, so a plan cut at `gate_cut` replays the resize only for an image that
     leaves here.  `thr`: the device word the 'max' gate compares against.
-    Where the library does not take the shape (`addk_gate_upsample_supported` == 0, e.g. C != 19) or with ADDK_FUSE_GATE=0, the same
+    Where the library does not take the shape (`addk_gate_upsample_supported` == 0, e.g. a class count outside `_lib.gate_head_classes()`) or with ADDK_FUSE_GATE=0, the same
     plan uses the stand-alone kernels on the materialised logits (_gate_alone) — `resize_nchw` first, then `entropy_sum` ('entropy':
     gate_out[0, 0] holds the un-normalised sum, `gate_scale` the factor the host applies) or a count in torch ops ('max':
     gate_out[0, 1]); nothing is left behind the cut and the host copies `gate_out` itself (`gate_fused` False).
@@ -389,8 +389,8 @@ def gate_head(g, src, OH, OW, host_out, thr, kind='entropy', temp=None):
     N, H, W, Cc = src.N, src.H, src.W, src.C
     fused = _on('ADDK_FUSE_GATE') and g.lib.addk_gate_upsample_supported(N, H, W, OH, OW, Cc) == 1
     if temp is not None and not fused:
-        raise L.AddkError('a tempered gate needs the fused gate launch: 19 classes and ADDK_FUSE_GATE=1 (got %d classes, [%d,%d,%d] -> %dx%d)'
-                          % (Cc, N, H, W, OH, OW))
+        raise L.AddkError('a tempered gate needs the fused gate launch: %s and ADDK_FUSE_GATE=1 (got %d classes, [%d,%d,%d] -> %dx%d)'
+                          % (L.gate_head_classes_text(), Cc, N, H, W, OH, OW))
     labels = g.head == 'labels'
     # the [N,C,OH,OW] logits and their resize: not where the fused launch of a label plan leaves the map itself
     y, emit_resize = (None, None) if labels and fused else _logits_resize(g, src, OH, OW)
@@ -436,6 +436,8 @@ def _gate_alone(g, out, y, lab, emit_resize, thr, kind):
         g.keep.append(ws)
         g._add(g.fwd, 'entropy_sum', g.lib.addk_entropy_sum, y.data_ptr(), N, Cc, OH * OW, out.gate_out.data_ptr(), ws.data_ptr(),
                rd=[y], wr=[out.gate_out, ws])
+        # log 19 at every class count, as the fused launch (csrc/up.h, up_tail_fill): the reference's gate calls
+        # normalized_shannon_entropy without num_class (modeling/ADD.py:474), whatever the dataset
         out.gate_scale = 1.0 / (math.log(19.0) * OH * OW)
     else:
         g._add(g.fwd, 'gate_count_torch', _gate_count_torch, y, thr, out.gate_out, rd=[y, thr], wr=[out.gate_out], pin=True)

@@ -1,6 +1,6 @@
 """Static label-map inference (reference eval.py:218-221: `pred = argmax(output, 1)`): one exit of the path in inference form,
 ending in the label head — ONE `addk_label_upsample` launch writes the uint8 [N,H,W] arg-max map straight from the decoder's
-low-resolution logits (plan.Graph.head 'labels': heads._label_head), so the [N,19,H,W] logits are never written and no such buffer exists.  The plan holds
+low-resolution logits (plan.Graph.head 'labels': heads._label_head), so the [N,C,H,W] logits are never written and no such buffer exists.  The plan holds
 the trunk only up to the chosen exit's cell: an early exit costs its share of the network.  Emitted once over a resident input
 buffer and replayed as a single hipGraph launch.
 
@@ -12,7 +12,9 @@ Multi-scale + flip inference (what a DeepLab-family submission is scored on): th
 probabilities over several input scales and each scale's horizontal mirror.  ONE plan holds every view — the staged input, resized per
 scale (Graph.resize), runs through the model once per scale at batch 2N, the mirrored images riding along — and ends in ONE
 `addk_label_views_upsample` launch (plan.Graph.head 'views': heads._views_head) that reads every view's low-resolution logits and writes the map: each view
-is interpolated once, from the decoder's grid straight to (H, W), and no [N,19,·,·] tensor exists for any of them.
+is interpolated once, from the decoder's grid straight to (H, W), and no [N,C,·,·] tensor exists for any of them.
+The label head takes the class counts of `_lib.head_classes()` (19: Cityscapes, 21: Pascal VOC) and Segmenter uses the stand-alone kernels
+at any other; the multi-view head takes `_lib.gate_head_classes()` (19) and MultiViewSegmenter raises at any other.
 
     seg = MultiViewSegmenter(model, (N, 3, H, W), scales=(0.75, 1.0, 1.25), flip=True, label_lut=decode_segmap_lut())
     labels = seg.step(images)                # uint8 [N,H,W], plan-owned; no host synchronisation
@@ -105,7 +107,8 @@ class MultiViewSegmenter(InferenceStep):
         for i, (s, (hv, wv)) in enumerate(zip(self.scales, self.sizes)):
             av = a if (hv, wv) == (H, W) else g.resize(a, hv, wv)
             out = self.model._emit_exit(g, av, self.exit)
-            assert out.head == 'views' and tuple(out.shape) == (per * N, 19, hv, wv), 'the model did not end in Graph.resize_to_nchw'
+            assert out.head == 'views' and out.shape[1] in L.gate_head_classes() and (out.shape[0],) + tuple(out.shape[2:]) == (per * N, hv, wv), \
+                'the model did not end in Graph.resize_to_nchw'
             out.binding = {'N': N, 'size': (H, W),
                            'views': [(m * N, m, self.weights[i * per + m]) for m in range(per)]}
             self.outs.append(out)
@@ -127,6 +130,6 @@ class MultiViewSegmenter(InferenceStep):
         return self.g.view_labels
 
     def view_logits(self):
-        """Copies of every view's low-resolution NHWC logits [N,h_v,w_v,19], in the order of `views` (inspection and tests)."""
+        """Copies of every view's low-resolution NHWC logits [N,h_v,w_v,C], in the order of `views` (inspection and tests)."""
         N = self.image_shape[0]
         return [o.src.raw.view()[n0:n0 + N].clone() for o in self.outs for n0, _, _ in o.binding['views']]

@@ -130,14 +130,17 @@ class TrainStep:
         self.outs = outs
         nex = len(outs)
         if self.ohem is not None and any(o.head != 'ce' for o in outs):
-            raise ValueError('ohem: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
+            raise ValueError('ohem: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0: the head takes '
+                             '%s and at most 16 output rows per input row)' % L.head_classes_text())
         if self.dice is not None and any(o.head != 'ce' for o in outs):
-            raise ValueError('dice: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
+            raise ValueError('dice: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0: the head takes '
+                             '%s and at most 16 output rows per input row)' % L.head_classes_text())
         if self.distill is not None:
             if nex < 2:
                 raise ValueError('distill: this model has a single exit, nobody to teach')
             if any(o.head != 'ce' for o in outs):
-                raise ValueError('distill: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0)')
+                raise ValueError('distill: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0: the head takes '
+                                 '%s and at most 16 output rows per input row)' % L.head_classes_text())
             if len({(o.src.N, o.src.H, o.src.W, o.src.C) for o in outs}) != 1:
                 raise ValueError('distill: the exits\' low-resolution logits differ in shape: %r'
                                  % ([(o.src.N, o.src.H, o.src.W, o.src.C) for o in outs],))

@@ -498,11 +498,23 @@ int addk_ce_fwd_bwd(const float* logits, const int64_t* target, int32_t N, int32
                     float* loss_out, float* dlogits, float* ws, void* stream);
 int64_t addk_ce_ws_floats(int32_t N, int64_t HW);
 
+/* The class counts C the fused heads on the low-resolution logits are compiled for, two lists in csrc/up.h.
+ *   addk_head_classes       the training heads (addk_ce_upsample_fwd_bwd and its _ohem, _kd and _dice forms, addk_ohem_select,
+ *                           addk_dice_stats), the label head (addk_label_upsample) and the compile-time form of addk_ce_fwd_bwd:
+ *                           19 (Cityscapes) and 21 (Pascal VOC).
+ *   addk_gate_head_classes  the scoring, profile, calibration, gate and multi-view heads (addk_score_upsample, addk_profile_upsample[_t],
+ *                           addk_calib_upsample, addk_gate_upsample[_t], addk_gate_label_upsample, addk_label_views_upsample): 19.
+ * Each writes the first min(count, cap) counts to out (out may be NULL with cap <= 0) and returns the count.  A head's *_supported(..., C)
+ * is 0 for a C outside its list.  The normalised entropy of the gate and profile heads divides by log 19, as the reference's gate
+ * does whatever the dataset (modeling/ADD.py:474 calls normalized_shannon_entropy without num_class). */
+int addk_head_classes(int32_t* out, int32_t cap);
+int addk_gate_head_classes(int32_t* out, int32_t cap);
+
 /* Fused form for the training step: the bilinear up-sampling of the decoder's logits (decoder.py:28,
  * F.interpolate(mode='bilinear', align_corners=False)) and the cross-entropy on it (train.py:70,231) in one pass over the
  * LOW-resolution NHWC logits [N,H,W,C] — loss_out[0] += scale * CE(upsample(logits) -> [N,C,OH,OW], target), and
  * g (+)= d loss / d logits.  The [N,C,OH,OW] tensor and its gradient are never materialised.  Deterministic (gather, fixed
- * summation order).  addk_ce_upsample_supported() is 0 for shapes the kernel does not take (C != 19, more than 16 output
+ * summation order).  addk_ce_upsample_supported() is 0 for shapes the kernel does not take (C not in addk_head_classes(), more than 16 output
  * rows per input row): the caller then runs addk_resize_fwd + addk_ce_fwd_bwd + addk_resize_bwd. */
 typedef struct {
   const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
@@ -538,7 +550,7 @@ int addk_ce_upsample_fwd_bwd(const addk_ce_upsample_args* a, void* stream);
  *   tau[0], wsum_kept[0] = sum over kept pixels of class_w[target] (or 1), counts[0] = n, counts[1] = #kept
  * Selection is EXACT: tau carries the bits a full sort of pix_loss gives — a three-pass radix select on the bit pattern of l
  * (bits 31..21 binned while the map is written, then 20..10 and 9..0 over the stored map), integer histograms only.
- * wsum_kept is a fixed-order two-stage sum: bit-reproducible.  addk_ohem_select_supported() is 0 for C != 19, non-positive
+ * wsum_kept is a fixed-order two-stage sum: bit-reproducible.  addk_ohem_select_supported() is 0 for C not in addk_head_classes(), non-positive
  * sizes, a grid beyond the limits of addk_score_upsample_supported or N*OH*OW >= 2^31 (32-bit histogram counters).
  *
  * addk_ce_upsample_ohem_fwd_bwd is addk_ce_upsample_fwd_bwd with the per-pixel weight w = kept ? class_w[t] (or 1) : 0, where
@@ -626,7 +638,7 @@ int addk_ce_upsample_kd_fwd_bwd(const addk_ce_upsample_kd_args* a, void* stream)
  * and leaves in ws, as 32-bit words, [0..C) the counts Y_c (uint32), [32..32+C) I_c and [64..64+C) P_c (float) of this call; the rest is
  * scratch.  Y_c is exact (integer atomics); I_c and P_c are per-workgroup fp32 partials added in a fixed order in fp64; D_c, A_c, B_c and
  * the term are formed in fp64 and rounded once.  No float atomics: two calls give equal bits.  addk_dice_stats_supported() is 0 for
- * C != 19, non-positive sizes, a grid beyond the limits of addk_score_upsample_supported or N*OH*OW >= 2^31 (32-bit counters).
+ * C not in addk_head_classes(), non-positive sizes, a grid beyond the limits of addk_score_upsample_supported or N*OH*OW >= 2^31 (32-bit counters).
  * Returns ADDK_ERR_INVALID and launches nothing for a null pointer, ld < C, a non-finite weight or smooth, weight <= 0 or smooth < 0. */
 typedef struct {
   const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
@@ -637,9 +649,14 @@ typedef struct {
   float* coef;                       /* [2*C], written */
   float* dice_out;                   /* [1 + C], written */
   float* loss_out;                   /* device scalar, accumulated */
-  void* ws;                          /* addk_dice_stats_ws_bytes() bytes */
+  void* ws;                          /* addk_dice_stats_ws_bytes_classes(N, OH, OW, C) bytes */
 } addk_dice_stats_args;
 int addk_dice_stats_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+/* The workspace of a launch with C classes: 0 for a C not in addk_head_classes().  The partial rows hold 2 x C floats per workgroup. */
+int64_t addk_dice_stats_ws_bytes_classes(int32_t N, int32_t OH, int32_t OW, int32_t C);
+/* WARNING: the 19-class size ONLY, = addk_dice_stats_ws_bytes_classes(N, OH, OW, 19); kept for callers from before the class-count list.
+ * addk_dice_stats cannot check the size of ws: a launch with C = 21 on a workspace of this size writes past its end.  Size ws with the
+ * query above. */
 int64_t addk_dice_stats_ws_bytes(int32_t N, int32_t OH, int32_t OW);
 int addk_dice_stats(const addk_dice_stats_args* a, void* stream);
 /* The loss head with the term's gradient: addk_ce_upsample_kd_fwd_bwd (kd.teacher == NULL: no distillation, and alpha, temperature, nvalid
@@ -664,7 +681,7 @@ int addk_ce_upsample_dice_fwd_bwd(const addk_ce_upsample_dice_args* a, void* str
  *   pred_out[n,y,x]  = pred       uint8 [N,OH,OW], optional (NULL: not written)
  * Deterministic: integer atomics for the matrix, fixed-order two-stage sums for the two scalars.  It is a gather (one thread
  * per high-resolution pixel), so the 16-rows-per-input-row limit of addk_ce_upsample_supported does NOT apply here:
- * addk_score_upsample_supported() is 0 only for C != 19, non-positive sizes or a grid beyond 65535 x 32 rows / 65535 images. */
+ * addk_score_upsample_supported() is 0 only for C not in addk_gate_head_classes(), non-positive sizes or a grid beyond 65535 x 32 rows / 65535 images. */
 typedef struct {
   const float* logits; int32_t ld;   /* NHWC, pixel stride ld >= C */
   int32_t N, H, W, C, OH, OW;
@@ -687,13 +704,13 @@ int addk_score_upsample(const addk_score_upsample_args* a, void* stream);
  * full-resolution prediction softmax(interpolate(logits, (OH,OW), bilinear, align_corners=False)) straight from the
  * LOW-resolution NHWC logits [N,H,W,C] (the arithmetic of addk_resize_fwd bit for bit; the [N,C,OH,OW] tensor is never
  * materialised), in ONE launch:
- *   out[2n]     = sum_pixels (log sum e - sum e*d / sum e) / (log C * OH*OW)     normalised Shannon entropy of image n
+ *   out[2n]     = sum_pixels (log sum e - sum e*d / sum e) / (log 19 * OH*OW)    normalised Shannon entropy of image n (addk_gate_head_classes)
  *   out[2n + 1] = #{pixels: pmax > *max_thr} / (OH*OW),  pmax = 1 / sum_c exp(z_c - max_c z)   (operations.py:172-180)
  * max_thr is read from memory when the launch runs, so a captured graph serves every threshold.  out_host: optional
  * host-mapped (pinned) [N][2] words that receive the same bits — the host gate then needs no device-to-host copy, only
  * the completion of the launch.  ws: addk_gate_upsample_ws_bytes() bytes, ZERO-initialised once (the kernel leaves its
  * ticket word at zero: replayable from a hipGraph).  Deterministic: the last-arriving workgroup adds the per-workgroup
- * partials in a fixed order.  addk_gate_upsample_supported() is 0 for C != 19, non-positive sizes or a grid beyond
+ * partials in a fixed order.  addk_gate_upsample_supported() is 0 for C not in addk_gate_head_classes(), non-positive sizes or a grid beyond
  * 65535 x 32 rows / 65535 images (the limits of addk_score_upsample_supported); addk_gate_upsample then returns
  * ADDK_ERR_INVALID without launching. */
 typedef struct {
@@ -744,7 +761,7 @@ int addk_gate_label_upsample(const addk_gate_label_upsample_args* a, void* strea
  *   p_v  = softmax(z_v) in fp32 (max subtracted);  acc[c] += weight * p_v[c]
  *   labels[n,Y,X] = am, or lut256[am];  am = arg-max of acc (strict >: a tie keeps the lowest channel)
  * The mirrored half of a batch-2N logits tensor is addressed with n0 = N.  No workspace, no atomics: deterministic.
- * addk_label_views_upsample_supported() is 0 for nview outside 1..ADDK_MAX_VIEWS, C != 19, non-positive sizes or a grid beyond
+ * addk_label_views_upsample_supported() is 0 for nview outside 1..ADDK_MAX_VIEWS, C not in addk_gate_head_classes(), non-positive sizes or a grid beyond
  * 65535 x 16 rows / 65535 images; addk_label_views_upsample then returns ADDK_ERR_INVALID without launching, as it does for a
  * null pointer, a view with a non-positive size or a stride below C, and a weight that is not positive and finite. */
 #define ADDK_MAX_VIEWS 8
