@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('ADDK_LIB') or os.path.join(_HERE, 'libaddk.so')      
 
 MAX_SRC, MAX_SLAB, MAX_TERMS = 12, 32, 4
 MAX_VIEWS = 8
+MAX_TILES_AXIS = 16
 fp = C.POINTER(C.c_float)
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -114,6 +115,16 @@ class View(C.Structure):
 
 class LabelViewsArgs(C.Structure):
     _fields_ = [('view', View * MAX_VIEWS), ('nview', i32), ('N', i32), ('C', i32), ('OH', i32), ('OW', i32),
+                ('lut256', vp), ('labels', vp)]
+
+
+class TileDesc(C.Structure):
+    _fields_ = [('image', vp), ('H', i32), ('W', i32), ('y0', i32), ('x0', i32)]
+
+
+class LabelTilesArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('h', i32), ('w', i32), ('th', i32), ('tw', i32), ('N', i32), ('C', i32), ('OH', i32),
+                ('OW', i32), ('t0', i32), ('ny', i32), ('nx', i32), ('y0', i32 * MAX_TILES_AXIS), ('x0', i32 * MAX_TILES_AXIS),
                 ('lut256', vp), ('labels', vp)]
 
 
@@ -230,6 +241,7 @@ STRUCTS = {
     'addk_ce_upsample_kd_args': CeUpsampleKdArgs, 'addk_dice_stats_args': DiceStatsArgs, 'addk_ce_upsample_dice_args': CeUpsampleDiceArgs,
     'addk_score_upsample_args': ScoreUpsampleArgs, 'addk_gate_upsample_args': GateUpsampleArgs, 'addk_label_upsample_args': LabelUpsampleArgs,
     'addk_gate_label_upsample_args': GateLabelUpsampleArgs, 'addk_view': View, 'addk_label_views_args': LabelViewsArgs,
+    'addk_tile_desc': TileDesc, 'addk_label_tiles_args': LabelTilesArgs,
     'addk_profile_upsample_args': ProfileUpsampleArgs, 'addk_gate_upsample_t_args': GateUpsampleTArgs,
     'addk_profile_upsample_t_args': ProfileUpsampleTArgs, 'addk_calib_upsample_args': CalibUpsampleArgs,
     'addk_boundary_dist_args': BoundaryDistArgs, 'addk_confusion_banded_args': ConfusionBandedArgs, 'addk_rows_item': RowsItem,
@@ -369,6 +381,9 @@ _SIGS = {
     'addk_gate_label_upsample': (i32, [C.POINTER(GateLabelUpsampleArgs), vp]),
     'addk_label_views_upsample_supported': (i32, [i32, i32, i32, i32, i32]),
     'addk_label_views_upsample': (i32, [C.POINTER(LabelViewsArgs), vp]),
+    'addk_gather_tiles': (i32, [vp, i32, i32, i32, i32, vp, i32, vp]),
+    'addk_label_tiles_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
+    'addk_label_tiles_upsample': (i32, [C.POINTER(LabelTilesArgs), vp]),
     'addk_profile_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
     'addk_profile_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_profile_upsample': (i32, [C.POINTER(ProfileUpsampleArgs), vp]),

@@ -1,5 +1,6 @@
 // The inference heads on the decoder's low-resolution logits: the label map of one exit (label_up_kernel), of several views
-// (label_views_kernel), and the early-exit gate with and without the label map, plain and tempered (gate_up_kernel).
+// (label_views_kernel), of the sliding windows that cover an image (label_tiles_kernel), and the early-exit gate with and without the
+// label map, plain and tempered (gate_up_kernel).
 #include "up.h"
 
 namespace {
@@ -103,6 +104,104 @@ bool lvu_ok(int nview, int N, int OH, int OW, int C) {
   if (nview < 1 || nview > ADDK_MAX_VIEWS || !gate_class_ok(C) || N <= 0 || OH <= 0 || OW <= 0) return false;
   const dim3 g = lvu_grid(N, OH, OW);
   return N <= 65535 && g.y <= 65535 && (long)(int)g.z * (int)g.y * (int)g.x < (1L << 30);
+}
+
+// ---- fused tiled label map: up-sample every window that covers a pixel, softmax, sum, arg-max (sliding-window inference) ------------
+// What sliding-window inference keeps: the arg-max of the summed class probabilities of the windows that cover a pixel, one byte per
+// image pixel, from the stored low-resolution NHWC logits of the windows (all of one grid (h, w), one size (th, tw) in output pixels).
+// The tile and the walk are label_views_kernel's: a wave owns 64 consecutive columns and LVU_R rows, a thread one column X, acc[LVU_R][CC]
+// lives in registers.  The window grid is ny x nx origins from the argument block.  The window-row loop and its cover test are wave-
+// uniform (a wave's rows are the same in every lane); the window-column cover test is per lane: a lane outside [x0, x0 + tw) sits the
+// window out — it loads nothing and adds nothing — and a wave with no lane inside skips it.  Within a window the two W-interpolated rows
+// t0 / t1 are reloaded only when the wave-uniform row pair changes; z = lh0*t0 + lh1*t1 carries the bits addk_resize_fwd writes at
+// (Y - y0, X - x0) of a (h, w) -> (th, tw) resize.  Clamped last windows let three or more windows overlap on an axis: nothing here
+// counts on two.  Rows Y >= OH are never sampled, so the padded part of a window larger than the image is not.  No LDS, no atomics, no
+// workspace: every pixel's sum runs in the same order (ascending iy, then ix) on every launch.
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) label_tiles_kernel(const addk_label_tiles_args p) {
+  const int lane = threadIdx.x & (LVU_W - 1), wv = threadIdx.x / LVU_W;
+  const int X = blockIdx.x * LVU_W + lane, n = blockIdx.z;
+  if (X >= p.OW) return;
+  const int ybeg = (blockIdx.y * LVU_WAVES + wv) * LVU_R;
+  if (ybeg >= p.OH) return;                                            // wave-uniform
+  const int ylast = (ybeg + LVU_R < p.OH ? ybeg + LVU_R : p.OH) - 1;
+  const float sh = (float)p.h / (float)p.th, sw = (float)p.w / (float)p.tw;
+  const long tile_floats = (long)p.h * p.w * p.ld;
+  float acc[LVU_R][CC];
+#pragma unroll
+  for (int r = 0; r < LVU_R; ++r)
+#pragma unroll
+    for (int c = 0; c < CC; ++c) acc[r][c] = 0.f;
+  for (int iy = 0; iy < p.ny; ++iy) {
+    const int y0 = p.y0[iy];
+    if (y0 > ylast || y0 + p.th <= ybeg) continue;                      // wave-uniform: the window row misses this wave's rows
+    for (int ix = 0; ix < p.nx; ++ix) {
+      const int lx = X - p.x0[ix];
+      if (lx >= 0 && lx < p.tw) {                                       // per lane: this window covers column X
+        const float* x = p.logits + ((long)p.t0 + ((long)n * p.ny + iy) * p.nx + ix) * tile_floats;
+        int w0, w1; float lw0, lw1;
+        src_index(lx, sw, p.w, w0, w1, lw0, lw1);
+        float t0[CC], t1[CC];
+        int ph0 = -1, ph1 = -1;
+#pragma unroll
+        for (int r = 0; r < LVU_R; ++r) {
+          const int ly = ybeg + r - y0;
+          if (ybeg + r < p.OH && ly >= 0 && ly < p.th) {               // wave-uniform
+            int h0, h1; float lh0, lh1;
+            src_index(ly, sh, p.h, h0, h1, lh0, lh1);
+            if (h0 != ph0 || h1 != ph1) {                              // wave-uniform
+              const float* r0 = x + ((long)h0 * p.w) * p.ld;
+              const float* r1 = x + ((long)h1 * p.w) * p.ld;
+              float a[cpad(CC)], b[cpad(CC)];
+              load_px<CC>(r0 + (long)w0 * p.ld, a, VEC); load_px<CC>(r0 + (long)w1 * p.ld, b, VEC);
+#pragma unroll
+              for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
+              load_px<CC>(r1 + (long)w0 * p.ld, a, VEC); load_px<CC>(r1 + (long)w1 * p.ld, b, VEC);
+#pragma unroll
+              for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
+              ph0 = h0; ph1 = h1;
+            }
+            float e[CC];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) { e[c] = lh0 * t0[c] + lh1 * t1[c]; mx = fmaxf(mx, e[c]); }
+            float se = 0.f;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) { e[c] = __expf(e[c] - mx); se += e[c]; }
+            const float s = 1.0f / se;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) acc[r][c] += s * e[c];
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < LVU_R; ++r) {
+    const int Y = ybeg + r;
+    if (Y < p.OH) {
+      float mx = -INFINITY; int am = 0;
+#pragma unroll
+      for (int c = 0; c < CC; ++c)
+        if (acc[r][c] > mx) { mx = acc[r][c]; am = c; }            // strict: a tie keeps the lowest channel
+      label_px(p.lut256, p.labels, ((long)n * p.OH + Y) * p.OW + X, am);
+    }
+  }
+}
+
+bool ltu_ok(int N, int OH, int OW, int ny, int nx, int C) {
+  if (!head_class_ok(C) || ny < 1 || ny > ADDK_MAX_TILES_AXIS || nx < 1 || nx > ADDK_MAX_TILES_AXIS || N <= 0 || OH <= 0 || OW <= 0) return false;
+  const dim3 g = lvu_grid(N, OH, OW);
+  return N <= 65535 && g.y <= 65535 && (long)(int)g.z * (int)g.y * (int)g.x < (1L << 30);
+}
+// the origins of one axis are a window grid of an image of L pixels: from 0, strictly increasing, no gap, inside the image, up to its end
+bool ltu_axis_ok(const int32_t* o, int n, int t, int L) {
+  if (o[0] != 0) return false;
+  for (int i = 0; i < n; ++i) {
+    if (o[i] < 0 || o[i] >= L) return false;
+    if (i + 1 < n && (o[i + 1] <= o[i] || (long)o[i + 1] > (long)o[i] + t)) return false;
+  }
+  return (long)o[n - 1] + t >= L;
 }
 
 // ---- fused logits up-sampling + early-exit gate (decoder.py:28 + operations.py:161-180) -----------------------------------
@@ -274,4 +373,22 @@ extern "C" int addk_label_views_upsample(const addk_label_views_args* a, void* s
     launch_vec(vec, label_views_kernel<CC, true>, label_views_kernel<CC, false>, lvu_grid(a->N, a->OH, a->OW), st, *a);
   });
   return addk_check_launch("label_views_upsample");
+}
+
+extern "C" int addk_label_tiles_upsample_supported(int32_t N, int32_t OH, int32_t OW, int32_t ny, int32_t nx, int32_t C) {
+  return ltu_ok(N, OH, OW, ny, nx, C) ? 1 : 0;
+}
+extern "C" int addk_label_tiles_upsample(const addk_label_tiles_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->labels, "label_tiles_upsample: null pointer");
+  ADDK_REQUIRE(ltu_ok(a->N, a->OH, a->OW, a->ny, a->nx, a->C), "label_tiles_upsample: unsupported shape (1..%d windows per axis, %s)",
+               ADDK_MAX_TILES_AXIS, head_classes_text().c_str());
+  ADDK_REQUIRE(a->h > 0 && a->w > 0 && a->th > 0 && a->tw > 0 && a->ld >= a->C && a->t0 >= 0, "label_tiles_upsample: bad size, first tile or stride");
+  ADDK_REQUIRE(ltu_axis_ok(a->y0, a->ny, a->th, a->OH) && ltu_axis_ok(a->x0, a->nx, a->tw, a->OW),
+               "label_tiles_upsample: the origins are no window grid of the image (from 0, increasing, no gap, inside it, up to its end)");
+  hipStream_t st = (hipStream_t)stream;
+  head_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), label_tiles_kernel<CC, true>, label_tiles_kernel<CC, false>, lvu_grid(a->N, a->OH, a->OW), st, *a);
+  });
+  return addk_check_launch("label_tiles_upsample");
 }

@@ -350,6 +350,22 @@ def _emit_views(g, outs, tag):
     g._add(g.fwd, 'label_views_upsample', lib.addk_label_views_upsample, C.byref(a), rd=rd + [lut], wr=[lab]).tag = tag
 
 
+def _tiles_head(g, src, OH, OW):
+    """Logits output of a tile plan (head 'tiles', set by segment.TiledSegmenter): the plan is ONE window of a sliding-window pass, and
+    what becomes of its logits is decided outside the plan — the step copies each chunk's low-resolution logits into its store and ends a
+    call with one `addk_label_tiles_upsample` launch per image, which up-samples, soft-maxes and sums every window that covers a pixel.  So,
+    as in _views_head, nothing is emitted here and no [N,C,OH,OW] buffer exists: the OutRef keeps the low-resolution source (`src`) and
+    `shape`.  There is no stand-alone form: a class count outside `_lib.head_classes()` is an error, and so is a gate."""
+    if g.gate is not None:
+        raise L.AddkError('the tiled label head has no gated form: a window is no image to leave early with')
+    if src.C not in L.head_classes():
+        raise L.AddkError('the tiled label head takes %s (got %d)' % (L.head_classes_text(), src.C))
+    out = OutRef(None)
+    out.head, out.shape, out.src = 'tiles', (src.N, src.C, OH, OW), src
+    g.lz(src)                                    # a still-deferred resize of the logits is emitted now: the step reads src.raw itself
+    return out
+
+
 def _labels_cold(g, y, lab, lut):
     """Cold path of the two label heads: the map from materialised logits y [N,C,OH,OW] — `argmax_nchw`, then the cast / table look-up
     to uint8 in torch ops."""
@@ -474,21 +490,22 @@ def label_lut(lut, device):
 
 # Graph.head / OutRef.head: who consumes the decoder's low-resolution logits -> the function that emits that head.  None (no entry) =
 # nobody: Graph.resize_to_nchw writes [N,C,OH,OW] itself.  A gate (Graph.gate) is no head of its own: it composes with None and 'labels'.
-HEADS = {'ce': _ce_head, 'score': _score_head, 'profile': _profile_head, 'calib': _calib_head, 'labels': _label_head, 'views': _views_head}
+HEADS = {'ce': _ce_head, 'score': _score_head, 'profile': _profile_head, 'calib': _calib_head, 'labels': _label_head, 'views': _views_head,
+         'tiles': _tiles_head}
 
 
 def logits_head(g, src, OH, OW):
     """The OutRef of the head that takes this logits output, or None where the plain resize does.  A plan with gradients only ever takes
     'ce', and only where the library takes the shape and the logits need a gradient.  An inference plan takes 'score', 'profile' or 'calib'
-    first; then its gate, over head None or 'labels'; then 'labels' or 'views'."""
+    first; then its gate, over head None or 'labels' ('tiles' refuses one); then 'labels', 'views' or 'tiles'."""
     head, gate = g.head, g.gate
     if g.want_grad:
         fused = head == 'ce' and src.needs_grad and g.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1
         return HEADS['ce'](g, src, OH, OW) if fused else None
     if head in ('score', 'profile', 'calib'):
         return HEADS[head](g, src, OH, OW)
-    if gate is not None:
+    if gate is not None and head != 'tiles':     # 'tiles' has no gated form: _tiles_head refuses the gate
         return gate_head(g, src, OH, OW, gate['host'], gate['thr'], gate['kind'], gate.get('temp'))
-    if head in ('labels', 'views'):
+    if head in ('labels', 'views', 'tiles'):
         return HEADS[head](g, src, OH, OW)
     return None

@@ -1362,7 +1362,7 @@ class OutRef:
         self.bwd_cmd = None      # generic nhwc path
         self.shape = None        # (N, C, OH, OW) of the logits a fused head stands for (y is None)
         self.head = None         # Graph.head of the head that consumed the logits; None: y is the real logits.  'labels': y is the label map
-        self.src = None          # 'views', 'ce': the lazy activation of the decoder's low-resolution logits this output stands for
+        self.src = None          # 'views', 'tiles', 'ce': the lazy activation of the decoder's low-resolution logits this output stands for
         # what the step binds to a 'ce' / 'score' / 'profile' head before finalize() — 'ce': target, class_w, ignore_index, wsum, scale, loss;
         # 'score': those + entropy, confusion, pred; 'profile': target, thr, nthr, entropy, share, confusion, pred and optionally temp (the
         # device word 1 / temperature: the tempered launch); 'views': N, views; 'calib': target, inv_temp, nt, bins, nll

@@ -18,14 +18,27 @@ at any other; the multi-view head takes `_lib.gate_head_classes()` (19) and Mult
 
     seg = MultiViewSegmenter(model, (N, 3, H, W), scales=(0.75, 1.0, 1.25), flip=True, label_lut=decode_segmap_lut())
     labels = seg.step(images)                # uint8 [N,H,W], plan-owned; no host synchronisation
+
+Sliding-window (tiled) inference: ONE plan of a fixed window size serves images of any size, a list of differently sized images
+included.  The windows of a call (tile_starts: the last window of an axis is clamped to the image edge, an image smaller than the
+window is one zero-padded window) are cut by `addk_gather_tiles`, one launch per chunk of B windows, run through the tile plan, and their
+low-resolution logits are kept in a store; ONE `addk_label_tiles_upsample` launch per image (plan.Graph.head 'tiles': heads._tiles_head)
+then writes the arg-max of the summed class probabilities of every window that covers a pixel.  No [T,C,th,tw] tensor and no
+full-resolution probability buffer exists.  The head takes `_lib.head_classes()` (19, 21) and TiledSegmenter raises at any other.
+
+    seg = TiledSegmenter(model, (B, 3, 769, 769), stride=(513, 513))
+    maps = seg.segment(images)               # [n,3,H,W] or a list of [3,H_i,W_i] -> list of uint8 [H_i,W_i], owned by `seg`
 """
+import ctypes as C
 import math
 
 import torch
 
 from . import _lib as L
+from . import plan as _plan
 from .heads import label_lut as _label_lut
 from .resident import InferenceStep
+from .sched import Cmd
 
 
 class Segmenter(InferenceStep):
@@ -133,3 +146,159 @@ class MultiViewSegmenter(InferenceStep):
         """Copies of every view's low-resolution NHWC logits [N,h_v,w_v,C], in the order of `views` (inspection and tests)."""
         N = self.image_shape[0]
         return [o.src.raw.view()[n0:n0 + N].clone() for o in self.outs for n0, _, _ in o.binding['views']]
+
+
+def tile_starts(L_, t, s):
+    """Window origins along one axis of L_ pixels, window t, stride s: [0] if L_ <= t (one window, the image padded to it), else
+    ceil((L_ - t) / s) + 1 origins min(i * s, L_ - t) — the last window is clamped to the image edge, not padded.  Needs 1 <= s <= t, so
+    that consecutive windows touch or overlap; the origins strictly increase (both checked).  More than MAX_TILES_AXIS windows is a
+    ValueError.  Clamping lets three windows overlap: tile_starts(70, 33, 17) == [0, 17, 34, 37]."""
+    L_, t, s = int(L_), int(t), int(s)
+    if L_ < 1 or t < 1:
+        raise ValueError('an axis of %d pixels and a window of %d: both must be positive' % (L_, t))
+    if not 1 <= s <= t:
+        raise ValueError('the stride must be within 1..window (got stride %d, window %d)' % (s, t))
+    if L_ <= t:
+        return [0]
+    n = -((t - L_) // s) + 1
+    if n > L.MAX_TILES_AXIS:
+        raise ValueError('%d windows of %d at stride %d along %d pixels: at most %d per axis' % (n, t, s, L_, L.MAX_TILES_AXIS))
+    starts = [min(i * s, L_ - t) for i in range(n)]
+    assert starts[0] == 0 and starts[-1] + t == L_ and all(a < b <= a + t for a, b in zip(starts, starts[1:])), starts
+    return starts
+
+
+class TiledSegmenter(InferenceStep):
+    """Label maps of images of any size from one tile plan at batch B (see the module text).  `tiles`: the last call's windows as
+    (image, y0, x0), in store order — image-major, then window row, then window column.  `maps`: the last call's label maps."""
+    head = 'tiles'
+
+    def __init__(self, model, tile_shape, stride, exit=-1, label_lut=None, use_graph=None, nstreams=None):
+        from .modeling.ADD import ADD
+        if not isinstance(model, ADD):
+            raise TypeError('TiledSegmenter takes an ADD model (got %s)' % type(model).__name__)
+        B, Cin, th, tw = (int(v) for v in tile_shape)
+        sy, sx = (int(v) for v in stride)
+        if B < 1 or Cin < 1 or th < 1 or tw < 1:
+            raise ValueError('tile_shape must be positive (got %r)' % (tuple(tile_shape),))
+        if not (1 <= sy <= th and 1 <= sx <= tw):
+            raise ValueError('the stride must be within 1..tile (got stride %r, tile %dx%d)' % ((sy, sx), th, tw))
+        self.stride = (sy, sx)
+        self.exit = range(model.num_exits())[exit]             # forward()'s output list; IndexError out of range
+        self.lut = _label_lut(label_lut, next(model.parameters()).device)
+        self.tiles, self.maps, self._images = [], [], []
+        self._store = None                                     # [Tcap,h,w,ld]: the low-resolution logits of a call's windows
+        self._desc_host = self._desc_dev = self._desc_evt = None
+        self._label_buf = None
+        super().__init__(model, (B, Cin, th, tw), use_graph, nstreams, target=False)
+        self._build()
+
+    def _emit(self, g, a):
+        B, _, th, tw = self.batch_shape
+        self.out = self.model._emit_exit(g, a, self.exit)
+        assert self.out.head == 'tiles' and (self.out.shape[0],) + tuple(self.out.shape[2:]) == (B, th, tw), \
+            'the model did not end in Graph.resize_to_nchw'
+        src = self.out.src.raw
+        self.ncls, self.low = src.C, (src.H, src.W)
+        self.ld = (src.C + 3) // 4 * 4                         # the store's pixel stride: what the head's 16-byte loader asks for
+
+    # ---------------- per call ----------------
+    def _launch(self, name, fn, *args):
+        """one launch on the current stream, through the plan's launch loop"""
+        self.g.run([Cmd(name, fn, args)], _plan.current_stream())
+
+    def _windows(self, images):
+        """-> ([(image tensor [Cin,H,W], H, W, y origins, x origins, first tile)], [(image, y0, x0)]) of a call"""
+        Cin, th, tw = self.batch_shape[1:]
+        if isinstance(images, torch.Tensor):
+            if images.dim() != 4:
+                raise ValueError('images: a tensor [n,%d,H,W] or a list of [%d,H,W] tensors (got %s)' % (Cin, Cin, tuple(images.shape)))
+            images = list(images.unbind(0))
+        images = list(images)
+        if not images:
+            raise ValueError('no image')
+        per, tiles = [], []
+        for k, im in enumerate(images):
+            if im.dim() != 3 or im.shape[0] != Cin or im.shape[1] < 1 or im.shape[2] < 1:
+                raise ValueError('image %d: expected [%d,H,W] (got %s)' % (k, Cin, tuple(im.shape)))
+            if im.dtype != torch.float32:
+                raise ValueError('image %d: expected normalised float32 (got %s)' % (k, im.dtype))
+            _plan.require_device(im)
+            H, W = int(im.shape[1]), int(im.shape[2])
+            ys, xs = tile_starts(H, th, self.stride[0]), tile_starts(W, tw, self.stride[1])
+            per.append((im.contiguous(), H, W, ys, xs, len(tiles)))
+            tiles += [(k, y, x) for y in ys for x in xs]
+        return per, tiles
+
+    def _upload(self, per, T):
+        """The call's descriptor table on the device: written into pinned host words, copied without blocking; an event guards the words'
+        reuse by the next call (it waits for that one copy, not for the device)."""
+        B = self.batch_shape[0]
+        cap = -(-T // B) * B
+        nb = cap * C.sizeof(L.TileDesc)
+        if self._desc_host is None or self._desc_host.numel() < nb:
+            self._desc_host = torch.zeros(nb, dtype=torch.uint8)
+            self._desc_dev = torch.zeros(nb, dtype=torch.uint8, device=self.dev)
+            if self.dev.type == 'cuda':
+                self._desc_host = self._desc_host.pin_memory()
+            self._desc_evt = None
+        if self._desc_evt is not None:
+            self._desc_evt.synchronize()
+        arr = (L.TileDesc * cap)()
+        i = 0
+        for im, H, W, ys, xs, _ in per:
+            for y in ys:
+                for x in xs:
+                    d = arr[i]
+                    d.image, d.H, d.W, d.y0, d.x0 = im.data_ptr(), H, W, y, x
+                    i += 1
+        self._desc_host[:nb].copy_(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8))
+        self._desc_dev[:nb].copy_(self._desc_host[:nb], non_blocking=True)
+        if self.dev.type == 'cuda':
+            if self._desc_evt is None:
+                self._desc_evt = torch.cuda.Event()
+            self._desc_evt.record()
+        return self._desc_dev.data_ptr()
+
+    def segment(self, images):
+        """-> the uint8 [H_i,W_i] label map of every image: `images` is a tensor [n,Cin,H,W] or a list of [Cin,H_i,W_i] tensors of any sizes,
+        normalised float32 on the plan's device.  The maps belong to this object and are overwritten by the next call.  No host
+        synchronisation, except once when the third replay captures the hipGraph."""
+        lib = self.lib
+        B, Cin, th, tw = self.batch_shape
+        h, w = self.low
+        per, tiles = self._windows(images)
+        T = len(tiles)
+        if self._storage() != self._ptrs:          # the parameters moved: the plan (and with it the class count and grid) is rebuilt first
+            self._build()
+            h, w = self.low
+        if self._store is None or self._store.shape[0] < T or tuple(self._store.shape[1:]) != (h, w, self.ld):
+            self._store = torch.zeros((T, h, w, self.ld), dtype=torch.float32, device=self.dev)      # outside the graph: it may grow
+        table = self._upload(per, T)
+        logits = self.out.src.raw.view()
+        with torch.no_grad():
+            for t in range(0, T, B):
+                nb = min(B, T - t)
+                self._launch('gather_tiles', lib.addk_gather_tiles, table + t * C.sizeof(L.TileDesc), nb, Cin, th, tw, self.x.data_ptr(), B)
+                self._replay()
+                self._store[t:t + nb, :, :, :self.ncls].copy_(logits[:nb])
+            npix = sum(H * W for _, H, W, _, _, _ in per)
+            if self._label_buf is None or self._label_buf.numel() < npix:
+                self._label_buf = torch.zeros(npix, dtype=torch.uint8, device=self.dev)
+            maps, off = [], 0
+            for im, H, W, ys, xs, t0 in per:
+                lab = self._label_buf[off:off + H * W].view(H, W)
+                off += H * W
+                a = L.LabelTilesArgs()
+                a.logits, a.ld, a.h, a.w, a.th, a.tw = self._store.data_ptr(), self.ld, h, w, th, tw
+                a.N, a.C, a.OH, a.OW, a.t0, a.ny, a.nx = 1, self.ncls, H, W, t0, len(ys), len(xs)
+                a.y0[:len(ys)], a.x0[:len(xs)] = ys, xs
+                a.lut256, a.labels = self.lut.data_ptr() if self.lut is not None else None, lab.data_ptr()
+                self._launch('label_tiles_upsample', lib.addk_label_tiles_upsample, C.byref(a))
+                maps.append(lab)
+        self.tiles, self.maps, self._images = tiles, maps, [p[0] for p in per]      # the images stay alive while the device may read them
+        return maps
+
+    def tile_logits(self):
+        """Copies of the stored low-resolution NHWC logits [T,h,w,C] of the last call's windows, in the order of `tiles` (inspection and tests)."""
+        return self._store[:len(self.tiles), :, :, :self.ncls].clone()

@@ -500,7 +500,7 @@ int64_t addk_ce_ws_floats(int32_t N, int64_t HW);
 
 /* The class counts C the fused heads on the low-resolution logits are compiled for, two lists in csrc/up.h.
  *   addk_head_classes       the training heads (addk_ce_upsample_fwd_bwd and its _ohem, _kd and _dice forms, addk_ohem_select,
- *                           addk_dice_stats), the label head (addk_label_upsample) and the compile-time form of addk_ce_fwd_bwd:
+ *                           addk_dice_stats), the label heads (addk_label_upsample, addk_label_tiles_upsample) and the compile-time form of addk_ce_fwd_bwd:
  *                           19 (Cityscapes) and 21 (Pascal VOC).
  *   addk_gate_head_classes  the scoring, profile, calibration, gate and multi-view heads (addk_score_upsample, addk_profile_upsample[_t],
  *                           addk_calib_upsample, addk_gate_upsample[_t], addk_gate_label_upsample, addk_label_views_upsample): 19.
@@ -778,6 +778,47 @@ typedef struct {
 } addk_label_views_args;
 int addk_label_views_upsample_supported(int32_t nview, int32_t N, int32_t OH, int32_t OW, int32_t C);
 int addk_label_views_upsample(const addk_label_views_args* a, void* stream);
+
+/* Sliding-window (tiled) label maps: a plan of one fixed window size (th, tw) serves images of any size.  The windows of an image form
+ * a grid of ny x nx origins (segment.tile_starts: the first at 0, the last clamped to the image edge, consecutive windows touch or overlap;
+ * an image smaller than the window is one window, zero-padded).
+ *
+ * addk_gather_tiles fills the plan's resident NCHW input x [B,Cin,th,tw] from a table of window descriptors in DEVICE memory, in ONE
+ * launch: slot b < ntiles gets image[c][y0 + i][x0 + j], 0.0f where that lies outside the image (the reference's ZeroPad2d after
+ * Normalize); the slots ntiles <= b < B are zero-filled.  Every descriptor names its own image and size, so windows of images of different
+ * sizes share a chunk.  Returns ADDK_ERR_INVALID without launching for a null pointer (the table may be null when ntiles == 0), ntiles
+ * outside 0..B and non-positive sizes. */
+typedef struct { const float* image; int32_t H, W, y0, x0; } addk_tile_desc;  /* image: NCHW planes of ONE image, [Cin][H][W] */
+int addk_gather_tiles(const addk_tile_desc* tiles_dev, int32_t ntiles, int32_t Cin, int32_t th, int32_t tw,
+                      float* x, int32_t B, void* stream);
+
+/* Tiled label head: the arg-max of the summed class probabilities of every window that covers a pixel, in ONE launch over the stored
+ * LOW-resolution NHWC logits of the windows; no [T,C,th,tw] tensor and no full-resolution probability buffer exists.  For output pixel
+ * (n, Y, X), over the tiles (iy, ix) with y0[iy] <= Y < y0[iy] + th and x0[ix] <= X < x0[ix] + tw, ascending iy, then ascending ix:
+ *   z      = bilinear sample (align_corners=False, scales h/th and w/tw) of the tile's logits at (Y - y0[iy], X - x0[ix]): the bits
+ *            addk_resize_fwd writes there when it resizes (h, w) to (th, tw)
+ *   e[c]   = exp(z[c] - max z);  acc[c] += (1.0f / sum e) * e[c]            (addk_label_views_upsample's expression, weight 1)
+ *   labels[n,Y,X] = am, or lut256[am];  am = arg-max of acc (strict >: a tie keeps the lowest channel)
+ * The sum is not divided by the cover count (the arg-max does not need it); the part of a tile beyond the image (OH < th) is never
+ * sampled.  No workspace, no atomics: deterministic.
+ * addk_label_tiles_upsample_supported() is 0 for C not in addk_head_classes(), ny or nx outside 1..ADDK_MAX_TILES_AXIS, non-positive
+ * sizes or a grid beyond 65535 x 16 rows / 65535 images; addk_label_tiles_upsample then returns ADDK_ERR_INVALID without launching, as it
+ * does for a null logits / labels pointer, non-positive h, w, th, tw, ld < C, t0 < 0, and origins that are no window grid of the image:
+ * y0[0] != 0, not strictly increasing, a gap (y0[i+1] > y0[i] + th), an origin at or beyond the image, a last window that ends before
+ * the image does (y0[ny-1] + th < OH); likewise x0. */
+#define ADDK_MAX_TILES_AXIS 16
+typedef struct {
+  const float* logits; int32_t ld;   /* store of low-resolution NHWC tile logits: tile t is [h][w] pixels of stride ld >= C at logits + t*h*w*ld */
+  int32_t h, w;                      /* a tile's low-resolution grid */
+  int32_t th, tw;                    /* a tile's size in output pixels */
+  int32_t N, C, OH, OW;              /* N images of one size (OH, OW) */
+  int32_t t0, ny, nx;                /* image n's tile (iy, ix) is tile t0 + (n*ny + iy)*nx + ix */
+  int32_t y0[ADDK_MAX_TILES_AXIS], x0[ADDK_MAX_TILES_AXIS];
+  const uint8_t* lut256;             /* NULL: the class index; else lut256[class] */
+  uint8_t* labels;                   /* [N,OH,OW] */
+} addk_label_tiles_args;
+int addk_label_tiles_upsample_supported(int32_t N, int32_t OH, int32_t OW, int32_t ny, int32_t nx, int32_t C);
+int addk_label_tiles_upsample(const addk_label_tiles_args* a, void* stream);
 
 /* Exit profile of a validation pass (eval.py:195-230): what the early-exit operating curve needs of one exit, PER IMAGE, in
  * ONE launch over the LOW-resolution NHWC logits [N,H,W,C] (the walk and the arithmetic of the two heads above):
