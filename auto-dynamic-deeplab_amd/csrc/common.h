@@ -157,6 +157,66 @@ __device__ __forceinline__ unsigned wave_umax(unsigned v) {
   const unsigned ab = a > b ? a : b, cd = c > d ? c : d;
   return ab > cd ? ab : cd;
 }
+// ---- statistics tail of the forward kernels (sepf.hip, pw.hip): totals of V per-lane values over the 16 pixel lanes of a DPP row ----------------
+// The all-reduce butterfly these kernels ended in computes, per value, T1[i] = x[i] + x[i^1], T2[i] = T1[i] + T1[i^2], T3[i] = T2[i] + T2[i^4],
+// T4 = T3[i] + T3[i^8] in every lane i, and lane 0 kept T4.  IEEE addition is commutative, so every lane of a 2^m-lane group holds the same
+// bits at level m and any lane that adds the same two partial sums gets them too.  rs16() is the reduce-scatter of that tree: at each level a
+// lane keeps half of its remaining values and adds the partner's partial sums of those — 12 + 6 + 3 + 2 exchanges for 24 values where the
+// butterfly takes 96, each a DPP move (two for a double) instead of an LDS permute.  Which half a lane keeps:
+//   level 1 (partner li ^ 1, quad_perm [1,0,3,2]): the upper half if bit 0 ^ bit 2 of li is set
+//   level 2 (partner li ^ 2, quad_perm [2,3,0,1]): the upper half if bit 1 ^ bit 2 is set
+//   level 3 (partner li ^ 7, row_half_mirror):     the upper half if bit 2 is set.  Bit 2 flips the choices of levels 1 and 2, so the mirrored
+//            lane of the other quad holds the same values as li ^ 4 would in a plain layout: the quad sums T2 of both quads meet, as in the tree
+//   level 4 (partner li ^ 8, row_ror:8):           the upper half if bit 3 is set
+// An odd count leaves one value without a sibling: both lanes add it (a plain butterfly step) and the lane that keeps the lower half owns it.
+// Written as unrolled templates with constant indices: as a loop over the levels the value array lands in scratch (conv3b.h, rs32).
+template <int CTL>
+__device__ __forceinline__ float rs16_from(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTL, 0xF, 0xF, true)); }
+template <int CTL>
+__device__ __forceinline__ double rs16_from(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+template <int NIN, int CTL, typename T>
+__device__ __forceinline__ void rs16_step(const T (&in)[NIN], T (&out)[(NIN + 1) / 2], const bool upper) {
+  constexpr int NOUT = (NIN + 1) / 2;
+#pragma unroll
+  for (int i = 0; i < NOUT; ++i) {
+    if (i + NOUT < NIN) {
+      T lo = in[i], hi = in[i + NOUT];
+      asm("" : "+v"(lo), "+v"(hi));              // two values, then two selects: without this the compiler selects the INDEX and walks the array with compares
+      const T keep = upper ? hi : lo, send = upper ? lo : hi;
+      out[i] = keep + rs16_from<CTL>(send);
+    } else {
+      out[i] = in[i] + rs16_from<CTL>(in[i]);
+    }
+  }
+}
+template <int V>
+struct Rs16 { static constexpr int N1 = (V + 1) / 2, N2 = (N1 + 1) / 2, N3 = (N2 + 1) / 2, NF = (N3 + 1) / 2; };   // values a lane holds after each level
+template <int V, typename T>
+__device__ __forceinline__ void rs16(const T (&v)[V], T (&tot)[Rs16<V>::NF], const int li) {      // (a step writes a new array: in place, one instantiation kept its values in scratch)
+  const bool q = (li & 4) != 0;
+  T t1[Rs16<V>::N1], t2[Rs16<V>::N2], t3[Rs16<V>::N3];
+  rs16_step<V, 0xB1>(v, t1, ((li & 1) != 0) != q);
+  rs16_step<Rs16<V>::N1, 0x4E>(t1, t2, ((li & 2) != 0) != q);
+  rs16_step<Rs16<V>::N2, 0x141>(t2, t3, q);
+  rs16_step<Rs16<V>::N3, 0x128>(t3, tot, (li & 8) != 0);
+}
+// the value whose row total tot[j] of lane li is after rs16(), -1: a copy that another lane owns
+template <int V>
+__device__ __forceinline__ int rs16_index(const int j, const int li) {
+  int idx = j; bool own = true;
+  auto up = [&](const int nin, const bool upper) {
+    const int nout = (nin + 1) / 2;
+    if (upper) { if (idx + nout < nin) idx += nout; else own = false; }
+  };
+  const bool q = (li & 4) != 0;
+  up(Rs16<V>::N3, (li & 8) != 0); up(Rs16<V>::N2, q); up(Rs16<V>::N1, ((li & 2) != 0) != q); up(V, ((li & 1) != 0) != q);
+  return own ? idx : -1;
+}
+
 __device__ __forceinline__ unsigned absbits4(const float4 v) {
   return __float_as_uint(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
 }

@@ -9,7 +9,7 @@
 //     that weights and pixels share, so the sum is unchanged), two tiles in flight per wave,
 //   * the lazy BatchNorm/ReLU prologue is applied to the fragment in registers,
 //   * the epilogue stores 16 B per lane and keeps the BN statistics / (dA,dB) sums in per-lane fp64 registers for the
-//     whole kernel; one butterfly + cross-wave LDS reduction at the very end writes the block's slab row.
+//     whole kernel; one reduction over the pixel lanes (registers) and the waves (LDS) at the very end writes the block's slab row.
 #include <stdlib.h>
 #include <type_traits>
 #include "conv.h"
@@ -35,6 +35,27 @@ struct PwK {
   // measurement of this file was taken on — next to each other the loads merge and the RS kernels' registers move (profiles/pw_epilogue_isa.txt)
   const void* gap0; int H, W; const void* gap1; int RH, RW; float* rs_y; int rs_ldy;
 };
+
+// The statistics tail the kernels of this file share: the totals of a wave's 8 CT per-lane sums (s1, s2 of channel 16 i + 4 kq + e) over its 16
+// pixel lanes, in red_t as the lanes summed them (fp32 lane sums are widened after the row total, as before), by the reduce-scatter of common.h
+// (rs16: the same tree as the butterfly of LDS permutes it replaces, the same bits); the owning lanes write red[wave][channel][0 / 1].
+// Value index 4 CT which + 4 i + e.
+template <int CT, typename red_t>
+__device__ __forceinline__ void pw_lane_totals(const red_t (&s1)[CT][4], const red_t (&s2)[CT][4], double (*red)[CT * 16][2], const int wave, const int li, const int kq) {
+  constexpr int V = 2 * 4 * CT;
+  red_t sv[V];
+#pragma unroll
+  for (int i = 0; i < CT; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { sv[i * 4 + e] = s1[i][e]; sv[4 * CT + i * 4 + e] = s2[i][e]; }
+  red_t tot[Rs16<V>::NF];
+  rs16(sv, tot, li);
+#pragma unroll
+  for (int j = 0; j < Rs16<V>::NF; ++j) {
+    const int idx = rs16_index<V>(j, li);
+    if (idx >= 0) { const int which = idx >= 4 * CT, c4 = idx - which * (4 * CT); red[wave][(c4 >> 2) * 16 + kq * 4 + (c4 & 3)][which] = (double)tot[j]; }
+  }
+}
 
 // These launches are latency chains (kernel arguments -> weight panel -> one or two pixel tiles -> store -> statistics)
 // run by a few thousand waves: what sets their duration is how many of those chains are resident at once, so the kernel
@@ -209,16 +230,8 @@ __device__ __forceinline__ void pw_body(const PwK& p, double (*red)[CT * 16][2])
     }
   }
 
-  if (p.slab) {     // once per kernel: butterfly over the 16 pixel lanes, then the four waves through LDS (fixed order)
-#pragma unroll
-    for (int i = 0; i < CT; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red_t a = s1[i][e], b = s2[i][e];
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
-        if (li == 0) { red[wave][i * 16 + kq * 4 + e][0] = (double)a; red[wave][i * 16 + kq * 4 + e][1] = (double)b; }
-      }
+  if (p.slab) {     // once per kernel: totals over the 16 pixel lanes, then the four waves through LDS (fixed order)
+    pw_lane_totals<CT>(s1, s2, red, wave, li, kq);
     __syncthreads();
     if (t < CT * 16 && n0 + t < p.Cn) {
       gdouble* o = (gdouble*)p.slab + ((long)blockIdx.x * p.slab_ld + n0 + t) * 2;
@@ -374,15 +387,7 @@ __global__ void __launch_bounds__(256, RS ? 2 : 3) pwk_kernel(const PwkK p) {
     }
   }
   if (p.slab) {
-#pragma unroll
-    for (int i = 0; i < CT; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red_t a = s1[i][e], b = s2[i][e];
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
-        if (li == 0) { red[wave][i * 16 + kq * 4 + e][0] = (double)a; red[wave][i * 16 + kq * 4 + e][1] = (double)b; }
-      }
+    pw_lane_totals<CT>(s1, s2, red, wave, li, kq);
     __syncthreads();
     if (t < CT * 16 && n0 + t < p.Cn) {
       gdouble* o = (gdouble*)p.slab + ((long)blockIdx.x * p.slab_ld + n0 + t) * 2;
@@ -570,15 +575,7 @@ __global__ void __launch_bounds__(256) stem0_kernel(const StemK p) {
     }
   }
   if (p.slab) {
-#pragma unroll
-    for (int i = 0; i < CT; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red_t a = s1[i][e], b = s2[i][e];
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
-        if (li == 0) { red[wave][i * 16 + kq * 4 + e][0] = (double)a; red[wave][i * 16 + kq * 4 + e][1] = (double)b; }
-      }
+    pw_lane_totals<CT>(s1, s2, red, wave, li, kq);
     __syncthreads();
     if (t < CT * 16) {
       gdouble* o = (gdouble*)p.slab + ((long)blockIdx.x * p.slab_ld + t) * 2;

@@ -70,6 +70,10 @@ __device__ unsigned int g_sepf_launch = 0, g_sepf_ticket = 0;
 #else
 #define SEPF_STAMP(i)
 #endif
+#ifndef ADDK_SEPF_TAIL_RS16
+#define ADDK_SEPF_TAIL_RS16 1     // 0 (with ADDK_SEPF_DIAG, scripts/sepf_phases.py): the statistics tail of before, to set its stamp beside this one's
+#endif
+constexpr bool SEPF_TAIL_RS16 = ADDK_SEPF_TAIL_RS16 != 0;
 
 template <int KS, int KG, int KP, int R>
 __device__ __forceinline__ void sepf_body(const SepfK& p, float* sm) {
@@ -385,31 +389,37 @@ __device__ __forceinline__ void sepf_body(const SepfK& p, float* sm) {
       for (int e = 0; e < 4; ++e) { const float f = get4(v, e); s1[i][e] += f; s2[i][e] = fmaf(f, f, s2[i][e]); }
     }
   }
+  SEPF_STAMP(5);
 #ifdef ADDK_SEPF_DIAG
-  if (t == 0) {
-    const unsigned long long diag_t5 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* d = g_sepf_diag[blockIdx.x & 63];
-    atomicAdd(&d[0], diag_t1 - diag_t0); atomicAdd(&d[1], diag_t23 - diag_t1); atomicAdd(&d[2], 0ull);
-    atomicAdd(&d[3], diag_t4 - diag_t23); atomicAdd(&d[4], diag_t5 - diag_t4); atomicAdd(&d[5], 1ull);
-    atomicMin(&g_sepf_span[0], diag_t0); atomicMax(&g_sepf_span[1], diag_t5);
-    const unsigned id = __hip_atomic_load(&g_sepf_launch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 63u;
-    atomicMin(&g_sepf_chain[id][0], diag_t0); atomicMax(&g_sepf_chain[id][1], diag_t0);
-    atomicMin(&g_sepf_chain[id][2], diag_t5); atomicMax(&g_sepf_chain[id][3], diag_t5);
-    __threadfence();
-    if (atomicAdd(&g_sepf_ticket, 1u) == (unsigned)p.gx - 1u) { g_sepf_ticket = 0; __threadfence(); atomicAdd(&g_sepf_launch, 1u); }
-  }
+  unsigned long long diag_tail = 0, diag_end = diag_t5;      // the statistics tail: from here to the slab row's store (training form only)
 #endif
-  if (p.slab) {            // butterfly over the 16 pixel lanes (fp64), the four waves through LDS, one slab row per workgroup
+  if (p.slab) {            // totals over the 16 pixel lanes (fp64, rs16: common.h), the four waves through LDS, one slab row per workgroup
     double (*rd)[CT * 16][2] = reinterpret_cast<double (*)[CT * 16][2]>(red);
+    if constexpr (SEPF_TAIL_RS16) {
+      constexpr int V = 2 * 4 * CT;                // value 4 CT which + 4 i + e: which = 0 the sum, 1 the sum of squares of channel 16 i + 4 kq + e
+      double sv[V];
 #pragma unroll
-    for (int i = 0; i < CT; ++i)
+      for (int i = 0; i < CT; ++i)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        double a = (double)s1[i][e], bsum = (double)s2[i][e];
+        for (int e = 0; e < 4; ++e) { sv[i * 4 + e] = (double)s1[i][e]; sv[4 * CT + i * 4 + e] = (double)s2[i][e]; }
+      double tot[Rs16<V>::NF];
+      rs16(sv, tot, li);
 #pragma unroll
-        for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m); bsum += __shfl_xor(bsum, m); }
-        if (li == 0) { rd[wave][i * 16 + kq * 4 + e][0] = a; rd[wave][i * 16 + kq * 4 + e][1] = bsum; }
+      for (int j = 0; j < Rs16<V>::NF; ++j) {
+        const int idx = rs16_index<V>(j, li);
+        if (idx >= 0) { const int which = idx >= 4 * CT, c4 = idx - which * (4 * CT); rd[wave][(c4 >> 2) * 16 + kq * 4 + (c4 & 3)][which] = tot[j]; }
       }
+    } else {                                       // the all-reduce butterfly by LDS permutes (diagnostic builds: the tail this one is measured against)
+#pragma unroll
+      for (int i = 0; i < CT; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          double a = (double)s1[i][e], bsum = (double)s2[i][e];
+#pragma unroll
+          for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m); bsum += __shfl_xor(bsum, m); }
+          if (li == 0) { rd[wave][i * 16 + kq * 4 + e][0] = a; rd[wave][i * 16 + kq * 4 + e][1] = bsum; }
+        }
+    }
     __syncthreads();
     const bool fused = p.fin.a != nullptr;
     if (t < CT * 16 && t < C) {
@@ -425,8 +435,25 @@ __device__ __forceinline__ void sepf_body(const SepfK& p, float* sm) {
         }
       }
     }
+    SEPF_STAMP(6);
+#ifdef ADDK_SEPF_DIAG
+    diag_tail = diag_t6 - diag_t5; diag_end = diag_t6;
+#endif
     if (fused) bn_finalize_by_last_block(p.fin, p.slab, p.slab_ld, C, blockIdx.x, (unsigned)p.gx, red);
   }
+#ifdef ADDK_SEPF_DIAG
+  if (t == 0) {                                    // after the tail: the record's own atomics lie outside every phase
+    unsigned long long* d = g_sepf_diag[blockIdx.x & 63];
+    atomicAdd(&d[0], diag_t1 - diag_t0); atomicAdd(&d[1], diag_t23 - diag_t1); atomicAdd(&d[2], 0ull);
+    atomicAdd(&d[3], diag_t4 - diag_t23); atomicAdd(&d[4], diag_t5 - diag_t4); atomicAdd(&d[5], 1ull); atomicAdd(&d[7], diag_tail);
+    atomicMin(&g_sepf_span[0], diag_t0); atomicMax(&g_sepf_span[1], diag_end);
+    const unsigned id = __hip_atomic_load(&g_sepf_launch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 63u;
+    atomicMin(&g_sepf_chain[id][0], diag_t0); atomicMax(&g_sepf_chain[id][1], diag_t0);
+    atomicMin(&g_sepf_chain[id][2], diag_end); atomicMax(&g_sepf_chain[id][3], diag_end);
+    __threadfence();
+    if (atomicAdd(&g_sepf_ticket, 1u) == (unsigned)p.gx - 1u) { g_sepf_ticket = 0; __threadfence(); atomicAdd(&g_sepf_launch, 1u); }
+  }
+#endif
 }
 
 template <int KS, int KG, int KP, int R>
@@ -500,7 +527,8 @@ int sepf_dispatch(const SepChoice& c, bool batch, dim3 grid, hipStream_t st, con
 
 #ifdef ADDK_SEPF_DIAG
 // out[0..4]: phase ticks (weights, patch loads + LDS stores, barrier, compute, epilogue issue) summed over workgroups, out[5]: workgroups,
-// out[6]: latest end - earliest start of all workgroups since the last call (10 ns ticks); resets
+// out[6]: latest end - earliest start of all workgroups since the last call (10 ns ticks), out[7]: ticks of the statistics tail (lane sums, LDS,
+// barrier, slab row) summed over workgroups; resets
 // the chain record: out[64][4] = (first start, last start, first end, last end) of the launches since the last call, 10 ns ticks; *n = launches; resets
 extern "C" int addk_sepf_chain(unsigned long long* out256, unsigned int* n) {
   unsigned long long h[64][4]; unsigned int z = 0;

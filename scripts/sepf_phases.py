@@ -3,7 +3,10 @@
 (-DADDK_SEPF_DIAG, built by scripts/sepf_phases.sh into /tmp) stamps s_memrealtime at the phase boundaries of every workgroup; this script
 runs single launches of the config-2 cell shapes (inference form with the block-sum epilogue, and the training form), reads the mean phase
 lengths and the in-kernel span (earliest workgroup start to latest end) and sets them against the launch's wall time (HIP events over a
-chain of dependent launches).   ADDK_LIB=/tmp/addk_diag/libaddk.so python scripts/sepf_phases.py"""
+chain of dependent launches).   ADDK_LIB=/tmp/addk_diag/libaddk.so python scripts/sepf_phases.py
+The training form's statistics tail has a stamp of its own (thread 0, from the last output store's issue to its slab row's store); a build with
+-DADDK_SEPF_TAIL_RS16=0 beside -DADDK_SEPF_DIAG runs the butterfly tail of before under the same stamps (profiles/fwd_tail_phases.txt).  The
+record's atomics inflate the diagnostic build's wall time: wall times are the product library's (scripts/fwd_tail_time.py)."""
 import ctypes as C
 import os
 import sys
@@ -79,6 +82,9 @@ def main():
                 ph = [out8[i] / n * 0.01 for i in range(5)]
                 line += ' | %d workgroups, in-kernel span %.1f us; mean per workgroup: weights %.2f  patch load+store %.2f  barrier %.2f  compute %.2f  epilogue issue %.2f us (sum %.2f)' % (
                     n, out8[6] * 0.01, ph[0], ph[1], ph[2], ph[3], ph[4], sum(ph))
+                if mode == 'train':
+                    # the statistics tail (lane totals, LDS, barrier, slab row): stamped behind the slab row's store, outside the sum above
+                    line += '  statistics tail %.2f us' % (out8[7] / n * 0.01)
             print(line, flush=True)
             chain = getattr(raw, 'addk_sepf_chain', None)
             if chain is not None:
