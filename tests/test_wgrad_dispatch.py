@@ -2,13 +2,16 @@
 wgrad_pix.hip, wgrad_h3.hip, wgrad_hk.hip and wgrad_rs.hip), no GPU: the library is called with aligned placeholder pointers (nothing is
 dereferenced before a launch).  For every shape x precision mode x fast-path mask: the launch key addk_conv_wgrad_config reports is the one a
 batch of that conv carries, and a workspace of exactly addk_conv_wgrad_ws floats passes the checked batch prepare.  The shapes of the GPU
-kernel tests get the kinds those tests assert, and every (case, mode) of the bit-for-bit fixture (tests/tools/make_wgrad_bits.py) its launch key."""
+kernel tests get the kinds those tests assert, and every (case, mode) of the bit-for-bit fixture (tests/tools/make_wgrad_bits.py) its launch key.
+The mixed batches of the fp64 test (tests/_wgrad_ref.BATCHES, tests/test_gpu_wgrad_fp64.py) get their keys member by member and as a whole, and a
+batch prepared for a split-precision kernel is refused, not launched, once the precision mode has changed."""
 import ctypes as C
 import importlib.util
 import os
 
 import pytest
 
+import _wgrad_ref as R
 import addk
 from addk import _lib as L
 
@@ -141,3 +144,73 @@ def test_bit_fixture_cases_get_their_launch_keys(lib):
     want |= {(m, 9, 8, 4) for m in ('f16x3', 'bf16x6')}
     want |= {(m, 7, t, k) for m in bits.MODES for t, k in ((3, 3), (3, 5), (5, 3))} | {(m, 6, la, lb) for m in bits.MODES for la in (3, 4) for lb in (3, 4)}
     assert want <= seen, sorted(want - seen)
+
+
+def _prepare(lib, ops):
+    """(meta, host blob) of a checked batch prepare of `ops` (tests/_wgrad_ref.Op) on placeholder pointers, exact workspaces"""
+    arr = (L.ConvWgradArgs * len(ops))(*[R.wgrad_args(L, op, PTR, lib.addk_conv_wgrad_ws(op.N * op.OH * op.OW, op.Cout, op.C, op.k * op.k)) for op in ops])
+    meta = (C.c_int64 * 8)()
+    size = lib.addk_conv_wgrad_batch_prepare(arr, len(ops), None, 0, meta)
+    assert size > 0, lib.addk_last_error()
+    blob = (C.c_uint8 * size)()
+    assert lib.addk_conv_wgrad_batch_prepare(arr, len(ops), blob, size, meta) == size, lib.addk_last_error()
+    return meta, blob
+
+
+@pytest.mark.parametrize('mode', list(MODES))
+def test_mixed_batches_of_the_fp64_test_get_their_keys(lib, mode):
+    """Every member of tests/_wgrad_ref.BATCHES, with the strides, source form and weight slice the GPU test gives it, gets its batch's key in
+    every mode (tail_x3: the split modes' key), and so does meta[:3] of a checked prepare of the whole batch with workspaces of exactly
+    addk_conv_wgrad_ws floats.  The h1 batch exists in the split modes only; in fp32 its members fall to other kernels."""
+    L.check(lib.addk_set_conv_precision(MODES[mode]), 'set_conv_precision')
+    assert len(R.BATCHES) == 18
+    for batch in R.BATCHES:
+        name, fast, keys, shapes = batch
+        key = keys.get('f16x3' if mode == 'tail_x3' else mode)
+        lib.addk_set_fast_paths(fast)
+        ops = R.batch_ops(batch)
+        assert [(op.form, op.accumulate) for op in ops] == [(i % 4, i % 2) for i in range(len(ops))]
+        got = [tuple(_config(lib, R.wgrad_args(L, op, PTR))[:3]) for op in ops]
+        if key is None:
+            assert name == 'h1' and mode == 'fp32' and all(g[0] != 9 for g in got), (name, mode, got)
+            continue
+        assert got == [key] * len(ops), (name, mode, got)
+        meta, _ = _prepare(lib, ops)
+        assert tuple(meta[:3]) == key and meta[3] == len(ops), (name, mode, list(meta))
+
+
+def test_batch_members_cover_what_the_table_promises(lib):
+    """The properties the batches are there for: mixed tap counts under the keys without taps, n >= 4, a kind-6 member with 9 pixel slices,
+    members without 16-byte loads, odd strides and slice offsets, and every source form and both accumulate flags among the members."""
+    by = {b[0]: R.batch_ops(b) for b in R.BATCHES}
+    for name in ('rs33', 'os1', 'os2', 'os3', 'pix33', 'pix21'):
+        assert len({op.k for op in by[name]}) > 1, name
+    assert all(len(by[name]) >= 4 for name in ('rs33', 'os2', 'pix33'))
+    op = by['rs33'][3]
+    P = op.N * op.OH * op.OW
+    assert -(-P // 2048) == 9
+    odd = [op for op in by['pix33'] if op.C % 4]
+    assert len(odd) == 2 and all(op.ld % 2 and op.w_choff % 2 and op.Cout % 4 for op in odd)
+    assert {(op.form, op.accumulate) for ops in by.values() for op in ops} == {(0, 0), (1, 1), (2, 0), (3, 1)}
+    assert any(op.ld > op.C and op.lddy > op.Cout for ops in by.values() for op in ops)
+    # the wave reduction (one block per 64 weights) and the block reduction (one per 256) in one batch: the reduce work list is longer than
+    # with the block form alone and shorter than with the wave form alone
+    lib.addk_set_fast_paths(31)
+    L.check(lib.addk_set_conv_precision(MODES['f16x3']), 'set_conv_precision')
+    for name in ('h3_41', 'h3_81', 'h3_8x', 'hk33', 'hk35', 'h1'):
+        ne = [op.Cout * op.k * op.k * op.C for op in by[name]]
+        meta, _ = _prepare(lib, by[name])
+        assert sum(-(-v // 256) for v in ne) < meta[7] < sum(-(-v // 64) for v in ne), (name, list(meta))
+
+
+@pytest.mark.parametrize('shape,key', [((1, 70, 130, 200, 128, 1, 1, 1), (9, 8, 4)), ((1, 40, 256, 32, 128, 3, 1, 1), (5, 8, 2))], ids=['h1', 'h3_ng2'])
+def test_batch_of_a_split_only_kernel_is_refused_after_a_mode_change(lib, shape, key):
+    """A batch prepared in f16x3 for a geometry only the split-precision kernels have is refused in fp32 before anything is launched or
+    dereferenced (wg_variant): the blob stays on the host and its pointers are placeholders."""
+    lib.addk_set_fast_paths(31)
+    L.check(lib.addk_set_conv_precision(MODES['f16x3']), 'set_conv_precision')
+    meta, blob = _prepare(lib, [R.make_op(shape, 1)])
+    assert tuple(meta[:3]) == key
+    L.check(lib.addk_set_conv_precision(MODES['fp32']), 'set_conv_precision')
+    rc = lib.addk_conv_wgrad_batch_run(C.cast(blob, C.c_void_p), meta, None)
+    assert rc == -1 and b'precision mode changed' in lib.addk_last_error(), (rc, lib.addk_last_error())
