@@ -20,6 +20,13 @@ enum ConvKind : int {
 };
 inline bool conv_kind_halo(int kind) { return kind >= CK_HALO; }
 
+// The kernel of a halo-kind launch.  Every unit that instantiates such kernels exposes them through plain lookup functions (conv3b.h: c3_variant_fp32,
+// c3b_variant_*, c3n_variant), so no kernel symbol crosses files; fn == nullptr: no such instantiation.  A lookup only takes addresses, it does not
+// touch the HIP runtime: raise_lds (null for a kernel with static LDS) lifts the kernel's dynamic-LDS limit and is called where the launch is.
+struct C3K;
+typedef void (*C3Fn)(const C3K);
+struct C3Variant { C3Fn fn; unsigned threads; void (*raise_lds)(); };
+
 struct ConvChoice {
   int kind;
   // template parameters, as cfg[1..4] reports them:
@@ -38,12 +45,13 @@ struct ConvChoice {
   int HT, spr, ntiles, nT; long wp_blk;
   int planes, bct, dil_odd, s2d, nchunks, pack_blocks;
   int64_t pack_floats;
+  C3Variant var;          // the kernel that kind and v[] name: a halo kind is only chosen when it exists
 };
 
 int conv_choose_fwd(const addk_conv_args* a, int mode, int mask, ConvChoice& c);
 int conv_choose_dgrad(const addk_conv_dgrad_args* a, int mode, int mask, ConvChoice& c);
 // pw.hip: STEM0, PW, PWK forward / PW, K1S data gradient; conv3.hip: the halo kinds (false: not covered, including a missing,
-// short or misaligned wpack)
+// short or misaligned wpack and a form that no unit instantiates)
 bool pw_choose_fwd(const addk_conv_args* a, ConvChoice& c);
 bool pw_choose_dgrad(const addk_conv_dgrad_args* a, ConvChoice& c);
 bool c3_choose_fwd(const addk_conv_args* a, int mode, int mask, ConvChoice& c);

@@ -55,38 +55,17 @@ struct ConvK {
 constexpr int BK = 32;
 constexpr int BKP = 36;
 
-// PREC_F32: exact fp32 products on v_mfma_f32_16x16x4_f32.
-// PREC_B3:  every fp32 operand x is split at LDS-staging time into bf16 hi = rn(x), lo = rn(x - hi) and a product is
-//           evaluated as hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (the dropped lo*lo term
-//           is <= 2^-16 relative): 3 bf16 MFMAs at 16x the fp32 matrix rate = 5.3x the exact path, error ~1e-5 relative
-//           per product, two orders below the 1e-3 parity bound.  Rows are 32 bf16 + 16 pad (96 B): ds_read_b128
-//           fragment reads of a 16-lane group then fall on 16 distinct 16-B slots of the 256-B bank row.
-enum { PREC_F32 = 0, PREC_B3 = 1 };
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-constexpr int RS = 48;      // bf16 elements per LDS row in the split path
-
-__device__ __forceinline__ void split4(float4 v, bf16x4& h, bf16x4& l) {
-  h[0] = (__bf16)v.x; h[1] = (__bf16)v.y; h[2] = (__bf16)v.z; h[3] = (__bf16)v.w;
-  l[0] = (__bf16)(v.x - (float)h[0]); l[1] = (__bf16)(v.y - (float)h[1]);
-  l[2] = (__bf16)(v.z - (float)h[2]); l[3] = (__bf16)(v.w - (float)h[3]);
-}
-
-template <int PT, int CT, int MODE, int PREC>
+// Exact fp32 products on v_mfma_f32_16x16x4_f32 in every arithmetic mode: the split-precision forms belong to the halo-patch kernels (conv3b.h).
+template <int PT, int CT, int MODE>
 __global__ void __launch_bounds__(256) conv_kernel(const ConvK p) {
   constexpr int BP = 64 * PT;
   constexpr int BC = 16 * CT;
   constexpr int NAJ = 2 * PT;             // float4 A slots per thread
   constexpr int NBJ = (CT + 1) / 2;       // float4 B slots per thread
-  // one LDS arena: fp32 path [BP+BC][36] floats; split path hi and lo panels of [BP+BC][48] bf16 (same bytes per row pair)
-  constexpr int LDS_BYTES = PREC == PREC_F32 ? (BP + BC) * BKP * 4 : (BP + BC) * RS * 2 * 2;
+  constexpr int LDS_BYTES = (BP + BC) * BKP * 4;      // [BP+BC][36] floats
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
   float* As = reinterpret_cast<float*>(lds_raw);
   float* Bs = As + BP * BKP;
-  __bf16* Ah = reinterpret_cast<__bf16*>(lds_raw);
-  __bf16* Al = Ah + BP * RS;
-  __bf16* Bh = Al + BP * RS;
-  __bf16* Bl = Bh + BC * RS;
   __shared__ double red[4][BC][2];
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -244,36 +223,6 @@ __global__ void __launch_bounds__(256) conv_kernel(const ConvK p) {
           }
         }
       }
-      if (PREC == PREC_B3) {
-#pragma unroll
-        for (int j = 0; j < NAJ; ++j) {
-          bf16x4 h, l; split4(ra[j], h, l);
-          *reinterpret_cast<bf16x4*>(&Ah[(ar + 32 * j) * RS + 4 * aq]) = h;
-          *reinterpret_cast<bf16x4*>(&Al[(ar + 32 * j) * RS + 4 * aq]) = l;
-        }
-        if (MODE == MODE_FWD) {
-#pragma unroll
-          for (int j = 0; j < NBJ; ++j) {
-            int slot = t + 256 * j, row = slot >> 3, q = slot & 7;
-            if (row < BC) {
-              bf16x4 h, l; split4(rb[j], h, l);
-              *reinterpret_cast<bf16x4*>(&Bh[row * RS + 4 * q]) = h;
-              *reinterpret_cast<bf16x4*>(&Bl[row * RS + 4 * q]) = l;
-            }
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < NBJ; ++j) {
-            int slot = t + 256 * j, k = slot / (4 * CT), ng = slot - k * (4 * CT);
-            if (k < BK) {
-              bf16x4 h, l; split4(rb[j], h, l);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) { Bh[(4 * ng + e) * RS + k] = h[e]; Bl[(4 * ng + e) * RS + k] = l[e]; }
-            }
-          }
-        }
-        return;
-      }
 #pragma unroll
       for (int j = 0; j < NAJ; ++j) lds_st4(&As[(ar + 32 * j) * BKP + 4 * aq], ra[j]);
       if (MODE == MODE_FWD) {
@@ -309,27 +258,6 @@ __global__ void __launch_bounds__(256) conv_kernel(const ConvK p) {
       const bool more = s2 < p.nsrc;
       if (more) load_chunk(s2, tap2, c2, ch2);
 
-      if (PREC == PREC_B3) {
-        bf16x8 wh[CT], wl[CT], xh[PT], xl[PT];
-#pragma unroll
-        for (int i = 0; i < CT; ++i) {
-          wh[i] = *reinterpret_cast<const bf16x8*>(&Bh[(i * 16 + li) * RS + 8 * kq]);
-          wl[i] = *reinterpret_cast<const bf16x8*>(&Bl[(i * 16 + li) * RS + 8 * kq]);
-        }
-#pragma unroll
-        for (int j = 0; j < PT; ++j) {
-          xh[j] = *reinterpret_cast<const bf16x8*>(&Ah[((wave * PT + j) * 16 + li) * RS + 8 * kq]);
-          xl[j] = *reinterpret_cast<const bf16x8*>(&Al[((wave * PT + j) * 16 + li) * RS + 8 * kq]);
-        }
-#pragma unroll
-        for (int i = 0; i < CT; ++i)
-#pragma unroll
-          for (int j = 0; j < PT; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[i], xh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], xl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[i], xh[j], acc[i][j], 0, 0, 0);
-          }
-      } else
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (u < nu) {
@@ -508,17 +436,31 @@ int launch(ConvK& k, int pt, int ct, int gx, hipStream_t st) {
   const int BP = 64 * pt;
   k.ntiles = cdiv(k.P, BP);
   for (int c = 0; c < k.ncls; ++c) k.cl[c].ntiles = cdiv(k.cl[c].P, BP);      // combined parity classes: k.P is the largest class
-  k.red32 = k.P >= 4096;
   dim3 grid(gx, cdiv(k.Cn, 16 * ct));      // workgroups beyond ntiles only write their (zero) slab row
 #define ADDK_CASE(PT_, CT_) \
   if (pt == PT_ && ct == CT_) { \
-    hipLaunchKernelGGL((conv_kernel<PT_, CT_, MODE, PREC_F32>), grid, dim3(256), 0, st, k); \
+    hipLaunchKernelGGL((conv_kernel<PT_, CT_, MODE>), grid, dim3(256), 0, st, k); \
     return addk_check_launch("conv"); }
   ADDK_CASE(1, 2) ADDK_CASE(1, 3) ADDK_CASE(1, 4) ADDK_CASE(1, 5) ADDK_CASE(1, 8)
   ADDK_CASE(2, 2) ADDK_CASE(2, 3) ADDK_CASE(2, 4) ADDK_CASE(2, 5) ADDK_CASE(2, 8)
 #undef ADDK_CASE
   addk_set_error("conv: no tile config");
   return ADDK_ERR_UNSUPPORTED;
+}
+
+// what a forward and a data gradient fill alike: kernel geometry, the weights, no parity classes, and the choice's pixel count and reduction width
+template <typename Args>
+void fill_shared(ConvK& k, const ConvChoice& c, const Args* a) {
+  k.KH = a->KH; k.KW = a->KW; k.stride = a->stride; k.pad = a->pad; k.dil = a->dil;
+  k.ldw = a->ldw; k.cin_total = a->cin_total; k.w_choff = a->w_choff; k.w = a->w;
+  k.sub = 1; k.ph = k.pw = 0; k.MH = k.MW = 0; k.ntaps_l = 0; k.kill = 0; k.ncls = 0;
+  k.P = c.P; k.red32 = c.v[2];
+}
+// a parity class of the choice into the kernel's class fields: ConvK's own (one launch per class) or one of its cl[] (all classes in one launch)
+template <typename Dst>
+void fill_class(Dst& d, const ConvChoice::Cls& q, double* slab) {
+  d.ph = q.ph; d.pw = q.pw; d.MH = q.MH; d.MW = q.MW; d.P = q.P; d.ntaps_l = q.ntaps; d.kill = q.kill; d.slab = slab;
+  for (int j = 0; j < 9; ++j) d.taplist[j] = q.taplist[j];
 }
 
 void choose_generic(ConvChoice& c, long P, int Cn) {
@@ -691,15 +633,13 @@ extern "C" int addk_conv_fwd(const addk_conv_args* a, void* stream) {
     if (!src_vec_ok(a->src[i])) k.vecA = 0;
     chan4 = chan4 && (a->src[i].C % 4 == 0);
   }
+  fill_shared(k, c, a);
   k.N = a->N; k.H = a->H; k.W = a->W; k.OH = a->OH; k.OW = a->OW;
-  k.KH = a->KH; k.KW = a->KW; k.stride = a->stride; k.pad = a->pad; k.dil = a->dil;
-  k.Cn = a->Cout; k.ldw = a->ldw; k.cin_total = a->cin_total; k.w_choff = a->w_choff; k.ldy = a->ldy;
-  k.w = a->w; k.y = a->y; k.bias = a->bias; k.bias_n = a->bias_n; k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
+  k.Cn = a->Cout; k.ldy = a->ldy;
+  k.y = a->y; k.bias = a->bias; k.bias_n = a->bias_n; k.slab = (double*)a->stats; k.slab_ld = a->stats_ld > 0 ? a->stats_ld : a->Cout;
   k.accumulate = 0; k.dst = addk_src{nullptr, nullptr, nullptr, 0, 0, 0, 0};
-  k.sub = 1; k.ph = k.pw = 0; k.MH = k.MW = 0; k.ntaps_l = 0; k.kill = 0; k.ncls = 0;
   k.vecB = aligned16(a->w) && a->ldw % 4 == 0 && a->cin_total % 4 == 0 && a->w_choff % 4 == 0 && chan4;
   k.vecY = aligned16(a->y) && a->ldy % 4 == 0;
-  k.P = c.P;
   return launch<MODE_FWD>(k, c.v[0], c.v[1], c.gx, st);
 }
 
@@ -713,36 +653,29 @@ extern "C" int addk_conv_dgrad(const addk_conv_dgrad_args* a, void* stream) {
   k.nsrc = 1;
   k.src[0] = addk_src{a->dy, nullptr, nullptr, a->lddy, a->Cout, 0, 0};
   k.vecA = src_vec_ok(k.src[0]);
+  fill_shared(k, c, a);
   k.N = a->N; k.H = a->OH; k.W = a->OW;      // A side = dy
   k.OH = a->H; k.OW = a->W;                  // M side = input pixels
-  k.KH = a->KH; k.KW = a->KW; k.stride = a->stride; k.pad = a->pad; k.dil = a->dil;
-  k.Cn = a->dst.C; k.ldw = a->ldw; k.cin_total = a->cin_total; k.w_choff = a->w_choff; k.ldy = a->ldg;
-  k.w = a->w; k.y = a->g; k.bias = nullptr; k.bias_n = nullptr; k.slab = (double*)a->dab; k.slab_ld = a->dst.C;
+  k.Cn = a->dst.C; k.ldy = a->ldg;
+  k.y = a->g; k.bias = nullptr; k.bias_n = nullptr; k.slab = (double*)a->dab; k.slab_ld = a->dst.C;
   k.dst = a->dst; k.accumulate = a->accumulate;
   k.vecB = aligned16(a->w) && a->ldw % 4 == 0 && a->cin_total % 4 == 0 && a->w_choff % 4 == 0 && a->dst.C % 4 == 0;
   k.vecY = aligned16(a->g) && a->ldg % 4 == 0 && src_vec_ok(a->dst);
-  k.sub = 1; k.ph = k.pw = 0; k.MH = k.MW = 0; k.ntaps_l = 0; k.kill = 0; k.ncls = 0;
-  k.P = c.P;
   if (c.kind == CK_GENERIC) return launch<MODE_DGRAD>(k, c.v[0], c.v[1], c.gx, st);
   k.sub = 2;
   auto slab_at = [&](int row) { return k.slab && row >= 0 ? k.slab + (long)row * k.slab_ld * 2 : nullptr; };
   if (c.launches == 1) {        // all classes in one launch: workgroups [gx0, gx0 + gx) run class i
     for (int i = 0; i < c.ncls; ++i) {
-      const ConvChoice::Cls& q = c.cls[i];
-      ConvK::Cls& d = k.cl[i];
-      d.ph = q.ph; d.pw = q.pw; d.MH = q.MH; d.MW = q.MW; d.P = q.P; d.ntaps_l = q.ntaps; d.kill = q.kill; d.pad_ = 0;
-      for (int j = 0; j < 9; ++j) d.taplist[j] = q.taplist[j];
-      d.slab = slab_at(q.slab_row); d.gx0 = q.gx0;
+      fill_class(k.cl[i], c.cls[i], slab_at(c.cls[i].slab_row));
+      k.cl[i].gx0 = c.cls[i].gx0; k.cl[i].pad_ = 0;
     }
     k.ncls = c.ncls;
     return launch<MODE_DGRAD>(k, c.v[0], c.v[1], c.gx, st);
   }
-  for (int i = 0; i < c.ncls; ++i) {
+  for (int i = 0; i < c.ncls; ++i) {      // (fewer than 16 slab rows = at most 480 pixels: every class is below the 4096 of red32, like the largest one the choice looked at)
     const ConvChoice::Cls& q = c.cls[i];
     ConvK s = k;
-    s.ph = q.ph; s.pw = q.pw; s.MH = q.MH; s.MW = q.MW; s.P = q.P; s.ntaps_l = q.ntaps; s.kill = q.kill;
-    for (int j = 0; j < 9; ++j) s.taplist[j] = q.taplist[j];
-    s.slab = slab_at(q.slab_row);
+    fill_class(s, q, slab_at(q.slab_row));
     if (const int rc = launch<MODE_DGRAD>(s, q.pt, q.ct, q.gx, st)) return rc;
   }
   return ADDK_OK;

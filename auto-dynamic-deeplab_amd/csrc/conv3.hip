@@ -15,7 +15,6 @@
 // Reference call sites: decoder.py:17-27 (3x3 conv+BN+ReLU x2), aspp_train.py:20-41 (dilated 3x3 branches),
 // ADD.py:220-232 (stem1); autograd of nn.Conv2d for the data gradient.
 #include "conv3b.h"
-#include "conv.h"
 
 namespace {
 
@@ -506,11 +505,11 @@ inline int c3_planes(int mode, int Cn) {
   return mode == 2 ? 3 : 2;
 }
 // Column block (16-channel tiles per block).  128-channel blocks (2x2 waves) for the wide heads when that still
-// yields >= 512 blocks; otherwise the narrowest of 3/4/5 tiles that pads the channel count least (cells: 40 -> 3 tiles,
-// 80 and 160 -> 5 tiles; stem / small ASPP maps: 4 tiles).
-int c3_bct(int Cn, long P) {
+// yields >= 512 blocks and the kernel has that form (the 3x3); otherwise the narrowest of 3/4/5 tiles that pads the channel count
+// least (cells: 40 -> 3 tiles, 80 and 160 -> 5 tiles; stem / small ASPP maps: 4 tiles).
+int c3_bct(int Cn, long P, int ks, int dir) {
   const long tiles = (P + C3_BP - 1) / C3_BP;
-  if (Cn >= 128 && Cn % 128 == 0 && tiles * (Cn / 128) >= 512) return 8;
+  if (Cn >= 128 && Cn % 128 == 0 && tiles * (Cn / 128) >= 512 && c3_variant_fp32(8, ks, dir).fn) return 8;
   int best = 4; long bc = -1;
   const int cands[3] = {5, 4, 3};
   for (int i = 0; i < 3; ++i) {
@@ -544,15 +543,16 @@ bool c3_geometry_ok(int mode, int mask, int KH, int KW, int stride, int pad, int
 }
 
 // Kind, tile walk, grid, LDS and weight-pack layout of a halo launch with Cn output channels over the N x H x W output map (data gradient: the
-// gradient map) whose K side is the chunks cvalid[0..nch) of <= 16 channels
-void c3_layout(ConvChoice& c, int mode, int dir, int Cn, int N, int H, int W, int taps, int dil, int st, int nch, const int* cvalid) {
+// gradient map) whose K side is the chunks cvalid[0..nch) of <= 16 channels, and the kernel itself.  false: no unit instantiates that form
+bool c3_layout(ConvChoice& c, int mode, int dir, int Cn, int N, int H, int W, int taps, int dil, int st, int nch, const int* cvalid) {
   const long P = (long)N * H * W;
   const int np = c3_planes(mode, Cn);
   const int ks = taps == 1 ? 1 : taps == 9 ? 3 : 5;
   const long trailer = np == 2 ? C3_TRAILER : 0;      // split-fp16: the scale trailer of the pack (PackK.amax)
   c.nchunks = nch; c.planes = np; c.dil_odd = 0; c.s2d = 0;
   if (!np) {                        // exact fp32: conv3_kernel, 128-pixel one-row tiles, 16 x bct columns per block
-    c.kind = CK_HALO; c.bct = c3_bct(Cn, P); c.v[0] = c.bct; c.v[1] = ks;
+    c.kind = CK_HALO; c.bct = c3_bct(Cn, P, ks, dir); c.v[0] = c.bct; c.v[1] = ks;
+    c.var = c3_variant_fp32(c.bct, ks, dir);
     c.nT = nch * taps; c.wp_blk = (long)nch * taps * c.bct * 256;
     c.spr = cdiv(W, C3_BP); c.HT = H; c.ntiles = N * H * c.spr;
     c.pack_floats = (long)cdiv(Cn, 16 * c.bct) * nch * taps * c.bct * 256;
@@ -562,6 +562,7 @@ void c3_layout(ConvChoice& c, int mode, int dir, int Cn, int N, int H, int W, in
     // stride-2 data gradient: every workgroup runs the four parity classes of the input pixel (1 / 2 / 2 / 4 taps) from one staged image of dy;
     // a tile is dy row a x 64 positions b (gradient rows 2a, 2a + 1 x 128 pixels)
     c.kind = CK_SPLIT_S2D; c.v[0] = np;
+    c.var = c3b_variant_s2d(np);
     c.bct = 2; c.s2d = 1;
     const long unit = (long)cdiv(Cn, 64) * nch * 2 * 64;       // 16-byte units per tap of the four class streams (c3b_pack_s2d_body)
     c.nT = 9 * nch; c.wp_blk = unit * np;
@@ -575,6 +576,7 @@ void c3_layout(ConvChoice& c, int mode, int dir, int Cn, int N, int H, int W, in
     // 40 channels, forward and data gradient).  The 3x3 stays on conv3b_kernel: 24.8 against 25.4-26.8 us at 2x125x253 — one workgroup per CU
     // leaves its 13 K-steps nothing to hide the staging behind.
     c.kind = CK_C3N; c.v[0] = ks; c.v[1] = np;
+    c.var = c3n_variant(ks, dir, np);
     c.bct = 3; c.dil_odd = dil & 1; c.s2d = 2;
     int steps = 0;
     for (int i = 0; i < nch; ++i) steps += c3n_steps(taps, cvalid[i]);
@@ -605,6 +607,10 @@ void c3_layout(ConvChoice& c, int mode, int dir, int Cn, int N, int H, int W, in
     const bool tworow = st == 1 && (ks == 3 || ks == 5) && !bigd && (bpx == C3_BP || (bpx == 64 && wc == 3)) && H >= 2 * dil;
     const int rpx = tworow ? bpx / 2 : bpx;                       // pixels per tile row
     c.v[0] = wc; c.v[1] = ks; c.v[2] = rpx; c.v[3] = tworow ? 2 : 1;
+    // the instantiations live in conv3b_tr3 / conv3b_tr5 / conv3b_row / conv3b_s2.hip (compiled in parallel)
+    c.var = tworow ? (ks == 3 ? c3b_variant_tr3(wc, rpx, dir, np) : c3b_variant_tr5(wc, rpx, dir, np))
+          : st == 2 ? c3b_variant_s2f(wc, rpx, np)          // (the forward: the stride-2 data gradient is CK_SPLIT_S2D)
+          : c3b_variant_row(wc, ks, bigd, rpx, dir, np);
     c.HT = tworow ? cdiv(H, 2 * dil) * dil : H;
     c.spr = cdiv(W, rpx); c.ntiles = N * c.HT * c.spr;
     c.pack_floats = (long)cdiv(Cn, 32 * wc) * nch * taps * wc * np * 256 + trailer;      // 1 KB per (tap, 32-row tile, plane)
@@ -614,6 +620,7 @@ void c3_layout(ConvChoice& c, int mode, int dir, int Cn, int N, int H, int W, in
     c.lds = (size_t)((ph * 32 * wc * 16 + 15) & ~15) + (size_t)np * (tworow ? ks + 1 : ks) * cb_pwmax(ks, bigd, rpx, st) * 32;
   }
   if (c.pack_blocks > 4096) c.pack_blocks = 4096;
+  return c.var.fn != nullptr;
 }
 
 inline bool c3_pack_fits(const float* wpack, int64_t floats, int64_t need) { return wpack && aligned16(wpack) && floats >= need; }
@@ -632,7 +639,7 @@ bool c3_choose_fwd(const addk_conv_args* a, int mode, int mask, ConvChoice& c) {
   }
   if (a->ldy % 4 || !aligned16(a->y)) return false;
   ConvChoice h = c;
-  c3_layout(h, mode, MODE_FWD, a->Cout, a->N, a->OH, a->OW, a->KH * a->KW, a->dil, a->stride, nch, cvalid);
+  if (!c3_layout(h, mode, MODE_FWD, a->Cout, a->N, a->OH, a->OW, a->KH * a->KW, a->dil, a->stride, nch, cvalid)) return false;
   if (!c3_pack_fits(a->wpack, a->wpack_floats, h.pack_floats)) return false;
   c = h;
   return true;
@@ -646,7 +653,7 @@ bool c3_choose_dgrad(const addk_conv_dgrad_args* a, int mode, int mask, ConvChoi
     cvalid[nch++] = a->Cout - c0 < C3_BK ? a->Cout - c0 : C3_BK;
   }
   ConvChoice h = c;
-  c3_layout(h, mode, MODE_DGRAD, a->dst.C, a->N, a->H, a->W, a->KH * a->KW, a->dil, a->stride, nch, cvalid);
+  if (!c3_layout(h, mode, MODE_DGRAD, a->dst.C, a->N, a->H, a->W, a->KH * a->KW, a->dil, a->stride, nch, cvalid)) return false;
   if (!c3_pack_fits(a->wpack, a->wpack_floats, h.pack_floats)) return false;
   c = h;
   return true;
@@ -683,7 +690,7 @@ void c3_pack_fill_dgrad(const ConvChoice& c, const addk_conv_dgrad_args* a, Pack
 }
 
 // the pack (unless a plan's addk_conv_pack_batch already wrote it), then the convolution; k holds the launch's tensors
-int c3_run(const ConvChoice& c, C3K& k, const PackK& pk, int dir, bool packed, hipStream_t st) {
+int c3_run(const ConvChoice& c, C3K& k, const PackK& pk, bool packed, hipStream_t st) {
   k.wp = pk.out; k.wsc = pk.amax ? pk.amax + C3_AMAX_WG : nullptr;
   k.nT = c.nT; k.wp_blk = c.wp_blk; k.HT = c.HT; k.spr = c.spr; k.ntiles = c.ntiles; k.slab_rows = c.rows;
   k.red32 = c.kind == CK_HALO ? k.P >= 4096 : 1;
@@ -692,39 +699,23 @@ int c3_run(const ConvChoice& c, C3K& k, const PackK& pk, int dir, bool packed, h
     if (pk.planes == 2) hipLaunchKernelGGL(c3_pack_amax_kernel, dim3(C3_AMAX_WG), dim3(256), 0, st, pk);
     hipLaunchKernelGGL(c3_pack_kernel, dim3(c.pack_blocks), dim3(256), 0, st, pk);
   }
-  const dim3 grid(c.gx, c.gy);
-  const int np = c.planes;
-  if (c.kind == CK_SPLIT_S2D) {
-    if (!c3b_run_s2d(&k, np, grid, c.lds, st)) { addk_set_error("conv3b stride-2 data gradient: no instantiation"); return ADDK_ERR_UNSUPPORTED; }
-    return addk_check_launch("conv3b stride-2 data gradient");
-  }
-  if (c.kind == CK_C3N) {
-    if (!c3n_run(&k, c.v[0], dir, np, grid, c.lds, st)) { addk_set_error("conv3n: no instantiation for %d taps", c.v[0] * c.v[0]); return ADDK_ERR_UNSUPPORTED; }
-    return addk_check_launch("conv3n");
-  }
-  if (c.kind == CK_SPLIT) {
-    // the instantiations live in conv3b_tr3 / conv3b_tr5 / conv3b_row / conv3b_s2.hip (compiled in parallel)
-    const int wc = c.v[0], ks = c.v[1], rpx = c.v[2];
-    const bool bigd = ks == 3 && k.dil > 2;
-    const bool done = c.v[3] == 2 ? (ks == 3 ? c3b_run_tr3(&k, wc, rpx, dir, np, grid, c.lds, st) : c3b_run_tr5(&k, wc, rpx, dir, np, grid, c.lds, st)) != 0
-                    : k.st == 2 ? (ks == 3 && dir == MODE_FWD && c3b_run_s2f(&k, wc, rpx, np, grid, c.lds, st) != 0)
-                    : c3b_run_row(&k, wc, ks, bigd, rpx, dir, np, grid, c.lds, st) != 0;
-    if (!done) { addk_set_error("conv3b: no instantiation for %d waves, %d taps", wc, ks * ks); return ADDK_ERR_UNSUPPORTED; }
-    return addk_check_launch("conv3b");
-  }
-  const int bct = c.v[0], ks = c.v[1];
-#define ADDK_C3(B_, K_) \
-  if (bct == B_ && ks == K_) { \
-    if (dir == MODE_FWD) hipLaunchKernelGGL((conv3_kernel<B_, K_, MODE_FWD>), grid, dim3(256), 0, st, k); \
-    else hipLaunchKernelGGL((conv3_kernel<B_, K_, MODE_DGRAD>), grid, dim3(256), 0, st, k); \
-    return addk_check_launch("conv3"); }
-  ADDK_C3(3, 3) ADDK_C3(4, 3) ADDK_C3(5, 3) ADDK_C3(8, 3) ADDK_C3(3, 5) ADDK_C3(4, 5) ADDK_C3(5, 5)
-#undef ADDK_C3
-  addk_set_error("conv3: no instantiation for %d column tiles, %d taps", bct, ks * ks);
-  return ADDK_ERR_UNSUPPORTED;
+  if (c.var.raise_lds) c.var.raise_lds();
+  hipLaunchKernelGGL(c.var.fn, dim3(c.gx, c.gy), dim3(c.var.threads), c.lds, st, k);      // (c.lds: 0 for conv3_kernel, whose LDS is static)
+  return addk_check_launch(c.kind == CK_HALO ? "conv3" : c.kind == CK_C3N ? "conv3n" : c.kind == CK_SPLIT_S2D ? "conv3b stride-2 data gradient" : "conv3b");
+}
+
+template <int BCT, int KS> C3Variant c3_fp32_pair(int mode) {
+  return mode == MODE_FWD ? c3_static_variant<conv3_kernel<BCT, KS, MODE_FWD>>(256) : c3_static_variant<conv3_kernel<BCT, KS, MODE_DGRAD>>(256);
 }
 
 }  // namespace
+
+C3Variant c3_variant_fp32(int bct, int ks, int mode) {
+  if (mode != MODE_FWD && mode != MODE_DGRAD) return {};
+  if (ks == 3) return bct == 3 ? c3_fp32_pair<3, 3>(mode) : bct == 4 ? c3_fp32_pair<4, 3>(mode) : bct == 5 ? c3_fp32_pair<5, 3>(mode) : bct == 8 ? c3_fp32_pair<8, 3>(mode) : C3Variant{};
+  if (ks == 5) return bct == 3 ? c3_fp32_pair<3, 5>(mode) : bct == 4 ? c3_fp32_pair<4, 5>(mode) : bct == 5 ? c3_fp32_pair<5, 5>(mode) : C3Variant{};      // (no 128-channel block: c3_bct)
+  return {};
+}
 
 int c3_run_fwd(const ConvChoice& c, const addk_conv_args* a, hipStream_t st) {
   C3K k; PackK pk;
@@ -738,7 +729,7 @@ int c3_run_fwd(const ConvChoice& c, const addk_conv_args* a, hipStream_t st) {
   k.dst = addk_src{nullptr, nullptr, nullptr, 0, 0, 0, 0}; k.accumulate = 0;
   k.vecY = 1;
   k.P = (long)a->N * a->OH * a->OW;
-  return c3_run(c, k, pk, MODE_FWD, a->wpack_ready != 0, st);
+  return c3_run(c, k, pk, a->wpack_ready != 0, st);
 }
 int c3_run_dgrad(const ConvChoice& c, const addk_conv_dgrad_args* a, hipStream_t st) {
   C3K k; PackK pk;
@@ -752,7 +743,7 @@ int c3_run_dgrad(const ConvChoice& c, const addk_conv_dgrad_args* a, hipStream_t
   k.dst = a->dst; k.accumulate = a->accumulate;
   k.vecY = 1;
   k.P = (long)a->N * a->H * a->W;
-  return c3_run(c, k, pk, MODE_DGRAD, a->wpack_ready != 0, st);
+  return c3_run(c, k, pk, a->wpack_ready != 0, st);
 }
 
 // Floats of `wpack` the launch's halo-patch kernel needs: the choice the launch would make with a large enough workspace.  0 = it takes another kernel.

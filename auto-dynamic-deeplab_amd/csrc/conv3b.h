@@ -1,21 +1,15 @@
-// conv3b.h — the split-bf16 halo-patch convolution kernel template (conv3b_body / conv3b_kernel) shared by the translation units
-// that instantiate it: conv3b_tr3.hip (two-row 3x3 tiles), conv3b_tr5.hip (two-row 5x5), conv3b_row.hip (one-row tiles: wide dilations, half / quarter
-// widths, the pointwise GEMM form) and conv3b_s2.hip (stride 2: stem2 forward and data gradient).  One file used to hold all ~140 instantiations and took
-// three minutes to compile; host logic, weight packing and the fp32 halo kernel stay in conv3.hip.  Everything here has internal linkage.
+// conv3b.h — the split-precision halo-patch convolution kernel template (conv3b_body / conv3b_kernel) shared by the translation units that instantiate it:
+// conv3b_tr3.hip (two-row 3x3 tiles), conv3b_tr5.hip (two-row 5x5), conv3b_row.hip (one-row tiles: wide dilations, half / quarter widths, the
+// pointwise GEMM form) and conv3b_s2.hip (stride 2: stem2 forward, and conv3s_kernel for its data gradient).  One file used to hold all ~140
+// instantiations and took three minutes to compile.  Each unit hands its instantiations out through a lookup function (declared at the end of this
+// file); the choice of a launch (conv3.hip c3_layout), weight packing and the fp32 halo kernel stay in conv3.hip.  The kernels have internal linkage.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
 #include <stdio.h>
-#include "common.h"
+#include "conv.h"
 
-namespace {
-
-enum { MODE_FWD = 0, MODE_DGRAD = 1 };
-constexpr int C3_BP = 128;                 // pixels per tile (one row segment)
-constexpr int C3_BK = 16;                  // channels per chunk
-constexpr int CN_BPX = 128;                 // conv3n_kernel: pixels per tile row
-constexpr int cn_pwp(int ks) { return CN_BPX + (ks - 1) * 2; }       // conv3n_kernel: LDS row pitch in pixels (dilation <= 2)
-
+// the argument of every halo-patch kernel: one type across the units, so that a kernel's pointer means the same in each (C3Fn, conv.h)
 struct C3K {
   addk_src src[ADDK_MAX_SRC];
   int nsrc;
@@ -37,6 +31,14 @@ struct C3K {
   int st;                   // stride (host-side dispatch; 2 = the de-interleaved 3x3 forward of conv3b_kernel)
   int om, oro, oco, OHo, OWo;   // output pixel of tile-grid position (oh, ow): (om oh + oro, om ow + oco) in an OHo x OWo map (om = 1: the grid itself)
 };
+
+namespace {
+
+enum { MODE_FWD = 0, MODE_DGRAD = 1 };
+constexpr int C3_BP = 128;                 // pixels per tile (one row segment)
+constexpr int C3_BK = 16;                  // channels per chunk
+constexpr int CN_BPX = 128;                 // conv3n_kernel: pixels per tile row
+constexpr int cn_pwp(int ks) { return CN_BPX + (ks - 1) * 2; }       // conv3n_kernel: LDS row pitch in pixels (dilation <= 2)
 
 // ======================================================================================================================
 // Split-bf16 form of the same halo-patch convolution: every fp32 operand is written as x = h + m + l with h, m, l in bf16
@@ -61,7 +63,7 @@ struct C3K {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int CB_PT = 4;                   // 32-pixel tiles per wave (128 pixels)
-constexpr int cb_pwmax(int ks, bool bigd, int bpx = C3_BP, int st = 1) { return st == 2 ? 2 * bpx + 16 : ks > 10 ? bpx + 4 : ks == 1 ? bpx : ks == 3 ? (bigd ? bpx + 2 * 18 : bpx + 2 * 2) : bpx + 4 * 2; }
+constexpr int cb_pwmax(int ks, bool bigd, int bpx = C3_BP, int st = 1) { return st == 2 ? 2 * bpx + 16 : ks == 1 ? bpx : ks == 3 ? (bigd ? bpx + 2 * 18 : bpx + 2 * 2) : bpx + 4 * 2; }
 
 __device__ __forceinline__ unsigned bf16_hi(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x); }
 __device__ __forceinline__ float bf16_f(unsigned b) { return __uint_as_float(b << 16); }
@@ -145,15 +147,12 @@ __device__ __forceinline__ void conv3b_body(const C3K& p, const int bx, const in
   unsigned long long dph[6] = {0, 0, 0, 0, 0, 0};
 #endif
   static_assert(ST == 1 || (ST == 2 && KS == 3 && !BIGD && MODE == MODE_FWD), "stride 2: 3x3 forward only");
-  // KS = 12 / 21 / 22: a 1x2 / 2x1 / 2x2 tap set anchored at its first tap (no centring) — the parity classes of the stride-2 data
-  // gradient (c3b_s2_dgrad below); 1, 3, 5: the centred square kernels
-  constexpr int KH_ = KS > 10 ? KS / 10 : KS, KW_ = KS > 10 ? KS % 10 : KS;
-  static_assert(KS < 10 || (MODE == MODE_DGRAD && !BIGD && ST == 1), "anchored tap sets: data gradient only");
+  static_assert(KS == 1 || KS == 3 || KS == 5, "the centred square kernels");
   constexpr int OB = BPX + 16;                                      // ST = 2: LDS position of the first odd patch column
-  static_assert(TR == 1 || (TR == 2 && (KS == 3 || KS == 5) && !BIGD && ST == 1), "two-row tiles: centred kernels at dilation 1");
+  static_assert(TR == 1 || (TR == 2 && (KS == 3 || KS == 5) && !BIGD && ST == 1), "two-row tiles: 3x3 / 5x5 at dilation <= 2");
   constexpr int BC = 32 * WC, NTHR = 64 * WC * PH, PT = TR * BPX / 32 / PH, TPR = BPX / 32;      // TPR: 32-pixel tiles per tile row
-  constexpr int PR_ = (KS > 10 ? KS / 10 : KS) + TR - 1;                                          // patch rows
-  constexpr int TAPS = KH_ * KW_, HK = KS > 10 ? 0 : KS / 2;
+  constexpr int PR_ = KS + TR - 1;                                                                // patch rows
+  constexpr int TAPS = KS * KS, HK = KS / 2;
   constexpr int PWP = cb_pwmax(KS, BIGD, BPX, ST);                         // LDS row pitch in pixels (compile time: tap offsets are immediates)
   constexpr int NS = (PR_ * PWP * 4 + NTHR - 1) / NTHR;           // 16-byte (4-channel) patch slots per thread, enumerated over the pitch grid
   static_assert(NS <= 32, "slot mask is 32 bits");
@@ -177,19 +176,19 @@ __device__ __forceinline__ void conv3b_body(const C3K& p, const int bx, const in
   auto slot_geo = [&](int k, int& r, int& sp, int& pj, bool& live) {
     const int pix = (t + NTHR * k) >> 2;
     r = pix / PWP; sp = pix - r * PWP;
-    if (ST == 1) { pj = sp; live = r < PR_ && pj < BPX + (KW_ - 1) * p.dil; }
-    else { const bool odd = sp >= OB; const int idx = odd ? sp - OB : sp; pj = 2 * idx + (odd ? 1 : 0); live = r < KH_ && (odd ? idx < BPX : idx <= BPX); }
+    if (ST == 1) { pj = sp; live = r < PR_ && pj < BPX + (KS - 1) * p.dil; }
+    else { const bool odd = sp >= OB; const int idx = odd ? sp - OB : sp; pj = 2 * idx + (odd ? 1 : 0); live = r < KS && (odd ? idx < BPX : idx <= BPX); }
   };
   // fragment read base per kernel column: pixel lane%32 + kw*d of patch row 0, the 16-byte half swizzled by bit 3 of the pixel
   // (tile j adds 32 pixels: bit 3 unchanged); patch row kh and tile j are immediate offsets
-  int xb[KW_];
+  int xb[KS];
   // 32-pixel tile j of this wave: tile row wrow + jrow(j), column tile wcol + jcol(j) (4-wave blocks of <= 64 channels split the tiles over two wave pairs:
   // by rows when the tile has two, else by columns)
   const int wrow = (PH == 2 && TR == 2) ? wpx : 0, wcol = (PH == 2 && TR == 1) ? wpx * PT : 0;
   auto jrow = [](int j) { return PH == 1 ? j / TPR : 0; };
   auto jcol = [](int j) { return PH == 1 ? j % TPR : j; };
 #pragma unroll
-  for (int kw = 0; kw < KW_; ++kw) {
+  for (int kw = 0; kw < KS; ++kw) {
     const int pj = ST == 2 ? (kw == 1 ? OB + lp32 : lp32 + (kw >> 1)) : lp32 + kw * d;
     xb[kw] = pj * 2 + (hh ^ ((pj >> 3) & 1)) + (wrow * PWP + wcol * 32) * 2;
   }
@@ -233,7 +232,7 @@ __device__ __forceinline__ void conv3b_body(const C3K& p, const int bx, const in
     // inherits its error from): the running sums are flushed into a second accumulator set after every 16-channel chunk, so a
     // rounding error grows with sqrt(MFMAs per chunk) + sqrt(chunks) instead of sqrt(all MFMAs) (stem1: 54 + 4 instead of 216) —
     // what a CPU library's blocked partial sums do (the even-size gradient deficit starts at stem1's K = 576 chain).
-    constexpr bool BLK = PH == 2 && (KS == 3 || KS > 10) && !BIGD;          // (the 5x5 and wide-dilation variants have no registers left: 256 + scratch with a second set)
+    constexpr bool BLK = PH == 2 && KS == 3 && !BIGD;          // (the 5x5 and wide-dilation variants have no registers left: 256 + scratch with a second set)
     f32x16 acc2[BLK ? PT : 1];
     if (BLK) {
 #pragma unroll
@@ -342,7 +341,7 @@ __device__ __forceinline__ void conv3b_body(const C3K& p, const int bx, const in
     };
     // pixel fragment of (tap, tile j): lane reads 16 bytes of pixel (32 j + lane%32 + kw*d) in patch row kh, k half lane/32
     auto read_x = [&](int tap, int j, uint4* x) {
-      const int kh = tap / KW_, kw = tap - kh * KW_;
+      const int kh = tap / KS, kw = tap - kh * KS;
       const uint4* b = Pl + xb[kw];
 #pragma unroll
       for (int m = 0; m < NP; ++m) x[m] = b[m * PLANE + ((kh + jrow(j)) * PWP + jcol(j) * 32) * 2];        // the wave's own tile row / first column tile sit in xb[]
@@ -584,6 +583,9 @@ __device__ __forceinline__ void conv3b_body(const C3K& p, const int bx, const in
   }
 }
 
+// The kernel is the workgroup's place in the grid plus conv3b_body, which stays a function of its own: the compiler optimises it before it inlines it, and
+// written into the kernel the same statements come out with other registers and another schedule in all 90 instantiations (138 against 139 VGPRs in
+// <3, 3, fwd, 2, false, 1, 32>): the same work, but not the instructions that were measured.
 template <int WC, int KS, int MODE, int NP, bool BIGD, int PH = 1, int BPX = C3_BP, int ST = 1, int TR = 1>
 __global__ void __launch_bounds__(64 * WC * PH, 2) conv3b_kernel(const C3K p) {
   // [r5] one-dimensional grid of (tile workgroups) x (channel blocks) with the channel blocks of a tile NEXT to each other on ONE XCD: workgroups are dealt
@@ -596,15 +598,43 @@ __global__ void __launch_bounds__(64 * WC * PH, 2) conv3b_kernel(const C3K p) {
   else { by = lin % ny; bx = lin / ny; }
   conv3b_body<WC, KS, MODE, NP, BIGD, PH, BPX, ST, TR>(p, bx, gx, by);
 }
+
+// one instantiation as the variant of a lookup: a kernel with dynamic LDS / with static LDS
+template <C3Fn F> void c3_raise_lds() { addk_dyn_lds<F>(); }
+template <C3Fn F> C3Variant c3_dyn_variant(unsigned threads) { return {F, threads, c3_raise_lds<F>}; }
+template <C3Fn F> C3Variant c3_static_variant(unsigned threads) { return {F, threads, nullptr}; }
+// the four (direction, planes) instantiations of one stride-1 tile form of conv3b_kernel; <= 64 channels (WC = 2): the 4-wave form with two pixel halves
+template <int WC, int KS, bool BIGD, int BPX, int TR>
+C3Variant c3b_tile_variant(int mode, int np) {
+  constexpr int PH = WC == 2 ? 2 : 1;
+  constexpr unsigned T = 64 * WC * PH;
+  if (mode == MODE_FWD && np == 3) return c3_dyn_variant<conv3b_kernel<WC, KS, MODE_FWD, 3, BIGD, PH, BPX, 1, TR>>(T);
+  if (mode == MODE_FWD && np == 2) return c3_dyn_variant<conv3b_kernel<WC, KS, MODE_FWD, 2, BIGD, PH, BPX, 1, TR>>(T);
+  if (mode == MODE_DGRAD && np == 3) return c3_dyn_variant<conv3b_kernel<WC, KS, MODE_DGRAD, 3, BIGD, PH, BPX, 1, TR>>(T);
+  if (mode == MODE_DGRAD && np == 2) return c3_dyn_variant<conv3b_kernel<WC, KS, MODE_DGRAD, 2, BIGD, PH, BPX, 1, TR>>(T);
+  return {};
+}
 }  // namespace
 
-// dispatch entry points of the instantiating translation units: 1 = launched, 0 = no instantiation for this shape
-int c3b_run_tr3(const void* k, int wc, int rpx, int mode, int np, dim3 grid, size_t lds, hipStream_t st);
-int c3b_run_tr5(const void* k, int wc, int rpx, int mode, int np, dim3 grid, size_t lds, hipStream_t st);
-int c3b_run_row(const void* k, int wc, int ks, bool bigd, int bpx, int mode, int np, dim3 grid, size_t lds, hipStream_t st);
-int c3b_run_s2f(const void* k, int wc, int bpx, int np, dim3 grid, size_t lds, hipStream_t st);
-int c3b_run_s2d(const void* k4, int np, dim3 grid, size_t lds, hipStream_t st);
-int c3n_run(const void* k, int ks, int mode, int np, dim3 grid, size_t lds, hipStream_t st);      // conv3n.hip: the <= 48-channel 5x5 launches on 16-wide tiles
+// The lookups of the instantiating units, keyed by the template values c3_layout computes (mode: MODE_FWD / MODE_DGRAD; np: planes).  C linkage:
+// tests/test_conv_variants.py walks them to compare what is instantiated with what the choice reaches.
+extern "C" {
+C3Variant c3_variant_fp32(int bct, int ks, int mode);                               // conv3.hip: conv3_kernel<bct, ks, mode>
+C3Variant c3b_variant_tr3(int wc, int rpx, int mode, int np);                       // conv3b_tr3.hip: two-row 3x3 tiles of 2 x rpx pixels
+C3Variant c3b_variant_tr5(int wc, int rpx, int mode, int np);                       // conv3b_tr5.hip: two-row 5x5 tiles
+C3Variant c3b_variant_row(int wc, int ks, int bigd, int bpx, int mode, int np);     // conv3b_row.hip: one-row tiles of bpx pixels
+C3Variant c3b_variant_s2f(int wc, int bpx, int np);                                 // conv3b_s2.hip: the stride-2 3x3 forward
+C3Variant c3b_variant_s2d(int np);                                                  //   conv3s_kernel<np>
+C3Variant c3n_variant(int ks, int mode, int np);                                    // conv3n.hip: conv3n_kernel<ks, mode, np>
+}
 #ifdef ADDK_C3B_DIAG
 void c3b_diag_tr3(unsigned long long* acc12); void c3b_diag_tr5(unsigned long long* acc12); void c3b_diag_row(unsigned long long* acc12); void c3b_diag_s2(unsigned long long* acc12);
+// every instantiating unit has its own copy of g_c3b_diag: its reader adds the counters to acc12 and clears them
+#define C3B_DIAG_READER(NAME) void NAME(unsigned long long* acc12) { \
+    unsigned long long h[64][12]; \
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_c3b_diag), sizeof h) != hipSuccess) { (void)hipGetLastError(); return; } \
+    for (int q = 0; q < 12; ++q) for (int i = 0; i < 64; ++i) acc12[q] += h[i][q]; \
+    memset(h, 0, sizeof h); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_c3b_diag), h, sizeof h); }
+#else
+#define C3B_DIAG_READER(NAME)
 #endif

@@ -1,25 +1,12 @@
-// conv3b_s2.hip — the stride-2 instantiations of conv3b_kernel (conv3b.h; launch logic: conv3.hip): stem2's 3x3 stride-2 forward on de-interleaved patch rows and
-// its data gradient: four input-pixel parity classes computed from ONE staged image of the two dy rows they share (conv3s_kernel).
+// conv3b_s2.hip — the stride-2 instantiations of conv3b_kernel (conv3b.h; chosen by conv3.hip c3_layout): stem2's 3x3 stride-2 forward on de-interleaved patch
+// rows and its data gradient: four input-pixel parity classes computed from ONE staged image of the two dy rows they share (conv3s_kernel).
 #include "conv3b.h"
 
-#define C3B_GO(KERNEL, THREADS) { \
-    addk_dyn_lds<KERNEL>(); \
-    hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), lds, st, k); return 1; }
-#ifdef ADDK_C3B_DIAG
-#define C3B_DIAG_READER(NAME) void NAME(unsigned long long* acc12) { \
-    unsigned long long h[64][12]; \
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_c3b_diag), sizeof h) != hipSuccess) { (void)hipGetLastError(); return; } \
-    for (int q = 0; q < 12; ++q) for (int i = 0; i < 64; ++i) acc12[q] += h[i][q]; \
-    memset(h, 0, sizeof h); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_c3b_diag), h, sizeof h); }
-#else
-#define C3B_DIAG_READER(NAME)
-#endif
-
-int c3b_run_s2f(const void* kp, int wc, int bpx, int np, dim3 grid, size_t lds, hipStream_t st) {
-  const C3K& k = *reinterpret_cast<const C3K*>(kp);
-  if (wc != 4) return 0;
-  if (bpx == 64) { if (np == 3) C3B_GO((conv3b_kernel<4, 3, MODE_FWD, 3, false, 1, 64, 2>), 256) else C3B_GO((conv3b_kernel<4, 3, MODE_FWD, 2, false, 1, 64, 2>), 256) }
-  return 0;
+C3Variant c3b_variant_s2f(int wc, int bpx, int np) {
+  if (wc != 4 || bpx != 64) return {};
+  if (np == 3) return c3_dyn_variant<conv3b_kernel<4, 3, MODE_FWD, 3, false, 1, 64, 2>>(256);
+  if (np == 2) return c3_dyn_variant<conv3b_kernel<4, 3, MODE_FWD, 2, false, 1, 64, 2>>(256);
+  return {};
 }
 // ---- [r5] the stride-2 data gradient with ONE staging for its four parity classes ------------------------------------------------------------------
 // Input pixel (2a + pi, 2b + pj) of the 3x3 / stride 2 / pad 1 convolution collects dy(a + th, b + tw) W[kh][kw] over th <= pi, tw <= pj (kh = 1 for pi = 0,
@@ -293,8 +280,9 @@ __global__ void __launch_bounds__(256, 2) conv3s_kernel(const C3K p) {
   }
 }
 
-int c3b_run_s2d(const void* kp, int np, dim3 grid, size_t lds, hipStream_t st) {
-  const C3K& k = *reinterpret_cast<const C3K*>(kp);
-  if (np == 3) C3B_GO(conv3s_kernel<3>, 256) else C3B_GO(conv3s_kernel<2>, 256)
+C3Variant c3b_variant_s2d(int np) {
+  if (np == 3) return c3_dyn_variant<conv3s_kernel<3>>(256);
+  if (np == 2) return c3_dyn_variant<conv3s_kernel<2>>(256);
+  return {};
 }
 C3B_DIAG_READER(c3b_diag_s2)

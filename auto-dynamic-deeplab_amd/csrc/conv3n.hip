@@ -397,14 +397,12 @@ __global__ void __launch_bounds__(256, 1) conv3n_kernel(const C3K p) {
 
 }  // namespace
 
-// 1 = launched, 0 = no instantiation; grid.x workgroups walk p.ntiles tiles of 2 rows x 128 pixels
-int c3n_run(const void* kp, int ks, int mode, int np, dim3 grid, size_t lds, hipStream_t st) {
-  const C3K& k = *reinterpret_cast<const C3K*>(kp);
-  if (ks != 5) return 0;
-#define C3N_GO(M_, P_) { \
-    addk_dyn_lds<conv3n_kernel<5, M_, P_>>(); \
-    hipLaunchKernelGGL((conv3n_kernel<5, M_, P_>), grid, dim3(256), lds, st, k); return 1; }
-  if (mode == MODE_FWD) { if (np == 3) C3N_GO(MODE_FWD, 3) else C3N_GO(MODE_FWD, 2) }
-  else { if (np == 3) C3N_GO(MODE_DGRAD, 3) else C3N_GO(MODE_DGRAD, 2) }
-#undef C3N_GO
+// grid.x workgroups walk p.ntiles tiles of 2 rows x 128 pixels
+C3Variant c3n_variant(int ks, int mode, int np) {
+  if (ks != 5) return {};
+  if (mode == MODE_FWD && np == 3) return c3_dyn_variant<conv3n_kernel<5, MODE_FWD, 3>>(256);
+  if (mode == MODE_FWD && np == 2) return c3_dyn_variant<conv3n_kernel<5, MODE_FWD, 2>>(256);
+  if (mode == MODE_DGRAD && np == 3) return c3_dyn_variant<conv3n_kernel<5, MODE_DGRAD, 3>>(256);
+  if (mode == MODE_DGRAD && np == 2) return c3_dyn_variant<conv3n_kernel<5, MODE_DGRAD, 2>>(256);
+  return {};
 }

@@ -41,6 +41,8 @@ SHAPES = [
     ('pw_aspp_400',    2, 64, 128, (400,), 256, 1, 1),
     ('pw_cat_1024',    1, 64, 128, (256, 256, 256, 256), 256, 1, 1),
     ('pw_odd_208',     2, 33,  65, (208,), 192, 1, 1),     # odd map, 192 output channels (the narrowest shape that takes this path)
+    # 5x5 on a wide head: 512 column-block tiles of 128 channels, which the fp32 halo kernel only has for the 3x3 (4 tiles per block here)
+    ('halo5_c256', 1, 128, 256, (16,), 256, 1, 5),
 ]
 BIAS_N = {'pw_cat_1024', 'pw_odd_208'}
 SPLIT_ONLY = {'l3_dil5_160', 'l3_dil3_160'}       # maps below the fp32 halo kernel's 8192-pixel floor: the split kernel's launch shapes only
