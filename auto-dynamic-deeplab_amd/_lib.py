@@ -128,6 +128,20 @@ class LabelTilesArgs(C.Structure):
                 ('lut256', vp), ('labels', vp)]
 
 
+class TileViewDesc(C.Structure):
+    _fields_ = [('image', vp), ('H', i32), ('W', i32), ('Hv', i32), ('Wv', i32), ('y0', i32), ('x0', i32), ('mirror', i32)]
+
+
+class TileView(C.Structure):
+    _fields_ = [('Hv', i32), ('Wv', i32), ('t0', i32), ('ny', i32), ('nx', i32), ('mirror', i32), ('weight', f32),
+                ('y0', i32 * MAX_TILES_AXIS), ('x0', i32 * MAX_TILES_AXIS)]
+
+
+class LabelTileViewsArgs(C.Structure):
+    _fields_ = [('view', TileView * MAX_VIEWS), ('nview', i32), ('logits', vp), ('ld', i32), ('h', i32), ('w', i32), ('th', i32), ('tw', i32),
+                ('N', i32), ('C', i32), ('OH', i32), ('OW', i32), ('lut256', vp), ('labels', vp)]
+
+
 class ProfileUpsampleArgs(C.Structure):
     _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
                 ('target', vp), ('thr', vp), ('nthr', i32), ('ent_out', vp), ('share_out', vp), ('cm', vp), ('pred_out', vp), ('ws', vp)]
@@ -242,6 +256,7 @@ STRUCTS = {
     'addk_score_upsample_args': ScoreUpsampleArgs, 'addk_gate_upsample_args': GateUpsampleArgs, 'addk_label_upsample_args': LabelUpsampleArgs,
     'addk_gate_label_upsample_args': GateLabelUpsampleArgs, 'addk_view': View, 'addk_label_views_args': LabelViewsArgs,
     'addk_tile_desc': TileDesc, 'addk_label_tiles_args': LabelTilesArgs,
+    'addk_tile_view_desc': TileViewDesc, 'addk_tile_view': TileView, 'addk_label_tile_views_args': LabelTileViewsArgs,
     'addk_profile_upsample_args': ProfileUpsampleArgs, 'addk_gate_upsample_t_args': GateUpsampleTArgs,
     'addk_profile_upsample_t_args': ProfileUpsampleTArgs, 'addk_calib_upsample_args': CalibUpsampleArgs,
     'addk_boundary_dist_args': BoundaryDistArgs, 'addk_confusion_banded_args': ConfusionBandedArgs, 'addk_rows_item': RowsItem,
@@ -384,6 +399,9 @@ _SIGS = {
     'addk_gather_tiles': (i32, [vp, i32, i32, i32, i32, vp, i32, vp]),
     'addk_label_tiles_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_label_tiles_upsample': (i32, [C.POINTER(LabelTilesArgs), vp]),
+    'addk_gather_tile_views': (i32, [vp, i32, i32, i32, i32, vp, i32, vp]),
+    'addk_label_tile_views_upsample_supported': (i32, [i32, i32, i32, i32, i32]),
+    'addk_label_tile_views_upsample': (i32, [C.POINTER(LabelTileViewsArgs), vp]),
     'addk_profile_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
     'addk_profile_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_profile_upsample': (i32, [C.POINTER(ProfileUpsampleArgs), vp]),

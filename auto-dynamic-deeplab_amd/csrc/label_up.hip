@@ -1,6 +1,6 @@
 // The inference heads on the decoder's low-resolution logits: the label map of one exit (label_up_kernel), of several views
-// (label_views_kernel), of the sliding windows that cover an image (label_tiles_kernel), and the early-exit gate with and without the
-// label map, plain and tempered (gate_up_kernel).
+// (label_views_kernel), of the sliding windows that cover an image (label_tiles_kernel), of the sliding windows of several scaled and
+// mirrored views (label_tile_views_kernel), and the early-exit gate with and without the label map, plain and tempered (gate_up_kernel).
 #include "up.h"
 
 namespace {
@@ -204,6 +204,137 @@ bool ltu_axis_ok(const int32_t* o, int n, int t, int L) {
   return (long)o[n - 1] + t >= L;
 }
 
+// ---- fused tiled multi-view label map: the windows of several scaled / mirrored views that cover a pixel (multi-scale + flip sliding windows) ----
+// What a multi-scale, flipped sliding-window evaluation keeps: the arg-max of the weighted mean over views of the MEAN class probabilities
+// of the view's windows that cover a pixel.  View v's windows lie on its scaled image (Hv, Wv); output pixel (Y, X) sits there at
+// u = ((Y + 1/2) Hv/OH, (Xm + 1/2) Wv/OW), Xm the mirrored column, and is covered by window (iy, ix) iff y0 <= u_y < y0 + th and
+// x0 <= u_x < x0 + tw — decided in 64-bit integers, 2 OH y0 <= (2Y+1) Hv < 2 OH (y0 + th), so no rounding moves a pixel in or out of a
+// window.  The tile and the walk are label_tiles_kernel's: a wave owns 64 columns and LTV_R rows, a thread one column, acc[LTV_R][CC] in
+// registers.  Per view the covering window rows of each of the wave's rows (bit mask rm[r]) and the weight over the cover count are wave-
+// uniform; the covering window columns (bit mask cm) and their count are per lane.  A window samples its logits at a = (u - origin) * h/th - 1/2
+// with src_index's border rule (src_at); at scale 1 the coordinate and z = lh0*t0 + lh1*t1 carry label_tiles_kernel's bits.  The row pair
+// t0 / t1 is reloaded only when the wave-uniform row pair changes.  Dividing by the cover count is what lets views with different overlap
+// be averaged.  No LDS, no atomics, no workspace: a pixel's sum runs in the same order (view, iy, ix) on every launch.
+constexpr int LTV_R = LVU_R;
+
+// src_index's tail for a source coordinate that is already computed
+__device__ __forceinline__ void src_at(float s, int in, int& i0, int& i1, float& l0, float& l1) {
+  if (!(s >= 0.f)) s = 0.f;
+  i0 = (int)s;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  l1 = s - (float)i0;
+  l0 = 1.f - l1;
+}
+
+template <int CC, bool VEC>
+__global__ void __launch_bounds__(256) label_tile_views_kernel(const addk_label_tile_views_args p) {
+  const int lane = threadIdx.x & (LVU_W - 1), wv = __builtin_amdgcn_readfirstlane(threadIdx.x / LVU_W);
+  const int X = blockIdx.x * LVU_W + lane, n = blockIdx.z;
+  if (X >= p.OW) return;
+  const int ybeg = (blockIdx.y * LVU_WAVES + wv) * LTV_R;
+  if (ybeg >= p.OH) return;                                            // wave-uniform
+  const float sh = (float)p.h / (float)p.th, sw = (float)p.w / (float)p.tw;
+  const long tile_floats = (long)p.h * p.w * p.ld;
+  const long OH2 = 2L * p.OH, OW2 = 2L * p.OW;
+  float acc[LTV_R][CC];
+#pragma unroll
+  for (int r = 0; r < LTV_R; ++r)
+#pragma unroll
+    for (int c = 0; c < CC; ++c) acc[r][c] = 0.f;
+  for (int v = 0; v < p.nview; ++v) {
+    const addk_tile_view& V = p.view[v];
+    const int ny = V.ny, nx = V.nx;
+    const int Xm = V.mirror ? p.OW - 1 - X : X;
+    const long cx = (long)(2 * Xm + 1) * V.Wv;
+    unsigned cm = 0;                                                    // per lane: the window columns that cover X
+    for (int ix = 0; ix < nx; ++ix) {
+      const long lo = OW2 * V.x0[ix];
+      if (lo <= cx && cx < lo + OW2 * p.tw) cm |= 1u << ix;
+    }
+    const int kx = __popc(cm);
+    unsigned rm[LTV_R], rows = 0;                                       // wave-uniform: the window rows that cover row ybeg + r
+    float wk[LTV_R];
+#pragma unroll
+    for (int r = 0; r < LTV_R; ++r) {
+      rm[r] = 0;
+      if (ybeg + r < p.OH) {
+        const long cy = (long)(2 * (ybeg + r) + 1) * V.Hv;
+        for (int iy = 0; iy < ny; ++iy) {
+          const long lo = OH2 * V.y0[iy];
+          if (lo <= cy && cy < lo + OH2 * p.th) rm[r] |= 1u << iy;
+        }
+      }
+      rows |= rm[r];
+      const int k = __popc(rm[r]) * kx;
+      wk[r] = V.weight / (float)(k > 0 ? k : 1);
+    }
+    const float ux = ((float)Xm + 0.5f) * ((float)V.Wv / (float)p.OW);
+    const float rh = (float)V.Hv / (float)p.OH;
+    for (int iy = 0; iy < ny; ++iy) {
+      if (!((rows >> iy) & 1u)) continue;                               // wave-uniform: the window row misses this wave's rows
+      const float fy0 = (float)V.y0[iy];
+      for (int ix = 0; ix < nx; ++ix) {
+        if ((cm >> ix) & 1u) {                                          // per lane: this window covers column X
+          const float* x = p.logits + ((long)V.t0 + ((long)n * ny + iy) * nx + ix) * tile_floats;
+          int w0, w1; float lw0, lw1;
+          src_at((ux - (float)V.x0[ix]) * sw - 0.5f, p.w, w0, w1, lw0, lw1);
+          float t0[CC], t1[CC];
+          int ph0 = -1, ph1 = -1;
+#pragma unroll
+          for (int r = 0; r < LTV_R; ++r) {
+            if ((rm[r] >> iy) & 1u) {                                   // wave-uniform
+              const float uy = ((float)(ybeg + r) + 0.5f) * rh;
+              int h0, h1; float lh0, lh1;
+              src_at((uy - fy0) * sh - 0.5f, p.h, h0, h1, lh0, lh1);
+              if (h0 != ph0 || h1 != ph1) {                             // wave-uniform
+                const float* r0 = x + ((long)h0 * p.w) * p.ld;
+                const float* r1 = x + ((long)h1 * p.w) * p.ld;
+                float a[cpad(CC)], b[cpad(CC)];
+                load_px<CC>(r0 + (long)w0 * p.ld, a, VEC); load_px<CC>(r0 + (long)w1 * p.ld, b, VEC);
+#pragma unroll
+                for (int c = 0; c < CC; ++c) t0[c] = lw0 * a[c] + lw1 * b[c];
+                load_px<CC>(r1 + (long)w0 * p.ld, a, VEC); load_px<CC>(r1 + (long)w1 * p.ld, b, VEC);
+#pragma unroll
+                for (int c = 0; c < CC; ++c) t1[c] = lw0 * a[c] + lw1 * b[c];
+                ph0 = h0; ph1 = h1;
+              }
+              float e[CC];
+              float mx = -INFINITY;
+#pragma unroll
+              for (int c = 0; c < CC; ++c) { e[c] = lh0 * t0[c] + lh1 * t1[c]; mx = fmaxf(mx, e[c]); }
+              float se = 0.f;
+#pragma unroll
+              for (int c = 0; c < CC; ++c) { e[c] = __expf(e[c] - mx); se += e[c]; }
+              const float s = wk[r] / se;
+#pragma unroll
+              for (int c = 0; c < CC; ++c) acc[r][c] += s * e[c];
+            }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < LTV_R; ++r) {
+    const int Y = ybeg + r;
+    if (Y < p.OH) {
+      float mx = -INFINITY; int am = 0;
+#pragma unroll
+      for (int c = 0; c < CC; ++c)
+        if (acc[r][c] > mx) { mx = acc[r][c]; am = c; }            // strict: a tie keeps the lowest channel
+      label_px(p.lut256, p.labels, ((long)n * p.OH + Y) * p.OW + X, am);
+    }
+  }
+}
+
+dim3 ltv_grid(int N, int OH, int OW) { return dim3(cdiv(OW, LVU_W), cdiv(OH, LVU_WAVES * LTV_R), N); }
+bool ltv_ok(int nview, int N, int OH, int OW, int C) {
+  if (nview < 1 || nview > ADDK_MAX_VIEWS || !head_class_ok(C) || N <= 0 || OH <= 0 || OW <= 0) return false;
+  const dim3 g = ltv_grid(N, OH, OW);
+  return N <= 65535 && g.y <= 65535 && (long)(int)g.z * (int)g.y * (int)g.x < (1L << 30);
+}
+
 // ---- fused logits up-sampling + early-exit gate (decoder.py:28 + operations.py:161-180) -----------------------------------
 // The two gates of dynamic inference that need no trained EDM: the normalised Shannon entropy of the up-sampled prediction and the
 // share of pixels whose top softmax probability passes a threshold.  The walk is scu_walk (same tile, same interpolation
@@ -391,4 +522,30 @@ extern "C" int addk_label_tiles_upsample(const addk_label_tiles_args* a, void* s
     launch_vec(px_vec_ok<CC>(a->logits, a->ld), label_tiles_kernel<CC, true>, label_tiles_kernel<CC, false>, lvu_grid(a->N, a->OH, a->OW), st, *a);
   });
   return addk_check_launch("label_tiles_upsample");
+}
+
+extern "C" int addk_label_tile_views_upsample_supported(int32_t nview, int32_t N, int32_t OH, int32_t OW, int32_t C) {
+  return ltv_ok(nview, N, OH, OW, C) ? 1 : 0;
+}
+extern "C" int addk_label_tile_views_upsample(const addk_label_tile_views_args* a, void* stream) {
+  ADDK_REQUIRE(a && a->logits && a->labels, "label_tile_views_upsample: null pointer");
+  ADDK_REQUIRE(ltv_ok(a->nview, a->N, a->OH, a->OW, a->C), "label_tile_views_upsample: unsupported shape (1..%d views, %s)", ADDK_MAX_VIEWS,
+               head_classes_text().c_str());
+  ADDK_REQUIRE(a->h > 0 && a->w > 0 && a->th > 0 && a->tw > 0 && a->ld >= a->C, "label_tile_views_upsample: bad size or stride");
+  for (int v = 0; v < a->nview; ++v) {
+    const addk_tile_view& w = a->view[v];
+    ADDK_REQUIRE(w.ny >= 1 && w.ny <= ADDK_MAX_TILES_AXIS && w.nx >= 1 && w.nx <= ADDK_MAX_TILES_AXIS,
+                 "label_tile_views_upsample: 1..%d windows per axis (view %d)", ADDK_MAX_TILES_AXIS, v);
+    ADDK_REQUIRE(w.Hv > 0 && w.Wv > 0 && w.t0 >= 0, "label_tile_views_upsample: bad scaled size or first tile (view %d)", v);
+    ADDK_REQUIRE(w.weight > 0.f && isfinite(w.weight), "label_tile_views_upsample: a weight must be positive and finite (view %d)", v);
+    ADDK_REQUIRE(ltu_axis_ok(w.y0, w.ny, a->th, w.Hv) && ltu_axis_ok(w.x0, w.nx, a->tw, w.Wv),
+                 "label_tile_views_upsample: the origins are no window grid of the scaled image (view %d)", v);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  head_classes(a->C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    launch_vec(px_vec_ok<CC>(a->logits, a->ld), label_tile_views_kernel<CC, true>, label_tile_views_kernel<CC, false>,
+               ltv_grid(a->N, a->OH, a->OW), st, *a);
+  });
+  return addk_check_launch("label_tile_views_upsample");
 }

@@ -28,6 +28,15 @@ full-resolution probability buffer exists.  The head takes `_lib.head_classes()`
 
     seg = TiledSegmenter(model, (B, 3, 769, 769), stride=(513, 513))
     maps = seg.segment(images)               # [n,3,H,W] or a list of [3,H_i,W_i] -> list of uint8 [H_i,W_i], owned by `seg`
+
+Both at once (how VOC and crop-trained Cityscapes models are scored): with `scales` / `flip` every view of an image — the image resized
+to view_size(H, W, scale), mirrored or not — is evaluated under the sliding window.  `addk_gather_tile_views` cuts the windows straight
+out of the resized, mirrored image without writing that image, and ONE `addk_label_tile_views_upsample` launch per image writes the arg-max
+of the weighted mean over views of the mean class probabilities of the view's windows that cover a pixel.  Still one tile plan, no
+[C,H,W] map of any view and no resized or flipped image.
+
+    seg = TiledSegmenter(model, (B, 3, 769, 769), stride=(513, 513), scales=(0.75, 1.0, 1.25), flip=True)
+    maps = seg.segment(images)
 """
 import ctypes as C
 import math
@@ -170,10 +179,14 @@ def tile_starts(L_, t, s):
 
 class TiledSegmenter(InferenceStep):
     """Label maps of images of any size from one tile plan at batch B (see the module text).  `tiles`: the last call's windows as
-    (image, y0, x0), in store order — image-major, then window row, then window column.  `maps`: the last call's label maps."""
+    (image, y0, x0), in store order — image-major, then window row, then window column.  `maps`: the last call's label maps.
+    With `scales`, `flip` or `weights` the windows run over views: `views` lists (scale, mirror, weight) in kernel order — per scale the plain
+    view, then (with `flip`) the mirrored one; `weights` is one positive number per view in that order (default 1/len(views)); `tiles` then
+    holds (image, view, y0, x0), origins in the view's scaled image, in store order — image-major, then view, window row, window column.
+    Without the three arguments `views` is None and the call is the single-view one above."""
     head = 'tiles'
 
-    def __init__(self, model, tile_shape, stride, exit=-1, label_lut=None, use_graph=None, nstreams=None):
+    def __init__(self, model, tile_shape, stride, exit=-1, label_lut=None, use_graph=None, nstreams=None, scales=None, flip=False, weights=None):
         from .modeling.ADD import ADD
         if not isinstance(model, ADD):
             raise TypeError('TiledSegmenter takes an ADD model (got %s)' % type(model).__name__)
@@ -184,6 +197,23 @@ class TiledSegmenter(InferenceStep):
         if not (1 <= sy <= th and 1 <= sx <= tw):
             raise ValueError('the stride must be within 1..tile (got stride %r, tile %dx%d)' % ((sy, sx), th, tw))
         self.stride = (sy, sx)
+        self.views = None
+        if scales is not None or flip or weights is not None:
+            scales = (1.0,) if scales is None else tuple(float(s) for s in scales)
+            per = 2 if flip else 1
+            if not scales:
+                raise ValueError('scales is empty')
+            if any(not (s > 0 and math.isfinite(s)) for s in scales):
+                raise ValueError('scales must be positive (got %r)' % (scales,))
+            if len(scales) * per > L.MAX_VIEWS:
+                raise ValueError('at most %d views (got %d scales%s)' % (L.MAX_VIEWS, len(scales), ' with flip' if flip else ''))
+            nview = len(scales) * per
+            weights = [1.0 / nview] * nview if weights is None else [float(w) for w in weights]
+            if len(weights) != nview:
+                raise ValueError('one weight per view: %d views, %d weights' % (nview, len(weights)))
+            if any(not (w > 0 and math.isfinite(w)) for w in weights):
+                raise ValueError('weights must be positive and finite (got %r)' % (weights,))
+            self.views = [(s, bool(m), weights[i * per + m]) for i, s in enumerate(scales) for m in range(per)]
         self.exit = range(model.num_exits())[exit]             # forward()'s output list; IndexError out of range
         self.lut = _label_lut(label_lut, next(model.parameters()).device)
         self.tiles, self.maps, self._images = [], [], []
@@ -225,17 +255,50 @@ class TiledSegmenter(InferenceStep):
                 raise ValueError('image %d: expected normalised float32 (got %s)' % (k, im.dtype))
             _plan.require_device(im)
             H, W = int(im.shape[1]), int(im.shape[2])
+            if self.views is not None:
+                grids = []                                     # per view: (Hv, Wv, y origins, x origins, first tile), on the scaled image
+                for v, (s, _, _) in enumerate(self.views):
+                    Hv, Wv = view_size(H, W, s)
+                    ys, xs = tile_starts(Hv, th, self.stride[0]), tile_starts(Wv, tw, self.stride[1])
+                    grids.append((Hv, Wv, ys, xs, len(tiles)))
+                    tiles += [(k, v, y, x) for y in ys for x in xs]
+                per.append((im.contiguous(), H, W, grids))
+                continue
             ys, xs = tile_starts(H, th, self.stride[0]), tile_starts(W, tw, self.stride[1])
             per.append((im.contiguous(), H, W, ys, xs, len(tiles)))
             tiles += [(k, y, x) for y in ys for x in xs]
         return per, tiles
+
+    def _descriptors(self, per, cap):
+        """the call's window descriptors in store order, as a ctypes array of `cap` entries (the ones behind the windows stay zero)"""
+        if self.views is None:
+            arr = (L.TileDesc * cap)()
+            i = 0
+            for im, H, W, ys, xs, _ in per:
+                for y in ys:
+                    for x in xs:
+                        d = arr[i]
+                        d.image, d.H, d.W, d.y0, d.x0 = im.data_ptr(), H, W, y, x
+                        i += 1
+            return arr
+        arr = (L.TileViewDesc * cap)()
+        i = 0
+        for im, H, W, grids in per:
+            for (_, mirror, _), (Hv, Wv, ys, xs, _) in zip(self.views, grids):
+                for y in ys:
+                    for x in xs:
+                        d = arr[i]
+                        d.image, d.H, d.W, d.Hv, d.Wv, d.y0, d.x0, d.mirror = im.data_ptr(), H, W, Hv, Wv, y, x, int(mirror)
+                        i += 1
+        return arr
 
     def _upload(self, per, T):
         """The call's descriptor table on the device: written into pinned host words, copied without blocking; an event guards the words'
         reuse by the next call (it waits for that one copy, not for the device)."""
         B = self.batch_shape[0]
         cap = -(-T // B) * B
-        nb = cap * C.sizeof(L.TileDesc)
+        arr = self._descriptors(per, cap)
+        nb = C.sizeof(arr)
         if self._desc_host is None or self._desc_host.numel() < nb:
             self._desc_host = torch.zeros(nb, dtype=torch.uint8)
             self._desc_dev = torch.zeros(nb, dtype=torch.uint8, device=self.dev)
@@ -244,14 +307,6 @@ class TiledSegmenter(InferenceStep):
             self._desc_evt = None
         if self._desc_evt is not None:
             self._desc_evt.synchronize()
-        arr = (L.TileDesc * cap)()
-        i = 0
-        for im, H, W, ys, xs, _ in per:
-            for y in ys:
-                for x in xs:
-                    d = arr[i]
-                    d.image, d.H, d.W, d.y0, d.x0 = im.data_ptr(), H, W, y, x
-                    i += 1
         self._desc_host[:nb].copy_(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8))
         self._desc_dev[:nb].copy_(self._desc_host[:nb], non_blocking=True)
         if self.dev.type == 'cuda':
@@ -276,19 +331,36 @@ class TiledSegmenter(InferenceStep):
             self._store = torch.zeros((T, h, w, self.ld), dtype=torch.float32, device=self.dev)      # outside the graph: it may grow
         table = self._upload(per, T)
         logits = self.out.src.raw.view()
+        if self.views is None:
+            gather = ('gather_tiles', lib.addk_gather_tiles, C.sizeof(L.TileDesc))
+        else:
+            gather = ('gather_tile_views', lib.addk_gather_tile_views, C.sizeof(L.TileViewDesc))
         with torch.no_grad():
             for t in range(0, T, B):
                 nb = min(B, T - t)
-                self._launch('gather_tiles', lib.addk_gather_tiles, table + t * C.sizeof(L.TileDesc), nb, Cin, th, tw, self.x.data_ptr(), B)
+                self._launch(gather[0], gather[1], table + t * gather[2], nb, Cin, th, tw, self.x.data_ptr(), B)
                 self._replay()
                 self._store[t:t + nb, :, :, :self.ncls].copy_(logits[:nb])
-            npix = sum(H * W for _, H, W, _, _, _ in per)
+            npix = sum(p[1] * p[2] for p in per)
             if self._label_buf is None or self._label_buf.numel() < npix:
                 self._label_buf = torch.zeros(npix, dtype=torch.uint8, device=self.dev)
             maps, off = [], 0
-            for im, H, W, ys, xs, t0 in per:
+            for p in per:
+                H, W = p[1], p[2]
                 lab = self._label_buf[off:off + H * W].view(H, W)
                 off += H * W
+                if self.views is not None:
+                    a = L.LabelTileViewsArgs()
+                    a.nview, a.logits, a.ld, a.h, a.w, a.th, a.tw = len(self.views), self._store.data_ptr(), self.ld, h, w, th, tw
+                    a.N, a.C, a.OH, a.OW = 1, self.ncls, H, W
+                    for v, (_, mirror, weight), (Hv, Wv, ys, xs, t0) in zip(a.view, self.views, p[3]):
+                        v.Hv, v.Wv, v.t0, v.ny, v.nx, v.mirror, v.weight = Hv, Wv, t0, len(ys), len(xs), int(mirror), weight
+                        v.y0[:len(ys)], v.x0[:len(xs)] = ys, xs
+                    a.lut256, a.labels = self.lut.data_ptr() if self.lut is not None else None, lab.data_ptr()
+                    self._launch('label_tile_views_upsample', lib.addk_label_tile_views_upsample, C.byref(a))
+                    maps.append(lab)
+                    continue
+                ys, xs, t0 = p[3:]
                 a = L.LabelTilesArgs()
                 a.logits, a.ld, a.h, a.w, a.th, a.tw = self._store.data_ptr(), self.ld, h, w, th, tw
                 a.N, a.C, a.OH, a.OW, a.t0, a.ny, a.nx = 1, self.ncls, H, W, t0, len(ys), len(xs)

@@ -500,7 +500,8 @@ int64_t addk_ce_ws_floats(int32_t N, int64_t HW);
 
 /* The class counts C the fused heads on the low-resolution logits are compiled for, two lists in csrc/up.h.
  *   addk_head_classes       the training heads (addk_ce_upsample_fwd_bwd and its _ohem, _kd and _dice forms, addk_ohem_select,
- *                           addk_dice_stats), the label heads (addk_label_upsample, addk_label_tiles_upsample) and the compile-time form of addk_ce_fwd_bwd:
+ *                           addk_dice_stats), the label heads (addk_label_upsample, addk_label_tiles_upsample,
+ *                           addk_label_tile_views_upsample) and the compile-time form of addk_ce_fwd_bwd:
  *                           19 (Cityscapes) and 21 (Pascal VOC).
  *   addk_gate_head_classes  the scoring, profile, calibration, gate and multi-view heads (addk_score_upsample, addk_profile_upsample[_t],
  *                           addk_calib_upsample, addk_gate_upsample[_t], addk_gate_label_upsample, addk_label_views_upsample): 19.
@@ -819,6 +820,57 @@ typedef struct {
 } addk_label_tiles_args;
 int addk_label_tiles_upsample_supported(int32_t N, int32_t OH, int32_t OW, int32_t ny, int32_t nx, int32_t C);
 int addk_label_tiles_upsample(const addk_label_tiles_args* a, void* stream);
+
+/* Multi-scale + flip sliding windows (segment.TiledSegmenter with scales / flip): a view v of an image (OH, OW) is (scale, mirror, weight);
+ * its scaled image S_v is the bilinear resize (align_corners=False) of the image to (Hv, Wv) = segment.view_size(OH, OW, scale), flipped
+ * along the width if `mirror`; the windows of the view are tile_starts(Hv, th, sy) x tile_starts(Wv, tw, sx) over S_v.
+ *
+ * addk_gather_tile_views is addk_gather_tiles over S_v, which is never materialised: slot b < ntiles, plane c, position (i, j) gets, with
+ * sy = y0 + i and sx = x0 + j, 0.0f outside [0, Hv) x [0, Wv) and else the bilinear sample of plane c of the (H, W) -> (Hv, Wv) resize at
+ * (sy, mirror ? Wv-1-sx : sx), computed with the index arithmetic and the lerp expression of addk_resize_fwd (the bits it writes there).
+ * A descriptor with Hv == H, Wv == W, mirror == 0 copies the pixel: addk_gather_tiles' bytes.  Slots >= ntiles are zero.  The refusals
+ * are addk_gather_tiles'; the table lives in device memory, so a descriptor with a non-positive Hv or Wv is refused where it is read:
+ * nothing of its image is touched and its slot is zero. */
+typedef struct { const float* image; int32_t H, W, Hv, Wv, y0, x0, mirror; } addk_tile_view_desc;  /* image: [Cin][H][W] of ONE image */
+int addk_gather_tile_views(const addk_tile_view_desc* tiles_dev, int32_t ntiles, int32_t Cin, int32_t th, int32_t tw,
+                           float* x, int32_t B, void* stream);
+
+/* Tiled multi-view label head: the arg-max of the weighted mean, over up to ADDK_MAX_VIEWS views, of the mean class probabilities of the
+ * windows of the view that cover a pixel, in ONE launch over the stored low-resolution NHWC logits of every view's windows.  For output
+ * pixel (n, Y, X), views in order:
+ *   Xm = mirror ? OW-1-X : X;   u_y = (Y + 1/2) * Hv / OH,  u_x = (Xm + 1/2) * Wv / OW       (the pixel centre in S_v's coordinates)
+ *   window (iy, ix) covers the pixel iff y0 <= u_y < y0 + th and x0 <= u_x < x0 + tw, decided in 64-bit integers:
+ *   2*OH*y0 <= (2Y+1)*Hv < 2*OH*(y0 + th), likewise x.  k = (covering window rows) * (covering window columns) >= 1.
+ *   for every covering window, ascending iy, then ix:
+ *     z    = bilinear sample of the window's logits at a_y = (u_y - y0) * h/th - 1/2, a_x = (u_x - x0) * w/tw - 1/2 with the border rule of
+ *            addk_resize_fwd (a < 0 -> 0, i0 = floor(a) capped at h-1, i1 = min(i0+1, h-1), lambda = a - i0), all in fp32
+ *     e[c] = exp(z[c] - max z);  acc[c] += ((weight / k) / sum e) * e[c]
+ *   labels[n,Y,X] = am, or lut256[am];  am = arg-max of acc (strict >: a tie keeps the lowest channel)
+ * Image n's window (iy, ix) of view v is tile t0_v + (n*ny_v + iy)*nx_v + ix of the store.  With one view of Hv == OH, Wv == OW, no mirror,
+ * weight 1 on a grid without overlap this is addk_label_tiles_upsample, bit for bit.  No workspace, no atomics: deterministic.
+ * addk_label_tile_views_upsample_supported() is 0 for nview outside 1..ADDK_MAX_VIEWS, C not in addk_head_classes(), non-positive sizes or
+ * a grid beyond 65535 x 16 rows / 65535 images; addk_label_tile_views_upsample then returns ADDK_ERR_INVALID without launching, as it does
+ * for a null logits / labels pointer, non-positive h, w, th, tw, ld < C, and per view: ny or nx outside 1..ADDK_MAX_TILES_AXIS, non-positive
+ * Hv or Wv, t0 < 0, a weight that is not positive and finite, and origins that are no window grid of (Hv, Wv) (addk_label_tiles_upsample's rule). */
+typedef struct {
+  int32_t Hv, Wv;                    /* the view's scaled image */
+  int32_t t0, ny, nx;                /* image n's window (iy, ix) is tile t0 + (n*ny + iy)*nx + ix */
+  int32_t mirror;
+  float weight;
+  int32_t y0[ADDK_MAX_TILES_AXIS], x0[ADDK_MAX_TILES_AXIS];      /* origins in the scaled image */
+} addk_tile_view;
+typedef struct {
+  addk_tile_view view[ADDK_MAX_VIEWS];
+  int32_t nview;
+  const float* logits; int32_t ld;   /* the store: tile t is [h][w] pixels of stride ld >= C at logits + t*h*w*ld */
+  int32_t h, w;                      /* a window's low-resolution grid */
+  int32_t th, tw;                    /* a window's size in pixels of a scaled image */
+  int32_t N, C, OH, OW;              /* N images of one size (OH, OW) */
+  const uint8_t* lut256;             /* NULL: the class index; else lut256[class] */
+  uint8_t* labels;                   /* [N,OH,OW] */
+} addk_label_tile_views_args;
+int addk_label_tile_views_upsample_supported(int32_t nview, int32_t N, int32_t OH, int32_t OW, int32_t C);
+int addk_label_tile_views_upsample(const addk_label_tile_views_args* a, void* stream);
 
 /* Exit profile of a validation pass (eval.py:195-230): what the early-exit operating curve needs of one exit, PER IMAGE, in
  * ONE launch over the LOW-resolution NHWC logits [N,H,W,C] (the walk and the arithmetic of the two heads above):
