@@ -142,6 +142,16 @@ class LabelTileViewsArgs(C.Structure):
                 ('N', i32), ('C', i32), ('OH', i32), ('OW', i32), ('lut256', vp), ('labels', vp)]
 
 
+class GateTilesArgs(C.Structure):
+    _fields_ = [('logits', vp), ('ld', i32), ('B', i32), ('nb', i32), ('h', i32), ('w', i32), ('C', i32), ('th', i32), ('tw', i32),
+                ('ext', vp), ('max_thr', vp), ('inv_temp', vp), ('out', vp), ('out_host', vp), ('ws', vp)]
+
+
+class ScatterTileLogitsArgs(C.Structure):
+    _fields_ = [('src', vp), ('lds', i32), ('B', i32), ('store', vp), ('ld', i32), ('T', i32), ('h', i32), ('w', i32), ('C', i32),
+                ('src_row', vp), ('dst_tile', vp), ('n', i32)]
+
+
 class ProfileUpsampleArgs(C.Structure):
     _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
                 ('target', vp), ('thr', vp), ('nthr', i32), ('ent_out', vp), ('share_out', vp), ('cm', vp), ('pred_out', vp), ('ws', vp)]
@@ -257,6 +267,7 @@ STRUCTS = {
     'addk_gate_label_upsample_args': GateLabelUpsampleArgs, 'addk_view': View, 'addk_label_views_args': LabelViewsArgs,
     'addk_tile_desc': TileDesc, 'addk_label_tiles_args': LabelTilesArgs,
     'addk_tile_view_desc': TileViewDesc, 'addk_tile_view': TileView, 'addk_label_tile_views_args': LabelTileViewsArgs,
+    'addk_gate_tiles_args': GateTilesArgs, 'addk_scatter_tile_logits_args': ScatterTileLogitsArgs,
     'addk_profile_upsample_args': ProfileUpsampleArgs, 'addk_gate_upsample_t_args': GateUpsampleTArgs,
     'addk_profile_upsample_t_args': ProfileUpsampleTArgs, 'addk_calib_upsample_args': CalibUpsampleArgs,
     'addk_boundary_dist_args': BoundaryDistArgs, 'addk_confusion_banded_args': ConfusionBandedArgs, 'addk_rows_item': RowsItem,
@@ -402,6 +413,10 @@ _SIGS = {
     'addk_gather_tile_views': (i32, [vp, i32, i32, i32, i32, vp, i32, vp]),
     'addk_label_tile_views_upsample_supported': (i32, [i32, i32, i32, i32, i32]),
     'addk_label_tile_views_upsample': (i32, [C.POINTER(LabelTileViewsArgs), vp]),
+    'addk_gate_tiles_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
+    'addk_gate_tiles_upsample_ws_bytes': (i64, [i32, i32, i32]),
+    'addk_gate_tiles_upsample': (i32, [C.POINTER(GateTilesArgs), vp]),
+    'addk_scatter_tile_logits': (i32, [C.POINTER(ScatterTileLogitsArgs), vp]),
     'addk_profile_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32, i32]),
     'addk_profile_upsample_ws_bytes': (i64, [i32, i32, i32]),
     'addk_profile_upsample': (i32, [C.POINTER(ProfileUpsampleArgs), vp]),

@@ -197,16 +197,21 @@ class GatePlan(DynamicPlan):
     plan, whose gate launches read 1 / T_k from device words (set_temperature: no rebuild, no recapture); exit k's logits and label
     map are what they are without it."""
 
-    def __init__(self, model, x, kind, output='logits', label_lut=None, batched=False, temperature=None):
+    def __init__(self, model, x, kind, output='logits', label_lut=None, batched=False, temperature=None, head=None, gate_extra=None):
+        """`head` / `gate_extra` (segment.TileGatePlan): another logits head than `output` names (a key of heads.HEADS) and further
+        entries of the gate's dict, for a head that emits its own gate launch."""
         from .modeling.ADD import _aspp_size
         if kind not in KINDS:
             raise ValueError('confidence must be one of %s (got %r)' % (('edm',) + KINDS, kind))
         self.kind = kind
+        self.image_dep, self._live = None, {}
         # (entropy, share) of the gated exit travel through pinned host memory: the gate launch writes them there itself; on the
         # stand-alone path an asynchronous 8-byte copy does.  Either way the host waits on ONE event, not on the whole device
         # (`batched`, a sub-plan of BatchedGate: the pair of every image of the batch)
         a = self._begin((model,), x, output, label_lut, 2 * x.shape[0] if batched else 2, batched)
         g = self.g
+        if head is not None:
+            g.head = head
         self._thr = torch.zeros(1, dtype=torch.float32, device=x.device)      # the word the 'max' gate compares against
         self.nex = model.num_exits()
         self.temperature, self._temp = None, None
@@ -221,7 +226,7 @@ class GatePlan(DynamicPlan):
                 self.final = model._head(g, y, low, size, aspp_size, it, lvl)
             else:
                 self.trunk_end.append(len(g.fwd))
-                g.gate = {'kind': kind, 'host': self._conf_host if x.is_cuda else None, 'thr': self._thr}
+                g.gate = dict(gate_extra or {}, kind=kind, host=self._conf_host if x.is_cuda else None, thr=self._thr)
                 if self._temp is not None:
                     g.gate['temp'] = self._temp[len(self.heads):len(self.heads) + 1]
                 h = model._head(g, y, low, size, aspp_size, it, lvl)
@@ -242,6 +247,52 @@ class GatePlan(DynamicPlan):
             if self.nex > 1:
                 self._temp.copy_(inverse_words(ts[:self.nex - 1]))
             self.temperature = ts
+
+    def taint(self):
+        """`image_dep`: which launches depend on the image — those that (transitively, in list order) read something written from the
+        staging buffer.  Nothing here is a hand-kept list of activations: everything is read off the launch list's named regions
+        (sched.Cmd.rd / wr)."""
+        tainted, self.image_dep = set(), []
+        for c in self.g.fwd:
+            dep = self.in_name in _names(c.wr) or bool(_names(c.rd) & tainted)
+            if dep:
+                tainted |= _names(c.wr)
+            self.image_dep.append(dep)
+
+    def live(self, pos):
+        """The state a run that continues at launch `pos` needs from fwd[:pos] -> (per-image plan buffers in order of first write,
+        the input-independent launches of fwd[:pos] to replay, in list order).  Live = plan buffers written by fwd[:pos] and read by
+        fwd[pos:].  Per-image = written by a launch that depends on the image; the rest (the eval-BN affine table, the hoisted weight
+        packs, anything computed from parameters only) is recomputed by replaying its producers, never copied.  On that side a buffer
+        that fwd[pos:] names as WRITTEN counts as read as well: a conv lists its hoisted weight pack under `wr` (without the hoist it
+        packs the weights itself) and reads what `conv_pack_batch` left there."""
+        got = self._live.get(pos)
+        if got is not None:
+            return got
+        if self.image_dep is None:
+            self.taint()
+        fwd = self.g.fwd
+        later, touched = set(), set()
+        for c in fwd[pos:]:
+            later |= _names(c.rd)
+            touched |= _names(c.wr)
+        first, per_image = {}, set()
+        for i, c in enumerate(fwd[:pos]):
+            for j, r in enumerate(c.wr):
+                if r[0][0] == 'buf':
+                    first.setdefault(r[0], (i, j))
+                    if self.image_dep[i]:
+                        per_image.add(r[0])
+        bufs = [self.g._bufs[n[1]] for n in sorted(first, key=first.get) if n in later and n in per_image]
+        needed, replay = (later | touched) - per_image, []
+        for i in range(pos - 1, -1, -1):
+            c = fwd[i]
+            if not self.image_dep[i] and _names(c.wr) & needed:
+                replay.append(c)
+                needed |= _names(c.rd)
+        replay.reverse()
+        self._live[pos] = bufs, replay
+        return bufs, replay
 
     def run(self, x, threshold):
         """-> (logits or label map, earlier_exit, gate value).  The image leaves at the first exit whose entropy is BELOW the threshold
@@ -282,53 +333,12 @@ def _names(regions, kind=None):
 
 
 class _SubPlan(GatePlan):
-    """The gate plan (label heads) at one live batch size of a BatchedGate, and what it hands over at a cut.  Nothing here is a
-    hand-kept list of activations: everything is read off the launch list's named regions (sched.Cmd.rd / wr)."""
+    """The gate plan (label heads) at one live batch size of a BatchedGate; what it hands over at a cut is GatePlan.live."""
 
     def __init__(self, model, x, kind, label_lut, temperature=None):
         super().__init__(model, x, kind, 'labels', label_lut, batched=True, temperature=temperature)
         self.batch = int(x.shape[0])
-        self._live = {}
-        # which launches depend on the image: those that (transitively, in list order) read something written from the staging buffer
-        tainted, self.image_dep = set(), []
-        for c in self.g.fwd:
-            dep = self.in_name in _names(c.wr) or bool(_names(c.rd) & tainted)
-            if dep:
-                tainted |= _names(c.wr)
-            self.image_dep.append(dep)
-
-    def live(self, pos):
-        """The state a run that continues at launch `pos` needs from fwd[:pos] -> (per-image plan buffers in order of first write,
-        the input-independent launches of fwd[:pos] to replay, in list order).  Live = plan buffers written by fwd[:pos] and read by
-        fwd[pos:].  Per-image = written by a launch that depends on the image; the rest (the eval-BN affine table, the hoisted weight
-        packs, anything computed from parameters only) is recomputed by replaying its producers, never copied.  On that side a buffer
-        that fwd[pos:] names as WRITTEN counts as read as well: a conv lists its hoisted weight pack under `wr` (without the hoist it
-        packs the weights itself) and reads what `conv_pack_batch` left there."""
-        got = self._live.get(pos)
-        if got is not None:
-            return got
-        fwd = self.g.fwd
-        later, touched = set(), set()
-        for c in fwd[pos:]:
-            later |= _names(c.rd)
-            touched |= _names(c.wr)
-        first, per_image = {}, set()
-        for i, c in enumerate(fwd[:pos]):
-            for j, r in enumerate(c.wr):
-                if r[0][0] == 'buf':
-                    first.setdefault(r[0], (i, j))
-                    if self.image_dep[i]:
-                        per_image.add(r[0])
-        bufs = [self.g._bufs[n[1]] for n in sorted(first, key=first.get) if n in later and n in per_image]
-        needed, replay = (later | touched) - per_image, []
-        for i in range(pos - 1, -1, -1):
-            c = fwd[i]
-            if not self.image_dep[i] and _names(c.wr) & needed:
-                replay.append(c)
-                needed |= _names(c.rd)
-        replay.reverse()
-        self._live[pos] = bufs, replay
-        return bufs, replay
+        self.taint()
 
 
 def pair_live(pm, pn, k):

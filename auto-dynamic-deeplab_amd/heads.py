@@ -366,6 +366,40 @@ def _tiles_head(g, src, OH, OW):
     return out
 
 
+def _tile_gate_head(g, src, OH, OW):
+    """Logits output of a gated tile plan (head 'tile_gate', set by segment.TileGatePlan): the plan is ONE chunk of windows of a
+    sliding-window pass whose windows leave at the first exit that is sure of them.  As in _tiles_head nothing becomes of the logits
+    inside the plan — the step scatters the rows that leave into its store (`addk_scatter_tile_logits`) — and the OutRef keeps the
+    low-resolution source (`src`) and `shape`.  An early exit (`Graph.gate` is set: GatePlan's dict plus 'ext', the int32 [B,2] device
+    words of every slot's valid extent) ends in ONE `gate_tiles_upsample` launch (`addk_gate_tiles_upsample`) that judges every window
+    over the part of it that lies on its image and writes (entropy, share) to `gate_out` [B,2] and to the pinned words; `gate_cut` is
+    the list position behind it.  The last exit (no gate) emits nothing.  There is no stand-alone form: a class count outside
+    `_lib.head_classes()` or a shape the gate launch does not take is an error."""
+    lib, gate = g.lib, g.gate
+    if src.C not in L.head_classes():
+        raise L.AddkError('the tiled label head takes %s (got %d)' % (L.head_classes_text(), src.C))
+    out = OutRef(None)
+    out.head, out.shape, out.src = 'tile_gate', (src.N, src.C, OH, OW), src
+    rd = g.lz(src)                               # a still-deferred resize of the logits is emitted now: the step reads src.raw itself
+    if gate is None:
+        return out
+    if lib.addk_gate_tiles_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) != 1:
+        raise L.AddkError('the tile gate takes %s (got %d classes, [%d,%d,%d] -> %dx%d)'
+                          % (L.head_classes_text(), src.C, src.N, src.H, src.W, OH, OW))
+    thr, host, ext, temp = gate['thr'], gate['host'], gate['ext'], gate.get('temp')
+    a, s = L.GateTilesArgs(), g.src(src)
+    a.logits, a.ld, a.B, a.nb, a.h, a.w, a.C, a.th, a.tw = s.x, s.ld, src.N, src.N, src.H, src.W, src.C, OH, OW
+    gout = torch.zeros((src.N, 2), dtype=torch.float32, device=g.device)
+    ws = g.buf((int(lib.addk_gate_tiles_upsample_ws_bytes(src.N, OH, OW)) + 3) // 4, zero=True)
+    a.ext, a.max_thr, a.inv_temp = ext.data_ptr(), thr.data_ptr(), temp.data_ptr() if temp is not None else None
+    a.out, a.out_host, a.ws = gout.data_ptr(), host.data_ptr() if host is not None else None, ws.ptr
+    g.keep += [a, gout, thr, host, ext, temp]
+    g._add(g.fwd, 'gate_tiles_upsample', lib.addk_gate_tiles_upsample, C.byref(a), rd=rd + [thr, ext] + [temp] * (temp is not None),
+           wr=[gout, ws])
+    out.gate_out, out.gate_fused, out.gate_cut = gout, True, len(g.fwd)
+    return out
+
+
 def _labels_cold(g, y, lab, lut):
     """Cold path of the two label heads: the map from materialised logits y [N,C,OH,OW] — `argmax_nchw`, then the cast / table look-up
     to uint8 in torch ops."""
@@ -491,18 +525,19 @@ def label_lut(lut, device):
 # Graph.head / OutRef.head: who consumes the decoder's low-resolution logits -> the function that emits that head.  None (no entry) =
 # nobody: Graph.resize_to_nchw writes [N,C,OH,OW] itself.  A gate (Graph.gate) is no head of its own: it composes with None and 'labels'.
 HEADS = {'ce': _ce_head, 'score': _score_head, 'profile': _profile_head, 'calib': _calib_head, 'labels': _label_head, 'views': _views_head,
-         'tiles': _tiles_head}
+         'tiles': _tiles_head, 'tile_gate': _tile_gate_head}
 
 
 def logits_head(g, src, OH, OW):
     """The OutRef of the head that takes this logits output, or None where the plain resize does.  A plan with gradients only ever takes
     'ce', and only where the library takes the shape and the logits need a gradient.  An inference plan takes 'score', 'profile' or 'calib'
-    first; then its gate, over head None or 'labels' ('tiles' refuses one); then 'labels', 'views' or 'tiles'."""
+    first ('tile_gate' among them: it emits its own gate); then its gate, over head None or 'labels' ('tiles' refuses one); then 'labels',
+    'views' or 'tiles'."""
     head, gate = g.head, g.gate
     if g.want_grad:
         fused = head == 'ce' and src.needs_grad and g.lib.addk_ce_upsample_supported(src.N, src.H, src.W, OH, OW, src.C) == 1
         return HEADS['ce'](g, src, OH, OW) if fused else None
-    if head in ('score', 'profile', 'calib'):
+    if head in ('score', 'profile', 'calib', 'tile_gate'):
         return HEADS[head](g, src, OH, OW)
     if gate is not None and head != 'tiles':     # 'tiles' has no gated form: _tiles_head refuses the gate
         return gate_head(g, src, OH, OW, gate['host'], gate['thr'], gate['kind'], gate.get('temp'))

@@ -501,7 +501,7 @@ int64_t addk_ce_ws_floats(int32_t N, int64_t HW);
 /* The class counts C the fused heads on the low-resolution logits are compiled for, two lists in csrc/up.h.
  *   addk_head_classes       the training heads (addk_ce_upsample_fwd_bwd and its _ohem, _kd and _dice forms, addk_ohem_select,
  *                           addk_dice_stats), the label heads (addk_label_upsample, addk_label_tiles_upsample,
- *                           addk_label_tile_views_upsample) and the compile-time form of addk_ce_fwd_bwd:
+ *                           addk_label_tile_views_upsample), the window gate (addk_gate_tiles_upsample) and the compile-time form of addk_ce_fwd_bwd:
  *                           19 (Cityscapes) and 21 (Pascal VOC).
  *   addk_gate_head_classes  the scoring, profile, calibration, gate and multi-view heads (addk_score_upsample, addk_profile_upsample[_t],
  *                           addk_calib_upsample, addk_gate_upsample[_t], addk_gate_label_upsample, addk_label_views_upsample): 19.
@@ -871,6 +871,57 @@ typedef struct {
 } addk_label_tile_views_args;
 int addk_label_tile_views_upsample_supported(int32_t nview, int32_t N, int32_t OH, int32_t OW, int32_t C);
 int addk_label_tile_views_upsample(const addk_label_tile_views_args* a, void* stream);
+
+/* Per-window early exits of the sliding window (segment.TiledSegmenter with `threshold`; csrc/tiles.hip).
+ *
+ * addk_gate_tiles_upsample is the gate of up to B windows of one chunk over their VALID EXTENT, in ONE launch, from the tile plan's
+ * low-resolution NHWC logits [B,h,w,ld].  A window that hangs over its image's edge is zero-padded (addk_gather_tiles), and the padding
+ * predicts one class with confidence: judged over the whole window such a window would leave early.  For slot b < nb with the extent
+ * (vh, vw) = ext[b], clamped in the kernel to 1..th and 1..tw (device data: the host cannot check it):
+ *   z          = the bilinear sample addk_resize_fwd writes at (Y, X) when it resizes (h, w) to (th, tw); s = *inv_temp, or 1 when it is NULL
+ *   d          = (z - max z) * s,  e = exp(d)                                     (addk_gate_upsample_t's sweep)
+ *   out[2b]     = sum over Y < vh, X < vw of (log sum e - sum e*d / sum e) / (log C * vh*vw)          normalised Shannon entropy
+ *   out[2b + 1] = #{Y < vh, X < vw: 1 / sum e > *max_thr} / (vh*vw)
+ * With the full extent, C == 19 and inv_temp NULL these are addk_gate_upsample's words.  Slots b >= nb are not written (nb == 0 launches
+ * nothing).  max_thr, inv_temp and ext are read when the launch runs, so a captured graph serves every threshold, temperature and chunk.
+ * out_host: optional pinned [B][2] words that receive the same bits.  ws: addk_gate_tiles_upsample_ws_bytes() bytes, ZERO-initialised
+ * once (the ticket word is left at zero: replayable from a hipGraph).  Deterministic: the last-arriving workgroup adds the per-workgroup
+ * partials in a fixed order.  addk_gate_tiles_upsample_supported() is 0 for C not in addk_head_classes(), non-positive sizes or a grid
+ * beyond 65535 x 32 rows / 65535 slots; addk_gate_tiles_upsample then returns ADDK_ERR_INVALID without launching, as it does for a null
+ * logits / ext / max_thr / out / ws pointer, nb outside 0..B and ld < C. */
+typedef struct {
+  const float* logits; int32_t ld;   /* NHWC [B,h,w,ld], pixel stride ld >= C */
+  int32_t B, nb;                     /* slots of the plan; windows of this chunk, 0..B */
+  int32_t h, w, C, th, tw;           /* a window's low-resolution grid, classes, a window's size */
+  const int32_t* ext;                /* device [B][2]: (vh, vw) of every slot */
+  const float* max_thr;              /* device-readable word: threshold of the 'max' gate */
+  const float* inv_temp;             /* device-readable word 1 / temperature, or NULL */
+  float* out;                        /* device [B][2]: (entropy, share) */
+  float* out_host;                   /* pinned host [B][2] or NULL */
+  void* ws;                          /* addk_gate_tiles_upsample_ws_bytes() zero-initialised bytes */
+} addk_gate_tiles_args;
+int addk_gate_tiles_upsample_supported(int32_t B, int32_t h, int32_t w, int32_t th, int32_t tw, int32_t C);
+int64_t addk_gate_tiles_upsample_ws_bytes(int32_t B, int32_t th, int32_t tw);
+int addk_gate_tiles_upsample(const addk_gate_tiles_args* a, void* stream);
+
+/* addk_scatter_tile_logits copies the low-resolution logits of the windows that leave into the store the tiled label heads read, in ONE
+ * launch: for i < n, the first C channels of row src_row[i] of src [B,h,w,lds] go to tile dst_tile[i] of store [T,h,w,ld], and the
+ * store's padding channels C..ld-1 of those tiles are written as zero.  src_row and dst_tile are DEVICE memory, read when the launch
+ * runs (src_row NULL stands for 0..n-1); an index outside 0..B-1 / 0..T-1 is skipped in the kernel.  Two entries of dst_tile must differ.
+ * 16-byte accesses where both strides and both bases allow them, single floats otherwise; nothing outside the named tiles is written.
+ * No atomics, no workspace: deterministic.  n == 0 launches nothing.  Returns ADDK_ERR_INVALID without launching for a null src / store /
+ * dst_tile pointer, n outside 0..B, non-positive B, T, h, w, C, and lds < C or ld < C. */
+typedef struct {
+  const float* src; int32_t lds;     /* the plan's logits [B,h,w,lds] */
+  int32_t B;
+  float* store; int32_t ld;          /* [T,h,w,ld] */
+  int32_t T;
+  int32_t h, w, C;
+  const int32_t* src_row;            /* device [n], or NULL: 0..n-1 */
+  const int32_t* dst_tile;           /* device [n] */
+  int32_t n;
+} addk_scatter_tile_logits_args;
+int addk_scatter_tile_logits(const addk_scatter_tile_logits_args* a, void* stream);
 
 /* Exit profile of a validation pass (eval.py:195-230): what the early-exit operating curve needs of one exit, PER IMAGE, in
  * ONE launch over the LOW-resolution NHWC logits [N,H,W,C] (the walk and the arithmetic of the two heads above):
