@@ -136,6 +136,7 @@ __device__ __forceinline__ void bn_finalize_body(const addk_bn_finalize_args& p,
     double mean = s0 / p.count;
     double var = s1 / p.count - mean * mean;
     if (var < 0.0) var = 0.0;
+    if (!(p.count > 1.0)) var = 0.0;     // one value per channel has no variance: what the subtraction leaves is the rounding of its fp32 square (bnfin.h)
     double invstd = 1.0 / sqrt(var + (double)p.eps);
     float g = p.gamma ? p.gamma[c] : 1.f, be = p.beta ? p.beta[c] : 0.f;
     float a = (float)(g * invstd);

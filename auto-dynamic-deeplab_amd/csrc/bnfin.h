@@ -125,6 +125,9 @@ __device__ __forceinline__ void bn_finalize_by_last_block(const BnFin& f, const 
     const double mean = m0 / f.count;
     double var = m1 / f.count - mean * mean;
     if (var < 0.0) var = 0.0;
+    // one value per channel has no variance.  The producers add squares that were rounded to fp32, so the subtraction leaves up to 2^-24 y^2 where 0 is exact:
+    // against eps = 1e-5 that moved invstd by up to 1.4e-3 of its value on a 1 x 1 map (tests/test_gpu_sep_fp64.py, the one-pixel batch member)
+    if (!(f.count > 1.0)) var = 0.0;
     const double invstd = 1.0 / sqrt(var + (double)f.eps);
     const float g = f.gamma ? ((const gfloat*)f.gamma)[c] : 1.f, be = f.beta ? ((const gfloat*)f.beta)[c] : 0.f;
     ((gfloat*)f.a)[c] = (float)(g * invstd);

@@ -42,6 +42,10 @@ inline bool sep_choose(int N, int H, int W, int C, int Cout, int K, SepChoice& c
   return built;
 }
 
+// a source or sum term as both kernels read it: (a, b) both or neither (they load b wherever a is set), rows that hold their channels, and no resampled
+// map (src.rs_hw is honoured by addk_conv_fwd alone: here the map would be read as a plain one of the wrong size)
+inline bool sep_src_ok(const addk_src& s) { return (s.a == nullptr) == (s.b == nullptr) && s.ld >= s.C && s.rs_hw == 0; }
+
 // the fast-path mask gates what the library RECOMMENDS (supported, addk_sep_bwd_rows, batch keys, cfg[0]), never a direct launch: include/addk.h
 inline bool sep_recommended() { return (addk_get_fast_paths() & ADDK_FAST_PW) != 0; }
 

@@ -357,7 +357,7 @@ bool sepb_choose(const addk_sep_bwd_args* a, SepChoice& c) {
 bool sepb_args_ok(const addk_sep_bwd_args* a, SepChoice& c) {
   if (!sepb_choose(a, c)) return false;
   const addk_src& s = a->src;
-  if (!s.x || !src_vec_ok(s) || !a->dw_w || !a->pw_w || !a->dy || !a->ws) return false;
+  if (!s.x || !src_vec_ok(s) || !sep_src_ok(s) || !a->dw_w || !a->pw_w || !a->dy || !a->ws) return false;
   if (!aligned16(a->dy) || a->lddy % 4 || a->lddy < a->Cout || a->ldw < s.C) return false;
   return !a->g || (aligned16(a->g) && a->ldg % 4 == 0 && a->ldg >= s.C);
 }

@@ -473,14 +473,14 @@ __global__ void __launch_bounds__(256, 2) sepf_batch_kernel(const SepfK* __restr
 bool sepf_args_ok(const addk_sep_args* a, SepChoice& c) {
   if (!a || !sep_choose(a->N, a->H, a->W, a->src.C, a->Cout, a->K, c)) return false;
   const addk_src& s = a->src;
-  if (!s.x || !src_vec_ok(s) || !a->dw_w || !a->pw_w || !a->y) return false;
+  if (!s.x || !src_vec_ok(s) || !sep_src_ok(s) || !a->dw_w || !a->pw_w || !a->y) return false;
   if (!aligned16(a->y) || a->ldy % 4 || a->ldy < a->Cout || !aligned16(a->pw_w) || a->ldw % 4 || a->ldw < s.C) return false;
   if (a->t && (!aligned16(a->t) || a->ldt % 4 || a->ldt < s.C)) return false;
   if (a->nterm < 0 || a->nterm > ADDK_MAX_TERMS || (a->ea == nullptr) != (a->eb == nullptr)) return false;
   if ((a->nterm > 0 || a->ea) && a->stats) return false;               // the sum epilogue is an inference form
   if (a->ea && (!aligned16(a->ea) || !aligned16(a->eb))) return false;
   if (a->fin.a && (!a->stats || !a->fin_counter || !a->fin.b || a->fin.count <= 0)) return false;
-  for (int i = 0; i < a->nterm; ++i) if (!a->term[i].x || a->term[i].C != a->Cout || !src_vec_ok(a->term[i])) return false;
+  for (int i = 0; i < a->nterm; ++i) if (!a->term[i].x || a->term[i].C != a->Cout || !src_vec_ok(a->term[i]) || !sep_src_ok(a->term[i])) return false;
   return !a->stats || c.gx <= a->stats_rows;               // the caller sizes the slab with addk_sep_rows
 }
 // the library recommends the fused kernel for this launch (sep.h: what follows the fast-path mask)

@@ -240,6 +240,8 @@ int addk_conv_wgrad_batch_run(const void* dev_blob, const int64_t* meta, void* s
  * (frozen) BatchNorm and add the other branches of the cell block (ADD.py:108):
  *     y = ea[c]*acc + eb[c] + sum_i relu_i?(a_i*term_i + b_i)        (ea == NULL: plain y = acc)
  * Covered shapes: K in {3,5}, C == Cout in (32, 48] or (64, 80], 16-byte aligned tensors; 80 channels up to 512 workgroups.
+ * `src` and every term, forward and backward: a and b both set or both NULL, ld >= C, rs_hw == 0 (a resampled source is addk_conv_fwd's
+ * alone).  Any other source is refused: not supported, batch key -1, an error from the launch and from *_batch_prepare.
  *
  * Forward and backward share ONE tile choice, made from (N, H, W, C, Cout, K) alone (csrc/sep.h): the same shape gets the same
  * variant (ks, kg, kp, r) and the same tiles in both directions.  The fast-path mask (ADDK_FAST_PW) gates what the library
@@ -260,7 +262,10 @@ typedef struct addk_sep_args {
   float* y; int32_t ldy;
   int32_t ldt; float* t;            /* depthwise output [P][ldt] or NULL */
   void* stats; int32_t stats_ld;    /* fp64 (sum, sumsq) partial slab [stats_rows][stats_ld][2] or NULL */
-  int32_t stats_rows;               /* rows the caller allocated: >= addk_sep_rows(a); rows no workgroup owns are zero-filled */
+  int32_t stats_rows;               /* rows the caller allocated: >= addk_sep_rows(a).  Without a fused finalize the rows no workgroup owns
+                                       (addk_sep_rows(a) .. stats_rows) are zero-filled, for a reduction over all stats_rows rows (addk_bn_finalize,
+                                       addk_slab_reduce).  With fin.a set they are left untouched: the launch's own finalize reads exactly its
+                                       addk_sep_rows(a) rows, and nothing may read the others afterwards */
   int32_t nterm;                    /* inference epilogue: number of extra terms (0..ADDK_MAX_TERMS) */
   const float* ea; const float* eb; /* inference epilogue: own affine (both NULL = none) */
   addk_src term[ADDK_MAX_TERMS];

@@ -18,6 +18,7 @@ import addk.plan as P
 from addk import _lib as L
 from _util import ARCH_C2, GENOTYPE_AUTODEEPLAB, make_args
 import test_gpu_fast_kernels as FK
+import _sep_ref as SR
 from test_conv_dispatch import MASKS, PTR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -176,6 +177,122 @@ def test_batch_keys_are_the_parents_and_decode_inverts_encode(lib, tmp_path):
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
     built = {int(l.split()[0]): tuple(map(int, l.split()[1:])) for l in out.strip().splitlines()}
     assert built == keys
+
+
+def _set(path, value):
+    """a change of an argument block: the field at the dotted `path` becomes `value`, or what `value` makes of (block, old value, channels)"""
+    def change(a, Cc):
+        *head, leaf = path.split('.')
+        for h in head:
+            a = a[int(h)] if h.isdigit() else getattr(a, h)
+        setattr(a, leaf, value(getattr(a, leaf), Cc) if callable(value) else value)
+    return change
+
+
+def _all(*changes):
+    return lambda a, Cc: [ch(a, Cc) for ch in changes]
+
+
+_off = lambda v, Cc: v + 4                 # four bytes on: no longer 16-byte aligned
+_odd = lambda v, Cc: v + 2                 # a row stride that is no multiple of 4 floats
+_short = lambda v, Cc: Cc - 4              # a row that does not hold its channels
+# what addk_sep_fwd refuses: (name, block, change).  Blocks: 'train' (t, statistics, fused finalize), 'infer' (EPILOGUES[5]: ea and four terms)
+FWD_REFUSED = [
+    ('a_without_b', 'train', _set('src.b', None)), ('b_without_a', 'train', _set('src.a', None)), ('src_rs_hw', 'train', _set('src.rs_hw', (7 << 16) | 19)),
+    ('term0_a_without_b', 'infer', _set('term.0.b', None)), ('term3_b_without_a', 'infer', _set('term.3.a', None)),
+    ('term0_rs_hw', 'infer', _set('term.0.rs_hw', (7 << 16) | 19)), ('term2_rs_hw', 'infer', _set('term.2.rs_hw', (7 << 16) | 19)),
+    ('y_misaligned', 'train', _set('y', _off)), ('t_misaligned', 'train', _set('t', _off)), ('pw_w_misaligned', 'train', _set('pw_w', _off)),
+    ('x_misaligned', 'train', _set('src.x', _off)), ('ea_misaligned', 'infer', _set('ea', _off)), ('eb_misaligned', 'infer', _set('eb', _off)),
+    ('term1_x_misaligned', 'infer', _set('term.1.x', _off)),
+    ('ldy_mod4', 'train', _set('ldy', _odd)), ('ldt_mod4', 'train', _set('ldt', _odd)), ('ldw_mod4', 'train', _set('ldw', _odd)),
+    ('src_ld_mod4', 'train', _set('src.ld', _odd)), ('term1_ld_mod4', 'infer', _set('term.1.ld', _odd)),
+    ('ldy_short', 'train', _set('ldy', _short)), ('ldt_short', 'train', _set('ldt', _short)), ('ldw_short', 'train', _set('ldw', _short)),
+    ('src_ld_short', 'train', _set('src.ld', _short)), ('term1_ld_short', 'infer', _set('term.1.ld', _short)),
+    ('nterm_5', 'infer', _set('nterm', L.MAX_TERMS + 1)), ('nterm_negative', 'infer', _set('nterm', -1)),
+    ('term1_other_C', 'infer', _set('term.1.C', _short)), ('ea_without_eb', 'infer', _set('eb', None)),
+    ('stats_with_sum_epilogue', 'infer', _all(_set('stats', SR.PTR['stats']), _set('stats_rows', 4096))),
+    ('stats_with_ea', 'train', _all(_set('ea', SR.PTR['ea']), _set('eb', SR.PTR['eb']))),
+    ('fin_without_counter', 'train', _set('fin_counter', None)), ('fin_without_stats', 'train', _set('stats', None)),
+    ('stats_rows_short', 'train', _set('stats_rows', lambda v, Cc: v - 1)),
+]
+BWD_REFUSED = [
+    ('a_without_b', _set('src.b', None)), ('b_without_a', _set('src.a', None)), ('src_rs_hw', _set('src.rs_hw', (7 << 16) | 19)),
+    ('g_misaligned', _set('g', _off)), ('dy_misaligned', _set('dy', _off)), ('x_misaligned', _set('src.x', _off)),
+    ('lddy_mod4', _set('lddy', _odd)), ('ldg_mod4', _set('ldg', _odd)), ('src_ld_mod4', _set('src.ld', _odd)),
+    ('lddy_short', _set('lddy', _short)), ('ldg_short', _set('ldg', _short)), ('ldw_short', _set('ldw', _short)), ('src_ld_short', _set('src.ld', _short)),
+    ('no_ws', _set('ws', None)), ('no_dy', _set('dy', None)),
+]
+
+
+def _fwd_block(lib, kind):
+    op = SR.CASES[0].op
+    if kind == 'infer':
+        return op, SR.fwd_args(L, op, SR.PTR, epilogue=5)
+    ar = SR.fwd_args(L, op, SR.PTR, t=True, stats_rows=1, fin=True)
+    ar.stats_rows = int(lib.addk_sep_rows(C.byref(ar)))           # exactly the launch's rows: one fewer is too few
+    return op, ar
+
+
+def _queries(lib, d, a):
+    q = {'batch_key': int(getattr(lib, 'addk_sep_%s_batch_key' % d)(C.byref(a))), 'batch_prepare': _prepare(lib, 'addk_sep_%s_batch_prepare' % d, [a])[0]}
+    if d == 'fwd':
+        q['supported'] = int(lib.addk_sep_fwd_supported(C.byref(a)))
+    return q
+
+
+@pytest.mark.parametrize('name,kind,change', FWD_REFUSED, ids=[r[0] for r in FWD_REFUSED])
+def test_sepconv_forward_refuses_what_its_kernel_cannot_read(lib, name, kind, change):
+    """Host only (a refused block never reaches a launch): the unchanged block is supported, has its batch key and prepares; with one field changed
+    addk_sep_fwd_supported is 0, the batch key -1 and addk_sep_fwd_batch_prepare fails, alone and as the second member of a batch."""
+    lib.addk_set_fast_paths(31)
+    op, ar = _fwd_block(lib, kind)
+    good = _queries(lib, 'fwd', ar)
+    assert good['supported'] == 1 and good['batch_key'] == _key(SR.config(L, lib, ar)) and good['batch_prepare'] > 0, (name, good, lib.addk_last_error())
+    _, bad = _fwd_block(lib, kind)
+    change(bad, op.C)
+    q = _queries(lib, 'fwd', bad)
+    assert q['supported'] == 0 and q['batch_key'] == -1 and q['batch_prepare'] < 0, (name, q)
+    assert _prepare(lib, 'addk_sep_fwd_batch_prepare', [ar, bad])[0] < 0 and b'launch 1' in lib.addk_last_error(), name
+    f = SR.config(L, lib, bad)
+    assert f[0] == 0 and f[7] == -1 and tuple(f[1:5]) == SR.CASES[0].variant, (name, f)        # the geometry is still the shape's
+
+
+@pytest.mark.parametrize('name,change', BWD_REFUSED, ids=[r[0] for r in BWD_REFUSED])
+def test_sepconv_backward_refuses_what_its_kernel_cannot_read(lib, name, change):
+    """The same for addk_sep_bwd: batch key -1 and a failing addk_sep_bwd_batch_prepare (addk_sep_bwd_rows reads the shape alone and stays)."""
+    lib.addk_set_fast_paths(31)
+    op = SR.CASES[0].op
+    ba = SR.bwd_args(L, op, SR.PTR, accumulate=1)
+    good = _queries(lib, 'bwd', ba)
+    assert good['batch_key'] == _key(SR.config(L, lib, ba)) and good['batch_prepare'] > 0, (name, good, lib.addk_last_error())
+    bad = SR.bwd_args(L, op, SR.PTR, accumulate=1)
+    change(bad, op.C)
+    q = _queries(lib, 'bwd', bad)
+    assert q['batch_key'] == -1 and q['batch_prepare'] < 0, (name, q)
+    assert _prepare(lib, 'addk_sep_bwd_batch_prepare', [ba, bad])[0] < 0 and b'launch 1' in lib.addk_last_error(), name
+    assert int(lib.addk_sep_bwd_rows(C.byref(bad))) == int(lib.addk_sep_bwd_rows(C.byref(ba))) == 24
+
+
+def test_sepconv_takes_every_source_form_it_documents(lib):
+    """the four forms of addk_src (a, b present or not, relu 0 or 1) on the source and on the terms, g = NULL and dab = NULL: all supported"""
+    lib.addk_set_fast_paths(31)
+    op = SR.CASES[0].op
+    for form in range(4):
+        assert _queries(lib, 'fwd', SR.fwd_args(L, op, SR.PTR, form, t=True, stats_rows=64))['supported'] == 1, form
+        for g, dab in ((True, True), (True, False), (False, False)):
+            assert _queries(lib, 'bwd', SR.bwd_args(L, op, SR.PTR, form, g=g, dab=dab))['batch_prepare'] > 0, (form, g, dab)
+    for j in range(len(SR.EPILOGUES)):
+        assert _queries(lib, 'fwd', SR.fwd_args(L, op, SR.PTR, epilogue=j))['supported'] == 1, j
+
+
+def test_no_plan_hands_a_sepconv_a_resampled_or_half_affine_source():
+    """Graph.src sets rs_hw only with fold=True, and a and b together or not at all; sep_half, _sep_bwd_args and the sum terms never ask for a fold"""
+    import inspect
+    src = inspect.getsource(P.Graph.src)
+    assert 's.a, s.b = act.bn.a.ptr, act.bn.b.ptr' in src and 'if r is not act.raw' in src
+    for fn in (P.Graph.sep_half, P.Graph._sep_bwd_args):
+        text = inspect.getsource(fn)
+        assert 'self.src(' in text and 'fold' not in text, fn.__name__
 
 
 @pytest.mark.parametrize('shape,expect', DW, ids=DW_IDS)
