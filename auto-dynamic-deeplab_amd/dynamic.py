@@ -18,7 +18,11 @@ quirk of the working 'edm' path and stays only there: the heads training optimis
 output='labels' (both plans): every exit ends in a label head instead (plan.Graph.head 'labels', heads.py) and returns the plan-owned uint8 [1,H,W]
 arg-max map of its logits; no [N,C,H,W] buffer exists.  'edm': [early head k] and the final head end in one `label_upsample` launch.
 'entropy' / 'max': the gate launch leaves the map as well (`gate_label_upsample`), so nothing is left to replay for the image that
-leaves — [trunk up to exit k] [head k + the gate-and-labels launch] ... [remaining cells + final head + its `label_upsample`]."""
+leaves — [trunk up to exit k] [head k + the gate-and-labels launch] ... [remaining cells + final head + its `label_upsample`].
+
+What every gated front end shares lives here (BatchedGate below, segment.TiledSegmenter): the gate is read by GatePlan.set_threshold /
+gate_values / leaves and by nothing else; gate_thresholds maps a threshold argument to one float per gate; PinnedWords carries a call's
+index words and tables to the device; rows_table / gather_rows build and issue an `addk_gather_rows` launch; whole_rows says what it can move."""
 import collections
 import ctypes as C
 import os
@@ -94,11 +98,9 @@ class DynamicPlan:
         self.g = g = Graph(x.device, False, False, None)
         if output == 'labels':
             g.head, g.lut = 'labels', lut
-        self._conf_host = torch.zeros(words, dtype=torch.float32)
-        self._conf_evt = None
-        if x.is_cuda:                                   # (dry-run planning on CPU in tests/test_plan_dryrun.py builds plans without a device)
-            self._conf_host = self._conf_host.pin_memory()
-            self._conf_evt = torch.cuda.Event()
+        self._conf_host = host_words(words, torch.float32, x.device)
+        # (dry-run planning on CPU in tests/test_plan_dryrun.py builds plans without a device)
+        self._conf_evt = torch.cuda.Event() if x.is_cuda else None
         a, self.inref = g.input_nchw(x)
         self.in_name = a.raw.buf.region[0]             # the input staging buffer: what depends on the image is reachable from it
         return a
@@ -170,6 +172,76 @@ class DynamicPlan:
 KINDS = ('entropy', 'max')
 
 
+def host_words(shape, dtype, device):
+    """zeroed host words that `device` copies from or writes to: pinned when it is a GPU, plain memory in a dry run"""
+    t = torch.zeros(shape, dtype=dtype)
+    return t.pin_memory() if device.type == 'cuda' else t
+
+
+class PinnedWords:
+    """Host words [slots, ...] (host_words), their device copy and one event per slot: what a call's index words and tables travel
+    through.  put(slot, *rows) waits for the slot's previous copy — that one copy, not the device —, writes the rows, copies the slot
+    without blocking and records.  Which slot to take is the caller's business; on the CPU there is nothing to pin or to wait for."""
+
+    def __init__(self, shape, dtype, device):
+        self.host = host_words(shape, dtype, device)
+        self.dev = torch.zeros(shape, dtype=dtype, device=device)
+        self.evt = [torch.cuda.Event() for _ in range(shape[0])] if device.type == 'cuda' else None
+
+    def put(self, slot, *rows):
+        """row r of the slot begins with rows[r] (a list or a tensor; what lies behind it stays) -> the slot's device words"""
+        if self.evt:
+            self.evt[slot].synchronize()               # the previous copy out of these pinned words has been made
+        for r, vals in enumerate(rows):
+            if len(vals):
+                self.host[slot, r, :len(vals)] = torch.as_tensor(vals, dtype=self.host.dtype)
+        self.dev[slot].copy_(self.host[slot], non_blocking=True)
+        if self.evt:
+            self.evt[slot].record()
+        return self.dev[slot]
+
+
+def rows_table(g, triples):
+    """(src, dst, bytes per row) of every buffer an `addk_gather_rows` launch moves -> (its item table on the device of plan `g`, kept
+    alive with the plan; the number of items)"""
+    arr = (L.RowsItem * len(triples))()
+    for it, (src, dst, nbytes) in zip(arr, triples):
+        it.src, it.dst, it.row_bytes = src, dst, nbytes
+    return g._table(bytes(arr)), len(triples)
+
+
+def gather_rows(g, table, src_row, dst_row, nrows):
+    """one addk_gather_rows launch on the current stream, through the plan's launch loop: row src_row[i] of every item's source -> row
+    dst_row[i] of its destination (device int32 words; None: row i)"""
+    a = L.GatherRowsArgs()
+    a.items, a.nitems, a.nrows = table[0].data_ptr(), table[1], nrows
+    a.src_row = None if src_row is None else src_row.data_ptr()
+    a.dst_row = None if dst_row is None else dst_row.data_ptr()
+    g.run([Cmd('gather_rows', g.lib.addk_gather_rows, (C.byref(a),))], _plan.current_stream())
+
+
+def whole_rows(buf, batch):
+    """is plan buffer `buf` one whole NHWC tensor of `batch` images — what gather_rows can move image by image"""
+    return buf.geom is not None and buf.geom[0] == batch and buf.n == batch * buf.geom[1] * buf.geom[2] * buf.geom[3]
+
+
+def finite_threshold(thr):
+    """a finite word for the kernel: every top probability lies in (0, 1], so clamping an infinite threshold changes no comparison"""
+    return min(max(thr, -1.0), 2.0)
+
+
+def gate_thresholds(threshold, gates):
+    """a number, or one number per gate -> one float per gate"""
+    try:
+        return [float(threshold)] * gates
+    except TypeError:
+        pass
+    thr = [float(v) for v in threshold]
+    if len(thr) != gates:
+        raise ValueError('one threshold per gate: %d gates, %d thresholds' % (gates, len(thr)))
+    return thr
+
+
 def check_temperature(temperature, nex):
     """`temperature` of a tempered gate or profile -> None, or one positive finite float per exit of forward() (`nex` of them: what
     calibrate.ExitCalibration.fit() returns).  A scalar serves every exit; anything else is a ValueError."""
@@ -213,6 +285,7 @@ class GatePlan(DynamicPlan):
         if head is not None:
             g.head = head
         self._thr = torch.zeros(1, dtype=torch.float32, device=x.device)      # the word the 'max' gate compares against
+        self._thr_word = 0.0                                                  # ... and what it holds
         self.nex = model.num_exits()
         self.temperature, self._temp = None, None
         if temperature is not None:
@@ -247,6 +320,31 @@ class GatePlan(DynamicPlan):
             if self.nex > 1:
                 self._temp.copy_(inverse_words(ts[:self.nex - 1]))
             self.temperature = ts
+
+    def set_threshold(self, thr):
+        """The threshold of the gate launches that follow, as the finite word they read; written only when it changes."""
+        word = finite_threshold(thr)
+        if word != self._thr_word:
+            self._thr.fill_(word)
+            self._thr_word = word
+
+    def gate_values(self, k, n=1):
+        """The gate values of exit k for rows 0 .. n-1 as Python floats, once the launches issued so far have run: the host waits on
+        ONE event for the 2n pinned words (entropy, share) per row — the gate launch wrote them itself, or an asynchronous copy of
+        `gate_out` does.  The words are fp32 widened exactly to double, and the fused heads leave gate_scale == 1.0, so a value is bit for
+        bit the word the device wrote; only the stand-alone entropy kernel leaves a sum for the host to scale."""
+        h = self.heads[k]
+        if not h.gate_fused:
+            self._conf_host[:2 * n].copy_(h.gate_out.reshape(-1)[:2 * n], non_blocking=True)
+        if self._conf_evt is not None:
+            self._conf_evt.record()
+            self._conf_evt.synchronize()
+        words = self._conf_host[:2 * n].tolist()
+        return [w * h.gate_scale for w in words[0::2]] if self.kind == 'entropy' else words[1::2]
+
+    def leaves(self, value, thr):
+        """the rule: entropy BELOW the threshold, or the share of pixels with top probability above the threshold ABOVE it"""
+        return value < thr if self.kind == 'entropy' else value > thr
 
     def taint(self):
         """`image_dep`: which launches depend on the image — those that (transitively, in list order) read something written from the
@@ -301,25 +399,16 @@ class GatePlan(DynamicPlan):
         self.calls += 1
         self.x_static.copy_(x)
         thr = float(threshold)
-        # a finite word for the kernel: every top probability lies in (0, 1], so clamping an infinite threshold changes no comparison
-        self._thr.fill_(min(max(thr, -1.0), 2.0))
+        self.set_threshold(thr)
         pos, value = 0, None
-        col = 0 if self.kind == 'entropy' else 1
         with torch.no_grad():
-            for k, end in enumerate(self.trunk_end):
-                h = self.heads[k]
-                cut, hend = self.head_rng[k]
+            for k, (cut, hend) in enumerate(self.head_rng):
                 self._seg(pos, cut)
-                if not h.gate_fused:
-                    self._conf_host.copy_(h.gate_out.reshape(-1)[:2], non_blocking=True)
-                if self._conf_evt is not None:
-                    self._conf_evt.record()
-                    self._conf_evt.synchronize()                      # the host waits for these two words only
-                value = float(self._conf_host[col]) * (h.gate_scale if col == 0 else 1.0)
-                if (value < thr) if self.kind == 'entropy' else (value > thr):
+                value = self.gate_values(k)[0]
+                if self.leaves(value, thr):
                     if hend > cut:
                         self._seg(cut, hend)
-                    return h.y, 1, value
+                    return self.heads[k].y, 1, value
                 pos = hend
             self._seg(pos, -1)
         return self.final.y, 0, value
@@ -351,7 +440,7 @@ def pair_live(pm, pn, k):
     pairs = []
     for x, y in zip(a, b):
         for p, buf in ((pm, x), (pn, y)):
-            if buf.geom is None or buf.geom[0] != p.batch or buf.n != p.batch * buf.geom[1] * buf.geom[2] * buf.geom[3]:
+            if not whole_rows(buf, p.batch):
                 raise L.AddkError('gate %d: live buffer %r of the batch-%d plan is not one whole NHWC tensor of its batch' % (k, buf.region[0], p.batch))
         if x.geom[1:] != y.geom[1:]:
             raise L.AddkError('gate %d: live buffers %r / %r differ per image: (H, W, ld) %r and %r' % (k, x.region[0], y.region[0], x.geom[1:], y.geom[1:]))
@@ -392,15 +481,10 @@ class BatchedGate:
         self.temperature = check_temperature(temperature, self.gates + 1)
         self.subs = {}                 # live batch size -> _SubPlan
         self.tables = {}               # ('state', m, n, k) / ('labels', n, k) -> (device item table, items, pairs)
-        cuda = self.device.type == 'cuda'
         self.labels = torch.zeros((self.N,) + shape[2:], dtype=torch.uint8, device=self.device)
-        # index words: per gate (and once more for the final head) three rows — the leavers' rows in the plan, their original indices, the
-        # stayers' rows in the plan.  Written on the host, copied to the device words the launches read; one event per slot guards the reuse
-        self._idx_host = torch.zeros((self.gates + 1, 3, self.N), dtype=torch.int32)
-        self._idx_dev = torch.zeros((self.gates + 1, 3, self.N), dtype=torch.int32, device=self.device)
-        self._idx_evt = [None] * (self.gates + 1)
-        if cuda:
-            self._idx_host = self._idx_host.pin_memory()
+        # index words: per gate (and once more for the final head) a slot of three rows — the leavers' rows in the plan, their original
+        # indices, the stayers' rows in the plan; a row that is not given keeps what it held
+        self._idx = PinnedWords((self.gates + 1, 3, self.N), torch.int32, self.device)
         self.counts = collections.Counter()    # 'state' / 'labels' gather_rows launches, ('seg', n) segments run per sub-plan; all calls
         self.trace = []                # last call: (live batch, begin, end) of every segment run
         self.moves = []                # last call: (batch before, batch after, gate, rows that stayed)
@@ -430,7 +514,7 @@ class BatchedGate:
     def nbytes(self):
         """device bytes: {live batch size: its sub-plan's} and 'total' (the sub-plans built so far, the output map, the index words)"""
         per = {n: int(p.g.nbytes) for n, p in sorted(self.subs.items())}
-        per['total'] = sum(per.values()) + self.labels.numel() + 4 * self._idx_dev.numel()
+        per['total'] = sum(per.values()) + self.labels.numel() + 4 * self._idx.dev.numel()
         return per
 
     def close(self):
@@ -449,51 +533,24 @@ class BatchedGate:
         self.counts[('seg', plan.batch)] += 1
         plan._seg(i0, i1)
 
-    def _items(self, key, triples):
-        tab = self.tables.get(key)
-        if tab is None:
-            arr = (L.RowsItem * len(triples))()
-            for it, (src, dst, nbytes) in zip(arr, triples):
-                it.src, it.dst, it.row_bytes = src, dst, nbytes
-            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            tab = self.tables[key] = (host.to(self.device) if self.device.type == 'cuda' else host.clone(), len(triples))
-        return tab
-
     def _gather(self, what, plan, table, src_row, dst_row, nrows):
-        """one addk_gather_rows launch on the current stream, through the plan's launch loop"""
-        a = L.GatherRowsArgs()
-        a.items, a.nitems, a.nrows = table[0].data_ptr(), table[1], nrows
-        a.src_row = None if src_row is None else src_row.data_ptr()
-        a.dst_row = None if dst_row is None else dst_row.data_ptr()
         self.counts[what] += 1
-        plan.g.run([Cmd('gather_rows', plan.g.lib.addk_gather_rows, (C.byref(a),))], _plan.current_stream())
-
-    def _set_idx(self, slot, *rows):
-        if self._idx_evt[slot] is not None:
-            self._idx_evt[slot].synchronize()          # the previous copy out of these pinned words has been made
-        for r, vals in enumerate(rows):
-            if vals:
-                self._idx_host[slot, r, :len(vals)] = torch.tensor(vals, dtype=torch.int32)
-        self._idx_dev[slot].copy_(self._idx_host[slot], non_blocking=True)
-        if self.device.type == 'cuda':
-            if self._idx_evt[slot] is None:
-                self._idx_evt[slot] = torch.cuda.Event()
-            self._idx_evt[slot].record()
-        return self._idx_dev[slot]
+        gather_rows(plan.g, table, src_row, dst_row, nrows)
 
     def _scatter(self, plan, k, y, src_row, dst_row, nrows):
         """rows of exit k's label map of `plan` -> the output map, at the images' original indices"""
         H, W = self.shape[2:]
-        table = self._items(('labels', plan.batch, k), [(y.data_ptr(), self.labels.data_ptr(), H * W)])
-        self._gather('labels', plan, table, src_row, dst_row, nrows)
+        key = ('labels', plan.batch, k)
+        if key not in self.tables:
+            self.tables[key] = rows_table(plan.g, [(y.data_ptr(), self.labels.data_ptr(), H * W)])
+        self._gather('labels', plan, self.tables[key], src_row, dst_row, nrows)
 
     def _move(self, pm, pn, k, stay, src_row):
         """the live state behind gate k: rows `stay` of plan pm -> rows 0.. of plan pn"""
         key = ('state', pm.batch, pn.batch, k)
         if key not in self.tables:
             pairs = pair_live(pm, pn, k)
-            self._items(key, [(x.ptr, y.ptr, 4 * words) for x, y, words in pairs])
-            self.tables[key] += (pairs,)
+            self.tables[key] = rows_table(pn.g, [(x.ptr, y.ptr, 4 * words) for x, y, words in pairs]) + (pairs,)
         replay = pn.live(pn.head_rng[k][1])[1]
         if replay:
             pn.g.run(replay, _plan.current_stream())
@@ -510,18 +567,8 @@ class BatchedGate:
         return out
 
     # ---- one call --------------------------------------------------------------------------------------------------------
-    def _thresholds(self, threshold):
-        try:
-            return [float(threshold)] * self.gates
-        except TypeError:
-            pass
-        thr = [float(v) for v in threshold]
-        if len(thr) != self.gates:
-            raise ValueError('one threshold per gate: %d gates, %d thresholds' % (self.gates, len(thr)))
-        return thr
-
     def run(self, images, threshold):
-        thr = self._thresholds(threshold)
+        thr = gate_thresholds(threshold, self.gates)
         if tuple(images.shape) != self.shape:
             raise ValueError('this BatchedGate was built for %r (got %r)' % (self.shape, tuple(images.shape)))
         N, G = self.N, self.gates
@@ -529,36 +576,26 @@ class BatchedGate:
         values = torch.full((N, G), float('nan'), dtype=torch.float32)
         self.calls += 1
         self.trace, self.moves = [], []
-        entropy = self.kind == 'entropy'
-        col = 0 if entropy else 1
         plan = self.sub(N)
         plan.calls += 1
         plan.x_static.copy_(images)
         idx, pos = list(range(N)), 0            # original index of every live row; where the live plan continues
         with torch.no_grad():
             for k in range(G):
-                h = plan.heads[k]
                 cut, hend = plan.head_rng[k]
-                # a finite word for the kernel: every top probability lies in (0, 1], so clamping an infinite threshold changes no comparison
-                plan._thr.fill_(min(max(thr[k], -1.0), 2.0))
+                plan.set_threshold(thr[k])
                 self._seg(plan, pos, cut)
                 n = len(idx)
-                if not h.gate_fused:
-                    plan._conf_host.copy_(h.gate_out.reshape(-1)[:2 * n], non_blocking=True)
-                if plan._conf_evt is not None:
-                    plan._conf_evt.record()
-                    plan._conf_evt.synchronize()                  # the host waits for these 2n words only
-                words = plan._conf_host.tolist()
-                vals = [words[2 * i + col] * (h.gate_scale if col == 0 else 1.0) for i in range(n)]
-                leave = [i for i in range(n) if ((vals[i] < thr[k]) if entropy else (vals[i] > thr[k]))]
+                vals = plan.gate_values(k, n)
+                leave = [i for i in range(n) if plan.leaves(vals[i], thr[k])]
                 stay = [i for i in range(n) if i not in leave]
                 for i in range(n):
                     values[idx[i], k] = vals[i]
                 if leave:
                     if hend > cut:
                         self._seg(plan, cut, hend)
-                    d = self._set_idx(k, leave, [idx[i] for i in leave], stay)
-                    self._scatter(plan, k, h.y, d[0], d[1], len(leave))
+                    d = self._idx.put(k, leave, [idx[i] for i in leave], stay)
+                    self._scatter(plan, k, plan.heads[k].y, d[0], d[1], len(leave))
                     for i in leave:
                         exits[idx[i]] = k
                     if not stay:
@@ -570,6 +607,6 @@ class BatchedGate:
                     idx = [idx[i] for i in stay]
                 pos = plan.head_rng[k][1]
             self._seg(plan, pos, -1)
-            d = self._set_idx(G, [], idx, [])
+            d = self._idx.put(G, [], idx, [])
             self._scatter(plan, G, plan.final.y, None, d[1], len(idx))
         return self.labels, exits, values

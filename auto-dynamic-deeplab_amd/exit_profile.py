@@ -23,7 +23,7 @@ import torch
 
 from . import _lib as L
 from . import trimap as _trimap
-from .dynamic import KINDS, check_temperature, inverse_words
+from .dynamic import KINDS, check_temperature, finite_threshold, inverse_words
 from .metrics import mean_iou
 from .resident import InferenceStep
 
@@ -129,9 +129,9 @@ class ExitProfile(InferenceStep):
         self.reset()
 
     def _write_thresholds(self):
-        # the word GatePlan.run hands its kernel: every top probability lies in (0, 1], so the clamp changes no comparison
+        # the words GatePlan.set_threshold hands its kernel
         if self.max_thresholds:
-            self.thr.copy_(torch.tensor([min(max(t, -1.0), 2.0) for t in self.max_thresholds], dtype=torch.float32))
+            self.thr.copy_(torch.tensor([finite_threshold(t) for t in self.max_thresholds], dtype=torch.float32))
 
     def set_max_thresholds(self, max_thresholds):
         """Other top-probability thresholds for the steps that follow.  The same number of them: the words live in a device buffer the

@@ -1,6 +1,7 @@
 """The resident inference plan: the path in inference form, emitted ONCE over resident input (and target) buffers into a static
 plan.Graph and replayed as a single hipGraph launch.  validate.ValidationStep, exit_profile.ExitProfile and segment.Segmenter are
-this plan with another logits head (plan.Graph.head, emitted by heads.py) and another result; each supplies `head`, `_emit` and its own `step`."""
+this plan with another logits head (plan.Graph.head, emitted by heads.py) and another result; each supplies `head`, `_emit` and its own `step`
+(segment.Segmenter and MultiViewSegmenter share theirs: segment._LabelStep)."""
 import torch
 
 from . import _lib as L

@@ -46,6 +46,11 @@ window's stored logits are the static plan's at the exit it left at; the stitchi
 
     seg = TiledSegmenter(model, (B, 3, 769, 769), stride=(513, 513), threshold=0.35, confidence='entropy')
     maps = seg.segment(images)               # seg.exits: the exit of every window of seg.tiles; seg.values: its gate values
+
+The view arguments of both multi-view front ends are checked by view_spec.  Inside TiledSegmenter every image is (im, H, W, grids), one grid
+per view — the single-view call is one view under its own kernels, chosen once in __init__ —, and a call is _windows (bookkeeping),
+_run_static / _run_gated (the chunks) and _stitch.  The gate reader, the thresholds, the pinned index words and the `addk_gather_rows`
+tables and launches are dynamic.py's (GatePlan.gate_values / leaves, gate_thresholds, PinnedWords, rows_table, gather_rows).
 """
 import collections
 import ctypes as C
@@ -61,13 +66,30 @@ from .resident import InferenceStep
 from .sched import Cmd
 
 
-class Segmenter(InferenceStep):
+def _require_add(who, model):
+    from .modeling.ADD import ADD
+    if not isinstance(model, ADD):
+        raise TypeError('%s takes an ADD model (got %s)' % (type(who).__name__, type(model).__name__))
+
+
+class _LabelStep(InferenceStep):
+    """What the resident segmenters share: the step.  `_labels()`: the plan-owned map the head of the CURRENT plan writes."""
+
+    def step(self, images=None):
+        """-> the uint8 [N,H,W] label map of the resident batch (or of `images` if given).  The tensor belongs to the plan and is
+        overwritten by the next step.  No host synchronisation, except once when the third call captures the hipGraph."""
+        if images is not None:
+            self.load_batch(images)
+        with torch.no_grad():
+            self._replay()
+        return self._labels()
+
+
+class Segmenter(_LabelStep):
     head = 'labels'
 
     def __init__(self, model, batch_shape, exit=-1, label_lut=None, use_graph=None, nstreams=None):
-        from .modeling.ADD import ADD
-        if not isinstance(model, ADD):
-            raise TypeError('Segmenter takes an ADD model (got %s)' % type(model).__name__)
+        _require_add(self, model)
         self.exit = range(model.num_exits())[exit]             # forward()'s output list; IndexError out of range
         self.lut = _label_lut(label_lut, next(model.parameters()).device)
         super().__init__(model, batch_shape, use_graph, nstreams, target=False)
@@ -78,13 +100,7 @@ class Segmenter(InferenceStep):
         self.out = self.model._emit_exit(g, a, self.exit)
         assert self.out.head == 'labels' and tuple(self.out.y.shape) == (N, H, W), 'the model did not end in Graph.resize_to_nchw'
 
-    def step(self, images=None):
-        """-> the uint8 [N,H,W] label map of the resident batch (or of `images` if given).  The tensor belongs to the plan and is
-        overwritten by the next step.  No host synchronisation, except once when the third call captures the hipGraph."""
-        if images is not None:
-            self.load_batch(images)
-        with torch.no_grad():
-            self._replay()
+    def _labels(self):
         return self.out.y
 
 
@@ -93,7 +109,33 @@ def view_size(H, W, scale):
     return int(math.floor(H * scale + 0.5)), int(math.floor(W * scale + 0.5))
 
 
-class MultiViewSegmenter(InferenceStep):
+def view_spec(scales, flip, weights, size=None):
+    """The view list of `scales` / `flip` / `weights`, checked -> (the scales as floats, views per scale: the plain one and with `flip`
+    the mirrored one, one positive weight per view in kernel order — default 1 / views).  `size`: the (H, W) a resident plan builds
+    every view of."""
+    scales = tuple(float(s) for s in scales)
+    per = 2 if flip else 1
+    if not scales:
+        raise ValueError('scales is empty')
+    if any(not (s > 0 and math.isfinite(s)) for s in scales):
+        raise ValueError('scales must be positive (got %r)' % (scales,))
+    if len(scales) * per > L.MAX_VIEWS:
+        raise ValueError('at most %d views (got %d scales%s)' % (L.MAX_VIEWS, len(scales), ' with flip' if flip else ''))
+    for s in scales if size is not None else ():
+        hv, wv = view_size(*size, s)
+        # below one pixel nothing is left to run; at 2^15 rows / 2^16 columns the plan's resized sources no longer describe their map
+        if not (1 <= hv < (1 << 15) and 1 <= wv < (1 << 16)):
+            raise ValueError('the plan cannot build the view of scale %g: %dx%d -> %dx%d' % ((s,) + tuple(size) + (hv, wv)))
+    nview = len(scales) * per
+    weights = [1.0 / nview] * nview if weights is None else [float(w) for w in weights]
+    if len(weights) != nview:
+        raise ValueError('one weight per view: %d views, %d weights' % (nview, len(weights)))
+    if any(not (w > 0 and math.isfinite(w)) for w in weights):
+        raise ValueError('weights must be positive and finite (got %r)' % (weights,))
+    return scales, per, weights
+
+
+class MultiViewSegmenter(_LabelStep):
     """Label map of one exit averaged over views.  `views`: [(scale, mirror, (H_v, W_v), (h_v, w_v)), ...] in kernel order — per scale the
     plain view, then (with `flip`) the mirrored one; (H_v, W_v) is the view's input size, (h_v, w_v) its low-resolution logits grid.
     `weights`: one positive number per view in that order (default 1/len(views)).  With `flip` the resident input `x` is [2N,3,H,W]:
@@ -102,31 +144,11 @@ class MultiViewSegmenter(InferenceStep):
 
     def __init__(self, model, batch_shape, scales=(0.75, 1.0, 1.25), flip=True, exit=-1, weights=None, label_lut=None, use_graph=None,
                  nstreams=None):
-        from .modeling.ADD import ADD
-        if not isinstance(model, ADD):
-            raise TypeError('MultiViewSegmenter takes an ADD model (got %s)' % type(model).__name__)
+        _require_add(self, model)
         N, Cin, H, W = (int(v) for v in batch_shape)
-        scales = tuple(float(s) for s in scales)
         self.flip = bool(flip)
-        per = 2 if self.flip else 1
-        if not scales:
-            raise ValueError('scales is empty')
-        if any(not (s > 0 and math.isfinite(s)) for s in scales):
-            raise ValueError('scales must be positive (got %r)' % (scales,))
-        if len(scales) * per > L.MAX_VIEWS:
-            raise ValueError('at most %d views (got %d scales%s)' % (L.MAX_VIEWS, len(scales), ' with flip' if self.flip else ''))
-        self.sizes = [view_size(H, W, s) for s in scales]
-        for s, (hv, wv) in zip(scales, self.sizes):
-            # below one pixel nothing is left to run; at 2^15 rows / 2^16 columns the plan's resized sources no longer describe their map
-            if not (1 <= hv < (1 << 15) and 1 <= wv < (1 << 16)):
-                raise ValueError('the plan cannot build the view of scale %g: %dx%d -> %dx%d' % (s, H, W, hv, wv))
-        nview = len(scales) * per
-        weights = [1.0 / nview] * nview if weights is None else [float(w) for w in weights]
-        if len(weights) != nview:
-            raise ValueError('one weight per view: %d views, %d weights' % (nview, len(weights)))
-        if any(not (w > 0 and math.isfinite(w)) for w in weights):
-            raise ValueError('weights must be positive and finite (got %r)' % (weights,))
-        self.scales, self.weights = scales, weights
+        self.scales, per, self.weights = view_spec(scales, self.flip, weights, (H, W))
+        self.sizes = [view_size(H, W, s) for s in self.scales]
         self.exit = range(model.num_exits())[exit]             # forward()'s output list; IndexError out of range
         self.lut = _label_lut(label_lut, next(model.parameters()).device)
         self.image_shape = (N, Cin, H, W)
@@ -153,13 +175,7 @@ class MultiViewSegmenter(InferenceStep):
         if self.flip:
             self.x[N:].copy_(self.x[:N].flip(3))
 
-    def step(self, images=None):
-        """-> the uint8 [N,H,W] label map of the resident batch (or of `images` if given).  The tensor belongs to the plan and is
-        overwritten by the next step.  No host synchronisation, except once when the third call captures the hipGraph."""
-        if images is not None:
-            self.load_batch(images)
-        with torch.no_grad():
-            self._replay()
+    def _labels(self):
         return self.g.view_labels
 
     def view_logits(self):
@@ -302,7 +318,7 @@ class TileGatePlan(_dynamic.GatePlan):
         for k, cut in enumerate(self.cuts):
             bufs = self.live(cut)[0]
             for b in bufs:
-                if b.geom is None or b.geom[0] != B or b.n != B * b.geom[1] * b.geom[2] * b.geom[3]:
+                if not _dynamic.whole_rows(b, B):
                     raise L.AddkError('gate %d: live buffer %r is not one whole NHWC tensor of the plan\'s batch' % (k, b.region[0]))
             words = [b.n // B for b in bufs]
             pool = [torch.zeros(2 * B * w, dtype=torch.float32, device=x.device) for w in words]
@@ -310,14 +326,8 @@ class TileGatePlan(_dynamic.GatePlan):
             self.pool_bytes += sum(4 * p.numel() for p in pool) + 4 * pext.numel()
             there = [(b.ptr, p.data_ptr(), 4 * w) for b, p, w in zip(bufs, pool, words)] + [(self.ext.data_ptr(), pext.data_ptr(), 8)]
             self.pools.append((bufs, pool, pext))
-            self.park.append(self._items(there))
-            self.unpark.append(self._items([(d, s, n) for s, d, n in there]))
-
-    def _items(self, triples):
-        arr = (L.RowsItem * len(triples))()
-        for it, (src, dst, nbytes) in zip(arr, triples):
-            it.src, it.dst, it.row_bytes = src, dst, nbytes
-        return self.g._table(bytes(arr)), len(triples)
+            self.park.append(_dynamic.rows_table(self.g, there))
+            self.unpark.append(_dynamic.rows_table(self.g, [(d, s, n) for s, d, n in there]))
 
     def stage(self, k):
         """the launch-list range [begin, end) of stage k; end -1: to the end of the list"""
@@ -330,6 +340,17 @@ class TileGatePlan(_dynamic.GatePlan):
         self.runs[key] += 1
         self.calls = self.runs[key] if self.use_graph else 0
         super()._seg(i0, i1)
+
+
+def _fill(block, **vals):
+    """Set those of `vals` that the ctypes block declares (an array field: its first len(value) entries).  The single-view blocks
+    declare no Hv / Wv / mirror / weight / nview: their one view is the image itself."""
+    for f, t in block._fields_:
+        if f in vals:
+            if issubclass(t, C.Array):
+                getattr(block, f)[:len(vals[f])] = vals[f]
+            else:
+                setattr(block, f, vals[f])
 
 
 class TiledSegmenter(InferenceStep):
@@ -347,9 +368,7 @@ class TiledSegmenter(InferenceStep):
 
     def __init__(self, model, tile_shape, stride, exit=-1, label_lut=None, use_graph=None, nstreams=None, scales=None, flip=False, weights=None,
                  threshold=None, confidence='entropy', temperature=None):
-        from .modeling.ADD import ADD
-        if not isinstance(model, ADD):
-            raise TypeError('TiledSegmenter takes an ADD model (got %s)' % type(model).__name__)
+        _require_add(self, model)
         B, Cin, th, tw = (int(v) for v in tile_shape)
         sy, sx = (int(v) for v in stride)
         if B < 1 or Cin < 1 or th < 1 or tw < 1:
@@ -357,23 +376,18 @@ class TiledSegmenter(InferenceStep):
         if not (1 <= sy <= th and 1 <= sx <= tw):
             raise ValueError('the stride must be within 1..tile (got stride %r, tile %dx%d)' % ((sy, sx), th, tw))
         self.stride = (sy, sx)
-        self.views = None
-        if scales is not None or flip or weights is not None:
-            scales = (1.0,) if scales is None else tuple(float(s) for s in scales)
-            per = 2 if flip else 1
-            if not scales:
-                raise ValueError('scales is empty')
-            if any(not (s > 0 and math.isfinite(s)) for s in scales):
-                raise ValueError('scales must be positive (got %r)' % (scales,))
-            if len(scales) * per > L.MAX_VIEWS:
-                raise ValueError('at most %d views (got %d scales%s)' % (L.MAX_VIEWS, len(scales), ' with flip' if flip else ''))
-            nview = len(scales) * per
-            weights = [1.0 / nview] * nview if weights is None else [float(w) for w in weights]
-            if len(weights) != nview:
-                raise ValueError('one weight per view: %d views, %d weights' % (nview, len(weights)))
-            if any(not (w > 0 and math.isfinite(w)) for w in weights):
-                raise ValueError('weights must be positive and finite (got %r)' % (weights,))
-            self.views = [(s, bool(m), weights[i * per + m]) for i, s in enumerate(scales) for m in range(per)]
+        # The ONE place that tells the two forms of a call apart.  Inside, every image is (im, H, W, grids) with one grid per view; the
+        # single-view form is the view (1.0, not mirrored) under its own kernels: window descriptor, gather launch, stitching head, the
+        # head's argument block, where in that block a view's grid goes, and what `tiles` shows of a window
+        if scales is None and not flip and weights is None:
+            self.views, self._views = None, [(1.0, False, 1.0)]
+            self._desc_type, self._gather, self._tile_id = L.TileDesc, 'gather_tiles', lambda k, v, y, x: (k, y, x)
+            self._head = ('label_tiles_upsample', L.LabelTilesArgs, lambda a: [a])
+        else:
+            scales, per, weights = view_spec((1.0,) if scales is None else scales, flip, weights)
+            self.views = self._views = [(s, bool(m), weights[i * per + m]) for i, s in enumerate(scales) for m in range(per)]
+            self._desc_type, self._gather, self._tile_id = L.TileViewDesc, 'gather_tile_views', lambda k, v, y, x: (k, v, y, x)
+            self._head = ('label_tile_views_upsample', L.LabelTileViewsArgs, lambda a: a.view)
         self.exit = range(model.num_exits())[exit]             # forward()'s output list; IndexError out of range
         self.threshold = threshold
         if threshold is not None:
@@ -381,7 +395,7 @@ class TiledSegmenter(InferenceStep):
         self.lut = _label_lut(label_lut, next(model.parameters()).device)
         self.tiles, self.maps, self._images = [], [], []
         self._store = None                                     # [Tcap,h,w,ld]: the low-resolution logits of a call's windows
-        self._desc_host = self._desc_dev = self._desc_evt = None
+        self._desc = None                                      # the call's descriptor table (and extents): dynamic.PinnedWords, one slot
         self._label_buf = None
         super().__init__(model, (B, Cin, th, tw), use_graph, nstreams, target=False)
         self._build()
@@ -391,9 +405,12 @@ class TiledSegmenter(InferenceStep):
         self.out = self.model._emit_exit(g, a, self.exit)
         assert self.out.head == 'tiles' and (self.out.shape[0],) + tuple(self.out.shape[2:]) == (B, th, tw), \
             'the model did not end in Graph.resize_to_nchw'
-        src = self.out.src.raw
+        self._logits_grid(self.out.src.raw)
+
+    def _logits_grid(self, src):
+        """what the store and the heads take from the plan's low-resolution logits `src`: class count, grid, the store's pixel stride"""
         self.ncls, self.low = src.C, (src.H, src.W)
-        self.ld = (src.C + 3) // 4 * 4                         # the store's pixel stride: what the head's 16-byte loader asks for
+        self.ld = (src.C + 3) // 4 * 4                         # what the head's 16-byte loader asks for
 
     # ---------------- gated mode: per-window early exits ----------------
     def _init_gated(self, model, B, confidence, temperature):
@@ -410,21 +427,10 @@ class TiledSegmenter(InferenceStep):
             raise ValueError('gated windows run up to the last exit: exit=%d with a threshold is a contradiction' % self.exit)
         self.kind, self.gates = confidence, nex - 1
         self.temperature = _dynamic.check_temperature(temperature, nex)
-        self._thresholds(self.threshold)
+        _dynamic.gate_thresholds(self.threshold, self.gates)
         self.exits = self.values = None
         self.counts, self.trace = collections.Counter(), []
         self.schedule = TileGateSchedule(B, self.gates)
-
-    def _thresholds(self, threshold):
-        """a number, or one number per gate (BatchedGate._thresholds' rule) -> one float per gate"""
-        try:
-            return [float(threshold)] * self.gates
-        except TypeError:
-            pass
-        thr = [float(v) for v in threshold]
-        if len(thr) != self.gates:
-            raise ValueError('one threshold per gate: %d gates, %d thresholds' % (self.gates, len(thr)))
-        return thr
 
     def set_temperature(self, temperature):
         """Other temperatures for the calls that follow (a tempered gated segmenter only): device words, no rebuild."""
@@ -436,128 +442,88 @@ class TiledSegmenter(InferenceStep):
     def _build(self):
         if self.threshold is None:
             return super()._build()
-        B = self.batch_shape[0]
         plan = self.plan = TileGatePlan(self.model, self.x, self.kind, self.temperature)
         g = self.g = plan.g
         g.nstreams, plan.use_graph = self.nstreams, self.use_graph
         assert not g.bwd and not g.nbt and len(plan.heads) == self.gates
-        src = plan.final.src.raw
-        self.ncls, self.low = src.C, (src.H, src.W)
-        self.ld = (src.C + 3) // 4 * 4
+        self._logits_grid(plan.final.src.raw)
         self._ptrs = self._storage()
         self.nbytes = g.nbytes + plan.pool_bytes
         self.graph, self.calls = None, 0
-        # index words of the scatter / park / unpark launches: written on the host, copied to the device words the launches read; a ring of
-        # slots, one event per slot guards the reuse of its pinned words
-        self._idx_host = torch.zeros((4, 2, B), dtype=torch.int32)
-        self._idx_dev = torch.zeros((4, 2, B), dtype=torch.int32, device=self.dev)
-        if self.dev.type == 'cuda':
-            self._idx_host = self._idx_host.pin_memory()
-        self._idx_evt, self._idx_next = [None] * 4, 0
+        # index words of the scatter / park / unpark launches: a ring of slots, taken in turn (_index)
+        self._idx, self._idx_next = _dynamic.PinnedWords((4, 2, self.batch_shape[0]), torch.int32, self.dev), 0
 
-    def _idx(self, *rows):
-        slot = self._idx_next
-        self._idx_next = (slot + 1) % len(self._idx_evt)
-        if self._idx_evt[slot] is not None:
-            self._idx_evt[slot].synchronize()                  # the previous copy out of these pinned words has been made
-        for r, vals in enumerate(rows):
-            self._idx_host[slot, r, :len(vals)] = torch.tensor(vals, dtype=torch.int32)
-        self._idx_dev[slot].copy_(self._idx_host[slot], non_blocking=True)
-        if self.dev.type == 'cuda':
-            if self._idx_evt[slot] is None:
-                self._idx_evt[slot] = torch.cuda.Event()
-            self._idx_evt[slot].record()
-        return self._idx_dev[slot]
+    def _index(self, *rows):
+        slot, self._idx_next = self._idx_next, (self._idx_next + 1) % 4
+        return self._idx.put(slot, *rows)
 
     def _extents(self, per, cap):
         """the valid extent (vh, vw) of every window in store order, as the bytes of int32 [cap][2]: the part of the window that lies on
         its (view's scaled) image; the rest of it is zero padding, which the gate must not judge"""
         th, tw = self.batch_shape[2:]
-        ext = []
-        for p in per:
-            grids = [(p[1], p[2], p[3], p[4])] if self.views is None else [g[:4] for g in p[3]]
-            for Hv, Wv, ys, xs in grids:
-                ext += [(min(th, Hv - y), min(tw, Wv - x)) for y in ys for x in xs]
+        ext = [(min(th, Hv - y), min(tw, Wv - x)) for _, _, _, grids in per for Hv, Wv, ys, xs, _ in grids for y in ys for x in xs]
         arr = torch.zeros((cap, 2), dtype=torch.int32)
         arr[:len(ext)] = torch.tensor(ext, dtype=torch.int32)
         return arr.numpy().tobytes()
 
-    def _rows(self, table, src_row, dst_row, nrows):
-        a = L.GatherRowsArgs()
-        a.items, a.nitems, a.nrows = table[0].data_ptr(), table[1], nrows
-        a.src_row, a.dst_row = src_row.data_ptr(), None if dst_row is None else dst_row.data_ptr()
-        self._launch('gather_rows', self.lib.addk_gather_rows, C.byref(a))
-
-    def _run_gated(self, table, gather, T, thr):
+    def _run_gated(self, table, T, thr):
         """The windows of a call through the gated plan, in TileGateSchedule's order: every window's logits reach the store from the exit
         it left at, through `addk_scatter_tile_logits`."""
-        plan, (B, Cin, th, tw), G = self.plan, self.batch_shape, self.gates
+        plan, B, G = self.plan, self.batch_shape[0], self.gates
         h, w = self.low
-        entropy = plan.kind == 'entropy'
-        col = 0 if entropy else 1
         self.exits = torch.full((T,), G, dtype=torch.int64)
         self.values = torch.full((T, G), float('nan'), dtype=torch.float32)
         self.trace = []
         cap = -(-T // B) * B
-        ext = self._desc_dev[self._ext_off:self._ext_off + 8 * cap].view(torch.int32).view(cap, 2)
-        word = [None]                                          # what the threshold word holds
+        ext = self._desc.dev.view(-1)[self._ext_off:self._ext_off + 8 * cap].view(torch.int32).view(cap, 2)
 
         def execute(op):
             what = op[0]
             if what == 'gather':
                 _, t0, n = op
-                self._launch(gather[0], gather[1], table + t0 * gather[2], n, Cin, th, tw, self.x.data_ptr(), B)
+                self._cut(table, t0, n)
                 plan.ext[:n].copy_(ext[t0:t0 + n], non_blocking=True)
             elif what == 'run':
                 _, k, ids = op
-                n = len(ids)
                 if k < G:
-                    # a finite word for the kernel: every top probability lies in (0, 1], so clamping an infinite threshold changes no comparison
-                    v = min(max(thr[k], -1.0), 2.0)
-                    if v != word[0]:
-                        plan._thr.fill_(v)
-                        word[0] = v
+                    plan.set_threshold(thr[k])
                 plan._seg(*plan.stage(k))
                 self.counts[('seg', k)] += 1
-                self.trace.append((k, n))
+                self.trace.append((k, len(ids)))
                 if k == G:
                     return None
-                if plan._conf_evt is not None:
-                    plan._conf_evt.record()
-                    plan._conf_evt.synchronize()               # the host waits for these 2n words only
-                words = plan._conf_host[:2 * n].tolist()
-                vals = [words[2 * i + col] for i in range(n)]
+                vals = plan.gate_values(k, len(ids))           # the host waits for these words only
                 self.values[ids, k] = torch.tensor(vals, dtype=torch.float32)
-                return [(v < thr[k]) if entropy else (v > thr[k]) for v in vals]
+                return [plan.leaves(v, thr[k]) for v in vals]
             elif what == 'scatter':
                 _, k, rows, ids = op
-                d = self._idx(rows, ids)
+                d = self._index(rows, ids)
                 src = plan.outs[k].src.raw
                 a = L.ScatterTileLogitsArgs()
                 a.src, a.lds, a.B, a.store, a.ld, a.T = src.ptr, src.ld, B, self._store.data_ptr(), self.ld, self._store.shape[0]
                 a.h, a.w, a.C, a.src_row, a.dst_tile, a.n = h, w, self.ncls, d[0].data_ptr(), d[1].data_ptr(), len(rows)
-                self._launch('scatter_tile_logits', self.lib.addk_scatter_tile_logits, C.byref(a))
+                self._launch('scatter_tile_logits', C.byref(a))
                 self.counts['scatter'] += 1
                 self.exits[ids] = k
             elif what == 'park':
                 _, k, rows, slots = op
-                d = self._idx(rows, slots)
-                self._rows(plan.park[k], d[0], d[1], len(rows))
+                d = self._index(rows, slots)
+                _dynamic.gather_rows(self.g, plan.park[k], d[0], d[1], len(rows))
                 self.counts['park'] += 1
             else:
                 _, k, slots = op
-                d = self._idx(slots)
-                self._rows(plan.unpark[k], d[0], None, len(slots))
+                _dynamic.gather_rows(self.g, plan.unpark[k], self._index(slots)[0], None, len(slots))
                 self.counts['unpark'] += 1
         self.schedule.run(T, execute)
 
     # ---------------- per call ----------------
-    def _launch(self, name, fn, *args):
-        """one launch on the current stream, through the plan's launch loop"""
-        self.g.run([Cmd(name, fn, args)], _plan.current_stream())
+    def _launch(self, name, *args):
+        """one launch of the library's addk_<name> on the current stream, through the plan's launch loop"""
+        self.g.run([Cmd(name, getattr(self.lib, 'addk_' + name), args)], _plan.current_stream())
 
     def _windows(self, images):
-        """-> ([(image tensor [Cin,H,W], H, W, y origins, x origins, first tile)], [(image, y0, x0)]) of a call"""
+        """The window bookkeeping of a call -> ([(image tensor [Cin,H,W], H, W, grids)], `tiles`); grids: per view (Hv, Wv, y origins,
+        x origins, first tile) on the view's scaled image"""
         Cin, th, tw = self.batch_shape[1:]
         if isinstance(images, torch.Tensor):
             if images.dim() != 4:
@@ -574,69 +540,75 @@ class TiledSegmenter(InferenceStep):
                 raise ValueError('image %d: expected normalised float32 (got %s)' % (k, im.dtype))
             _plan.require_device(im)
             H, W = int(im.shape[1]), int(im.shape[2])
-            if self.views is not None:
-                grids = []                                     # per view: (Hv, Wv, y origins, x origins, first tile), on the scaled image
-                for v, (s, _, _) in enumerate(self.views):
-                    Hv, Wv = view_size(H, W, s)
-                    ys, xs = tile_starts(Hv, th, self.stride[0]), tile_starts(Wv, tw, self.stride[1])
-                    grids.append((Hv, Wv, ys, xs, len(tiles)))
-                    tiles += [(k, v, y, x) for y in ys for x in xs]
-                per.append((im.contiguous(), H, W, grids))
-                continue
-            ys, xs = tile_starts(H, th, self.stride[0]), tile_starts(W, tw, self.stride[1])
-            per.append((im.contiguous(), H, W, ys, xs, len(tiles)))
-            tiles += [(k, y, x) for y in ys for x in xs]
+            grids = []
+            for v, (s, _, _) in enumerate(self._views):
+                Hv, Wv = view_size(H, W, s)                    # (H, W) at scale 1
+                ys, xs = tile_starts(Hv, th, self.stride[0]), tile_starts(Wv, tw, self.stride[1])
+                grids.append((Hv, Wv, ys, xs, len(tiles)))
+                tiles += [self._tile_id(k, v, y, x) for y in ys for x in xs]
+            per.append((im.contiguous(), H, W, grids))
         return per, tiles
 
     def _descriptors(self, per, cap):
         """the call's window descriptors in store order, as a ctypes array of `cap` entries (the ones behind the windows stay zero)"""
-        if self.views is None:
-            arr = (L.TileDesc * cap)()
-            i = 0
-            for im, H, W, ys, xs, _ in per:
-                for y in ys:
-                    for x in xs:
-                        d = arr[i]
-                        d.image, d.H, d.W, d.y0, d.x0 = im.data_ptr(), H, W, y, x
-                        i += 1
-            return arr
-        arr = (L.TileViewDesc * cap)()
+        arr = (self._desc_type * cap)()
         i = 0
         for im, H, W, grids in per:
-            for (_, mirror, _), (Hv, Wv, ys, xs, _) in zip(self.views, grids):
+            for (_, mirror, _), (Hv, Wv, ys, xs, _) in zip(self._views, grids):
                 for y in ys:
                     for x in xs:
-                        d = arr[i]
-                        d.image, d.H, d.W, d.Hv, d.Wv, d.y0, d.x0, d.mirror = im.data_ptr(), H, W, Hv, Wv, y, x, int(mirror)
+                        _fill(arr[i], image=im.data_ptr(), H=H, W=W, Hv=Hv, Wv=Wv, y0=y, x0=x, mirror=int(mirror))
                         i += 1
         return arr
 
-    def _upload(self, per, T, gated=False):
-        """The call's descriptor table on the device: written into pinned host words, copied without blocking; an event guards the words'
-        reuse by the next call (it waits for that one copy, not for the device).  `gated`: the windows' valid extents (_extents) travel
-        behind the table, from byte `_ext_off` on."""
+    def _upload(self, per, T):
+        """The call's descriptor table on the device -> its address.  It travels through pinned host words (dynamic.PinnedWords, made
+        again when the table grows): the next call waits for this one copy, not for the device.  Gated: the windows' valid extents
+        (_extents) travel behind the table, from byte `_ext_off` on."""
         B = self.batch_shape[0]
         cap = -(-T // B) * B
-        arr = self._descriptors(per, cap)
-        if gated:
-            self._ext_off = (C.sizeof(arr) + 15) // 16 * 16
-            arr = bytes(arr).ljust(self._ext_off, b'\0') + self._extents(per, cap)
-        nb = len(bytes(arr))
-        if self._desc_host is None or self._desc_host.numel() < nb:
-            self._desc_host = torch.zeros(nb, dtype=torch.uint8)
-            self._desc_dev = torch.zeros(nb, dtype=torch.uint8, device=self.dev)
-            if self.dev.type == 'cuda':
-                self._desc_host = self._desc_host.pin_memory()
-            self._desc_evt = None
-        if self._desc_evt is not None:
-            self._desc_evt.synchronize()
-        self._desc_host[:nb].copy_(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8))
-        self._desc_dev[:nb].copy_(self._desc_host[:nb], non_blocking=True)
-        if self.dev.type == 'cuda':
-            if self._desc_evt is None:
-                self._desc_evt = torch.cuda.Event()
-            self._desc_evt.record()
-        return self._desc_dev.data_ptr()
+        data = bytes(self._descriptors(per, cap))
+        if self.threshold is not None:
+            self._ext_off = (len(data) + 15) // 16 * 16
+            data = data.ljust(self._ext_off, b'\0') + self._extents(per, cap)
+        if self._desc is None or self._desc.host.numel() < len(data):
+            self._desc = _dynamic.PinnedWords((1, 1, len(data)), torch.uint8, self.dev)
+        return self._desc.put(0, torch.frombuffer(bytearray(data), dtype=torch.uint8)).data_ptr()
+
+    def _cut(self, table, t0, n):
+        """one gather launch: windows t0 .. t0+n-1 of the descriptor table -> rows 0 .. n-1 of the resident input"""
+        B, Cin, th, tw = self.batch_shape
+        self._launch(self._gather, table + t0 * C.sizeof(self._desc_type), n, Cin, th, tw, self.x.data_ptr(), B)
+
+    def _run_static(self, table, T):
+        """chunk by chunk through the static plan: gather, replay, the chunk's logits into the store"""
+        B = self.batch_shape[0]
+        logits = self.out.src.raw.view()
+        for t in range(0, T, B):
+            nb = min(B, T - t)
+            self._cut(table, t, nb)
+            self._replay()
+            self._store[t:t + nb, :, :, :self.ncls].copy_(logits[:nb])
+
+    def _stitch(self, per):
+        """one stitching-head launch per image: the store's windows -> the image's label map, a slice of the call's label bytes"""
+        (th, tw), (h, w) = self.batch_shape[2:], self.low
+        name, block, views_of = self._head
+        npix = sum(H * W for _, H, W, _ in per)
+        if self._label_buf is None or self._label_buf.numel() < npix:
+            self._label_buf = torch.zeros(npix, dtype=torch.uint8, device=self.dev)
+        maps, off = [], 0
+        for _, H, W, grids in per:
+            lab = self._label_buf[off:off + H * W].view(H, W)
+            off += H * W
+            a = block()
+            _fill(a, nview=len(grids), logits=self._store.data_ptr(), ld=self.ld, h=h, w=w, th=th, tw=tw, N=1, C=self.ncls, OH=H, OW=W,
+                  lut256=self.lut.data_ptr() if self.lut is not None else None, labels=lab.data_ptr())
+            for v, (_, mirror, weight), (Hv, Wv, ys, xs, t0) in zip(views_of(a), self._views, grids):
+                _fill(v, Hv=Hv, Wv=Wv, t0=t0, ny=len(ys), nx=len(xs), mirror=int(mirror), weight=weight, y0=ys, x0=xs)
+            self._launch(name, C.byref(a))
+            maps.append(lab)
+        return maps
 
     def segment(self, images, threshold=None):
         """-> the uint8 [H_i,W_i] label map of every image: `images` is a tensor [n,Cin,H,W] or a list of [Cin,H_i,W_i] tensors of any sizes,
@@ -650,64 +622,25 @@ class TiledSegmenter(InferenceStep):
         number or one per gate).  Afterwards `exits` is int64 [T] on the host, the exit each window of `tiles` left at; `values` float32
         [T, gates] on the host, NaN where a gate was not evaluated for that window; `counts` ('seg', k) -> how often stage k ran, and the
         'park' / 'unpark' / 'scatter' launches, over all calls; `trace` the last call's (stage, rows) in run order."""
-        lib = self.lib
-        B, Cin, th, tw = self.batch_shape
-        h, w = self.low
         per, tiles = self._windows(images)
         T = len(tiles)
-        gated = self.threshold is not None
-        if gated:
-            thr = self._thresholds(self.threshold if threshold is None else threshold)
+        if self.threshold is not None:
+            thr = _dynamic.gate_thresholds(self.threshold if threshold is None else threshold, self.gates)
         elif threshold is not None:
             raise ValueError('this TiledSegmenter was built without a threshold: its plan has no gates')
         if self._storage() != self._ptrs:          # the parameters moved: the plan (and with it the class count and grid) is rebuilt first
             self._build()
-            h, w = self.low
-        if self._store is None or self._store.shape[0] < T or tuple(self._store.shape[1:]) != (h, w, self.ld):
-            self._store = torch.zeros((T, h, w, self.ld), dtype=torch.float32, device=self.dev)      # outside the graph: it may grow
-        if self.views is None:
-            gather = ('gather_tiles', lib.addk_gather_tiles, C.sizeof(L.TileDesc))
-        else:
-            gather = ('gather_tile_views', lib.addk_gather_tile_views, C.sizeof(L.TileViewDesc))
+        row = self.low + (self.ld,)
+        if self._store is None or self._store.shape[0] < T or tuple(self._store.shape[1:]) != row:
+            self._store = torch.zeros((T,) + row, dtype=torch.float32, device=self.dev)      # outside the graph: it may grow
         with torch.no_grad():
-            if gated:
-                self.calls += 1
-                self._run_gated(self._upload(per, T, gated=True), gather, T, thr)
+            table = self._upload(per, T)
+            if self.threshold is None:
+                self._run_static(table, T)
             else:
-                table = self._upload(per, T)
-                logits = self.out.src.raw.view()
-                for t in range(0, T, B):
-                    nb = min(B, T - t)
-                    self._launch(gather[0], gather[1], table + t * gather[2], nb, Cin, th, tw, self.x.data_ptr(), B)
-                    self._replay()
-                    self._store[t:t + nb, :, :, :self.ncls].copy_(logits[:nb])
-            npix = sum(p[1] * p[2] for p in per)
-            if self._label_buf is None or self._label_buf.numel() < npix:
-                self._label_buf = torch.zeros(npix, dtype=torch.uint8, device=self.dev)
-            maps, off = [], 0
-            for p in per:
-                H, W = p[1], p[2]
-                lab = self._label_buf[off:off + H * W].view(H, W)
-                off += H * W
-                if self.views is not None:
-                    a = L.LabelTileViewsArgs()
-                    a.nview, a.logits, a.ld, a.h, a.w, a.th, a.tw = len(self.views), self._store.data_ptr(), self.ld, h, w, th, tw
-                    a.N, a.C, a.OH, a.OW = 1, self.ncls, H, W
-                    for v, (_, mirror, weight), (Hv, Wv, ys, xs, t0) in zip(a.view, self.views, p[3]):
-                        v.Hv, v.Wv, v.t0, v.ny, v.nx, v.mirror, v.weight = Hv, Wv, t0, len(ys), len(xs), int(mirror), weight
-                        v.y0[:len(ys)], v.x0[:len(xs)] = ys, xs
-                    a.lut256, a.labels = self.lut.data_ptr() if self.lut is not None else None, lab.data_ptr()
-                    self._launch('label_tile_views_upsample', lib.addk_label_tile_views_upsample, C.byref(a))
-                    maps.append(lab)
-                    continue
-                ys, xs, t0 = p[3:]
-                a = L.LabelTilesArgs()
-                a.logits, a.ld, a.h, a.w, a.th, a.tw = self._store.data_ptr(), self.ld, h, w, th, tw
-                a.N, a.C, a.OH, a.OW, a.t0, a.ny, a.nx = 1, self.ncls, H, W, t0, len(ys), len(xs)
-                a.y0[:len(ys)], a.x0[:len(xs)] = ys, xs
-                a.lut256, a.labels = self.lut.data_ptr() if self.lut is not None else None, lab.data_ptr()
-                self._launch('label_tiles_upsample', lib.addk_label_tiles_upsample, C.byref(a))
-                maps.append(lab)
+                self.calls += 1
+                self._run_gated(table, T, thr)
+            maps = self._stitch(per)
         self.tiles, self.maps, self._images = tiles, maps, [p[0] for p in per]      # the images stay alive while the device may read them
         return maps
 

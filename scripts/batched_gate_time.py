@@ -104,7 +104,7 @@ def main():
     moved = sum(4 * words for _, _, words in pairs) * len(stay)
     say('state transition %d -> %d behind gate %d: %d buffers, %.3f MB per image, %.3f MB moved (read once, written once)' % (
         m_, n_, k_, len(pairs), sum(4 * w for _, _, w in pairs) / 1e6, moved / 1e6))
-    src_row = bg._idx_dev[k_][2]
+    src_row = bg._idx.dev[k_][2]
     views = [(x_.t[:m_ * w].view(m_, w), y_.t[:n_ * w].view(n_, w)) for x_, y_, w in pairs]
 
     def copies():

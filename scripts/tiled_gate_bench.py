@@ -29,6 +29,7 @@ for p in (ROOT, os.path.join(ROOT, 'tests')):
 import addk                                                      # noqa: E402,F401
 from addk import _lib as L                                       # noqa: E402
 from addk import plan as _plan                                   # noqa: E402
+from addk.dynamic import gather_rows                             # noqa: E402
 from addk.synth import fill_params, rand_tensor                  # noqa: E402
 from _util import ARCH_C2, GENOTYPE_AUTODEEPLAB, make_args       # noqa: E402
 
@@ -102,7 +103,7 @@ def main():
     assert exits.count(0) == T // 2, exits
     say('g/half exits: %s; trace (stage, rows): %s; plan %.1f MB + pools %.1f MB' % (exits, seg.trace, seg.g.nbytes / 1e6, seg.plan.pool_bytes / 1e6))
     # the new launches alone, at B rows
-    plan, lib = seg.plan, seg.lib
+    plan = seg.plan
     gate = [plan.g.fwd[plan.cuts[0] - 1]]
     assert gate[0].name == 'gate_tiles_upsample'
     # index words of this script's own (rows 0..B-1 -> tiles / ring slots 0..B-1): the segmenter's ring of index words is rewritten by every
@@ -117,9 +118,9 @@ def main():
     moved = {'l/scatter': 4 * h * w * seg.ncls * B, 'l/park': state * B, 'l/unpark': state * B}
     say('live state behind gate 0: %d buffers, %.3f MB per window; a window\'s logits: %.3f MB' % (len(plan.pools[0][0]), state / 1e6, 4 * h * w * seg.ncls / 1e6))
     forms['l/gate'] = lambda: plan.g.run(gate, _plan.current_stream())
-    forms['l/scatter'] = lambda: seg._launch('scatter_tile_logits', lib.addk_scatter_tile_logits, C.byref(sa))
-    forms['l/park'] = lambda: seg._rows(plan.park[0], idx[0], idx[1], B)
-    forms['l/unpark'] = lambda: seg._rows(plan.unpark[0], idx[0], None, B)
+    forms['l/scatter'] = lambda: seg._launch('scatter_tile_logits', C.byref(sa))
+    forms['l/park'] = lambda: gather_rows(seg.g, plan.park[0], idx[0], idx[1], B)
+    forms['l/unpark'] = lambda: gather_rows(seg.g, plan.unpark[0], idx[0], None, B)
     for name in ('l/gate', 'l/scatter', 'l/park', 'l/unpark'):
         for _ in range(4):
             forms[name]()

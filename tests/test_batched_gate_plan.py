@@ -184,8 +184,8 @@ def test_forced_scenario_launches(dry, monkeypatch):
     assert dry['gate_label_upsample'] == 1 and dry['label_upsample'] == 1
     assert dry['nchw_to_nhwc'] == 1                                                              # the batch-2 plan did not stage an input
     assert dry['bn_eval_affine_batch'] == 2                                                      # ... but recomputed its affine table
-    assert bg._idx_host[0].tolist() == [[0, 2, 0, 0], [0, 2, 0, 0], [1, 3, 0, 0]]
-    assert bg._idx_host[1][1].tolist()[:2] == [1, 3]
+    assert bg._idx.host[0].tolist() == [[0, 2, 0, 0], [0, 2, 0, 0], [1, 3, 0, 0]]
+    assert bg._idx.host[1][1].tolist()[:2] == [1, 3]
     # nobody leaves: no state moves, one scatter (the final head's)
     p4._conf_host[:] = 0.9
     dry.clear()

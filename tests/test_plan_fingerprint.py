@@ -6,8 +6,9 @@ a validation plan with its scoring heads and with the stand-alone fallback of 7 
 output='labels', the latter also with ADDK_FUSE_GATE=0), train steps with hard example mining, with self-distillation and with both,
 a MultiViewSegmenter with its default scales and flip, the tempered entropy gate and the tempered top-probability gate with
 output='labels', a calibration plan, a validation plan and a tempered exit-profile plan with the trimap metric, the batch-2 sub-plan of
-a BatchedGate, a Segmenter of 7 classes (the stand-alone label path), and train steps with the soft-Dice term alone and with mining and
-self-distillation, each with and without level batching.
+a BatchedGate, a Segmenter of 7 classes (the stand-alone label path), train steps with the soft-Dice term alone and with mining and
+self-distillation, and the tile plans of a TiledSegmenter (single-view, with two scales and flip, gated by entropy with every stage
+segment of TileGatePlan.stage, gated by the tempered top-probability share), each with and without level batching.
 Every command of every list is compared: order, stream, waits, events, regions and each argument byte, with addresses replaced by
 (allocation, offset); also the plan's size and its buffers.  A refactor of the planner leaves all of it as it is; a change that is
 meant to alter a plan re-records the fixture with the tool and says so."""

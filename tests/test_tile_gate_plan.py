@@ -157,7 +157,7 @@ def test_gated_plan_builds_and_a_call_launches(dry, arch, gates):
     assert seg.exits.tolist() == [0] * T and seg.values[:, 0].tolist() == [0.0] * T and bool(seg.values[:, 1:].isnan().all())
     assert seg.counts == {('seg', 0): 2, 'scatter': 2} and seg.trace == [(0, 3), (0, 3)]
     # the extents travel behind the descriptor table: the window on the 40 x 100 image hangs over it
-    ext = torch.frombuffer(bytearray(seg._desc_host[seg._ext_off:seg._ext_off + 8 * T].numpy().tobytes()), dtype=torch.int32).view(T, 2)
+    ext = torch.frombuffer(bytearray(seg._desc.host.view(-1)[seg._ext_off:seg._ext_off + 8 * T].numpy().tobytes()), dtype=torch.int32).view(T, 2)
     assert ext.tolist() == [[65, 129], [40, 100]] + [[65, 129]] * 4 and seg._ext_off % 16 == 0
     # a threshold nobody passes: every stage runs for every chunk, nothing is parked, the last exit's logits take the same scatter launch
     dry.clear()
@@ -171,7 +171,7 @@ def test_gated_plan_builds_and_a_call_launches(dry, arch, gates):
     assert sv.plan._temp is not None and sv.temperature == (1.5,) * (gates + 1)
     sv.segment([torch.randn(3, 97, 200)])
     assert dry['gather_tile_views'] == math.ceil(len(sv.tiles) / 3) and dry['label_tile_views_upsample'] == 1 and len(sv.tiles) == 2 * (1 + 4)
-    ext = torch.frombuffer(bytearray(sv._desc_host[sv._ext_off:sv._ext_off + 8 * 10].numpy().tobytes()), dtype=torch.int32).view(10, 2)
+    ext = torch.frombuffer(bytearray(sv._desc.host.view(-1)[sv._ext_off:sv._ext_off + 8 * 10].numpy().tobytes()), dtype=torch.int32).view(10, 2)
     assert ext.tolist() == [[49, 100]] * 2 + [[65, 129]] * 8
     sv.set_temperature(2.0)
     assert sv.temperature == (2.0,) * (gates + 1)

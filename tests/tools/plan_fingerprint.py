@@ -367,6 +367,32 @@ def _batched_gate(F, shape, kind, n):
     return g, [('fwd', g.fwd)], extra, (bg, m)
 
 
+def _tiled(F, tile, stride, **kw):
+    """sliding-window label maps: the tile plan of a TiledSegmenter; with `threshold=` the gated tile plan (TileGatePlan), its launch
+    list and every stage segment it replays (TileGatePlan.stage).  The known tensors are named one by one, so that no attribute the
+    front end gains or loses moves an ordinal."""
+    from addk.segment import TiledSegmenter
+    m = _model(F, train=False)
+    seg = TiledSegmenter(m, tile, stride, use_graph=False, nstreams=2, **kw)
+    g = seg.g
+    lists, extra = [('fwd', g.fwd)], [seg.x]
+    if seg.threshold is None:
+        extra += _tensors(seg.inref, seg.out)
+    else:
+        plan = seg.plan
+        with torch.no_grad():
+            for k in range(seg.gates + 1):
+                i0, i1 = plan.stage(k)
+                plan._seg(i0, i1)
+                lists.append(('stage%d' % k, plan.segs[(i0, i1 if i1 >= 0 else len(g.fwd))]))
+        extra += [plan.ext, plan._thr, plan._temp] + _tensors(plan.inref, *plan.outs)
+        for _, pool, pext in plan.pools:
+            extra += list(pool) + [pext]
+    return g, lists, extra + list(m.buffers()), (seg, m)
+
+
+TILE, TILE_STRIDE = (3, 3, 65, 129), (32, 71)            # what the tile dry tests use (tests/test_tile_gate_plan.py)
+
 PLANS = (
     ('c2_train_step', lambda: _train_step(20, (2, 3, 1024, 2048))),          # the flagship: config 2, F = 20, want_grad
     ('c2_inference', lambda: _module_plan(20, (1, 3, 1024, 2048), False)),
@@ -399,6 +425,10 @@ PLANS = (
     ('segmenter_7_classes', lambda: _segmenter(4, (1, 3, 33, 65), classes=7)),                          # addk_label_upsample_supported == 0: the cold path
     ('train_step_dice', lambda: _train_step(4, (2, 3, 65, 129), dice=(0.5, 1.0))),                      # dice_stats + ce_upsample_dice per exit
     ('train_step_dice_distill_ohem', lambda: _train_step(4, (2, 3, 65, 129), ohem=(0.7, 1000), distill=(0.5, 2.0), dice=(0.5, 1.0))),
+    ('tiled_segmenter', lambda: _tiled(4, TILE, TILE_STRIDE)),                                          # the 'tiles' head: the exit's low-resolution logits
+    ('tiled_segmenter_views', lambda: _tiled(4, TILE, TILE_STRIDE, scales=(0.75, 1.0), flip=True)),    # the same tile plan
+    ('tiled_gate_entropy', lambda: _tiled(4, TILE, TILE_STRIDE, threshold=0.35, confidence='entropy')),   # gate_tiles_upsample, cut into stages
+    ('tiled_gate_max_tempered', lambda: _tiled(4, TILE, TILE_STRIDE, threshold=0.35, confidence='max', temperature=1.5)),
 )
 
 
