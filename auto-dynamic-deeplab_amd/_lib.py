@@ -89,6 +89,13 @@ class CeUpsampleDiceArgs(C.Structure):
     _fields_ = [('kd', CeUpsampleKdArgs), ('coef', vp)]
 
 
+CE_SHAPE_NONE, CE_SHAPE_FOCAL, CE_SHAPE_SMOOTH = 0, 1, 2
+
+
+class CeUpsampleShapedArgs(C.Structure):
+    _fields_ = [('dice', CeUpsampleDiceArgs), ('shape', i32), ('gamma', f32), ('eps', f32)]
+
+
 class ScoreUpsampleArgs(C.Structure):
     _fields_ = [('logits', vp), ('ld', i32), ('N', i32), ('H', i32), ('W', i32), ('C', i32), ('OH', i32), ('OW', i32),
                 ('target', vp), ('class_w', vp), ('ignore_index', i32), ('wsum', vp), ('scale', f32), ('loss_out', vp),
@@ -263,6 +270,7 @@ STRUCTS = {
     'addk_bn_finalize_args': BnFinalizeArgs, 'addk_sep_args': SepArgs, 'addk_sep_bwd_args': SepBwdArgs,
     'addk_ce_upsample_args': CeUpsampleArgs, 'addk_ohem_select_args': OhemSelectArgs, 'addk_ce_upsample_ohem_args': CeUpsampleOhemArgs,
     'addk_ce_upsample_kd_args': CeUpsampleKdArgs, 'addk_dice_stats_args': DiceStatsArgs, 'addk_ce_upsample_dice_args': CeUpsampleDiceArgs,
+    'addk_ce_upsample_shaped_args': CeUpsampleShapedArgs,
     'addk_score_upsample_args': ScoreUpsampleArgs, 'addk_gate_upsample_args': GateUpsampleArgs, 'addk_label_upsample_args': LabelUpsampleArgs,
     'addk_gate_label_upsample_args': GateLabelUpsampleArgs, 'addk_view': View, 'addk_label_views_args': LabelViewsArgs,
     'addk_tile_desc': TileDesc, 'addk_label_tiles_args': LabelTilesArgs,
@@ -396,6 +404,8 @@ _SIGS = {
     'addk_dice_stats_ws_bytes_classes': (i64, [i32, i32, i32, i32]),
     'addk_dice_stats': (i32, [C.POINTER(DiceStatsArgs), vp]),
     'addk_ce_upsample_dice_fwd_bwd': (i32, [C.POINTER(CeUpsampleDiceArgs), vp]),
+    'addk_ce_upsample_shaped_supported': (i32, [i32, i32, i32, i32, i32, i32]),
+    'addk_ce_upsample_shaped_fwd_bwd': (i32, [C.POINTER(CeUpsampleShapedArgs), vp]),
     'addk_score_upsample_supported': (i32, [i32, i32, i32, i32, i32, i32]),
     'addk_score_upsample_ws_floats': (i64, [i32, i32, i32]),
     'addk_score_upsample': (i32, [C.POINTER(ScoreUpsampleArgs), vp]),

@@ -1,4 +1,5 @@
-// Device and host code that more than one family of logits heads uses (loss_up.hip: the training head and hard example mining;
+// Device and host code that more than one family of logits heads uses (ce_up.h: the training head's kernel, instantiated by loss_up.hip, with
+// hard example mining, and by loss_shape.hip, the focal and label-smoothed forms;
 // dice_up.hip: the soft-Dice term's reduction; score_up.hip: the validation scoring head and the exit profile; label_up.hip: the
 // label-map heads and the exit gate; calib_up.hip: the calibration head; loss.hip: the drop-in criterion): the block sum and the second-stage sum of partials, the argument prefix and pixel loader of the decoder's
 // low-resolution NHWC logits, the up-sampling walk of the gather heads with its grid, the label store, and the last-arriver tail of

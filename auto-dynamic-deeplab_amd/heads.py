@@ -63,9 +63,15 @@ def _ce_head(g, src, OH, OW):
     of `ce_upsample` / `ce_upsample_ohem`, and the binding gets `distill_state` (TrainStep.distill_stats).  A binding with
     `dice = (weight, smooth)` adds the soft-Dice region term (include/addk.h, addk_dice_stats): `dice_stats`, directly in front of the
     head, leaves the coefficient table and the term; the head is `ce_upsample_dice`, whatever else it is, and reads the table; the
-    binding gets `dice_state` (TrainStep.dice_stats)."""
+    binding gets `dice_state` (TrainStep.dice_stats).  A binding with `focal = gamma` or `smooth = eps` (never both, never with `distill`)
+    shapes the per-pixel loss (include/addk.h, addk_ce_upsample_shaped_fwd_bwd): the ONE launch `ce_upsample_shaped` stands where
+    `ce_upsample`, `ce_upsample_ohem` or `ce_upsample_dice` would, with their arguments inside its own, their reads and their writes;
+    `ohem_select` and `dice_stats` in front of it are untouched."""
     def emit_ce(ce):
         lib, ohem, kd, dice = g.lib, ce.get('ohem'), ce.get('distill'), ce.get('dice')
+        focal, smooth = ce.get('focal'), ce.get('smooth')
+        shaped = focal is not None or smooth is not None
+        assert not (shaped and kd) and (focal is None or smooth is None), 'a shaped loss head has no distillation form and one shape'
         f32 = dict(dtype=torch.float32, device=g.device)
         a = _up_args(g, L.CeUpsampleArgs, src, OH, OW)
         _bind_loss(a, ce)
@@ -79,7 +85,7 @@ def _ce_head(g, src, OH, OW):
             kdo = torch.zeros(1, **f32)
             g.keep.append(kdo)
         # the launch: the plain head, unless a block below changes it; the KD struct is a superset of the mining struct
-        args = L.CeUpsampleKdArgs() if kd or dice else L.CeUpsampleOhemArgs() if ohem else a
+        args = L.CeUpsampleKdArgs() if kd or dice or shaped else L.CeUpsampleOhemArgs() if ohem else a
         name, fn, norm = 'ce_upsample', lib.addk_ce_upsample_fwd_bwd, [ce['wsum']]
         rd_more, wr = [], [gs, ce['loss'], ws]
         if ohem:
@@ -131,6 +137,19 @@ def _ce_head(g, src, OH, OW):
             head.kd, head.coef = args, coef.data_ptr()       # a copy of the head's arguments, complete by now
             g.keep += [d, coef, dout, dws, head]
             args, name, fn, rd_more = head, 'ce_upsample_dice', lib.addk_ce_upsample_dice_fwd_bwd, rd_more + [coef]
+        if shaped:
+            # the shape: the head's arguments, complete by now (kept set and table included), inside the shaped launch's own
+            sh = L.CeUpsampleShapedArgs()
+            if dice:
+                sh.dice = args
+            else:
+                sh.dice.kd = args
+            if focal is not None:
+                sh.shape, sh.gamma = L.CE_SHAPE_FOCAL, focal
+            else:
+                sh.shape, sh.eps = L.CE_SHAPE_SMOOTH, smooth
+            g.keep.append(sh)
+            args, name, fn = sh, 'ce_upsample_shaped', lib.addk_ce_upsample_shaped_fwd_bwd
         g._add(g.bwd, name, fn, C.byref(args), rd=g.lz(src) + [ce['target']] + norm + rd_more, wr=wr)
     out = _late_head(g, 'ce', src, OH, OW, g.bwd, g._bwd_emitters, emit_ce)
     out.src = src

@@ -84,9 +84,36 @@ def _check_dice(dice):
     return weight, smooth
 
 
+def _check_shape(focal, label_smoothing, distill):
+    """(gamma, eps), at most one of them not None: a finite gamma >= 1 or an eps in (0, 1); ValueError for what the library would refuse."""
+    if focal is None and label_smoothing is None:
+        return None, None
+    name = 'focal' if focal is not None else 'label_smoothing'
+    if focal is not None and label_smoothing is not None:
+        raise ValueError('focal and label_smoothing are two shapes of the same per-pixel loss: give one of them')
+    if distill is not None:
+        raise ValueError('%s: the fused loss head has no focal or label-smoothed form with distill (smoothed targets are known to hurt '
+                         'distillation, and the distillation head has no registers left for a shape)' % name)
+    if os.environ.get('ADDK_FUSE_CE', '1') != '1':
+        raise ValueError('%s needs the fused loss head (ADDK_FUSE_CE=1): there is no form over full-resolution logits' % name)
+    try:
+        v = float(focal if focal is not None else label_smoothing)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a number, got %r' % (name, focal if focal is not None else label_smoothing))
+    v32 = C.c_float(v).value                                           # the word the library receives
+    if focal is not None:
+        if not (math.isfinite(v32) and v32 >= 1.0):
+            raise ValueError('focal: gamma must be finite and at least 1, got %r' % (focal,))
+        return v, None
+    if not (0.0 < v32 < 1.0):
+        raise ValueError('label_smoothing: eps must lie in (0, 1), got %r' % (label_smoothing,))
+    return None, v
+
+
 class TrainStep:
     def __init__(self, model, batch_shape, lr=0.05, momentum=0.9, weight_decay=4e-5, nesterov=True, class_weight=None,
-                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None, ohem=None, distill=None, dice=None):
+                 ignore_index=255, use_graph=None, sync_comm=None, nstreams=None, ohem=None, distill=None, dice=None,
+                 focal=None, label_smoothing=None):
         """ohem = (thresh, min_kept): online hard example mining in every exit's loss head (include/addk.h, addk_ohem_select) — per exit
         and per process, a pixel counts when its target-class probability is below `thresh`, and never fewer than `min_kept` pixels per
         image (min_kept * N of the batch) count.  Only the fused loss head has this form: ValueError otherwise.
@@ -95,11 +122,17 @@ class TrainStep:
         exit's logits are read detached.  Needs the fused head on every exit, more than one exit and exits on one low-resolution grid.
         dice = (weight, smooth): a soft-Dice region term in every exit's loss head (include/addk.h, addk_dice_stats) — per exit and per
         process, scale * weight * (1 - mean over the classes present in the batch of (2 I_c + smooth) / (P_c + Y_c + smooth)) over the valid
-        pixels; class_weight does not weigh it and ohem does not filter it.  Only the fused loss head has this form: ValueError otherwise."""
+        pixels; class_weight does not weigh it and ohem does not filter it.  Only the fused loss head has this form: ValueError otherwise.
+        focal = gamma (finite, >= 1) or label_smoothing = eps (0 < eps < 1), never both: the shape of every exit's per-pixel loss
+        (include/addk.h, addk_ce_upsample_shaped_fwd_bwd) — w_t (1 - p_t)^gamma (-log p_t) in the place of w_t (-log p_t), or
+        torch.nn.functional.cross_entropy(label_smoothing=eps); the normaliser stays the head's.  Both compose with class_weight, ohem (the
+        kept set is still chosen on the plain per-pixel cross-entropy) and dice; neither has a form with distill or over full-resolution
+        logits: ValueError.  ValidationStep keeps reporting the plain cross-entropy."""
         lib = self.lib = L.load()
         self.ohem = _check_ohem(ohem, batch_shape[0])
         self.distill = _check_distill(distill)
         self.dice = _check_dice(dice)
+        self.focal, self.label_smoothing = _check_shape(focal, label_smoothing, distill)
         dev = next(model.parameters()).device
         _plan.require_device(next(model.parameters()))
         self.model, self.dev = model, dev
@@ -135,6 +168,10 @@ class TrainStep:
         if self.dice is not None and any(o.head != 'ce' for o in outs):
             raise ValueError('dice: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0: the head takes '
                              '%s and at most 16 output rows per input row)' % L.head_classes_text())
+        for name, v in (('focal', self.focal), ('label_smoothing', self.label_smoothing)):
+            if v is not None and any(o.head != 'ce' for o in outs):
+                raise ValueError('%s: an exit of this model has no fused loss head at this shape (addk_ce_upsample_supported == 0: the head '
+                                 'takes %s and at most 16 output rows per input row)' % (name, L.head_classes_text()))
         if self.distill is not None:
             if nex < 2:
                 raise ValueError('distill: this model has a single exit, nobody to teach')
@@ -177,6 +214,10 @@ class TrainStep:
                     o.binding['nvalid'] = nvalid
                 if self.dice is not None:
                     o.binding['dice'] = self.dice
+                if self.focal is not None:
+                    o.binding['focal'] = self.focal
+                if self.label_smoothing is not None:
+                    o.binding['smooth'] = self.label_smoothing
                 self.dlogits.append(None)
                 continue
             d = torch.empty_like(o.y)

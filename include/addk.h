@@ -504,7 +504,7 @@ int addk_ce_fwd_bwd(const float* logits, const int64_t* target, int32_t N, int32
 int64_t addk_ce_ws_floats(int32_t N, int64_t HW);
 
 /* The class counts C the fused heads on the low-resolution logits are compiled for, two lists in csrc/up.h.
- *   addk_head_classes       the training heads (addk_ce_upsample_fwd_bwd and its _ohem, _kd and _dice forms, addk_ohem_select,
+ *   addk_head_classes       the training heads (addk_ce_upsample_fwd_bwd and its _ohem, _kd, _dice and _shaped forms, addk_ohem_select,
  *                           addk_dice_stats), the label heads (addk_label_upsample, addk_label_tiles_upsample,
  *                           addk_label_tile_views_upsample), the window gate (addk_gate_tiles_upsample) and the compile-time form of addk_ce_fwd_bwd:
  *                           19 (Cityscapes) and 21 (Pascal VOC).
@@ -676,6 +676,36 @@ typedef struct {
   const float* coef;                 /* [2*C] from addk_dice_stats */
 } addk_ce_upsample_dice_args;
 int addk_ce_upsample_dice_fwd_bwd(const addk_ce_upsample_dice_args* a, void* stream);
+
+/* Per-pixel loss shapes for the fused loss head: what stands in the place of the plain head's w_t * (-log p_t), with p = softmax(z) of the
+ * up-sampled logits, t the pixel's target, w_c = class_w[c] (or 1), W = sum_c w_c, s = ce.scale and n = *ce.wsum, the head's normaliser as it is
+ * (sum of w_t over the valid pixels, or over the kept ones with a kept set).  The sums run over the valid pixels (with a kept set: the kept ones).
+ *   ADDK_CE_SHAPE_FOCAL   gamma >= 1, finite (Lin et al., "Focal Loss for Dense Object Detection"):
+ *       loss_out[0] += (s / n) * sum w_t * (1 - p_t)^gamma * (-log p_t)
+ *       d / d z_j    = (s / n) * w_t * F * (p_j - [j = t]),    F = (1 - p_t)^(gamma-1) * ((1 - p_t) + gamma * p_t * (-log p_t))
+ *     1 - p_t is the sum of the OTHER classes' exponentials over the sum of all; 0^0 = 1 at gamma == 1.
+ *   ADDK_CE_SHAPE_SMOOTH  0 < eps < 1: torch.nn.functional.cross_entropy(weight=, ignore_index=, label_smoothing=eps), mean reduction:
+ *       loss_out[0] += (s / n) * sum [ (1-eps) * w_t * (-log p_t) + (eps/C) * sum_c w_c * (-log p_c) ]
+ *       d / d z_j    = (s / n) * [ (1-eps) * w_t * (p_j - [j = t]) + (eps/C) * (p_j * W - w_j) ]
+ *   ADDK_CE_SHAPE_NONE    the call is forwarded to addk_ce_upsample_dice_fwd_bwd (dice.coef set), addk_ce_upsample_kd_fwd_bwd (a teacher),
+ *     addk_ce_upsample_ohem_fwd_bwd (a kept set) or addk_ce_upsample_fwd_bwd, whose bits it leaves; gamma and eps are not read.
+ * A shaped head composes with a kept set (dice.kd.pix_loss / tau, both or neither: addk_ohem_select chooses the set on the plain per-pixel
+ * cross-entropy, as ever) and with the soft-Dice term (dice.coef, or NULL for none: the term goes by the plain predicate, unweighted and
+ * unfiltered, as in addk_ce_upsample_dice_fwd_bwd).  It has NO distillation form: a non-NULL dice.kd.teacher is refused.  n == 0 (no valid
+ * pixel): the loss word gets 0 and g gets 0 (or stays, with accumulate).  Deterministic as the head it extends; ws holds
+ * addk_ce_upsample_ws_floats() floats.  addk_ce_upsample_shaped_supported() is addk_ce_upsample_supported().  Returns ADDK_ERR_INVALID and launches
+ * nothing for a shape outside the three, a gamma that is not finite or below 1, an eps outside (0, 1), a teacher, and what the plain head refuses. */
+#define ADDK_CE_SHAPE_NONE 0
+#define ADDK_CE_SHAPE_FOCAL 1
+#define ADDK_CE_SHAPE_SMOOTH 2
+typedef struct {
+  addk_ce_upsample_dice_args dice;   /* dice.coef == NULL: no soft-Dice term */
+  int32_t shape;                     /* ADDK_CE_SHAPE_* */
+  float gamma;                       /* read by ADDK_CE_SHAPE_FOCAL */
+  float eps;                         /* read by ADDK_CE_SHAPE_SMOOTH */
+} addk_ce_upsample_shaped_args;
+int addk_ce_upsample_shaped_supported(int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t C);
+int addk_ce_upsample_shaped_fwd_bwd(const addk_ce_upsample_shaped_args* a, void* stream);
 
 /* Scoring head of a validation pass (train.py:250-322, eval.py:165-193): what the evaluator, the criterion and the entropy
  * meter need of one exit, in ONE pass over the high-resolution pixel grid, straight from the LOW-resolution NHWC logits
